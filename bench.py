@@ -30,6 +30,8 @@ Prints ONE JSON line on rank 0, with
                 host <-> device copy rates of the box and the bound they put on one synchronous call
   sharded       (N>1, or --sharded) fill_sharded: per-rank D2H straight into one shared pinned
                 host slab; compute and gather time
+
+--dump-outputs DIR writes what the last timed step returned (rank 0's frames) as DIR/<name>.npy, see host_outputs().
 """
 import argparse
 import importlib
@@ -47,6 +49,8 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
 BYTES_PER_PIXEL = 16   # read f32 depth, write f32 depth + f32 distance + i32 index
 EXTRA_WORKLOADS = ("kitti_b32_scanline", "nyu_b64", "synth2048_b16")
 XSTEPS = 50  # timed passes of the extra workloads (behind the spin-up and 10 warm-up passes)
+DUMP_BYTES = 60 << 20  # --dump-outputs: all arrays together, below 64 MB
+DUMP_SEED = 0
 
 
 def host_cores():
@@ -102,9 +106,30 @@ def load_traffic():
         return {}
 
 
-def measure(op, torch, x, steps, warmup, path, barrier, reduce_max, repeats=0, workload=None, traffic=None):
+def host_outputs(torch, res):
+    """The outputs of one pass (res: name -> device tensor, what the caller receives) as numpy arrays: float32, the integer
+    outputs float64 (exact).  If they would take more than DUMP_BYTES, every output of more than n elements is cut to the
+    same DUMP_SEED-seeded sample of n flat positions in ascending order, n = DUMP_BYTES / (bytes of one element of each)."""
+    import numpy as np
+
+    item = {k: 4 if v.dtype == torch.float32 else 8 for k, v in res.items()}
+    n = DUMP_BYTES // sum(item.values())
+    sample = sum(v.numel() * item[k] for k, v in res.items()) > DUMP_BYTES
+    pos, out = {}, {}
+    for k, v in res.items():
+        if sample and v.numel() > n:
+            if v.numel() not in pos:
+                p = np.sort(np.random.default_rng(DUMP_SEED).choice(v.numel(), n, replace=False))
+                pos[v.numel()] = torch.from_numpy(p).to(v.device)
+            v = v.reshape(-1)[pos[v.numel()]]
+        out[k] = v.to(torch.float32 if item[k] == 4 else torch.float64).cpu().numpy()
+    return out
+
+
+def measure(op, torch, x, steps, warmup, path, barrier, reduce_max, repeats=0, workload=None, traffic=None, keep=None):
     """W untimed passes, then exactly `steps` timed ones between barrier + synchronize; per-kernel HIP-event
-    times from a few instrumented passes.  Returns (line fields, roofline dict)."""
+    times from a few instrumented passes.  keep, if given, is called with the last timed pass's result right after the
+    timed region (the passes after it overwrite the operator's output buffers).  Returns (line fields, roofline dict)."""
     B, H, W = x.shape
     # Spin-up, before the contract's W warm-up steps and just as untimed: the first few hundred passes after an idle spell run
     # slower (clocks, and whatever the process before left behind: 96 us per pass measured behind 10 passes, 90.7 behind 300
@@ -128,9 +153,11 @@ def measure(op, torch, x, steps, warmup, path, barrier, reduce_max, repeats=0, w
     barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
-        op.run(x, path=path)
+        last = op.run(x, path=path)
     barrier()
     elapsed = reduce_max(time.perf_counter() - t0)
+    if keep is not None:
+        keep(last)
     rep = []
     for _ in range(repeats):
         barrier()
@@ -210,7 +237,11 @@ def main():
     ap.add_argument("--path", default="auto", choices=["auto", "general", "fused"])
     ap.add_argument("--metric", default="l1_cv", choices=["l1_cv", "l2"],
                     help="l1_cv = the reference's cv2 transform (headline); l2 = exact Euclidean")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last one's outputs (rank 0) as DIR/<name>.npy (host_outputs())")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -287,8 +318,14 @@ def main():
     _, H, W = xh.shape
     x = torch.from_numpy(xh).to(dev)
     sfx = "_l2" if args.metric == "l2" else ""
+    dump = {}
+    keep = (lambda r: dump.update(host_outputs(torch, r))) if args.dump_outputs and rank == 0 else None
     res, roof = measure(op, torch, x, args.steps, args.warmup, args.path, barrier, reduce_max, repeats=5,
-                        workload=args.workload + sfx, traffic=traffic)
+                        workload=args.workload + sfx, traffic=traffic, keep=keep)
+    if dump:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
 
     sharded = None
     if world > 1 or args.sharded:
