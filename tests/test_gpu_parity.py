@@ -2,11 +2,13 @@
 golden vectors.  Bar: bit-exact distance map, label map and gathered depth (integer / index work;
 the float outputs are exact copies or integer-valued, so the float tolerance is 0)."""
 import importlib
+import itertools
 import os
 
 import numpy as np
 import pytest
 
+from guarded import poison_op
 from helpers import digest, labels_from_nearest, load_cases, load_l2_cases
 
 pytestmark = pytest.mark.gpu
@@ -15,6 +17,9 @@ L2_CASES, L2_DIGESTS = load_l2_cases()
 
 
 PATHS = ("auto", "general")  # every comparison runs through the fused+fallback pass AND the general kernels alone
+# every pass below starts from poisoned outputs and workspace (tests/guarded.py): the kind and seed of the next poison come from
+# this seeded counter, so that no comparison can pass on what an earlier pass left in the operator's buffers
+_POISON = itertools.count(7000)
 
 
 def run(op, x, st=0.1, vt=0.1, want=("depth", "dt", "index"), path="auto"):
@@ -23,6 +28,7 @@ def run(op, x, st=0.1, vt=0.1, want=("depth", "dt", "index"), path="auto"):
     import torch
 
     xd = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to("cuda:0")
+    poison_op(op, next(_POISON), xd.shape, path=path)
     res = op.run(xd, st, vt, want, path=path)
     torch.cuda.synchronize()
     out = {k: v.cpu().numpy() for k, v in res.items()}
@@ -281,6 +287,7 @@ def test_l2_metric_vs_oracle(pkg, oracle):
     frames.append(lat)
     for x in frames:
         depth, dt, idx, status = oracle.fill_batch(x, metric="l2")
+        poison_op(op, next(_POISON), x.shape)
         res = op.run(torch.from_numpy(x).to("cuda:0"))
         torch.cuda.synchronize()
         got = {k: v.cpu().numpy() for k, v in res.items()}
@@ -296,6 +303,7 @@ def _run_l2(pkg, x, path="auto"):
     import torch
 
     op2 = pkg.device.DtFill(device="cuda:0", metric="l2")
+    poison_op(op2, next(_POISON), np.shape(x), path=path)
     res = op2.run(torch.from_numpy(np.ascontiguousarray(x, np.float32)).to("cuda:0"), path=path)
     torch.cuda.synchronize()
     return {k: v.cpu().numpy() for k, v in res.items()}
@@ -341,6 +349,7 @@ def test_l2_full_size_properties(pkg, oracle):
     synth = importlib.import_module(pkg.__name__ + ".synth")
     op = pkg.device.DtFill(device="cuda:0", metric="l2")
     x = synth.make("kitti_b32", B=4)
+    poison_op(op, next(_POISON), x.shape)
     res = op.run(torch.from_numpy(x).to("cuda:0"))
     torch.cuda.synchronize()
     idx = res["index"].cpu().numpy()
@@ -398,6 +407,7 @@ def test_rows_handed_on_by_the_window_kernel(gpu_op, oracle):
     assert got["general"].tolist() == [False, True, True]
     # the depth epilogue: rows from 96 on, floored
     want = oracle.fill_batch(x)[0]
+    poison_op(gpu_op, next(_POISON), x.shape, depth_rows_from=96)
     res = gpu_op.run(torch.from_numpy(x).to("cuda:0"), want=("depth",), depth_rows_from=96, depth_floor=0.9)
     torch.cuda.synchronize()
     assert np.array_equal(res["depth"].cpu().numpy(), oracle.depth_floor(want[:, 96:], 0.9))
@@ -410,6 +420,7 @@ def assert_l2_equal_to_oracle(oracle, op2, x, st=0.1, vt=0.1, paths=("auto", "ge
 
     depth, dt, idx, status = oracle.fill_batch(x, st, vt, metric="l2")
     for path in paths:
+        poison_op(op2, next(_POISON), x.shape, path=path)
         res = op2.run(torch.from_numpy(x).to("cuda:0"), st, vt, path=path)
         torch.cuda.synchronize()
         got = {k: v.cpu().numpy() for k, v in res.items()}
@@ -618,6 +629,7 @@ def test_random_fuzz_both_metrics(pkg, gpu_op, oracle):
         st, vt = (0.001, 0.1) if t % 5 == 0 else (0.1, 0.1)
         assert_equal_to_oracle(oracle, gpu_op, x, st, vt)
         depth, dt, idx, status = oracle.fill_batch(x, st, vt, metric="l2")
+        poison_op(op2, next(_POISON), x.shape)
         res = op2.run(torch.from_numpy(x).to("cuda:0"), st, vt)
         torch.cuda.synchronize()
         assert np.array_equal(res["index"].cpu().numpy(), idx)
@@ -686,6 +698,7 @@ def test_outlier_removal_fused_into_the_predicates(pkg, gpu_op, oracle):
         for metric, op in (("l1_cv", gpu_op), ("l2", op2)):
             depth, dt, idx, status = oracle.fill_batch(xf, metric=metric)
             for path in ("auto", "general"):
+                poison_op(op, next(_POISON), x.shape, path=path, outlier_removal=True)
                 res = op.run(torch.from_numpy(x).to("cuda:0"), path=path, outlier_removal=True)
                 torch.cuda.synchronize()
                 got = {k: v.cpu().numpy() for k, v in res.items()}
@@ -881,6 +894,7 @@ def test_input_pointer_alignment_does_not_matter(gpu_op, oracle):
         view = flat[off:off + B * H * W].view(B, H, W)
         view.copy_(torch.from_numpy(x))
         assert view.data_ptr() % 16 == (flat.data_ptr() + 4 * off) % 16
+        poison_op(gpu_op, next(_POISON), view.shape)
         res = gpu_op.run(view, 0.1, 0.1)
         torch.cuda.synchronize()
         assert np.array_equal(res["index"].cpu().numpy(), lbl) and np.array_equal(res["dt"].cpu().numpy(), dt), off
@@ -996,17 +1010,22 @@ def test_config1_one_kitti_frame_through_the_reference_functions(pkg, oracle):
     Distance_Transform, numpy in / numpy out, as demo.py:289-290 and eval_NYU.py:195 call them."""
     synth = importlib.import_module(pkg.__name__ + ".synth")
     x = synth.make("kitti_b1")[0]
+    op = pkg.device.default_op()  # the operator behind the reference-named functions: poisoned before each of them
+    poison_op(op, next(_POISON), (1,) + x.shape)
     dt, lbl = pkg.nearest_point(x)
     dt0, lbl0 = oracle.nearest_point(x)
     assert dt.shape == (352, 1216) and np.array_equal(dt, dt0) and np.array_equal(lbl, lbl0)
     batch = x[None, :, :, None]
+    poison_op(op, next(_POISON), (1,) + x.shape)
     out = pkg.DT_complete_batch(batch)
     assert out.shape == (1, 352, 1216, 1) and out.dtype == np.float32
     assert np.array_equal(out, oracle.DT_complete_batch(batch))
+    poison_op(op, next(_POISON), (1,) + x.shape)
     one = pkg.Distance_Transform(batch, 0.1)  # the notebooks' thresholds (0.1 / 0.1)
     assert one.shape == (352, 1216) and np.array_equal(one, oracle.Distance_Transform(batch, 0.1))
     # a LiDAR-like frame (empty sky, ring rows) takes the other kernel family through the same functions
     xs = synth.make("kitti_b32_scanline", B=1)[0]
+    poison_op(op, next(_POISON), (1,) + xs.shape)
     assert np.array_equal(pkg.Distance_Transform(xs[None, :, :, None], 0.1), oracle.Distance_Transform(xs, 0.1))
 
 
@@ -1113,6 +1132,7 @@ def test_depth_epilogue_fused_into_the_stores(gpu_op, oracle, pkg):
                 want = oracle.depth_floor(want, fl)
             for path in PATHS:
                 xd = torch.from_numpy(x).to("cuda:0")
+                poison_op(gpu_op, next(_POISON), x.shape, path=path, depth_rows_from=r0)
                 res = gpu_op.run(xd, path=path, depth_rows_from=r0, depth_floor=fl)
                 torch.cuda.synchronize()
                 assert tuple(res["depth"].shape) == want.shape
