@@ -82,39 +82,26 @@ namespace {
 // ------------------------------------------------------------------------------------------------
 inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
-struct Carve {
-    u8 *planes;          // k_rows -> k_fin: bit planes d & 1, d >> 1 & 1, d >> 2 & 1, live, tie; k_fin -> k_tiesx: unresolved; Wd * 8 bytes per row
-    size_t plane_bytes;  // bytes of one plane
-    u64 *srcbits, *valbits;
-    u16 *wpre_s, *wpre_v;
-    u32 *rowcnt_s, *rowcnt_v, *rowbase_s, *rowbase_v;
-    u32 *rowfar;         // per row: l1_cv: k_fused left a pixel undecided (-> k_rows, k_fin, k_tiesx); l2: far pixels (k_l2win -> k_l2far, k_l2env)
-    uint2 *ct;           // k_colT -> k_rows: per 32-row band and column {the band's source bits of the column, distances
-                         // from the band's first / last row to the nearest source above / below}; rows of ctp columns
-    int nb, ctp;         // bands per frame, columns per row of ct
-    u32 *xlist, *xptr;   // k_fin -> k_tiesx: the pixels whose chain left their tile, and where each goes on
-    float *dscratch;     // k_fin -> k_tiesx: depths of the rows a depth epilogue drops from the output
-    u32 *spix;           // k_rows -> k_fin: per pixel, the frame offset of its nearest source in column kmin
-    uint4 *rec;          // k_colT -> k_fin, k_l2env: rank records, per 64-pixel word of a row (label_from_rec)
-    int *finfo, *fflag2, *route, *status, *negflag;
-    float *vlist;
-    PtsSrc *ptslist;     // k_frame -> k_pts: the sources of a frame that has a handful (l1_cv, ROUTE_POINTS)
-    size_t total;
-};
-
-Carve carve(void *ws, int B, int H, int W) {
+// The workspace of a pass, 256-byte aligned pieces in this order; with ws = nullptr only the total is worked out
+// (dtfill_workspace_bytes).  status is the workspace's frame status (make_pass puts the caller's in its place).
+Pass carve(void *ws, int B, int H, int W, size_t *total = nullptr) {
     const size_t N = (size_t)B * H * W;
     const size_t Wd = (size_t)(W + 63) / 64;
     const size_t NW = (size_t)B * H * Wd;
     const size_t NR = (size_t)B * H;
-    char *p = static_cast<char *>(ws);
+    char *base = static_cast<char *>(ws);
     size_t off = 0;
-    Carve c;
+    Pass c{};
     auto take = [&](size_t bytes) {
-        char *r = p ? p + off : nullptr;
+        char *r = base ? base + off : nullptr;
         off += align256(bytes);
         return r;
     };
+    c.B = B;
+    c.H = H;
+    c.W = W;
+    c.Wd = (int)Wd;
+    c.Wp = (int)Wd * 8;
     c.srcbits = (u64 *)take(NW * 8);
     c.valbits = (u64 *)take(NW * 8);
     c.wpre_s = (u16 *)take(NW * 2);
@@ -125,7 +112,7 @@ Carve carve(void *ws, int B, int H, int W) {
     c.rowbase_v = (u32 *)take(NR * 4);
     c.finfo = (int *)take((size_t)B * FI_STRIDE * 4);
     c.fflag2 = (int *)take((size_t)B * 4);
-    c.rowfar = (u32 *)take(NR * 4);  // right behind fflag2: rowflag_of()
+    c.rowfar = (u32 *)take(NR * 4);
     c.route = (int *)take((size_t)B * 4);
     c.status = (int *)take((size_t)B * 4);
     c.negflag = (int *)take((size_t)B * 4);
@@ -142,8 +129,24 @@ Carve carve(void *ws, int B, int H, int W) {
     c.planes = (u8 *)take(PL_N * c.plane_bytes);
     c.vlist = (float *)take(N * 4);
     c.ptslist = (PtsSrc *)take((size_t)B * L2_PTS_MAX * sizeof(PtsSrc));
-    c.total = off;
+    if (total) *total = off;
     return c;
+}
+
+// the pass record of one call: the carved workspace, the input and the caller's outputs
+Pass make_pass(const float *x, int B, int H, int W, float src_thr, float val_thr, float *out_depth, float *out_dt, int32_t *out_index,
+               int32_t *frame_status, void *workspace, DepthEpilogue ep = DepthEpilogue{0, 0, 0.0f}) {
+    Pass p = carve(workspace, B, H, W);
+    p.x = x;
+    p.src_thr = src_thr;
+    p.val_thr = val_thr;
+    p.out_depth = out_depth;
+    p.out_dt = out_dt;
+    p.out_index = out_index;
+    if (frame_status) p.status = frame_status;
+    p.ep = ep;
+    if (!out_depth && !out_index) p.rec = nullptr, p.spix = nullptr;  // the distance map alone needs neither sources nor labels
+    return p;
 }
 
 bool shape_ok(int B, int H, int W) {
@@ -151,53 +154,74 @@ bool shape_ok(int B, int H, int W) {
            (long long)B * H * W < (1ll << 31);  // B is a grid dimension; pixel indices are 32-bit
 }
 
-constexpr int NK_L1 = 7;
+// kernel_ms slots of dtfill_batch_timed, in launch order
+enum { S1_MASK, S1_FRAME, S1_FUSED, S1_COLT, S1_ROWS, S1_FIN, S1_TIESX, NK_L1 };
 const char *const kNamesL1[NK_L1] = {"k_mask", "k_frame", "k_fused", "k_colT", "k_rows", "k_fin", "k_tiesx"};
+enum { S2_MASK, S2_FRAME, S2_WIN16, S2_WIN32, S2_FAR, S2_COLT, S2_ENV, NK_L2 };
+const char *const kNamesL2[NK_L2] = {"k_mask", "k_frame", "k_l2win<10>", "k_l2win<15>", "k_l2far", "k_colT", "k_l2env"};
+
+// Launch bookkeeping of a pass: ok after every launch; with events (dtfill_batch_timed) slot k's time runs from ev[k] to
+// ev[k + 1].  at(k) records every boundary up to ev[k]: the slot of a kernel that does not run is left at 0 ms.
+struct Marks {
+    hipStream_t st;
+    hipEvent_t *ev;
+    int k = 0;
+    bool ok = true;
+    void at(int slot) {
+        ok = ok && hipGetLastError() == hipSuccess;
+        if (ev)
+            for (; k <= slot; ++k) (void)hipEventRecord(ev[k], st);
+    }
+};
 
 // k_mask4 when the rows can be read 16 bytes at a time, k_mask otherwise (same outputs); with DTFILL_FLAG_OUTLIER_REMOVAL the
 // predicates see outlier_removal(x) (k_mask_o, then its exhaustive variant for the frames that hold a negative value)
-void launch_mask(const float *x, int B, int H, int W, int Wd, float src_thr, float val_thr, const Carve &c, unsigned flags,
-                 hipStream_t st) {
-    const bool vec = (W & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-    const dim3 g4((H + 3) / 4, B), g4m(B, (H + 3) / 4);  // (k_mask4: frames along x)
+void launch_mask(const Pass &p, unsigned flags, hipStream_t st) {
+    const bool vec = (p.W & 3) == 0 && (reinterpret_cast<uintptr_t>(p.x) & 15) == 0;
+    const dim3 g4((p.H + 3) / 4, p.B), g4m(p.B, (p.H + 3) / 4);  // (k_mask4: frames along x)
     // negflag ("this frame holds a negative value", raised by the first outlier launch, read by the second) starts clear whatever
     // the workspace held before
-    if (flags & DTFILL_FLAG_OUTLIER_REMOVAL) (void)hipMemsetAsync(c.negflag, 0, (size_t)B * sizeof(int), st);
+    if (flags & DTFILL_FLAG_OUTLIER_REMOVAL) (void)hipMemsetAsync(p.negflag, 0, (size_t)p.B * sizeof(int), st);
     if ((flags & DTFILL_FLAG_OUTLIER_REMOVAL) && vec) {
-        k_mask4<1, 1><<<g4m, 256, 0, st>>>(x, H, W, Wd, src_thr, val_thr, c.srcbits, c.valbits, c.wpre_s, c.wpre_v, c.rowcnt_s, c.rowcnt_v, c.negflag);
-        k_mask4<2, 1><<<g4m, 256, 0, st>>>(x, H, W, Wd, src_thr, val_thr, c.srcbits, c.valbits, c.wpre_s, c.wpre_v, c.rowcnt_s, c.rowcnt_v, c.negflag);
+        k_mask4<1, 1><<<g4m, 256, 0, st>>>(p);
+        k_mask4<2, 1><<<g4m, 256, 0, st>>>(p);
     } else if (flags & DTFILL_FLAG_OUTLIER_REMOVAL) {
-        k_mask_o<false><<<g4, 256, 0, st>>>(x, H, W, Wd, src_thr, val_thr, c.srcbits, c.valbits, c.wpre_s, c.wpre_v, c.rowcnt_s, c.rowcnt_v,
-                                            c.negflag);
-        k_mask_o<true><<<g4, 256, 0, st>>>(x, H, W, Wd, src_thr, val_thr, c.srcbits, c.valbits, c.wpre_s, c.wpre_v, c.rowcnt_s, c.rowcnt_v,
-                                           c.negflag);
-    }
-    else if (vec)
-        k_mask4<0, 1><<<g4m, 256, 0, st>>>(x, H, W, Wd, src_thr, val_thr, c.srcbits, c.valbits, c.wpre_s, c.wpre_v, c.rowcnt_s, c.rowcnt_v,
-                                          c.negflag);
+        k_mask_o<false><<<g4, 256, 0, st>>>(p);
+        k_mask_o<true><<<g4, 256, 0, st>>>(p);
+    } else if (vec)
+        k_mask4<0, 1><<<g4m, 256, 0, st>>>(p);
     else
-        k_mask<<<dim3((H + 4 * M_RPW - 1) / (4 * M_RPW), B), 256, 0, st>>>(x, H, W, Wd, src_thr, val_thr, c.srcbits,
-                                                                          c.valbits, c.wpre_s, c.wpre_v, c.rowcnt_s,
-                                                                          c.rowcnt_v);
+        k_mask<<<dim3((p.H + 4 * M_RPW - 1) / (4 * M_RPW), p.B), 256, 0, st>>>(p);
 }
 
-int run_l1(const float *x, int B, int H, int W, float src_thr, float val_thr, float *out_depth,
-           float *out_dt, int32_t *out_index, int32_t *frame_status, void *workspace, unsigned flags,
-           hipStream_t st, hipEvent_t *ev, DepthEpilogue ep = DepthEpilogue{0, 0, 0.0f}) {
-    const Carve c = carve(workspace, B, H, W);
-    const int Wd = (W + 63) / 64;
-    int *status = frame_status ? frame_status : c.status;
+// waves per k_colT block: two iterations of two bands per wave (fewer, longer waves fit the CUs in one round)
+int colT_waves(int nb) { return min(16, max(2, (nb + 3) / 4)); }
+
+// k_colT, with k_sky's blocks behind the column blocks when sky.nblocks > 0; false if its LDS could not be granted
+bool launch_colT(const Pass &p, const SkyArgs &sky, hipStream_t st) {
+    int cw = colT_waves(p.nb);
+    size_t lds = colT_lds(p.nb);
+    if (sky.nblocks) {
+        cw = SKY_NT / 64;
+        lds = max(lds, sky_lds(sky_span_max(p.H, p.W)));
+    }
+    bool ok = true;
+    if (lds > 48 * 1024)  // (set per call: the attribute belongs to the current device)
+        ok = hipFuncSetAttribute(reinterpret_cast<const void *>(k_colT), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+    const int ncol = (p.ctp + 63) / 64;
+    const int fx = cw <= 4;  // frames along grid x for frames of up to 512 rows (k_colT's comment)
+    k_colT<<<fx ? dim3(p.B, ncol + sky.nblocks) : dim3(ncol + sky.nblocks, p.B), 64 * cw, lds, st>>>(p, ncol, sky, fx);
+    return ok;
+}
+
+int run_l1(Pass p, unsigned flags, hipStream_t st, hipEvent_t *ev) {
+    const int B = p.B, H = p.H, W = p.W;
     const bool general_only = flags & DTFILL_FLAG_GENERAL_ONLY;
     const bool fused_only = flags & DTFILL_FLAG_FUSED_ONLY;
-    int k = 0;
-    bool ok = true;
-    auto mark = [&]() {
-        ok = ok && hipGetLastError() == hipSuccess;  // after every launch
-        if (ev) (void)hipEventRecord(ev[k++], st);
-    };
-    mark();
-    launch_mask(x, B, H, W, Wd, src_thr, val_thr, c, flags, st);
-    mark();
+    Marks m{st, ev};
+    m.at(S1_MASK);
+    launch_mask(p, flags, st);
+    m.at(S1_FRAME);
     // geometry of the window kernel's two tilings (k_frame pre-marks whole tile rows)
     auto tiling = [&](int R) {
             const int THM = F_WHM - 2 * R, TWM = F_WWM - 2 * R;
@@ -213,64 +237,45 @@ int run_l1(const float *x, int B, int H, int W, float src_thr, float val_thr, fl
             return t;
         };
     const FusedTiles t16 = tiling(16), t32 = tiling(32);
-    const bool epi = ep.row0 != 0 || ep.use_floor;
+    const bool epi = p.ep.row0 != 0 || p.ep.use_floor;
     // row flags (k_frame): the sky above the first source row goes to k_sky, rows too far from every source row to the
     // any-distance kernels, the rest of the frame to the window kernel.  Not with a depth epilogue (a handed-on row costs the
     // whole frame there) and not on the forced paths of the tests.
     const bool rowflags = !epi && !fused_only && !general_only;
     // k_sky takes the distances of its two base rows from the distance map: without one from the caller, the scratch frame
-    float *const out_dt_caller = out_dt;
-    if (rowflags && !out_dt) out_dt = c.dscratch;
-    k_frame<<<B, 256, 0, st>>>(x, c.valbits, c.wpre_v, c.srcbits, c.wpre_s, c.ptslist, c.rowcnt_s, c.rowcnt_v, H, W, Wd, c.rowbase_s, c.rowbase_v,
-                               c.finfo, c.vlist, c.fflag2, c.route, status, (general_only ? 1 : 0) | (rowflags ? 4 | 8 : 0), c.negflag, c.rowfar,
-                               t16.nty, t32.nty);
-    mark();
+    float *const out_dt_caller = p.out_dt;
+    if (rowflags && !p.out_dt) p.out_dt = p.dscratch;
+    k_frame<<<B, 256, 0, st>>>(p, (general_only ? 1 : 0) | (rowflags ? 4 | 8 : 0), t16.nty, t32.nty);
+    m.at(S1_FUSED);
     if (!general_only) {
-        // dense frames: the window kernel, halo 16 or 32 per frame (k_frame's route).  It hands rows on (fflag2, rowflag) when a
+        // dense frames: the window kernel, halo 16 or 32 per frame (k_frame's route).  It hands rows on (fflag2, rowfar) when a
         // tile pixel turns out to be farther than the halo from every source.
         // streaming stores only where every run of tile pixels a wave stores is whole 128-byte lines
-        auto line = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 127) == 0; };
-        const bool stream = (W & 31) == 0 && (t16.TW & 31) == 0 && (t32.TW & 31) == 0 && line(out_depth) && line(out_dt) && line(out_index);
+        auto line = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 127) == 0; };
+        const bool stream = (W & 31) == 0 && (t16.TW & 31) == 0 && (t32.TW & 31) == 0 && line(p.out_depth) && line(p.out_dt) &&
+                            line(p.out_index);
         const dim3 fg(B, max(t16.ntiles, t32.ntiles));  // frames along x: a frame's tiles beyond its own tiling (they exit) come last
-        if (stream)
-            k_fused<true><<<fg, F_NT, 0, st>>>(x, c.srcbits, c.wpre_s, c.rowbase_s, c.finfo, c.vlist, H, W, Wd, t16, t32, out_depth, out_dt,
-                                               out_index, c.route, c.fflag2, status, ep);
-        else
-            k_fused<false><<<fg, F_NT, 0, st>>>(x, c.srcbits, c.wpre_s, c.rowbase_s, c.finfo, c.vlist, H, W, Wd, t16, t32, out_depth, out_dt,
-                                                out_index, c.route, c.fflag2, status, ep);
+        (stream ? k_fused<true> : k_fused<false>)<<<fg, F_NT, 0, st>>>(p.x, p.srcbits, p.wpre_s, p.rowbase_s, p.finfo, p.vlist, H, W, p.Wd, t16, t32,
+                                                                      p.out_depth, p.out_dt, p.out_index, p.route, p.fflag2, p.rowfar, p.status, p.ep);
     }
-    mark();
+    m.at(S1_COLT);
     if (!fused_only) {
         // every other frame: argmin scans, any distance (dtfill_rows.hpp)
-        const int nb = c.nb;
-        int cw = min(16, max(2, (nb + 3) / 4));  // two iterations of two bands per wave: fewer, longer waves fit the CUs in one round
         // k_sky's blocks (the rows above the first source row, dtfill_sky.hpp) ride behind the column blocks
-        SkyArgs sky = {c.finfo, out_dt, out_dt_caller, out_depth, out_index, (W + SKY_SW - 1) / SKY_SW, 0};
-        size_t lds = colT_lds(nb);
-        const bool sky_rides = rowflags && cw <= SKY_NT / 64;  // (taller frames: a launch of its own, below)
-        if (sky_rides) {
-            sky.nblocks = sky.nstrips * ((H + SKY_RG - 1) / SKY_RG);
-            cw = SKY_NT / 64;
-            lds = max(lds, sky_lds(sky_span_max(H, W)));
-        }
-        if (lds > 48 * 1024)  // (set per call: the attribute belongs to the current device)
-            ok = ok && hipFuncSetAttribute(reinterpret_cast<const void *>(k_colT), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-        const int ncol = (c.ctp + 63) / 64;
-        const int fx = cw <= 4;  // frames along grid x for frames of up to 512 rows (k_colT's comment)
-        k_colT<<<fx ? dim3(B, ncol + sky.nblocks) : dim3(ncol + sky.nblocks, B), 64 * cw, lds, st>>>(
-            c.srcbits, c.fflag2, H, W, Wd, nb, c.ctp, c.ct, c.wpre_s, c.rowbase_s, (out_depth || out_index) ? c.rec : nullptr, ncol, sky, fx);
+        SkyArgs sky = {out_dt_caller, (W + SKY_SW - 1) / SKY_SW, 0};
+        const bool sky_rides = rowflags && colT_waves(p.nb) <= SKY_NT / 64;  // (taller frames: a launch of its own, below)
+        if (sky_rides) sky.nblocks = sky.nstrips * ((H + SKY_RG - 1) / SKY_RG);
+        m.ok = launch_colT(p, sky, st) && m.ok;
         if (rowflags && !sky_rides)
-            k_sky<<<dim3(sky.nstrips * ((H + SKY_RG - 1) / SKY_RG), B), SKY_NT, sky_lds(sky_span_max(H, W)), st>>>(
-                c.finfo, H, W, out_dt, out_dt_caller, out_depth, out_index, sky.nstrips);
-        mark();
-        const int Wp = Wd * 8;
+            k_sky<<<dim3(sky.nstrips * ((H + SKY_RG - 1) / SKY_RG), B), SKY_NT, sky_lds(sky_span_max(H, W)), st>>>(p, sky);
+        m.at(S1_ROWS);
         // columns per lane: 8 or 10, whichever leaves fewer idle lanes in the row's last wave
         const int nw8 = (W + 511) / 512, nw10 = (W + 639) / 640;
         const bool ten = nw10 * 640 < nw8 * 512;
-        auto aligned = [](const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
+        auto aligned = [](const void *q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; };
         const int nwv = ten ? nw10 : nw8;
-        const bool fin = out_depth || out_index;  // the distance map alone needs neither sources nor tie-breaks
-        float *dt = out_dt;
+        const bool fin = p.out_depth || p.out_index;  // the distance map alone needs neither sources nor tie-breaks
+        const float *dt = p.out_dt;
         // bit 0: a lane's pixels can leave as vectors; bit 1: the distance map goes through LDS and leaves as whole lines
         const int ovec = (ten ? ((W & 1) == 0 && aligned(dt, 8)) : ((W & 3) == 0 && aligned(dt, 16))) |
                          (((W & 31) == 0 && dt && aligned(dt, 128)) ? 2 : 0);
@@ -278,120 +283,85 @@ int run_l1(const float *x, int B, int H, int W, float src_thr, float val_thr, fl
         // rows per block: several where a row is one wave, or where there are very many rows (the exit of a frame that has none, or of
         // a row far from every handed-on row, costs a block dispatch per row)
         const int rpb = (nwv == 1 || (long long)H * B >= 16384) && nwv <= 4 ? R_RPB : 1;
-        const dim3 grid((H + rpb - 1) / rpb, B);
-#define LAUNCH_ROWS(PPL_, MAXT_, MULTI_)                                                                                        \
-    k_rows<PPL_, MAXT_, MULTI_><<<grid, 64 * nwv, rlds, st>>>(c.ct, c.ctp, c.fflag2, H, W, nb, Wp, c.planes, c.plane_bytes, dt, \
-                                                           fin ? c.spix : nullptr, ovec, c.rowfar, c.finfo, rpb)
-        if (rpb > 1 && ten)
-            LAUNCH_ROWS(10, 256, true);
-        else if (rpb > 1)
-            LAUNCH_ROWS(8, 256, true);
-        else if (ten && nwv <= 4)
-            LAUNCH_ROWS(10, 256, false);
-        else if (ten)
-            LAUNCH_ROWS(10, 1024, false);
-        else if (nwv <= 4)
-            LAUNCH_ROWS(8, 256, false);
-        else
-            LAUNCH_ROWS(8, 1024, false);
-#undef LAUNCH_ROWS
-        mark();
+        auto *const rows = rpb > 1   ? (ten ? k_rows<10, 256, true> : k_rows<8, 256, true>)
+                                             : nwv <= 4 ? (ten ? k_rows<10, 256, false> : k_rows<8, 256, false>)
+                                                        : (ten ? k_rows<10, 1024, false> : k_rows<8, 1024, false>);
+        rows<<<dim3((H + rpb - 1) / rpb, B), 64 * nwv, rlds, st>>>(p.ct, p.ctp, p.fflag2, H, W, p.nb, p.Wp, p.planes, p.plane_bytes, p.out_dt, p.spix,
+                                                                  ovec, p.rowfar, p.finfo, rpb);
+        m.at(S1_FIN);
         // the frames with a handful of sources (k_frame: ROUTE_POINTS, fflag 3; only with the row flags) ride in k_fin's launch:
         // their tiles, from the source list to the outputs (dtfill_pts.hpp); k_tiesx finishes the chains that leave a tile
         PtsArgs pa;
-        pa.ptslist = c.ptslist;
-        pa.out_dt = out_dt;
+        pa.ptslist = p.ptslist;
+        pa.out_dt = p.out_dt;
         // 32 x 256 tiles or 64 x 128: whichever wastes fewer waves on this shape (640 columns are 2.5 tiles of 256 but 5 of 128)
         const int nwide = ((W + 255) / 256) * ((H + 31) / 32), ntall = ((W + 127) / 128) * ((H + 63) / 64);
         pa.tall = ntall < nwide;
         pa.tiles_x = pa.tall ? (W + 127) / 128 : (W + 255) / 256;
         pa.ntiles = rowflags ? (pa.tall ? ntall : nwide) : 0;
-        const int ttx = (W + Q_TW - 1) / Q_TW, tty = (H + Q_TH - 1) / Q_TH;
-        pa.fin_ntiles = fin ? ttx * tty : 0;
+        const int ttx = (W + Q_TW - 1) / Q_TW;
+        pa.fin_ntiles = fin ? ttx * ((H + Q_TH - 1) / Q_TH) : 0;
         if (fin || pa.ntiles) {
-            const int vec = (W & 3) == 0 && aligned(out_depth, 16) && aligned(out_index, 16);
-            k_fin<<<dim3(max(pa.fin_ntiles, pa.ntiles), B), Q_NT, 0, st>>>(c.planes, c.plane_bytes, Wp, c.fflag2, H, W, Wd, ttx, c.spix, x, c.rec,
-                                                       c.vlist, out_depth, out_index, status, c.finfo,
-                                                       c.xlist, c.xptr, c.planes + PL_UNRES * c.plane_bytes, vec, ep, c.dscratch, c.rowfar, pa);
-            mark();
-            if (fin)
-                k_tiesx<<<dim3(XL_BLOCKS, B), 256, 0, st>>>(c.planes + PL_UNRES * c.plane_bytes, Wp, c.fflag2, c.finfo, c.xlist,
-                                                            c.xptr, H, W, out_depth, out_index, ep, c.dscratch, c.rowfar);
-            mark();
-        } else {
-            mark();
-            mark();
+            const int vec = (W & 3) == 0 && aligned(p.out_depth, 16) && aligned(p.out_index, 16);
+            k_fin<<<dim3(max(pa.fin_ntiles, pa.ntiles), B), Q_NT, 0, st>>>(p.planes, p.plane_bytes, p.Wp, p.fflag2, H, W, p.Wd, ttx, p.spix, p.x, p.rec,
+                                                                           p.vlist, p.out_depth, p.out_index, p.status, p.finfo, p.xlist, p.xptr,
+                                                                           p.planes + PL_UNRES * p.plane_bytes, vec, p.ep, p.dscratch, p.rowfar, pa);
+            m.at(S1_TIESX);
+            if (fin) k_tiesx<<<dim3(XL_BLOCKS, B), 256, 0, st>>>(p);
         }
-    } else {
-        for (int t = 0; t < 4; ++t) mark();
     }
-    return ok ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+    m.at(NK_L1);
+    return m.ok ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 
-constexpr int NK_L2 = 7;
-const char *const kNamesL2[NK_L2] = {"k_mask", "k_frame", "k_l2win<10>", "k_l2win<15>", "k_l2far", "k_colT", "k_l2env"};
-
-int run_l2(const float *x, int B, int H, int W, float src_thr, float val_thr, float *out_depth, float *out_dt,
-           int32_t *out_index, int32_t *frame_status, void *workspace, unsigned flags, hipStream_t st, hipEvent_t *ev) {
-    const Carve c = carve(workspace, B, H, W);
-    const int Wd = (W + 63) / 64;
-    int *status = frame_status ? frame_status : c.status;
-    const bool general_only = flags & DTFILL_FLAG_GENERAL_ONLY;
-    int k = 0;
-    bool ok = true;
-    auto mark = [&]() {
-        ok = ok && hipGetLastError() == hipSuccess;  // after every launch
-        if (ev) (void)hipEventRecord(ev[k++], st);
-    };
-    mark();
-    launch_mask(x, B, H, W, Wd, src_thr, val_thr, c, flags, st);
-    mark();
-    k_frame<<<B, 256, 0, st>>>(x, c.valbits, c.wpre_v, c.srcbits, c.wpre_s, c.ptslist, c.rowcnt_s, c.rowcnt_v, H, W, Wd, c.rowbase_s, c.rowbase_v,
-                               c.finfo, c.vlist, c.fflag2, c.route, status, (general_only ? 1 : 0) | 2, c.negflag, c.rowfar, 0, 0);
-    mark();
+int run_l2(const Pass &p, unsigned flags, hipStream_t st, hipEvent_t *ev) {
+    const int B = p.B, H = p.H, W = p.W;
+    Marks m{st, ev};
+    m.at(S2_MASK);
+    launch_mask(p, flags, st);
+    m.at(S2_FRAME);
+    k_frame<<<B, 256, 0, st>>>(p, ((flags & DTFILL_FLAG_GENERAL_ONLY) ? 1 : 0) | 2, 0, 0);
+    m.at(S2_WIN16);
     // dense frames (k_frame's route 16 / 32): windows of 15 x 15 / 31 x 31 around every pixel, the few pixels with no source
     // that near one by one
     const int ttx = (W + W2_TW - 1) / W2_TW, tty = (H + W2_TH - 1) / W2_TH;
-    k_l2win<W2_R16><<<dim3(ttx * tty, B), 256, L2Win<W2_R16>::LDS, st>>>(x, c.srcbits, c.wpre_s, c.rowbase_s, c.finfo, c.vlist, c.xlist,
-                                                                         c.route, 16, c.rowfar, c.fflag2, H, W, Wd, ttx, out_depth, out_dt, out_index, status);
-    mark();
-    k_l2win<W2_R32><<<dim3(ttx * tty, B), 256, L2Win<W2_R32>::LDS, st>>>(x, c.srcbits, c.wpre_s, c.rowbase_s, c.finfo, c.vlist, c.xlist,
-                                                                         c.route, 32, c.rowfar, c.fflag2, H, W, Wd, ttx, out_depth, out_dt, out_index, status);
-    mark();
+    k_l2win<W2_R16><<<dim3(ttx * tty, B), 256, L2Win<W2_R16>::LDS, st>>>(
+        p.x, p.srcbits, p.wpre_s, p.rowbase_s, p.finfo, p.vlist, p.xlist, p.route, 16, p.rowfar, p.fflag2, H, W, p.Wd, ttx, p.out_depth, p.out_dt,
+        p.out_index, p.status);
+    m.at(S2_WIN32);
+    k_l2win<W2_R32><<<dim3(ttx * tty, B), 256, L2Win<W2_R32>::LDS, st>>>(
+        p.x, p.srcbits, p.wpre_s, p.rowbase_s, p.finfo, p.vlist, p.xlist, p.route, 32, p.rowfar, p.fflag2, H, W, p.Wd, ttx, p.out_depth, p.out_dt,
+        p.out_index, p.status);
+    m.at(S2_FAR);
     // one wave per listed pixel: enough blocks per frame for ~16 k waves in the batch
-    k_l2far<<<dim3(min(256, max(16, 4096 / B)), B), 256, 0, st>>>(x, c.srcbits, c.wpre_s, c.rowbase_s, c.finfo, c.vlist, c.xlist, c.route,
-                                                                  c.rowfar, H, W, Wd, out_depth, out_dt, out_index, status);
-    mark();
+    k_l2far<<<dim3(min(256, max(16, 4096 / B)), B), 256, 0, st>>>(p);
+    m.at(S2_COLT);
     // vertical distances per column (k_colT) for the frames that need them: route 0, or a row handed on by k_l2win
-    {
-        const int cw = min(16, max(2, (c.nb + 3) / 4));
-        const size_t lds = colT_lds(c.nb);
-        if (lds > 48 * 1024)
-            ok = ok && hipFuncSetAttribute(reinterpret_cast<const void *>(k_colT), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-        const int fx = cw <= 4, ncb = (c.ctp + 63) / 64;  // (frames along grid x for frames of up to 512 rows: k_colT's comment)
-        k_colT<<<fx ? dim3(B, ncb) : dim3(ncb, B), 64 * cw, lds, st>>>(c.srcbits, c.fflag2, H, W, Wd, c.nb, c.ctp, c.ct, c.wpre_s, c.rowbase_s,
-                                                                        (out_depth || out_index) ? c.rec : nullptr, ncb, SkyArgs{}, fx);
-    }
-    mark();
-    {
-        // the rows, one wave each; then the 32 x 32 tiles of the frames with a handful of sources, one wave each
-        const size_t wave_lds = max(max(l2env_lds(W), (size_t)L2_PTS_MAX * 8), (size_t)(W + 2 * L2S_R) * 8);
-        const int ntile = ((H + PT_T - 1) / PT_T) * ((W + PT_T - 1) / PT_T);
-        if (4 * wave_lds <= 64 * 1024) {
-            const int nrowblk = (H + 3) / 4;
-            k_l2env<4><<<dim3(B, nrowblk + (ntile + 3) / 4), 256, 4 * wave_lds, st>>>(x, c.ct, c.ctp, c.nb, c.rec, Wd, c.finfo, c.vlist, c.route,
-                                                                                  c.rowfar, c.xlist, H, W, nrowblk, wave_lds, 1, out_depth,
-                                                                                  out_dt, out_index, status);
-        } else {
-            if (wave_lds > 48 * 1024)  // rows wider than ~4900 pixels (set per call: the attribute belongs to the current device)
-                ok = ok && hipFuncSetAttribute(reinterpret_cast<const void *>(k_l2env<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    m.ok = launch_colT(p, SkyArgs{}, st) && m.ok;
+    m.at(S2_ENV);
+    // the rows, one wave each; then the 32 x 32 tiles of the frames with a handful of sources, one wave each
+    const size_t wave_lds = max(max(l2env_lds(W), (size_t)L2_PTS_MAX * 8), (size_t)(W + 2 * L2S_R) * 8);
+    const int ntile = ((H + PT_T - 1) / PT_T) * ((W + PT_T - 1) / PT_T);
+    if (4 * wave_lds <= 64 * 1024) {
+        const int nrowblk = (H + 3) / 4;
+        k_l2env<4><<<dim3(B, nrowblk + (ntile + 3) / 4), 256, 4 * wave_lds, st>>>(p.x, p.ct, p.ctp, p.nb, p.rec, p.Wd, p.finfo, p.vlist, p.route,
+                                                                                  p.rowfar, p.srclist(), H, W, nrowblk, wave_lds, 1, p.out_depth,
+                                                                                  p.out_dt, p.out_index, p.status);
+    } else {
+        if (wave_lds > 48 * 1024)  // rows wider than ~4900 pixels (set per call: the attribute belongs to the current device)
+            m.ok = m.ok && hipFuncSetAttribute(reinterpret_cast<const void *>(k_l2env<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                (int)l2env_lds(8192)) == hipSuccess;
-            k_l2env<1><<<dim3(B, H + (ntile + 7) / 8), 64, wave_lds, st>>>(x, c.ct, c.ctp, c.nb, c.rec, Wd, c.finfo, c.vlist, c.route, c.rowfar, c.xlist,
-                                                               H, W, H, wave_lds, 8, out_depth, out_dt, out_index, status);
-        }
+        k_l2env<1><<<dim3(B, H + (ntile + 7) / 8), 64, wave_lds, st>>>(p.x, p.ct, p.ctp, p.nb, p.rec, p.Wd, p.finfo, p.vlist, p.route, p.rowfar,
+                                                                       p.srclist(), H, W, H, wave_lds, 8, p.out_depth, p.out_dt, p.out_index,
+                                                                       p.status);
     }
-    mark();
-    return ok ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+    m.at(NK_L2);
+    return m.ok ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+int run(const Pass &p, int metric, unsigned flags, void *stream, hipEvent_t *ev) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return metric == DTFILL_METRIC_L2 ? run_l2(p, flags, st, ev) : run_l1(p, flags, st, ev);
 }
 
 int check_args(const float *x, int B, int H, int W, int metric, float *out_depth, float *out_dt,
@@ -427,7 +397,9 @@ const char *dtfill_strerror(int code) {
 size_t dtfill_workspace_bytes(int B, int H, int W, int metric) {
     if (!shape_ok(B, H, W)) return 0;
     if (metric != DTFILL_METRIC_L1_CV && metric != DTFILL_METRIC_L2) return 0;
-    return carve(nullptr, B, H, W).total;
+    size_t total = 0;
+    carve(nullptr, B, H, W, &total);
+    return total;
 }
 
 int dtfill_batch_flags(const float *x, int B, int H, int W, float src_thr, float val_thr, int metric,
@@ -435,11 +407,8 @@ int dtfill_batch_flags(const float *x, int B, int H, int W, float src_thr, float
                        void *workspace, size_t ws_bytes, void *stream, unsigned flags) {
     int rc = check_args(x, B, H, W, metric, out_depth, out_dt, out_index, workspace, ws_bytes, flags);
     if (rc != DTFILL_OK) return rc;
-    if (metric == DTFILL_METRIC_L2)
-        return run_l2(x, B, H, W, src_thr, val_thr, out_depth, out_dt, out_index, frame_status, workspace, flags,
-                      static_cast<hipStream_t>(stream), nullptr);
-    return run_l1(x, B, H, W, src_thr, val_thr, out_depth, out_dt, out_index, frame_status, workspace, flags,
-                  static_cast<hipStream_t>(stream), nullptr);
+    return run(make_pass(x, B, H, W, src_thr, val_thr, out_depth, out_dt, out_index, frame_status, workspace), metric, flags, stream,
+               nullptr);
 }
 
 int dtfill_batch(const float *x, int B, int H, int W, float src_thr, float val_thr, int metric,
@@ -457,8 +426,9 @@ int dtfill_batch_epilogue(const float *x, int B, int H, int W, float src_thr, fl
     if (rc != DTFILL_OK) return rc;
     if (depth_row0 < 0 || depth_row0 >= H) return DTFILL_ERR_SHAPE;
     if (metric != DTFILL_METRIC_L1_CV) return (depth_row0 || use_floor) ? DTFILL_ERR_METRIC : dtfill_batch_flags(x, B, H, W, src_thr, val_thr, metric, out_depth, out_dt, out_index, frame_status, workspace, ws_bytes, stream, flags);
-    return run_l1(x, B, H, W, src_thr, val_thr, out_depth, out_dt, out_index, frame_status, workspace, flags,
-                  static_cast<hipStream_t>(stream), nullptr, DepthEpilogue{depth_row0, use_floor ? 1 : 0, floor_});
+    return run(make_pass(x, B, H, W, src_thr, val_thr, out_depth, out_dt, out_index, frame_status, workspace,
+                         DepthEpilogue{depth_row0, use_floor ? 1 : 0, floor_}),
+               metric, flags, stream, nullptr);
 }
 
 int dtfill_outlier_removal(const float *x, int B, int H, int W, float *out, void *stream) {
@@ -514,7 +484,6 @@ int dtfill_batch_timed(const float *x, int B, int H, int W, float src_thr, float
     int rc = check_args(x, B, H, W, metric, out_depth, out_dt, out_index, workspace, ws_bytes, flags);
     if (rc != DTFILL_OK) return rc;
     if (!kernel_ms) return DTFILL_ERR_NULL;
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const int nk = dtfill_num_kernels(metric);
     static_assert(NK_L2 <= NK_L1, "event array");
     hipEvent_t ev[NK_L1 + 1];
@@ -523,10 +492,7 @@ int dtfill_batch_timed(const float *x, int B, int H, int W, float src_thr, float
             while (k-- > 0) (void)hipEventDestroy(ev[k]);  // nothing created so far is left behind
             return DTFILL_ERR_NO_DEVICE;
         }
-    rc = metric == DTFILL_METRIC_L2
-             ? run_l2(x, B, H, W, src_thr, val_thr, out_depth, out_dt, out_index, frame_status, workspace, flags, st, ev)
-             : run_l1(x, B, H, W, src_thr, val_thr, out_depth, out_dt, out_index, frame_status, workspace, flags, st,
-                      ev);
+    rc = run(make_pass(x, B, H, W, src_thr, val_thr, out_depth, out_dt, out_index, frame_status, workspace), metric, flags, stream, ev);
     (void)hipEventSynchronize(ev[nk]);
     for (int k = 0; k < nk; ++k) (void)hipEventElapsedTime(&kernel_ms[k], ev[k], ev[k + 1]);
     for (int k = 0; k <= nk; ++k) (void)hipEventDestroy(ev[k]);
@@ -538,10 +504,9 @@ int dtfill_pass_stats(const void *workspace, size_t ws_bytes, int B, int H, int 
     if (!shape_ok(B, H, W)) return DTFILL_ERR_SHAPE;
     if (metric != DTFILL_METRIC_L1_CV && metric != DTFILL_METRIC_L2) return DTFILL_ERR_METRIC;
     if (ws_bytes < dtfill_workspace_bytes(B, H, W, metric) || ((uintptr_t)workspace & 255)) return DTFILL_ERR_WORKSPACE;
-    const Carve c = carve(const_cast<void *>(workspace), B, H, W);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (hipMemsetAsync(out_px, 0, DTFILL_STATS_N * sizeof(long long), st) != hipSuccess) return DTFILL_ERR_LAUNCH;
-    k_stats<<<B, 256, 0, st>>>(c.route, c.fflag2, c.rowfar, c.finfo, H, W, metric == DTFILL_METRIC_L2 ? 1 : 0, out_px);
+    k_stats<<<B, 256, 0, st>>>(carve(const_cast<void *>(workspace), B, H, W), metric == DTFILL_METRIC_L2 ? 1 : 0, out_px);
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 

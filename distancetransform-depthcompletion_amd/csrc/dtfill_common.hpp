@@ -63,13 +63,44 @@ __device__ __forceinline__ float depth_epilogue(float d, const DepthEpilogue &ep
     return ep.use_floor ? __fadd_rn(fmaxf(__fsub_rn(d, ep.floor_), 0.0f), ep.floor_) : d;
 }
 
-// The per-row flags (l1_cv: "k_fused left a pixel of this row undecided"; l2: far pixels counted by k_l2win) live in the
-// workspace right behind the per-frame flags (carve(): fflag2, then rowfar), so that k_fused needs no pointer of its own
-// for something it touches once in a blue moon.  B = frames of the batch (gridDim.y of every kernel here).
-__host__ __device__ inline size_t rowflag_offset_bytes(int B) { return ((size_t)B * 4 + 255) & ~(size_t)255; }
-__device__ __forceinline__ u32 *rowflag_of(int *fflag, int B) {
-    return reinterpret_cast<u32 *>(reinterpret_cast<char *>(fflag) + rowflag_offset_bytes(B));
-}
+// The pass record: what the kernels of one pass share -- the batch's shape, the input, the outputs and the workspace (carve()
+// in dtfill.hip lays it out).  A kernel that takes it by value only unpacks it into the __restrict__ parameters of its body:
+// clang ignores __restrict__ on struct members, and without it uniform loads can no longer be proven unclobbered.  k_fused,
+// k_rows, k_fin, k_l2win and k_l2env keep positional __restrict__ parameters (their launches unpack the record by name): moved
+// into a forceinline body, the same code comes out with more registers (k_l2win: 51 -> 70 VGPRs, with or without the record).
+struct Pass {
+    int B, H, W;
+    int Wd, Wp;          // 64-pixel words per row; bytes per row of a bit plane (Wd * 8)
+    int nb, ctp;         // 32-row bands per frame, columns per row of ct
+    size_t plane_bytes;  // bytes of one plane
+    const float *x;
+    float src_thr, val_thr;
+    float *out_depth, *out_dt;  // out_dt: the caller's, or (l1_cv with row flags, none from the caller) dscratch for k_sky
+    int32_t *out_index;
+    int *status;                // the caller's frame status, or the workspace's
+    DepthEpilogue ep;
+    // the workspace
+    u64 *srcbits, *valbits;
+    u16 *wpre_s, *wpre_v;
+    u32 *rowcnt_s, *rowcnt_v, *rowbase_s, *rowbase_v;
+    int *finfo, *fflag2;
+    u32 *rowfar;         // per row: l1_cv: k_fused left a pixel undecided (-> k_rows, k_fin, k_tiesx); l2: far pixels (k_l2win -> k_l2far, k_l2env)
+    int *route, *negflag;
+    uint2 *ct;           // k_colT -> k_rows: per 32-row band and column {the band's source bits of the column, distances
+                         // from the band's first / last row to the nearest source above / below}; rows of ctp columns
+    uint4 *rec;          // k_colT -> k_fin, k_l2env: rank records, per 64-pixel word of a row (label_from_rec); null when neither
+                         // labels nor depths are wanted
+    u32 *spix;           // k_rows -> k_fin: per pixel, the frame offset of its nearest source in column kmin (null as rec)
+    float *dscratch;     // k_fin -> k_tiesx: depths of the rows a depth epilogue drops from the output
+    u32 *xlist;          // l1_cv: k_fin -> k_tiesx: the pixels whose chain left their tile; l2: k_l2win -> k_l2far: far pixels
+    // l2, ROUTE_POINTS: k_l2win's idle blocks -> k_l2env: the frame's sources in raster order (such a frame has no far list: its
+    // slice of xlist holds the source list)
+    u32 *srclist() const { return xlist; }
+    u32 *xptr;           // k_fin -> k_tiesx: where each listed pixel's chain goes on
+    u8 *planes;          // k_rows -> k_fin: bit planes d & 1, d >> 1 & 1, d >> 2 & 1, live, tie; k_fin -> k_tiesx: unresolved; Wp bytes per row
+    float *vlist;
+    PtsSrc *ptslist;     // k_frame -> k_pts: the sources of a frame that has a handful (l1_cv, ROUTE_POINTS)
+};
 
 // row flag f of a frame whose sky is / is not k_sky's: is the row one of the any-distance kernels'?
 __device__ __forceinline__ bool row_is_anydist(u32 f, int sky_live) { return f == 1u || (f == 2u && !sky_live); }

@@ -124,7 +124,7 @@ __device__ __forceinline__ bool fused_walk_epilogue(
     int W, int th, int tw, int r0, int c0, int wr0, int wc0, int sh, const float *__restrict__ x,
     const float *__restrict__ vlist,
     int *__restrict__ finfo, float *__restrict__ out_depth, float *__restrict__ out_dt,
-    int32_t *__restrict__ out_index, int *__restrict__ frame_status, const DepthEpilogue ep, int *__restrict__ fflag) {
+    int32_t *__restrict__ out_index, int *__restrict__ frame_status, const DepthEpilogue ep, u32 *__restrict__ rowflag) {
     // ---- P3: tile pixels: walk to the source, d, rank -> label, gather, store.  Each lane walks F_EB
     // pixels in lock-step (their LDS reads are independent, so the hop latencies overlap) and then has
     // F_EB global gathers in flight together.
@@ -275,7 +275,6 @@ __device__ __forceinline__ bool fused_walk_epilogue(
     // same values again).  With a depth epilogue the whole frame is (its chains may end on finished pixels whose stored
     // depth is already cropped / floored).  Rare, so a wave that met one looks for its rows only now (s_par is still there).
     if (any && !EPI) {
-        u32 *rowflag = rowflag_of(fflag, (int)gridDim.x);  // the workspace keeps the row flags right behind the frame flags (gridDim.x = frames)
         for (int L = threadIdx.x; L < nslots; L += NT) {  // the slots this thread walked above
             const int g = L / tw, tc = L - g * tw;
             for (int tr = g * F_EB; tr < min(g * F_EB + F_EB, th); ++tr)
@@ -302,7 +301,7 @@ __device__ __forceinline__ void fused_body(bool premarked,
     const u32 *__restrict__ rowbase_s, int *__restrict__ finfo, const float *__restrict__ vlist,
     int H, int W, int Wd, int nty, int TW, int tiles_x, float *__restrict__ out_depth,
     float *__restrict__ out_dt, int32_t *__restrict__ out_index,
-    int *__restrict__ fflag, int *__restrict__ frame_status, const DepthEpilogue ep, u32 *__restrict__ s_ring, uint2 *__restrict__ s_rw,
+    int *__restrict__ fflag, u32 *__restrict__ rowfar, int *__restrict__ frame_status, const DepthEpilogue ep, u32 *__restrict__ s_ring, uint2 *__restrict__ s_rw,
     short *__restrict__ s_tab, u32 (*__restrict__ s_any)[F_NT / 64]) {
     const int tid = threadIdx.x;
     // (frames along x, tiles along y: the tiles beyond a frame's own tiling, which exit, are dispatched after every working block)
@@ -320,7 +319,7 @@ __device__ __forceinline__ void fused_body(bool premarked,
         // k_frame handed rows of this frame to the any-distance kernels up front (the empty sky): the tile shrinks to the span
         // of its rows that are still this kernel's; a tile without any is done.  (A row another block marks meanwhile is
         // redone whole as well: whether this block still stores its part of it does not matter.)
-        const u32 *rowflag = rowflag_of(fflag, (int)gridDim.x) + (size_t)b * H;
+        const u32 *rowflag = rowfar + (size_t)b * H;
         if (tid == 0) {
             s_any[0][0] = 0xFFFFFFFFu;
             s_any[0][1] = 0u;
@@ -563,7 +562,7 @@ __device__ __forceinline__ void fused_body(bool premarked,
     __syncthreads();
 
     const bool overflow = fused_walk_epilogue<FR, F_NT, EPI, STREAM>(s_par, s_tab, s_rw, b, H, W, th, tw, r0, c0, wr0, wc0, sh, x, vlist,
-                                                        finfo, out_depth, out_dt, out_index, frame_status, ep, fflag);
+                                                        finfo, out_depth, out_dt, out_index, frame_status, ep, rowfar);
     if (overflow && (threadIdx.x & 63) == 0) {  // wave-uniform
         // 1: the rows marked in rowflag, 2: the whole frame.  Same-value race: every writer of a frame stores the same value,
         // the any-distance kernels read it after this kernel
@@ -588,7 +587,7 @@ __global__ __launch_bounds__(F_NT, 4) void k_fused(
     const u32 *__restrict__ rowbase_s, int *__restrict__ finfo, const float *__restrict__ vlist,
     int H, int W, int Wd, FusedTiles t16, FusedTiles t32, float *__restrict__ out_depth,
     float *__restrict__ out_dt, int32_t *__restrict__ out_index,
-    const int *__restrict__ route, int *__restrict__ fflag, int *__restrict__ frame_status, const DepthEpilogue ep) {
+    const int *__restrict__ route, int *__restrict__ fflag, u32 *__restrict__ rowfar, int *__restrict__ frame_status, const DepthEpilogue ep) {
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[F_LDS];
     u32 *s_ring = reinterpret_cast<u32 *>(s_raw);  // later: s_par bytes
     // per window row, the eight image-aligned 32-pixel half words it touches: {source bits, sources before them
@@ -603,7 +602,7 @@ __global__ __launch_bounds__(F_NT, 4) void k_fused(
     const bool epi = ep.row0 != 0 || ep.use_floor;  // uniform: the plain pass runs code compiled without the epilogue
 #define FUSED_CALL(FR_, EPI_, T_)                                                                                        \
     fused_body<FR_, EPI_, STREAM && !(EPI_)>(pre, x, srcbits, wpre_s, rowbase_s, finfo, vlist, H, W, Wd, T_.nty, T_.TW, T_.tiles_x, out_depth, out_dt, \
-                          out_index, fflag, frame_status, ep, s_ring, s_rw, s_tab, s_any)
+                          out_index, fflag, rowfar, frame_status, ep, s_ring, s_rw, s_tab, s_any)
     if (r == 16 && (int)blockIdx.y < t16.ntiles) {
         if (epi)
             FUSED_CALL(16, true, t16);

@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void k_l2win(const float *__restrict__ x, cons
         // a frame with a handful of sources (ROUTE_POINTS): this launch's blocks, idle for it, write the list of its sources in
         // raster order (list index = label - 1; pixel offsets) for l2pts_tile -- each block a share of the frame's bit words
         if (R == W2_R32 && route[b] == ROUTE_POINTS) {  // (compiled into the route-32 instance only: the other one is the hot one)
-            u32 *srclist = xlist;  // such a frame has no far list: its slice of that buffer holds the source list
+            u32 *srclist = xlist;  // (Pass::srclist) such a frame has no far list: its slice of that buffer holds the source list
             const int nwords = H * Wd, per = (nwords + (int)gridDim.x - 1) / (int)gridDim.x;
             u32 *sl = srclist + (size_t)b * H * W;
             for (int w = (int)blockIdx.x * per + (int)threadIdx.x; w < min(nwords, ((int)blockIdx.x + 1) * per); w += 256) {
@@ -672,17 +672,11 @@ __device__ __forceinline__ void l2sky_row(const float *__restrict__ x, const uin
 // ------------------------------------------------------------------------------------------------
 // k_l2far: the far list of the window-kernel frames (l2far_list), one wave per listed pixel.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_l2far(const float *__restrict__ x, const u64 *__restrict__ srcbits,
-                                               const u16 *__restrict__ wpre_s, const u32 *__restrict__ rowbase_s,
-                                               const int *__restrict__ finfo, const float *__restrict__ vlist,
-                                               const u32 *__restrict__ xlist, const int *__restrict__ route,
-                                               const u32 *__restrict__ rowfar, int H, int W, int Wd,
-                                               float *__restrict__ out_depth, float *__restrict__ out_dt,
-                                               int32_t *__restrict__ out_index, int *__restrict__ frame_status) {
+__global__ __launch_bounds__(256) void k_l2far(const Pass p) {
     const int b = blockIdx.y;
-    if (route[b] != 0)
-        l2far_list(x, srcbits, wpre_s, rowbase_s, finfo, vlist, xlist, rowfar, b, (int)blockIdx.x, (int)gridDim.x, H, W, Wd, out_depth, out_dt,
-                   out_index, frame_status);
+    if (p.route[b] != 0)
+        l2far_list(p.x, p.srcbits, p.wpre_s, p.rowbase_s, p.finfo, p.vlist, p.xlist, p.rowfar, b, (int)blockIdx.x, (int)gridDim.x, p.H, p.W,
+                   p.Wd, p.out_depth, p.out_dt, p.out_index, p.status);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -118,10 +118,10 @@ __device__ __forceinline__ bool outlier_at(const float *__restrict__ xf, int H, 
 constexpr int MO_SEG = 2048;  // candidates are listed per segment of this many pixels
 
 template <bool ALL>
-__global__ __launch_bounds__(256) void k_mask_o(const float *__restrict__ x, int H, int W, int Wd, float src_thr, float val_thr,
-                                                u64 *__restrict__ srcbits, u64 *__restrict__ valbits, u16 *__restrict__ wpre_s,
-                                                u16 *__restrict__ wpre_v, u32 *__restrict__ rowcnt_s, u32 *__restrict__ rowcnt_v,
-                                                int *__restrict__ negflag) {
+__device__ __forceinline__ void mask_o_body(const float *__restrict__ x, int H, int W, int Wd, float src_thr, float val_thr,
+                                            u64 *__restrict__ srcbits, u64 *__restrict__ valbits, u16 *__restrict__ wpre_s,
+                                            u16 *__restrict__ wpre_v, u32 *__restrict__ rowcnt_s, u32 *__restrict__ rowcnt_v,
+                                            int *__restrict__ negflag) {
     __shared__ u16 s_list[4][MO_SEG];
     __shared__ u32 s_drop[4][MAX_HW_SUM / 32];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -193,4 +193,9 @@ __global__ __launch_bounds__(256) void k_mask_o(const float *__restrict__ x, int
         rowcnt_s[(size_t)b * H + i] = run_s;
         rowcnt_v[(size_t)b * H + i] = run_v | (mis ? 0x80000000u : 0u);
     }
+}
+template <bool ALL>
+__global__ __launch_bounds__(256) void k_mask_o(const Pass p) {
+    mask_o_body<ALL>(p.x, p.H, p.W, p.Wd, p.src_thr, p.val_thr, p.srcbits, p.valbits, p.wpre_s, p.wpre_v, p.rowcnt_s, p.rowcnt_v,
+                     p.negflag);
 }

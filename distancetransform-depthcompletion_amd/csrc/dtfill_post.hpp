@@ -151,8 +151,8 @@ __global__ __launch_bounds__(64) void k_metrics_final(const double *__restrict__
 // k_stats (dtfill_pass_stats): which kernel family owned how many pixels of the last pass, from the routing state the pass
 // left in the workspace.  One block per frame.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_stats(const int *__restrict__ route, const int *__restrict__ fflag, const u32 *__restrict__ rowfar,
-                                               const int *__restrict__ finfo, int H, int W, int l2, long long *__restrict__ out) {
+__device__ __forceinline__ void stats_body(const int *__restrict__ route, const int *__restrict__ fflag, const u32 *__restrict__ rowfar,
+                                           const int *__restrict__ finfo, int H, int W, int l2, long long *__restrict__ out) {
     const int b = blockIdx.x, tid = threadIdx.x;
     const int rt = route[b], r = rt > 0 ? (rt & 0xFF) : rt, ff = fflag[b];
     const u32 t = w2_row_t(W);
@@ -186,4 +186,7 @@ __global__ __launch_bounds__(256) void k_stats(const int *__restrict__ route, co
         add(DTFILL_STATS_POINTS, r == ROUTE_POINTS ? (long long)H * W : 0);
         add(DTFILL_STATS_COLT, (l2 ? (r == 0 || ff == 1) : (ff == 1 || ff == 2)) ? (long long)H * W : 0);
     }
+}
+__global__ __launch_bounds__(256) void k_stats(const Pass p, int l2, long long *out) {
+    stats_body(p.route, p.fflag2, p.rowfar, p.finfo, p.H, p.W, l2, out);
 }

@@ -19,11 +19,9 @@ __device__ __forceinline__ u32 wave_incl_sum(u32 v, int lane) {
     return v;
 }
 
-__global__ __launch_bounds__(256) void k_mask(const float *__restrict__ x, int H, int W, int Wd,
-                                              float src_thr, float val_thr, u64 *__restrict__ srcbits,
-                                              u64 *__restrict__ valbits, u16 *__restrict__ wpre_s,
-                                              u16 *__restrict__ wpre_v, u32 *__restrict__ rowcnt_s,
-                                              u32 *__restrict__ rowcnt_v) {
+__device__ __forceinline__ void mask_body(const float *__restrict__ x, int H, int W, int Wd, float src_thr, float val_thr,
+                                          u64 *__restrict__ srcbits, u64 *__restrict__ valbits, u16 *__restrict__ wpre_s,
+                                          u16 *__restrict__ wpre_v, u32 *__restrict__ rowcnt_s, u32 *__restrict__ rowcnt_v) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i0 = (blockIdx.x * 4 + wave) * M_RPW, b = blockIdx.y;
     if (i0 >= H) return;
@@ -86,6 +84,9 @@ __global__ __launch_bounds__(256) void k_mask(const float *__restrict__ x, int H
             }
     }
 }
+__global__ __launch_bounds__(256) void k_mask(const Pass p) {
+    mask_body(p.x, p.H, p.W, p.Wd, p.src_thr, p.val_thr, p.srcbits, p.valbits, p.wpre_s, p.wpre_v, p.rowcnt_s, p.rowcnt_v);
+}
 
 // ------------------------------------------------------------------------------------------------
 // k_mask4: the same outputs for rows whose pixels can be read 16 bytes at a time (W % 4 == 0, 16-byte aligned
@@ -116,10 +117,10 @@ __device__ __forceinline__ u64 row_word(u32 nib, int lane) {
 __device__ __forceinline__ bool outlier_at(const float *__restrict__ xf, int H, int W, int i, int j, float v);
 template <int OM, int R>  // R image rows per wave, the loads of all of them in flight before the first is worked on (R = 2 measured no
                           // faster than 1 on the KITTI batch: the kernel is not short of bytes in flight; only R = 1 is launched)
-__global__ __launch_bounds__(256) void k_mask4(const float *__restrict__ x, int H, int W, int Wd, float src_thr,
-                                               float val_thr, u64 *__restrict__ srcbits, u64 *__restrict__ valbits,
-                                               u16 *__restrict__ wpre_s, u16 *__restrict__ wpre_v,
-                                               u32 *__restrict__ rowcnt_s, u32 *__restrict__ rowcnt_v, int *__restrict__ negflag) {
+__device__ __forceinline__ void mask4_body(const float *__restrict__ x, int H, int W, int Wd, float src_thr, float val_thr,
+                                           u64 *__restrict__ srcbits, u64 *__restrict__ valbits, u16 *__restrict__ wpre_s,
+                                           u16 *__restrict__ wpre_v, u32 *__restrict__ rowcnt_s, u32 *__restrict__ rowcnt_v,
+                                           int *__restrict__ negflag) {
     __shared__ u16 s_list[OM ? 4 : 1][OM ? M4_NC * 256 : 1];
     __shared__ u32 s_drop[OM ? 4 : 1][OM ? M4_NC * 8 : 1];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -231,6 +232,11 @@ __global__ __launch_bounds__(256) void k_mask4(const float *__restrict__ x, int 
   }
     if (OM == 1 && __any(neg) && lane == 0) negflag[b] = 1;  // this frame is redone by the exhaustive launch
 }
+template <int OM, int R>
+__global__ __launch_bounds__(256) void k_mask4(const Pass p) {
+    mask4_body<OM, R>(p.x, p.H, p.W, p.Wd, p.src_thr, p.val_thr, p.srcbits, p.valbits, p.wpre_s, p.wpre_v, p.rowcnt_s, p.rowcnt_v,
+                      p.negflag);
+}
 
 // ------------------------------------------------------------------------------------------------
 // k_frame: one workgroup per frame.  Exclusive scan of the row counts = raster rank of the first
@@ -238,16 +244,14 @@ __global__ __launch_bounds__(256) void k_mask4(const float *__restrict__ x, int 
 // boolean compaction x[with_value] (tools.py:24).  The value list is only materialised when the two
 // masks differ somewhere in the frame.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_frame(const float *__restrict__ x, const u64 *__restrict__ valbits,
-                                               const u16 *__restrict__ wpre_v, const u64 *__restrict__ srcbits,
-                                               const u16 *__restrict__ wpre_s, PtsSrc *__restrict__ ptslist,
-                                               const u32 *__restrict__ rowcnt_s,
-                                               const u32 *__restrict__ rowcnt_v, int H, int W, int Wd,
-                                               u32 *__restrict__ rowbase_s, u32 *__restrict__ rowbase_v,
-                                               int *__restrict__ finfo, float *__restrict__ vlist,
-                                               int *__restrict__ fflag2,
-                                               int *__restrict__ route, int *__restrict__ frame_status, int mode, int *__restrict__ negflag,
-                                               u32 *__restrict__ rowfar, int nty16, int nty32) {
+__device__ __forceinline__ void frame_body(const float *__restrict__ x, const u64 *__restrict__ valbits,
+                                           const u16 *__restrict__ wpre_v, const u64 *__restrict__ srcbits,
+                                           const u16 *__restrict__ wpre_s, PtsSrc *__restrict__ ptslist,
+                                           const u32 *__restrict__ rowcnt_s, const u32 *__restrict__ rowcnt_v, int H, int W, int Wd,
+                                           u32 *__restrict__ rowbase_s, u32 *__restrict__ rowbase_v, int *__restrict__ finfo,
+                                           float *__restrict__ vlist, int *__restrict__ fflag2, int *__restrict__ route,
+                                           int *__restrict__ frame_status, int mode, int *__restrict__ negflag,
+                                           u32 *__restrict__ rowfar, int nty16, int nty32) {
     const bool force_general = mode & 1;  // every frame takes the any-distance kernels (tests)
     const bool l2 = mode & 2;             // l2: the window kernel's cost does not grow with the distances it meets
     const bool premark = mode & 4;        // l1_cv without a depth epilogue: rows too far from every source row are handed on up front
@@ -528,6 +532,10 @@ __global__ __launch_bounds__(256) void k_frame(const float *__restrict__ x, cons
             }
         }
     }
+}
+__global__ __launch_bounds__(256) void k_frame(const Pass p, int mode, int nty16, int nty32) {
+    frame_body(p.x, p.valbits, p.wpre_v, p.srcbits, p.wpre_s, p.ptslist, p.rowcnt_s, p.rowcnt_v, p.H, p.W, p.Wd, p.rowbase_s, p.rowbase_v,
+               p.finfo, p.vlist, p.fflag2, p.route, p.status, mode, p.negflag, p.rowfar, nty16, nty32);
 }
 
 // label of the source at (i, j): 1 + number of sources before it in raster order

@@ -140,19 +140,13 @@ __device__ __forceinline__ void colT_block(const u64 *__restrict__ srcbits, cons
 }
 
 struct SkyArgs {  // k_sky's blocks ride behind k_colT's (l1_cv with row flags): see dtfill_sky.hpp
-    const int *finfo;
-    const float *dt_src;
-    float *out_dt, *out_depth;
-    int32_t *out_index;
+    float *out_dt;         // the caller's distance map (they read their base rows from the pass's, which may be dscratch)
     int nstrips, nblocks;  // blocks = strips x row groups; 0: none
 };
 __device__ __forceinline__ void sky_body(unsigned char *s_sky, const int *__restrict__ finfo, int H, int W, const float *dt_src, float *out_dt,
                                          float *out_depth, int32_t *out_index, int strip, int rowgroup, int b);
 
-__global__ __launch_bounds__(1024) void k_colT(const u64 *__restrict__ srcbits, const int *__restrict__ fflag, int H,
-                                               int W, int Wd, int nb, int CTP, uint2 *__restrict__ ct,
-                                               const u16 *__restrict__ wpre_s, const u32 *__restrict__ rowbase_s,
-                                               uint4 *__restrict__ rec, int ncolblocks, const SkyArgs sky, int frames_x) {
+__global__ __launch_bounds__(1024) void k_colT(const Pass p, int ncolblocks, const SkyArgs sky, int frames_x) {
     extern __shared__ __attribute__((aligned(16))) u16 s_lf[];
     __shared__ u64 s_rowword[16][64];
     // frames_x: frames along grid x, a frame's blocks along y -- with a batch of a multiple of eight frames a frame's blocks then run
@@ -162,11 +156,11 @@ __global__ __launch_bounds__(1024) void k_colT(const u64 *__restrict__ srcbits, 
     const int b = frames_x ? blockIdx.x : blockIdx.y, blk = frames_x ? blockIdx.y : blockIdx.x;
     if (blk >= ncolblocks) {  // (block-uniform)
         const int k = blk - ncolblocks;
-        sky_body(reinterpret_cast<unsigned char *>(s_lf), sky.finfo, H, W, sky.dt_src, sky.out_dt, sky.out_depth, sky.out_index, k % sky.nstrips,
+        sky_body(reinterpret_cast<unsigned char *>(s_lf), p.finfo, p.H, p.W, p.out_dt, sky.out_dt, p.out_depth, p.out_index, k % sky.nstrips,
                  k / sky.nstrips, b);
         return;
     }
-    colT_block(srcbits, fflag, H, W, Wd, nb, CTP, ct, wpre_s, rowbase_s, rec, blk, b, s_lf, s_rowword);
+    colT_block(p.srcbits, p.fflag2, p.H, p.W, p.Wd, p.nb, p.ctp, p.ct, p.wpre_s, p.rowbase_s, p.rec, blk, b, s_lf, s_rowword);
 }
 
 __device__ __forceinline__ u32 ffbh_u32(u32 v) {  // position of the highest set bit from the top; 0xFFFFFFFF for 0
@@ -885,11 +879,10 @@ __device__ __forceinline__ void fin_body(
 // ------------------------------------------------------------------------------------------------
 constexpr int XL_BLOCKS = 16;  // blocks per frame (grid-stride over the list)
 
-__global__ __launch_bounds__(256) void k_tiesx(const u8 *__restrict__ unres, int Wp, const int *__restrict__ fflag,
-                                               const int *__restrict__ finfo, const u32 *__restrict__ xlist,
-                                               const u32 *__restrict__ xptr, int H, int W, float *out_depth,
-                                               int32_t *out_index, const DepthEpilogue ep,
-                                               const float *__restrict__ dscratch, const u32 *__restrict__ rowflag) {
+__device__ __forceinline__ void tiesx_body(const u8 *__restrict__ unres, int Wp, const int *__restrict__ fflag,
+                                           const int *__restrict__ finfo, const u32 *__restrict__ xlist, const u32 *__restrict__ xptr,
+                                           int H, int W, float *out_depth, int32_t *out_index, const DepthEpilogue ep,
+                                           const float *__restrict__ dscratch, const u32 *__restrict__ rowflag) {
     const int b = blockIdx.y;
     const int ff = fflag[b];
     if (!ff) return;
@@ -919,4 +912,8 @@ __global__ __launch_bounds__(256) void k_tiesx(const u8 *__restrict__ unres, int
         if (out_depth && q >= dcrop)
             wr_f[fod + q - dcrop] = p >= dcrop ? rd_f[fod + p - dcrop] : depth_epilogue(dscratch[fo + p], ep);
     }
+}
+__global__ __launch_bounds__(256) void k_tiesx(const Pass p) {
+    tiesx_body(p.planes + PL_UNRES * p.plane_bytes, p.Wp, p.fflag2, p.finfo, p.xlist, p.xptr, p.H, p.W, p.out_depth, p.out_index, p.ep,
+               p.dscratch, p.rowfar);
 }
