@@ -22,6 +22,7 @@
 //
 // Kernels of one l1_cv pass (seven launches):
 //   k_mask     source / value bit words + per-row prefix popcounts                    reads x once
+//              (16-byte or dword row loads; with the outlier filter a second launch redoes the frames with a negative value)
 //   k_frame    per-frame row-count scan -> compaction ranks; frame facts; the row structure (first source row, rows too far
 //              from every source row) and with it WHO takes which rows of the frame; value list when the source and value masks
 //              of a frame differ; the source list of a frame that holds a handful
@@ -174,24 +175,22 @@ struct Marks {
     }
 };
 
-// k_mask4 when the rows can be read 16 bytes at a time, k_mask otherwise (same outputs); with DTFILL_FLAG_OUTLIER_REMOVAL the
-// predicates see outlier_removal(x) (k_mask_o, then its exhaustive variant for the frames that hold a negative value)
+// k_mask<OM, VEC>, VEC when the rows can be read 16 bytes at a time.  With DTFILL_FLAG_OUTLIER_REMOVAL the predicates see
+// outlier_removal(x): k_mask<1>, then k_mask<2> redoes the frames that hold a negative value.
 void launch_mask(const Pass &p, unsigned flags, hipStream_t st) {
     const bool vec = (p.W & 3) == 0 && (reinterpret_cast<uintptr_t>(p.x) & 15) == 0;
-    const dim3 g4((p.H + 3) / 4, p.B), g4m(p.B, (p.H + 3) / 4);  // (k_mask4: frames along x)
-    // negflag ("this frame holds a negative value", raised by the first outlier launch, read by the second) starts clear whatever
-    // the workspace held before
-    if (flags & DTFILL_FLAG_OUTLIER_REMOVAL) (void)hipMemsetAsync(p.negflag, 0, (size_t)p.B * sizeof(int), st);
-    if ((flags & DTFILL_FLAG_OUTLIER_REMOVAL) && vec) {
-        k_mask4<1, 1><<<g4m, 256, 0, st>>>(p);
-        k_mask4<2, 1><<<g4m, 256, 0, st>>>(p);
-    } else if (flags & DTFILL_FLAG_OUTLIER_REMOVAL) {
-        k_mask_o<false><<<g4, 256, 0, st>>>(p);
-        k_mask_o<true><<<g4, 256, 0, st>>>(p);
-    } else if (vec)
-        k_mask4<0, 1><<<g4m, 256, 0, st>>>(p);
-    else
-        k_mask<<<dim3((p.H + 4 * M_RPW - 1) / (4 * M_RPW), p.B), 256, 0, st>>>(p);
+    const dim3 g(p.B, (p.H + 3) / 4);  // (frames along x)
+    if (flags & DTFILL_FLAG_OUTLIER_REMOVAL) {
+        // negflag ("this frame holds a negative value", raised by the first launch, read by the second) starts clear whatever
+        // the workspace held before
+        (void)hipMemsetAsync(p.negflag, 0, (size_t)p.B * sizeof(int), st);
+        auto *const filter = vec ? k_mask<1, true> : k_mask<1, false>, *const redo = vec ? k_mask<2, true> : k_mask<2, false>;
+        filter<<<g, 256, 0, st>>>(p);
+        redo<<<g, 256, 0, st>>>(p);
+    } else {
+        auto *const plain = vec ? k_mask<0, true> : k_mask<0, false>;
+        plain<<<g, 256, 0, st>>>(p);
+    }
 }
 
 // waves per k_colT block: two iterations of two bands per wave (fewer, longer waves fit the CUs in one round)

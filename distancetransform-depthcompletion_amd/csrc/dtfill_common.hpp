@@ -50,6 +50,31 @@ __device__ __forceinline__ void tap_decode(int code, int &di, int &dj) {
     }
 }
 
+// outlier_removal() (dtfill_outlier.hpp) as k_outlier and k_mask both apply it: cv2's reflect-101 border ...
+__device__ __forceinline__ int reflect101(int p, int n) {
+    p = p < 0 ? -p : p;
+    return p >= n ? 2 * n - 2 - p : p;
+}
+
+// ... and the decision for one pixel: tap(ti, tj) is the value of the 7 x 7 window's tap in row ti and column tj (0..6, the
+// pixel itself at (3, 3); border already reflected)
+template <class Tap>
+__device__ __forceinline__ bool is_outlier(Tap tap) {
+    float acc = 0.0f;
+    int cnt = 0;
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            if ((i < 3 ? 3 - i : i - 3) + (j < 3 ? 3 - j : j - 3) > 3) continue;  // the 25 taps of the diamond, row-major
+            const float t = tap(i, j);
+            acc = __fadd_rn(acc, t);  // no contraction, no reassociation
+            cnt += t > 0.1f;
+        }
+    }
+    const double mean = (double)acc / ((double)cnt + 0.00001);
+    return ((double)tap(3, 3) - mean) > 1.0;
+}
 
 // What the reference's drivers do to the filled depth right after the fill, folded into the depth stores:
 // rows [row0, H) only (demo.py:292-293: lidar_batch[:, 96:]) and / or the depth floor relu(d - floor) + floor in

@@ -3,98 +3,16 @@
 #pragma once
 
 // ------------------------------------------------------------------------------------------------
-// k_mask: one wave per M_RPW image rows.  Source predicate exactly as tools.py:8, mask = (1.0 - x) > thr
-// (1 = fill, 0 = source); value predicate as tools.py:22, x > thr.  Per 64-pixel word: the two bit
-// words and the row-local exclusive popcount; per row: totals (+ "masks differ" in bit 31).
+// k_mask: one wave per image row.  Source predicate exactly as tools.py:8, mask = (1.0 - x) > thr (1 = fill, 0 = source);
+// value predicate as tools.py:22, x > thr.  Per 64-pixel word: the two bit words and the row-local exclusive popcount; per
+// row: totals (+ "masks differ" in bit 31).  A row is read in chunks of 256 pixels = four words, a batch of chunks in flight:
+//   VEC (W % 4 == 0, 16-byte aligned frames): a lane reads 4 consecutive pixels in one load; its four predicate bits form a
+//        nibble, and the 16 lanes of a DPP row combine theirs into one word.
+//   !VEC: a lane reads pixel 64 q + lane of each of the chunk's four words q; word q is a ballot.
+// Either way the 16 lanes of group lane >> 4 hold word lane >> 4 of the chunk.
 // ------------------------------------------------------------------------------------------------
-constexpr int M_RPW = 1;  // image rows per wave in k_mask
-constexpr int M_KU = 8;   // 64-pixel steps whose loads are issued together (M_KU * M_RPW loads in flight per lane)
-
-__device__ __forceinline__ u32 wave_incl_sum(u32 v, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const u32 t = __shfl_up(v, off);
-        if (lane >= off) v += t;
-    }
-    return v;
-}
-
-__device__ __forceinline__ void mask_body(const float *__restrict__ x, int H, int W, int Wd, float src_thr, float val_thr,
-                                          u64 *__restrict__ srcbits, u64 *__restrict__ valbits, u16 *__restrict__ wpre_s,
-                                          u16 *__restrict__ wpre_v, u32 *__restrict__ rowcnt_s, u32 *__restrict__ rowcnt_v) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i0 = (blockIdx.x * 4 + wave) * M_RPW, b = blockIdx.y;
-    if (i0 >= H) return;
-    u32 run_s[M_RPW], run_v[M_RPW], mis[M_RPW];
-#pragma unroll
-    for (int q = 0; q < M_RPW; ++q) run_s[q] = run_v[q] = mis[q] = 0;
-    // 64 words (4096 pixels) of every row per chunk: lane k ends up holding word k0 + k of each row, so the
-    // words and their prefix counts leave as ONE coalesced store per row and array
-    for (int k0 = 0; k0 < Wd; k0 += 64) {
-        const int nk = min(64, Wd - k0);
-        u64 ws[M_RPW], wv[M_RPW];
-#pragma unroll
-        for (int q = 0; q < M_RPW; ++q) ws[q] = wv[q] = 0;
-        for (int kb = 0; kb < nk; kb += M_KU) {  // M_KU word steps x M_RPW rows: all loads first, then the ballots
-            float v[M_KU][M_RPW];
-#pragma unroll
-            for (int u = 0; u < M_KU; ++u) {
-                const int j = (k0 + kb + u) * 64 + lane;
-#pragma unroll
-                for (int q = 0; q < M_RPW; ++q) {
-                    const int i = min(i0 + q, H - 1);
-                    v[u][q] = (kb + u < nk && j < W) ? x[((size_t)b * H + i) * W + j] : 0.0f;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < M_KU; ++u) {
-                const int k = kb + u;
-                const bool in = k < nk && (k0 + k) * 64 + lane < W;
-#pragma unroll
-                for (int q = 0; q < M_RPW; ++q) {
-                    const u64 sb = __ballot(in && !((1.0f - v[u][q]) > src_thr));
-                    const u64 vb = __ballot(in && (v[u][q] > val_thr));
-                    ws[q] = lane == k ? sb : ws[q];
-                    wv[q] = lane == k ? vb : wv[q];
-                }
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < M_RPW; ++q) {
-            const u32 cs = __popcll(ws[q]), cv = __popcll(wv[q]);
-            const u32 is = wave_incl_sum(cs, lane), iv = wave_incl_sum(cv, lane);
-            mis[q] |= __any(ws[q] != wv[q]) ? 1u : 0u;
-            if (lane < nk && i0 + q < H) {
-                const size_t wi = ((size_t)b * H + i0 + q) * Wd + k0 + lane;
-                srcbits[wi] = ws[q];
-                valbits[wi] = wv[q];
-                wpre_s[wi] = (u16)(run_s[q] + is - cs);
-                wpre_v[wi] = (u16)(run_v[q] + iv - cv);
-            }
-            run_s[q] += __shfl(is, 63);
-            run_v[q] += __shfl(iv, 63);
-        }
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < M_RPW; ++q)
-            if (i0 + q < H) {
-                rowcnt_s[(size_t)b * H + i0 + q] = run_s[q];
-                rowcnt_v[(size_t)b * H + i0 + q] = run_v[q] | (mis[q] ? 0x80000000u : 0u);
-            }
-    }
-}
-__global__ __launch_bounds__(256) void k_mask(const Pass p) {
-    mask_body(p.x, p.H, p.W, p.Wd, p.src_thr, p.val_thr, p.srcbits, p.valbits, p.wpre_s, p.wpre_v, p.rowcnt_s, p.rowcnt_v);
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_mask4: the same outputs for rows whose pixels can be read 16 bytes at a time (W % 4 == 0, 16-byte aligned
-// frames): one wave per row, a lane reads 4 consecutive pixels, 256 pixels = four 64-pixel words per load
-// instruction, and all loads of a row (up to M4_NC at a time) are in flight together.  A lane's four predicate
-// bits form a nibble; the 16 lanes of a DPP row hold one word, combined with four DPP OR steps.
-// ------------------------------------------------------------------------------------------------
-constexpr int M4_NC = 8;  // 256-pixel chunks per batch (2048 pixels)
+constexpr int M4_NC = 8;  // 256-pixel chunks per batch (2048 pixels) with 16-byte loads
+constexpr int M1_NC = 2;  // ... with dword loads (more in flight measured slower without the filter)
 
 template <int CTRL>
 __device__ __forceinline__ u32 dpp_or(u32 v) {  // v | v of the lane CTRL pairs it with (inside a row of 16)
@@ -109,73 +27,83 @@ __device__ __forceinline__ u64 row_word(u32 nib, int lane) {
     const u32 other = (u32)__builtin_amdgcn_update_dpp(0, (int)part, 0x140, 0xF, 0xF, false);  // row_mirror
     return (lane & 8) ? ((u64)part << 32 | other) : ((u64)other << 32 | part);
 }
+// pixel q of the lane in a chunk, counted from the chunk's first pixel
+template <bool VEC>
+__device__ __forceinline__ int chunk_px(int q, int lane) { return VEC ? 4 * lane + q : 64 * q + lane; }
+// word lane >> 4 of the chunk from the lanes' predicate bits (bit q: pixel chunk_px(q, lane))
+template <bool VEC>
+__device__ __forceinline__ u64 chunk_word(u32 nib, int lane) {
+    if (VEC) return row_word(nib, lane);
+    u64 w = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const u64 bq = __ballot((nib >> q) & 1u);
+        w = (lane >> 4) == q ? bq : w;
+    }
+    return w;
+}
+// bit q: pixel chunk_px(q, lane) of the batch's chunk u is removed (s_drop: one bit per pixel of the batch)
+template <bool VEC>
+__device__ __forceinline__ u32 drop_bits(const u32 *s_drop, int u, int lane) {
+    if (VEC) return s_drop[(u << 3) + (lane >> 3)] >> ((4 * lane) & 31);  // the lane's four pixels are adjacent bits of one word
+    u32 d = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) d |= ((s_drop[(u << 3) + 2 * q + (lane >> 5)] >> (lane & 31)) & 1u) << q;
+    return d;
+}
 
 // OM != 0: outlier_removal() (data_read.py:103-128) in front of the predicates, see dtfill_outlier.hpp: the candidates of the
-// 2048 pixels in registers (v > 1.0; every pixel when OM == 2) are listed in LDS, one lane each gathers a candidate's 25 taps,
+// batch's pixels in registers (v > 1.0; every pixel when OM == 2) are listed in LDS, one lane each gathers a candidate's 25 taps,
 // and the pixels it removes read as 0.0f below.  OM == 1 raises negflag[b] on a negative value, the OM == 2 launch redoes
 // exactly those frames.
-__device__ __forceinline__ bool outlier_at(const float *__restrict__ xf, int H, int W, int i, int j, float v);
-template <int OM, int R>  // R image rows per wave, the loads of all of them in flight before the first is worked on (R = 2 measured no
-                          // faster than 1 on the KITTI batch: the kernel is not short of bytes in flight; only R = 1 is launched)
-__device__ __forceinline__ void mask4_body(const float *__restrict__ x, int H, int W, int Wd, float src_thr, float val_thr,
-                                           u64 *__restrict__ srcbits, u64 *__restrict__ valbits, u16 *__restrict__ wpre_s,
-                                           u16 *__restrict__ wpre_v, u32 *__restrict__ rowcnt_s, u32 *__restrict__ rowcnt_v,
-                                           int *__restrict__ negflag) {
+template <int OM, bool VEC>
+__device__ __forceinline__ void mask_body(const float *__restrict__ x, int H, int W, int Wd, float src_thr, float val_thr,
+                                          u64 *__restrict__ srcbits, u64 *__restrict__ valbits, u16 *__restrict__ wpre_s,
+                                          u16 *__restrict__ wpre_v, u32 *__restrict__ rowcnt_s, u32 *__restrict__ rowcnt_v,
+                                          int *__restrict__ negflag) {
     __shared__ u16 s_list[OM ? 4 : 1][OM ? M4_NC * 256 : 1];
     __shared__ u32 s_drop[OM ? 4 : 1][OM ? M4_NC * 8 : 1];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // (frames along grid x: with a batch of a multiple of eight frames a frame's rows are one XCD's, where the window kernel's blocks of
     // that frame will look for its bit words)
-    const int i0 = (blockIdx.y * 4 + wave) * R, b = blockIdx.x;
-    if (i0 >= H) return;
+    const int i = blockIdx.y * 4 + wave, b = blockIdx.x;
+    if (i >= H) return;
     if (OM == 2 && !negflag[b]) return;
     bool neg = false;
     const int w_in_chunk = lane >> 4;  // which of the chunk's four words this lane's row builds
     const int nchunk = (W + 255) >> 8;
-    // rows of at most M4_NC chunks (2048 pixels) with R > 1: the first batch of every row is loaded up front
-    float4 pre[R][M4_NC];
-    if (R > 1) {
-#pragma unroll
-        for (int rr = 0; rr < R; ++rr) {
-            const float4 *rowp = reinterpret_cast<const float4 *>(x + ((size_t)b * H + min(i0 + rr, H - 1)) * W);
-#pragma unroll
-            for (int u = 0; u < M4_NC; ++u) {
-                const int px = (u << 8) + 4 * lane;
-                pre[rr][u] = (u < nchunk && px < W) ? rowp[px >> 2] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            }
-        }
-    }
-#pragma unroll
-  for (int rr = 0; rr < R; ++rr) {
-    const int i = i0 + rr;
-    if (i >= H) break;  // wave-uniform
-    const float4 *row = reinterpret_cast<const float4 *>(x + ((size_t)b * H + i) * W);
+    constexpr int NC = VEC ? M4_NC : M1_NC;
+    const float *row = x + ((size_t)b * H + i) * W;
     const size_t wrow = ((size_t)b * H + i) * Wd;
     u32 run_s = 0, run_v = 0, mis = 0;  // wave-uniform
-    for (int c0 = 0; c0 < nchunk; c0 += M4_NC) {
-        float4 v[M4_NC];
+    for (int c0 = 0; c0 < nchunk; c0 += NC) {
+        float4 v[NC];
 #pragma unroll
-        for (int u = 0; u < M4_NC; ++u) {
-            const int px = ((c0 + u) << 8) + 4 * lane;
-            if (R > 1 && c0 == 0)
-                v[u] = pre[rr][u];
-            else
-                v[u] = (c0 + u < nchunk && px < W) ? row[px >> 2] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        for (int u = 0; u < NC; ++u) {
+            const int px = ((c0 + u) << 8) + chunk_px<VEC>(0, lane);
+            if (VEC) {
+                v[u] = (c0 + u < nchunk && px < W) ? reinterpret_cast<const float4 *>(row)[px >> 2] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            } else {  // W % 4 != 0 may split a lane's pixels: every pixel is tested
+                float f[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) f[q] = (c0 + u < nchunk && px + 64 * q < W) ? row[px + 64 * q] : 0.0f;
+                v[u] = make_float4(f[0], f[1], f[2], f[3]);
+            }
         }
         if (OM) {
             if (lane < M4_NC * 8) s_drop[wave][lane] = 0u;
             int n = 0;  // wave-uniform
 #pragma unroll
-            for (int u = 0; u < M4_NC; ++u) {
+            for (int u = 0; u < NC; ++u) {
                 if (c0 + u >= nchunk) break;
-                const int px = ((c0 + u) << 8) + 4 * lane;
                 const float f[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    neg |= px < W && f[q] < 0.0f;
-                    const bool cand = px < W && (OM == 2 || f[q] > 1.0f);
+                    const bool in = ((c0 + u) << 8) + chunk_px<VEC>(VEC ? 0 : q, lane) < W;
+                    neg |= in && f[q] < 0.0f;
+                    const bool cand = in && (OM == 2 || f[q] > 1.0f);
                     const u64 bal = __ballot(cand);
-                    if (cand) s_list[wave][n + (int)__builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0u))] = (u16)((u << 8) + 4 * lane + q);
+                    if (cand) s_list[wave][n + (int)__builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0u))] = (u16)((u << 8) + chunk_px<VEC>(q, lane));
                     n += __popcll(bal);
                 }
             }
@@ -183,28 +111,30 @@ __device__ __forceinline__ void mask4_body(const float *__restrict__ x, int H, i
             const float *xf = x + (size_t)b * H * W;
             for (int t = lane; t < n; t += 64) {
                 const int jr = s_list[wave][t], j = (c0 << 8) + jr;
-                if (outlier_at(xf, H, W, i, j, xf[(size_t)i * W + j])) atomicOr(&s_drop[wave][jr >> 5], 1u << (jr & 31));
+                const bool drop = is_outlier([&](int ti, int tj) {
+                    return xf[(size_t)reflect101(i + ti - 3, H) * W + reflect101(j + tj - 3, W)];  // neighbouring rows: cache hits
+                });
+                if (drop) atomicOr(&s_drop[wave][jr >> 5], 1u << (jr & 31));
             }
             __builtin_amdgcn_wave_barrier();
         }
 #pragma unroll
-        for (int u = 0; u < M4_NC; ++u) {
+        for (int u = 0; u < NC; ++u) {
             if (c0 + u >= nchunk) break;  // wave-uniform
-            const int px = ((c0 + u) << 8) + 4 * lane;
-            const bool in = px < W;  // W % 4 == 0: a lane's four pixels are inside or outside together
             float f[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
             if (OM) {
-                const u32 d = s_drop[wave][(u << 3) + (lane >> 3)] >> ((4 * lane) & 31);
+                const u32 d = drop_bits<VEC>(s_drop[wave], u, lane);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) f[q] = ((d >> q) & 1u) ? 0.0f : f[q];
             }
             u32 ns = 0, nv = 0;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
+                const bool in = ((c0 + u) << 8) + chunk_px<VEC>(VEC ? 0 : q, lane) < W;  // VEC: a lane's four pixels are inside or outside together
                 ns |= (in && !((1.0f - f[q]) > src_thr)) ? (1u << q) : 0u;
                 nv |= (in && (f[q] > val_thr)) ? (1u << q) : 0u;
             }
-            const u64 ws = row_word(ns, lane), wv = row_word(nv, lane);
+            const u64 ws = chunk_word<VEC>(ns, lane), wv = chunk_word<VEC>(nv, lane);
             const u32 cs = (u32)__popcll(ws), cv = (u32)__popcll(wv);
             // counts of the chunk's four words (every lane of a row holds its word's count)
             const u32 s0 = __builtin_amdgcn_readlane(cs, 0), s1 = __builtin_amdgcn_readlane(cs, 16),
@@ -229,13 +159,12 @@ __device__ __forceinline__ void mask4_body(const float *__restrict__ x, int H, i
         rowcnt_s[(size_t)b * H + i] = run_s;
         rowcnt_v[(size_t)b * H + i] = run_v | (mis ? 0x80000000u : 0u);
     }
-  }
     if (OM == 1 && __any(neg) && lane == 0) negflag[b] = 1;  // this frame is redone by the exhaustive launch
 }
-template <int OM, int R>
-__global__ __launch_bounds__(256) void k_mask4(const Pass p) {
-    mask4_body<OM, R>(p.x, p.H, p.W, p.Wd, p.src_thr, p.val_thr, p.srcbits, p.valbits, p.wpre_s, p.wpre_v, p.rowcnt_s, p.rowcnt_v,
-                      p.negflag);
+template <int OM, bool VEC>
+__global__ __launch_bounds__(256) void k_mask(const Pass p) {
+    mask_body<OM, VEC>(p.x, p.H, p.W, p.Wd, p.src_thr, p.val_thr, p.srcbits, p.valbits, p.wpre_s, p.wpre_v, p.rowcnt_s, p.rowcnt_v,
+                       p.negflag);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -508,7 +437,7 @@ __device__ __forceinline__ void frame_body(const float *__restrict__ x, const u6
         finfo[b * FI_STRIDE + FI_TR0] = (flags && r > 0 && sky_ok) ? r0 : 0;
         const bool marked = flags && r > 0 && (sky || any1);
         route[b] = marked ? (r | ROUTE_PREMARK) : r;
-        negflag[b] = 0;  // k_mask_o's "this frame holds a negative value": consumed before this kernel, reset for the next pass
+        negflag[b] = 0;  // k_mask's "this frame holds a negative value": consumed before this kernel, reset for the next pass
         const bool general = r == 0;
         // 2: the any-distance kernels take the whole frame; 1: the rows flagged 1 (pre-marked here, or by k_fused, or (l2) by
         // k_l2win when it hands a row of far pixels on); 0: nothing for them

@@ -12,8 +12,8 @@ Workspace regions of one pass (include/dtfill.h promises no initialisation contr
 of the same pass reads.  Audited before these tests first ran; no region is read as an index or a count before this pass
 has written it.
   region                         written (this pass)                                  read by
-  srcbits valbits wpre_* rowcnt_* k_mask / k_mask4 / k_mask_o: every word of every row  k_frame, window kernels, k_colT, k_pts, k_l2*
-  negflag                        memset in launch_mask (OUTLIER_REMOVAL), k_frame      second k_mask_o / k_mask4 launch
+  srcbits valbits wpre_* rowcnt_* k_mask: every word of every row                     k_frame, window kernels, k_colT, k_pts, k_l2*
+  negflag                        memset in launch_mask (OUTLIER_REMOVAL), k_frame      second k_mask launch (k_mask<2>)
   rowbase_*                      k_frame, every row                                   every later kernel (ranks)
   finfo (all FI_* fields)        k_frame, every frame; FI_NUNRES = 0, then counted up  k_fused, k_sky, k_fin, k_tiesx (FI_NUNRES
                                  by k_fin / k_pts / k_l2win; FI_SKY cleared by k_fused  bounds the xlist loop), k_l2far, k_stats

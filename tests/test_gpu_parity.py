@@ -881,24 +881,36 @@ def test_tie_regions_and_long_tie_chains(gpu_op, oracle):
 
 
 def test_input_pointer_alignment_does_not_matter(gpu_op, oracle):
-    """The 16-byte-load mask kernel is only used for 16-byte aligned frames with W % 4 == 0; a frame batch that
-    starts 4 bytes into an allocation takes the scalar-load kernel and must give the same maps."""
+    """The 16-byte-load mask kernel (k_mask<., true>) is only used for 16-byte aligned frames with W % 4 == 0; a frame batch
+    that starts 4 bytes into an allocation takes the dword-load layout and must give the same maps.  Every offset also runs
+    the outlier filter (planted outliers, a negative value in frame 1: both launches) and a row of more than 2048 pixels
+    (more than one batch of chunks per row; W = 2301 splits a lane's pixels, W = 2300 is 16-byte aligned at offset 0)."""
     import torch
 
     rng = np.random.default_rng(21)
-    B, H, W = 2, 96, 320
-    x = np.where(rng.random((B, H, W)) < 0.05, rng.uniform(1.0, 80.0, (B, H, W)), 0.0).astype(np.float32)
-    depth, dt, lbl, status = oracle.fill_batch(x, 0.1, 0.1)
-    flat = torch.zeros(B * H * W + 3, dtype=torch.float32, device="cuda:0")
+    cases = []
+    for (B, H, W) in [(2, 96, 320), (2, 24, 2300), (2, 24, 2301)]:
+        x = np.where(rng.random((B, H, W)) < 0.05, rng.uniform(1.0, 80.0, (B, H, W)), 0.0).astype(np.float32)
+        cases.append((x, False, oracle.fill_batch(x, 0.1, 0.1)))
+        xo = x.copy()
+        for b in range(B):
+            xo[b, rng.integers(0, H, 20), rng.integers(0, W, 20)] = 79.0  # far points in front of near neighbourhoods
+        xo[1, rng.integers(0, H), rng.integers(0, W)] = -30.0          # frame 1 takes the exhaustive launch
+        xf = np.stack([oracle.outlier_removal(f) for f in xo])
+        assert (xf != xo).any()
+        cases.append((xo, True, oracle.fill_batch(xf, 0.1, 0.1)))
+    flat = torch.zeros(max(x.size for x, _, _ in cases) + 3, dtype=torch.float32, device="cuda:0")
     for off in (0, 1, 2, 3):
-        view = flat[off:off + B * H * W].view(B, H, W)
-        view.copy_(torch.from_numpy(x))
-        assert view.data_ptr() % 16 == (flat.data_ptr() + 4 * off) % 16
-        poison_op(gpu_op, next(_POISON), view.shape)
-        res = gpu_op.run(view, 0.1, 0.1)
-        torch.cuda.synchronize()
-        assert np.array_equal(res["index"].cpu().numpy(), lbl) and np.array_equal(res["dt"].cpu().numpy(), dt), off
-        assert np.array_equal(res["depth"].cpu().numpy(), depth), off
+        for x, filt, (depth, dt, lbl, status) in cases:
+            view = flat[off:off + x.size].view(x.shape)
+            view.copy_(torch.from_numpy(x))
+            assert view.data_ptr() % 16 == (flat.data_ptr() + 4 * off) % 16
+            poison_op(gpu_op, next(_POISON), view.shape, outlier_removal=filt)
+            res = gpu_op.run(view, 0.1, 0.1, outlier_removal=filt)
+            torch.cuda.synchronize()
+            where = (off, x.shape, filt)
+            assert np.array_equal(res["index"].cpu().numpy(), lbl) and np.array_equal(res["dt"].cpu().numpy(), dt), where
+            assert np.array_equal(res["depth"].cpu().numpy(), depth), where
 
 
 def test_empty_bands_in_dense_frames(gpu_op, oracle):
