@@ -254,7 +254,8 @@ int run_l1(Pass p, unsigned flags, hipStream_t st, hipEvent_t *ev) {
         const bool stream = (W & 31) == 0 && (t16.TW & 31) == 0 && (t32.TW & 31) == 0 && line(p.out_depth) && line(p.out_dt) &&
                             line(p.out_index);
         const dim3 fg(B, max(t16.ntiles, t32.ntiles));  // frames along x: a frame's tiles beyond its own tiling (they exit) come last
-        (stream ? k_fused<true> : k_fused<false>)<<<fg, F_NT, 0, st>>>(p.x, p.srcbits, p.wpre_s, p.rowbase_s, p.finfo, p.vlist, H, W, p.Wd, t16, t32,
+        // the depth epilogue is a template parameter (no streaming stores with it): each instance holds two bodies, not four
+        (epi ? k_fused<false, true> : stream ? k_fused<true, false> : k_fused<false, false>)<<<fg, F_NT, 0, st>>>(p.x, p.srcbits, p.wpre_s, p.rowbase_s, p.finfo, p.vlist, H, W, p.Wd, t16, t32,
                                                                       p.out_depth, p.out_dt, p.out_index, p.route, p.fflag2, p.rowfar, p.status, p.ep);
     }
     m.at(S1_COLT);
@@ -555,6 +556,23 @@ int dtfill_metrics(const float *output, const float *target, int B, long long n,
 }
 
 }  // extern "C"
+
+#ifdef FUSED_PROF
+extern "C" int dtfill_fused_prof(unsigned long long *out16, int reset) {
+    static unsigned long long h[F_PROF_SLOTS][16];
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_fused_prof), sizeof(h)) != hipSuccess) return -1;
+    for (int k = 0; k < 16; ++k) {
+        out16[k] = 0;
+        for (int i = 0; i < F_PROF_SLOTS; ++i) out16[k] += h[i][k];
+    }
+    if (reset) {
+        for (auto &r : h)
+            for (auto &v : r) v = 0;
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_fused_prof), h, sizeof(h)) != hipSuccess) return -1;
+    }
+    return 0;
+}
+#endif
 
 #ifdef PTS_PROF
 extern "C" int dtfill_pts_prof(unsigned long long *out8, int reset) {

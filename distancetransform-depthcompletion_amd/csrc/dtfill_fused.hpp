@@ -101,6 +101,33 @@ __device__ __forceinline__ u32 mul_u24_opaque(u32 a, u32 b) {
     return r;
 }
 
+#ifdef FUSED_PROF  // development probe (scripts/dev/fused_phase_probe.py): cycles per phase summed over the waves, and trip counts
+// one record per wave slot (waves of the grid modulo F_PROF_SLOTS): no atomics contend for a line; the reader sums them
+constexpr int F_PROF_SLOTS = 8192;
+__device__ unsigned long long g_fused_prof[F_PROF_SLOTS][16];
+// per wave: t[k] cycles of phase k (P0 load, P1 levels, P1b backward taps, P2 un-slice, P3 hops, P3 epilogue + stores, tail),
+// n[k] counts (waves, levels run, batches, walkers, -, hop trips (two hops each), -, -)
+struct FusedProf {
+    unsigned long long t[8] = {}, n[8] = {}, tprev = __builtin_readcyclecounter();
+    __device__ void mark(int k) {
+        const unsigned long long t_ = __builtin_readcyclecounter();
+        t[k] += t_ - tprev;
+        tprev = t_;
+    }
+    __device__ void flush() {
+        const int slot = ((blockIdx.y * gridDim.x + blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6)) % F_PROF_SLOTS;
+        if ((threadIdx.x & 63) == 0)
+            for (int k = 0; k < 8; ++k) {
+                atomicAdd(&g_fused_prof[slot][k], t[k]);
+                atomicAdd(&g_fused_prof[slot][8 + k], n[k]);
+            }
+    }
+};
+#define FPROF(...) __VA_ARGS__
+#else
+#define FPROF(...)
+#endif
+
 // the lane's three words of a ring row plus one neighbour word on each side (pads / other half)
 __device__ __forceinline__ void ring_load5(const u32 *__restrict__ ring, int slot, int plane, int row, int wb,
                                            u32 (&a)[5]) {
@@ -124,7 +151,8 @@ __device__ __forceinline__ bool fused_walk_epilogue(
     int W, int th, int tw, int r0, int c0, int wr0, int wc0, int sh, const float *__restrict__ x,
     const float *__restrict__ vlist,
     int *__restrict__ finfo, float *__restrict__ out_depth, float *__restrict__ out_dt,
-    int32_t *__restrict__ out_index, int *__restrict__ frame_status, const DepthEpilogue ep, u32 *__restrict__ rowflag) {
+    int32_t *__restrict__ out_index, int *__restrict__ frame_status, const DepthEpilogue ep, u32 *__restrict__ rowflag
+    FPROF(, FusedProf &prof)) {
     // ---- P3: tile pixels: walk to the source, d, rank -> label, gather, store.  Each lane walks F_EB
     // pixels in lock-step (their LDS reads are independent, so the hop latencies overlap) and then has
     // F_EB global gathers in flight together.
@@ -136,67 +164,68 @@ __device__ __forceinline__ bool fused_walk_epilogue(
     // the depth output may drop the first ep.row0 rows (then frames are H - row0 rows apart)
     float *od = out_depth ? out_depth + (size_t)b * (H - ep.row0) * W : nullptr, *ot = out_dt ? out_dt + fo : nullptr;
     const u32 dcrop = (u32)(ep.row0 * W) << 2;  // bytes of a frame's dropped rows
-    constexpr bool plain = !EPI;  // the plain pass is compiled without the epilogue
     int32_t *oi = out_index ? out_index + fo : nullptr;
     const char *tab = reinterpret_cast<const char *>(s_tab);
+    auto step_of = [&](int c) { return (int)*reinterpret_cast<const short *>(tab + c); };
     const int src_base = wr0 * W + wc0;  // frame offset of window cell (0,0) (may be negative)
     const u32 last_px = (u32)(H * W - 1);
     bool overflow = false;
+    // STREAM (rows of whole 128-byte lines: W % 32 == 0, aligned outputs, tile columns in whole lines): a wave's run of
+    // consecutive tile pixels is whole lines, and nothing of the outputs is read again in this pass -- streaming stores
+    // keep them from pushing the inputs out of the caches.  Otherwise the L2 has to merge the partial lines: plain stores.
+    auto put = [](auto *p, auto v) {
+        if constexpr (STREAM)
+            __builtin_nontemporal_store(v, p);
+        else
+            *p = v;
+    };
     // A lane walks F_EB pixels of ONE column, rows 8 g .. 8 g + 7 of the tile: slot L = sb + tid is (row group g, column) =
     // divmod(L, tw), so the index arithmetic is done once per slot and the F_EB pixels differ by a row pitch each; a wave's store
     // is still a run of 64 consecutive pixels of a row (two runs where the slots wrap into the next group).
-    // Software pipeline: the gathers of one batch stay in flight during the walk of the next batch (LDS only);
-    // a batch's stores are issued just before the next batch's gathers.
+    // Software pipeline: the depth gathers of one batch stay in flight during the walk of the next batch (LDS only);
+    // a batch's depth stores are issued just before the next batch's gathers.  Label and distance are stored at once.
     const int nslots = ((th + F_EB - 1) / F_EB) * tw;
     const float inv_tw = 1.0f / (float)tw;
     const u32 w4 = (u32)W << 2;
-    int p_lab[F_EB], p_dd[F_EB];  // the batch whose gathers are in flight
-    u32 p_opix[F_EB];
-    float p_val[F_EB];
-    u32 p_ok = 0;
+    float p_val[F_EB];  // the batch whose gathers are in flight
+    u32 p_opix = 0, p_ok = 0;
+    bool p_full = false;  // wave-uniform: every walker of that batch is stored
+    // p_opix is a BYTE offset (< 2^32: a frame has < 2^26 pixels): scalar base + 32-bit vector offset
     auto retire = [&]() {
+        if (!od) return;
+        auto st = [&](int e) {
+            const u32 o = p_opix + (u32)e * w4;
+            if constexpr (!EPI)
+                put(reinterpret_cast<float *>(reinterpret_cast<char *>(od) + o), p_val[e]);
+            else if (o >= dcrop)
+                *reinterpret_cast<float *>(reinterpret_cast<char *>(od) + (o - dcrop)) = depth_epilogue(p_val[e], ep);
+        };
+        if (p_full) {
 #pragma unroll
-        for (int e = 0; e < F_EB; ++e) {
-            if (!((p_ok >> e) & 1u)) continue;
-            // p_opix is a BYTE offset (< 2^32: a frame has < 2^26 pixels): scalar base + 32-bit vector offset
-            // STREAM (rows of whole 128-byte lines: W % 32 == 0, aligned outputs, tile columns in whole lines): a wave's run of
-            // consecutive tile pixels is whole lines, and nothing of the outputs is read again in this pass -- streaming stores
-            // keep them from pushing the inputs out of the caches.  Otherwise the L2 has to merge the partial lines: plain stores.
-            auto put = [](auto *p, auto v) {
-                if constexpr (STREAM)
-                    __builtin_nontemporal_store(v, p);
-                else
-                    *p = v;
-            };
-            if (oi) put(reinterpret_cast<int32_t *>(reinterpret_cast<char *>(oi) + p_opix[e]), p_lab[e]);
-            if (ot) put(reinterpret_cast<float *>(reinterpret_cast<char *>(ot) + p_opix[e]), (float)p_dd[e]);
-            if (od && plain) {
-                put(reinterpret_cast<float *>(reinterpret_cast<char *>(od) + p_opix[e]), p_val[e]);
-            } else if (od && p_opix[e] >= dcrop) {  // block-uniform choice: the plain pass pays nothing for the epilogue
-                *reinterpret_cast<float *>(reinterpret_cast<char *>(od) + (p_opix[e] - dcrop)) = depth_epilogue(p_val[e], ep);
-            }
+            for (int e = 0; e < F_EB; ++e) st(e);
+        } else {
+#pragma unroll
+            for (int e = 0; e < F_EB; ++e)
+                if ((p_ok >> e) & 1u) st(e);
         }
     };
     for (int sb = 0; sb < nslots; sb += NT) {
-        int pos[F_EB], code[F_EB];  // pos = row * F_P + col: byte index in s_par
-        u32 home[F_EB];             // window row << 16 | window column of the walker's own pixel
-        u32 opix[F_EB];
-        u32 ok = 0;
+        int pos[F_EB], step[F_EB], code[F_EB];  // pos = row * F_P + col: byte index in s_par
+        u32 ok = 0, home0, opix0;   // home0: window row << 16 | window column of the slot's first pixel
+        FPROF(prof.mark(5); ++prof.n[2]);
         {
             const int L = sb + (int)threadIdx.x, Lc = min(L, nslots - 1);
             // L / tw: (L + 0.5) / tw is at least 0.5 / tw away from an integer, far above float rounding
             // for L < 2^14, tw < 2^8
             const int g = (int)(((float)Lc + 0.5f) * inv_tw);
             const int tc = Lc - __mul24(g, tw), trb = g * F_EB;
-            const u32 home0 = (u32)(FR + trb) << 16 | (u32)(FR + tc);
-            const u32 opix0 = (u32)(__mul24(r0 + trb, W) + c0 + tc) << 2;  // byte offset; 24-bit multiplies are full rate (H, W < 8192)
+            home0 = (u32)(FR + trb) << 16 | (u32)(FR + tc);
+            opix0 = (u32)(__mul24(r0 + trb, W) + c0 + tc) << 2;  // byte offset; 24-bit multiplies are full rate (H, W < 8192)
             const int pos0 = __mul24(FR + trb, F_P) + FR + tc;
             const int nv = L < nslots ? th - trb : 0;  // the slot's rows inside the tile (the rest: still cells of the window, read and dropped)
 #pragma unroll
             for (int e = 0; e < F_EB; ++e) {
                 const bool valid = e < nv;
-                home[e] = home0 + ((u32)e << 16);
-                opix[e] = opix0 + (u32)e * w4;
                 pos[e] = pos0 + e * F_P;
                 code[e] = s_par[pos[e]];
                 ok |= (valid && code[e] != F_NONE) ? (1u << e) : 0u;
@@ -208,29 +237,30 @@ __device__ __forceinline__ bool fused_walk_epilogue(
         // arrived just stays.  No selects, no divergent control flow -- the reads of the F_EB walkers
         // overlap.  Two hops between "everybody arrived?" checks.
         for (int hop = 0; hop < FR + 2; hop += 2) {
-            int step[F_EB];
 #pragma unroll
-            for (int e = 0; e < F_EB; ++e) step[e] = *reinterpret_cast<const short *>(tab + code[e]);
+            for (int e = 0; e < F_EB; ++e) step[e] = step_of(code[e]);
             // everybody arrived? -- asked right after the (cheap, broadcast) table read, so the last trip
             // through the loop costs those 8 reads and not two more full hops
             int moving = 0;
 #pragma unroll
             for (int e = 0; e < F_EB; ++e) moving |= step[e];
             if (!__any(moving != 0)) break;
+            FPROF(++prof.n[5]);
 #pragma unroll
             for (int e = 0; e < F_EB; ++e) pos[e] += step[e];
 #pragma unroll
             for (int e = 0; e < F_EB; ++e) code[e] = s_par[pos[e]];
 #pragma unroll
-            for (int e = 0; e < F_EB; ++e) step[e] = *reinterpret_cast<const short *>(tab + code[e]);
+            for (int e = 0; e < F_EB; ++e) step[e] = step_of(code[e]);
 #pragma unroll
             for (int e = 0; e < F_EB; ++e) pos[e] += step[e];
 #pragma unroll
             for (int e = 0; e < F_EB; ++e) code[e] = s_par[pos[e]];
         }
-        int lab[F_EB], dd[F_EB];
+        FPROF(prof.mark(4); for (int e = 0; e < F_EB; ++e) prof.n[3] += __popcll(__ballot((ok >> e) & 1u)));
+        int pr[F_EB], pc[F_EB];
         u32 goff[F_EB];
-        bool bad = false;
+        int lab[F_EB];
 #pragma unroll
         for (int e = 0; e < F_EB; ++e) {
             // a decided chain ends on a source inside the in-image window
@@ -238,37 +268,56 @@ __device__ __forceinline__ bool fused_walk_epilogue(
             // the quotient, whose fraction is at most 195 / 196: same integer part (three full-rate instructions with the remainder;
             // the integer division is a quarter-rate v_mul_hi_u32)
             static_assert(F_P == 196 && F_WHM * F_P < (1 << 15), "the reciprocal below is F_P's");
-            const int pr_ = (int)(__umul24((u32)pos[e], 5350u) >> 20), pc_ = pos[e] - __mul24(pr_, F_P);
-            // L1 distance to the nearest source IS d: |drow| + |dcol| of the two 16-bit halves in one instruction
-            dd[e] = (int)__builtin_amdgcn_sad_u16((u32)pr_ << 16 | (u32)pc_, home[e], 0u);
-            const int bitpos = sh + pc_;  // bit index in the row's image-aligned bit string, from word w0
-            const uint2 rw = s_rw[pr_ * 8 + (bitpos >> 5)];  // {32 source bits, sources before them in the frame}
-            lab[e] = (int)rw.y + __popc(rw.x & ((1u << (bitpos & 31)) - 1u)) + 1;
-            // depth_list[label-1] (tools.py:26).  A decided pixel has label >= 1, so the numpy wrap of index -1
-            // cannot occur here.  Masks agree (block-uniform): the label-th value is x at the source, and
-            // label <= nsrc = nval.  Masks differ: an index past the value list is numpy's IndexError.
-            // The min only makes sure that a logic error could never become a wild global access (an LDS index
-            // out of range reads garbage at worst).
-            if (!misaligned) {
-                goff[e] = min((u32)(src_base + __mul24(pr_, W) + pc_), last_px) << 2;  // byte offset
-            } else {
+            pr[e] = (int)(__umul24((u32)pos[e], 5350u) >> 20);
+            pc[e] = pos[e] - __mul24(pr[e], F_P);
+            const int bitpos = sh + pc[e];  // bit index in the row's image-aligned bit string, from word w0
+            const uint2 rw = s_rw[pr[e] * 8 + (bitpos >> 5)];  // {32 source bits, 1 + sources before them in the frame}
+            lab[e] = (int)rw.y + __popc(rw.x & ((1u << (bitpos & 31)) - 1u));
+        }
+        // depth_list[label-1] (tools.py:26).  A decided pixel has label >= 1, so the numpy wrap of index -1
+        // cannot occur here.  Masks agree (block-uniform): the label-th value is x at the source, and
+        // label <= nsrc = nval.  Masks differ: an index past the value list is numpy's IndexError.
+        // The min only makes sure that a logic error could never become a wild global access (an LDS index
+        // out of range reads garbage at worst).
+        if (!misaligned) {
+#pragma unroll
+            for (int e = 0; e < F_EB; ++e) goff[e] = min((u32)(src_base + __mul24(pr[e], W) + pc[e]), last_px) << 2;  // byte offset
+        } else {
+            bool bad = false;
+#pragma unroll
+            for (int e = 0; e < F_EB; ++e) {
                 const int idx = lab[e] - 1;
                 const bool oob = idx >= nval;
                 bad |= ((ok >> e) & 1u) && oob;
                 goff[e] = (oob ? 0u : min((u32)idx, last_px)) << 2;
             }
+            if (bad && out_depth) atomicOr(frame_status + b, DTFILL_FRAME_INDEX_ERROR);
         }
-        if (bad && out_depth) atomicOr(frame_status + b, DTFILL_FRAME_INDEX_ERROR);
         retire();  // the previous batch: its gathers had the whole walk above to arrive
 #pragma unroll
-        for (int e = 0; e < F_EB; ++e) {
-            p_val[e] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(gbase) + goff[e]);
-            p_lab[e] = lab[e];
-            p_dd[e] = dd[e];
-            p_opix[e] = opix[e];
-        }
+        for (int e = 0; e < F_EB; ++e) p_val[e] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(gbase) + goff[e]);
+        p_opix = opix0;
         p_ok = ok;
+        p_full = __all(ok == (1u << F_EB) - 1u);
+        if (oi || ot) {
+            auto st = [&](int e) {
+                const u32 o = opix0 + (u32)e * w4;
+                if (oi) put(reinterpret_cast<int32_t *>(reinterpret_cast<char *>(oi) + o), lab[e]);
+                // L1 distance to the nearest source IS d: |drow| + |dcol| of the two 16-bit halves in one instruction
+                if (ot) put(reinterpret_cast<float *>(reinterpret_cast<char *>(ot) + o),
+                            (float)__builtin_amdgcn_sad_u16((u32)pr[e] << 16 | (u32)pc[e], home0 + ((u32)e << 16), 0u));
+            };
+            if (p_full) {
+#pragma unroll
+                for (int e = 0; e < F_EB; ++e) st(e);
+            } else {
+#pragma unroll
+                for (int e = 0; e < F_EB; ++e)
+                    if ((ok >> e) & 1u) st(e);
+            }
+        }
     }
+    FPROF(prof.mark(5));
     retire();
     const bool any = __any(overflow);  // wave-uniform
     // The rows with an undecided pixel are redone by the any-distance kernels (every pixel of them; the decided ones get the
@@ -335,6 +384,7 @@ __device__ __forceinline__ void fused_body(bool premarked,
         r0 += (int)lo;
         th = (int)(hi - lo);
     }
+    FPROF(FusedProf prof; prof.n[0] = 1);
     const int wr0 = r0 - FR, wc0 = c0 - FR;  // image coords of window cell (0,0)
     const int WH = th + 2 * FR, WW = tw + 2 * FR;
     const int ca = max(0, -wc0), cb = min(WW, W - wc0);  // in-image window columns [ca, cb)
@@ -371,8 +421,8 @@ __device__ __forceinline__ void fused_body(bool premarked,
             // if half 1 starts later), half 1 the rest
             const bool mine = hf == 0 ? kk < 2 : (kk >= 2 && kk < 4);
             if (mine) {
-                s_rw[r * 8 + 2 * kk] = make_uint2((u32)sb, rk);
-                s_rw[r * 8 + 2 * kk + 1] = make_uint2((u32)(sb >> 32), rk + (u32)__popc((u32)sb));
+                s_rw[r * 8 + 2 * kk] = make_uint2((u32)sb, rk + 1u);
+                s_rw[r * 8 + 2 * kk + 1] = make_uint2((u32)(sb >> 32), rk + 1u + (u32)__popc((u32)sb));
             }
         }
         g[6] = 0;
@@ -415,12 +465,14 @@ __device__ __forceinline__ void fused_body(bool premarked,
 #pragma unroll
     for (int i = 0; i < F_HW; ++i) Dup[i] = Ddn[i] = 0;
     __syncthreads();
+    FPROF(prof.mark(0));
 
     // ---- P1: levels.  Per level: E_t (dilation), L_t (forward taps, winners recorded), d mod 8 planes.
     u32 P0[F_HW], P1[F_HW], P2[F_HW];  // bits 0..2 of the level at which a pixel was decided (sources: 0)
 #pragma unroll
     for (int i = 0; i < F_HW; ++i) P0[i] = P1[i] = P2[i] = 0;
     for (int t = 1; t <= FR; ++t) {
+        FPROF(++prof.n[1]);
         const int s1 = (t - 1) & 3, s2 = (t - 2) & 3, s3 = (t - 3) & 3, sw = t & 3;
         u32 nb[5], e1[5], l1[5], taken[F_HW], Et[F_HW], Lt[F_HW];
         // dilation of D_{t-1}: left/right in registers (+ the neighbour words), up/down through E_{t-1}
@@ -493,6 +545,7 @@ __device__ __forceinline__ void fused_body(bool premarked,
             if (any != 3u) break;
         }
     }
+    FPROF(prof.mark(1));
     // ---- P1b: the backward taps of ALL levels in one pass (pixels that are decided but not live).  The d mod 8
     // planes and D go through the ring's memory (slots 0 and 1; its guard rows and pad words are still zero).
     __syncthreads();  // every wave is out of the level loop: the ring is dead
@@ -536,6 +589,7 @@ __device__ __forceinline__ void fused_body(bool premarked,
     // ---- P2: un-slice the code planes of this half row into bytes (2 * enc), 8 pixels per step: a byte of a plane goes
     // through the table above (one 8-byte LDS read), two shift-ors put it into its bit of the eight bytes.  Undecided pixels
     // (not in D) get every plane bit: 2 * 63 = F_NONE.
+    FPROF(prof.mark(2));
     u8 *s_par = reinterpret_cast<u8 *>(s_ring);
     __syncthreads();  // the ring is dead for everybody before its memory becomes s_par
     {
@@ -560,15 +614,17 @@ __device__ __forceinline__ void fused_body(bool premarked,
         }
     }
     __syncthreads();
+    FPROF(prof.mark(3));
 
     const bool overflow = fused_walk_epilogue<FR, F_NT, EPI, STREAM>(s_par, s_tab, s_rw, b, H, W, th, tw, r0, c0, wr0, wc0, sh, x, vlist,
-                                                        finfo, out_depth, out_dt, out_index, frame_status, ep, rowfar);
+                                                        finfo, out_depth, out_dt, out_index, frame_status, ep, rowfar FPROF(, prof));
     if (overflow && (threadIdx.x & 63) == 0) {  // wave-uniform
         // 1: the rows marked in rowflag, 2: the whole frame.  Same-value race: every writer of a frame stores the same value,
         // the any-distance kernels read it after this kernel
         fflag[b] = EPI ? 2 : 1;
         atomicOr(frame_status + b, DTFILL_FRAME_GENERAL_PATH);
     }
+    FPROF(prof.mark(6); prof.flush());
 }
 
 // k_fused: one launch for both halos.  route[b] (k_frame): 16 / 32 = the halo that is expected to decide every pixel of
@@ -581,7 +637,7 @@ constexpr size_t F_OFF_RW = (sizeof(u32) * F_RING + 15) & ~(size_t)15, F_OFF_TAB
                  F_LDS_OWN = F_OFF_ANY + sizeof(u32) * 2 * (F_NT / 64);
 constexpr size_t F_LDS = F_LDS_OWN;
 
-template <bool STREAM>
+template <bool STREAM, bool EPI>
 __global__ __launch_bounds__(F_NT, 4) void k_fused(
     const float *__restrict__ x, const u64 *__restrict__ srcbits, const u16 *__restrict__ wpre_s,
     const u32 *__restrict__ rowbase_s, int *__restrict__ finfo, const float *__restrict__ vlist,
@@ -590,7 +646,7 @@ __global__ __launch_bounds__(F_NT, 4) void k_fused(
     const int *__restrict__ route, int *__restrict__ fflag, u32 *__restrict__ rowfar, int *__restrict__ frame_status, const DepthEpilogue ep) {
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[F_LDS];
     u32 *s_ring = reinterpret_cast<u32 *>(s_raw);  // later: s_par bytes
-    // per window row, the eight image-aligned 32-pixel half words it touches: {source bits, sources before them
+    // per window row, the eight image-aligned 32-pixel half words it touches: {source bits, 1 + sources before them
     // in frame raster order} -- one 8-byte LDS read and a 32-bit popcount per rank lookup
     uint2 *s_rw = reinterpret_cast<uint2 *>(s_raw + F_OFF_RW);
     short *s_tab = reinterpret_cast<short *>(s_raw + F_OFF_TAB);  // s_par displacement of the step enc (0 for the codes that are no step)
@@ -599,20 +655,13 @@ __global__ __launch_bounds__(F_NT, 4) void k_fused(
     if (rt == ROUTE_POINTS) return;  // a frame with a handful of sources: k_pts's tiles ride in k_fin's launch (dtfill_pts.hpp)
     const int r = rt > 0 ? (rt & 0xFF) : 0;
     const bool pre = rt > 0 && (rt & ROUTE_PREMARK);
-    const bool epi = ep.row0 != 0 || ep.use_floor;  // uniform: the plain pass runs code compiled without the epilogue
-#define FUSED_CALL(FR_, EPI_, T_)                                                                                        \
-    fused_body<FR_, EPI_, STREAM && !(EPI_)>(pre, x, srcbits, wpre_s, rowbase_s, finfo, vlist, H, W, Wd, T_.nty, T_.TW, T_.tiles_x, out_depth, out_dt, \
+    // EPI (a depth epilogue: ep.row0 != 0 || ep.use_floor) is chosen on the host: the plain pass runs code compiled without it
+#define FUSED_CALL(FR_, T_)                                                                                        \
+    fused_body<FR_, EPI, STREAM>(pre, x, srcbits, wpre_s, rowbase_s, finfo, vlist, H, W, Wd, T_.nty, T_.TW, T_.tiles_x, out_depth, out_dt, \
                           out_index, fflag, rowfar, frame_status, ep, s_ring, s_rw, s_tab, s_any)
-    if (r == 16 && (int)blockIdx.y < t16.ntiles) {
-        if (epi)
-            FUSED_CALL(16, true, t16);
-        else
-            FUSED_CALL(16, false, t16);
-    } else if (r == 32 && (int)blockIdx.y < t32.ntiles) {
-        if (epi)
-            FUSED_CALL(32, true, t32);
-        else
-            FUSED_CALL(32, false, t32);
-    }
+    if (r == 16 && (int)blockIdx.y < t16.ntiles)
+        FUSED_CALL(16, t16);
+    else if (r == 32 && (int)blockIdx.y < t32.ntiles)
+        FUSED_CALL(32, t32);
 #undef FUSED_CALL
 }
