@@ -11,7 +11,7 @@ or through the `dtfill_amd` alias module at the repository root.
 from . import _lib
 from ._lib import METRICS, DtfillError, build, load
 from .sharding import shard_range, gather_frames, fill_sharded, release_host_slab
-from .tools import DT_complete_batch, Distance_Transform, generate_multi_channel, nearest_point, outlier_removal
+from .tools import DT_complete_batch, Distance_Transform, generate_multi_channel, nearest_point, outlier_removal, subsample_lidar
 from .postfill import Result, Result_NYU, depth_floor, depth_to_png16, kitti_rows, nyu_eval_crop
 
 
@@ -26,7 +26,8 @@ def __getattr__(name):
 
 
 __all__ = [
-    "nearest_point", "DT_complete_batch", "Distance_Transform", "outlier_removal", "generate_multi_channel", "fill", "DtFill",
+    "nearest_point", "DT_complete_batch", "Distance_Transform", "outlier_removal", "generate_multi_channel", "subsample_lidar",
+    "fill", "DtFill",
     "shard_range", "gather_frames", "fill_sharded", "release_host_slab", "build", "load", "METRICS", "DtfillError",
     "Result", "Result_NYU", "depth_floor", "depth_to_png16", "kitti_rows", "nyu_eval_crop",
 ]

@@ -21,6 +21,9 @@ FRAME_GENERAL_PATH = 2  # bit, informational
 FLAG_GENERAL_ONLY = 1
 FLAG_FUSED_ONLY = 2
 FLAG_OUTLIER_REMOVAL = 4  # outlier_removal() (data_read.py:103-128) in front of the predicates
+LINES_NO_POINTS = 1  # bit: no valid pixel in the frame (DTFILL_LINES_*)
+LINES_BAD_INTERVAL = 2  # bit: the pitch interval is 0 or not finite
+LINES_SINGULAR = 4  # bit: K or E is singular
 PATHS = {"auto": 0, "general": FLAG_GENERAL_ONLY, "fused": FLAG_FUSED_ONLY}
 
 # every symbol include/dtfill.h declares (tests/test_abi.py checks the .so exports exactly these)
@@ -39,6 +42,8 @@ SYMBOLS = (
     "dtfill_generate_multi_channel",
     "dtfill_crop_floor",
     "dtfill_png16",
+    "dtfill_line_subsample_workspace_bytes",
+    "dtfill_line_subsample",
     "dtfill_metrics_workspace_bytes",
     "dtfill_metrics",
 )
@@ -108,6 +113,10 @@ def load():
     L.dtfill_crop_floor.restype = ci
     L.dtfill_png16.argtypes = [vp, ci, ci, ci, ci, ci, cf, cf, cf, cf, vp, vp]
     L.dtfill_png16.restype = ci
+    L.dtfill_line_subsample_workspace_bytes.argtypes = [ci, ci, ci]
+    L.dtfill_line_subsample_workspace_bytes.restype = sz
+    L.dtfill_line_subsample.argtypes = [vp, ci, ci, ci, vp, vp, ci, ci, vp, vp, vp, sz, vp]
+    L.dtfill_line_subsample.restype = ci
     L.dtfill_metrics_workspace_bytes.argtypes = [ci]
     L.dtfill_metrics_workspace_bytes.restype = sz
     L.dtfill_metrics.argtypes = [vp, vp, ci, ctypes.c_longlong, ci, vp, vp, sz, vp]

@@ -77,6 +77,7 @@ namespace {
 #include "dtfill_outlier.hpp"
 #include "dtfill_gmc.hpp"
 #include "dtfill_post.hpp"
+#include "dtfill_lines.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -377,6 +378,16 @@ int check_args(const float *x, int B, int H, int W, int metric, float *out_depth
 
 }  // namespace
 
+// dtfill_line_subsample: tiles of LS_TILE pixels per frame, split evenly over at most LS_MAXNB blocks per frame
+struct LinesGrid {
+    int tpb, nb;  // tiles per block, blocks per frame
+};
+inline LinesGrid lines_grid(int H, int W) {
+    const int T = (int)(((long long)H * W + LS_TILE - 1) / LS_TILE);
+    const int tpb = (T + LS_MAXNB - 1) / LS_MAXNB;
+    return LinesGrid{tpb, (T + tpb - 1) / tpb};
+}
+
 extern "C" {
 
 int dtfill_abi_version(void) { return DTFILL_ABI_VERSION; }
@@ -529,6 +540,35 @@ int dtfill_png16(const float *x, int B, int H, int W, int pad_top, int use_floor
         return DTFILL_ERR_SHAPE;
     k_png16<<<dim3(min((W + 255) / 256, 8), H + pad_top, B), 256, 0, static_cast<hipStream_t>(stream)>>>(
         x, H, W, pad_top, use_floor, floor_, lo, hi, scale, out);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+size_t dtfill_line_subsample_workspace_bytes(int B, int H, int W) {
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long long)B * H * W >= (1ll << 31)) return 0;
+    return align256((size_t)B * LS_REC * sizeof(double)) + align256((size_t)B * lines_grid(H, W).nb * sizeof(double2));
+}
+
+int dtfill_line_subsample(const float *x, int B, int H, int W, const double *K, const double *E, int n_bins, int keep_every,
+                          float *out, int32_t *frame_status, void *workspace, size_t ws_bytes, void *stream) {
+    if (!x || !K || !E || !out || !frame_status || !workspace || n_bins < 1 || keep_every < 1) return DTFILL_ERR_NULL;
+    const size_t need = dtfill_line_subsample_workspace_bytes(B, H, W);
+    if (need == 0) return DTFILL_ERR_SHAPE;
+    if (ws_bytes < need || ((uintptr_t)workspace & 255)) return DTFILL_ERR_WORKSPACE;
+    const LinesGrid g = lines_grid(H, W);
+    const int HW = H * W;
+    double *rec = static_cast<double *>(workspace);
+    double2 *part = reinterpret_cast<double2 *>(static_cast<char *>(workspace) + align256((size_t)B * LS_REC * sizeof(double)));
+    const bool vec = (HW & 3) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)out & 15) == 0;
+    const dim3 grid(g.nb, B);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    k_lines_calib<<<B, 64, 0, st>>>(K, E, rec);
+    if (vec) {
+        k_lines_range<true><<<grid, 256, 0, st>>>(x, W, HW, g.tpb, rec, part);
+        k_lines_keep<true><<<grid, 256, 0, st>>>(x, W, HW, n_bins, keep_every, g.tpb, rec, part, out, frame_status);
+    } else {
+        k_lines_range<false><<<grid, 256, 0, st>>>(x, W, HW, g.tpb, rec, part);
+        k_lines_keep<false><<<grid, 256, 0, st>>>(x, W, HW, n_bins, keep_every, g.tpb, rec, part, out, frame_status);
+    }
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 

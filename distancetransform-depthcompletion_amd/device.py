@@ -359,6 +359,59 @@ def metrics_device(output, target, kind="kitti"):
     return out
 
 
+def keep_every_of(keep_ratio):
+    """1 / keep_ratio as the integer the kernel takes (sample()'s `label % (1.0 / keep_ratio) == 0`): 0.5 -> 2 (the
+    reference's 32-line input), 0.25 -> 4 (16 lines).  ValueError unless 1 / keep_ratio is an integer >= 1."""
+    try:
+        inv = 1.0 / float(keep_ratio)
+    except (TypeError, ValueError, ZeroDivisionError):
+        raise ValueError("keep_ratio must be a number whose inverse is an integer >= 1, got %r" % (keep_ratio,)) from None
+    if not (np.isfinite(inv) and inv >= 1.0 and inv == np.round(inv) and inv < 2 ** 31):
+        raise ValueError("keep_ratio must be 1/k for an integer k >= 1, got %r" % (keep_ratio,))
+    return int(inv)
+
+
+def _calibration(m, n, B, device, what):
+    """[n,n] (broadcast to B) or [B,n,n], numpy or tensor of any real dtype -> contiguous float64 CUDA tensor [B,n,n]."""
+    t = m if isinstance(m, torch.Tensor) else torch.from_numpy(np.asarray(m, dtype=np.float64))
+    t = t.to(device=device, dtype=torch.float64)
+    if t.dim() == 2 and tuple(t.shape) == (n, n):
+        t = t.unsqueeze(0).expand(B, n, n)
+    if tuple(t.shape) != (B, n, n):
+        raise ValueError("%s must be [%d,%d] or [B,%d,%d] with B = %d, got shape %s" % (what, n, n, n, n, B, tuple(t.shape)))
+    return t.contiguous()
+
+
+def line_subsample_device(x, K, E, keep_ratio=0.25, n_bins=64):
+    """subsample_Lidar_{train,val}.py's get_all_points -> calculate_angle -> sample -> map_points_on_image on the device
+    (include/dtfill.h, dtfill_line_subsample): keep the valid pixels whose pitch bin (n_bins equal bins over the frame's
+    pitch range) is a multiple of 1 / keep_ratio.  x: contiguous float32 CUDA tensor [B,H,W]; K: intrinsics [3,3] or
+    [B,3,3]; E: velo->cam extrinsics [4,4] or [B,4,4] (numpy or tensors, any real dtype; used in float64).
+    Returns (out float32 [B,H,W] -- kept pixels hold their input value, the others +0.0 --, status int32 [B], bits
+    _lib.LINES_*; a frame with a bit set is all zeros)."""
+    keep_every = keep_every_of(keep_ratio)
+    if int(n_bins) != n_bins or n_bins < 1:
+        raise ValueError("n_bins must be an integer >= 1, got %r" % (n_bins,))
+    _require_gpu()
+    _check_frames(x, "x")
+    B, H, W = x.shape
+    Kd = _calibration(K, 3, B, x.device, "K")
+    Ed = _calibration(E, 4, B, x.device, "E")
+    L = _lib.load()
+    nbytes = L.dtfill_line_subsample_workspace_bytes(B, H, W)
+    if nbytes == 0:
+        _lib.check(-2)
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=x.device)
+    off = (-ws.data_ptr()) % 256
+    out = torch.empty_like(x)
+    status = torch.empty((B,), dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(L.dtfill_line_subsample(x.data_ptr(), B, H, W, Kd.data_ptr(), Ed.data_ptr(), int(n_bins), keep_every,
+                                           out.data_ptr(), status.data_ptr(), ws.data_ptr() + off, nbytes,
+                                           torch.cuda.current_stream(x.device).cuda_stream))
+    return out, status
+
+
 _default_ops = {}
 
 

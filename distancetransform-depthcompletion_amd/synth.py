@@ -9,6 +9,8 @@ There is no dataset in the container, so bench.py and the tests draw frames from
                   (data_read.py:360-364), n = 200 by default (eval_NYU.py:40)
   iid             generic HxW Bernoulli mask, depths U(lo,hi)
 All return float32 [B,H,W] with zeros at invalid pixels.
+  velodyne_scan   a simulated 64-laser spinning scanner projected into the camera, with the calibration that goes with
+                  it: (x, K, E).  The input of the scan-line subsampling (line_subsample_device); not a bench.py config.
 """
 import numpy as np
 
@@ -53,6 +55,82 @@ def iid(B, H, W, p, seed=0, lo=1.0, hi=80.0):
     mask = rng.random((B, H, W)) < p
     vals = rng.uniform(lo, hi, size=(B, H, W)).astype(np.float32)
     return np.where(mask, vals, np.float32(0)).astype(np.float32)
+
+
+def _rot(rng, sigma_deg):
+    """A small random rotation (Rodrigues), angle ~ N(0, sigma) degrees about a random axis."""
+    axis = rng.normal(size=3)
+    axis /= np.linalg.norm(axis)
+    a = np.deg2rad(rng.normal(0.0, sigma_deg))
+    k = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+    return np.eye(3) + np.sin(a) * k + (1 - np.cos(a)) * (k @ k)
+
+
+def _ray_box(o_dirs, lo, hi):
+    """Entry distance of rays from the origin along unit directions [N,3] into the box [lo, hi]; inf where they miss."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t1 = lo[None] / o_dirs
+        t2 = hi[None] / o_dirs
+    tmin = np.nanmax(np.minimum(t1, t2), axis=1)
+    tmax = np.nanmin(np.maximum(t1, t2), axis=1)
+    return np.where((tmax >= tmin) & (tmin > 0), tmin, np.inf)
+
+
+def velodyne_scan(B, seed=0, hw=KITTI_HW, lasers=64, max_range=80.0):
+    """B frames of a simulated spinning `lasers`-beam LiDAR (elevations spread over +2 .. -24.9 degrees, 0.08-degree
+    azimuth steps across the camera's field of view) in a simple scene -- a ground plane 1.73 m below the sensor, a wall
+    on either side, a few boxes, returns up to max_range -- projected into a KITTI-like camera with the nearest return kept
+    per pixel and depths rounded to the k/256 grid.  Each frame has its own scene and its own slightly jittered
+    calibration.  Returns (x float32 [B,H,W], K float64 [B,3,3] intrinsics, E float64 [B,4,4] velo->cam extrinsics).
+    Deterministic for a given seed."""
+    rng = np.random.default_rng(seed)
+    H, W = hw
+    x = np.zeros((B, H, W), np.float32)
+    K = np.zeros((B, 3, 3))
+    E = np.zeros((B, 4, 4))
+    perm = np.array([[0.0, -1.0, 0.0], [0.0, 0.0, -1.0], [1.0, 0.0, 0.0]])  # velo (x fwd, y left, z up) -> cam (x right, y down, z fwd)
+    for b in range(B):
+        f = 721.5 * (1.0 + rng.normal(0.0, 0.01))
+        K[b] = [[f, 0.0, W * 0.4906 + rng.normal(0.0, 2.0)], [0.0, f * (1.0 + rng.normal(0.0, 0.001)), H * 0.4585 + rng.normal(0.0, 2.0)],
+                [0.0, 0.0, 1.0]]
+        E[b, :3, :3] = _rot(rng, 0.5) @ perm
+        E[b, :3, 3] = np.array([-0.004, -0.076, -0.272]) + rng.normal(0.0, 0.01, 3)
+        E[b, 3, 3] = 1.0
+        # rays: per-laser elevation with a small calibration offset, azimuth steps with a per-laser phase (ragged rings)
+        elev = np.deg2rad(np.linspace(2.0, -24.9, lasers) + rng.normal(0.0, 0.02, lasers))
+        half = np.arctan2(W * 0.55, f) + np.deg2rad(3.0)
+        az = np.arange(-half, half, np.deg2rad(0.08))
+        azl = az[None, :] + rng.uniform(0.0, np.deg2rad(0.08), (lasers, 1))
+        el = np.broadcast_to(elev[:, None], azl.shape)
+        d = np.stack([np.cos(el) * np.cos(azl), np.cos(el) * np.sin(azl), np.sin(el)], -1).reshape(-1, 3)
+        t = np.full(d.shape[0], np.inf)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ground = -1.73 / d[:, 2]
+            t = np.where(d[:, 2] < 0, ground, t)
+            for side, off in ((1.0, rng.uniform(5.0, 9.0)), (-1.0, rng.uniform(4.0, 8.0))):
+                tw = side * off / d[:, 1]
+                pw = tw[:, None] * d
+                hit = (tw > 0) & (pw[:, 0] > 3.0) & (pw[:, 2] < 2.5)
+                t = np.where(hit & (tw < t), tw, t)
+        for _ in range(int(rng.integers(2, 6))):
+            c = np.array([rng.uniform(6.0, 45.0), rng.uniform(-5.0, 5.0), -1.73])
+            size = np.array([rng.uniform(1.5, 4.5), rng.uniform(1.5, 2.0), rng.uniform(1.2, 2.5)])
+            tb = _ray_box(d, c - [size[0] / 2, size[1] / 2, 0.0], c + [size[0] / 2, size[1] / 2, size[2]])
+            t = np.minimum(t, tb)
+        keep = (t <= max_range) & (rng.random(t.shape) > 0.03)  # range cap, a few dropped returns
+        p = t[keep, None] * d[keep]
+        pc = p @ E[b, :3, :3].T + E[b, :3, 3]
+        pc = pc[pc[:, 2] > 0.5]
+        u = np.round(K[b, 0, 0] * pc[:, 0] / pc[:, 2] + K[b, 0, 2]).astype(np.int64)
+        v = np.round(K[b, 1, 1] * pc[:, 1] / pc[:, 2] + K[b, 1, 2]).astype(np.int64)
+        z = pc[:, 2]
+        inside = (u >= 0) & (u < W) & (v >= 0) & (v < H)
+        u, v, z = u[inside], v[inside], z[inside]
+        order = np.argsort(-z, kind="stable")  # farthest first: the nearest return of a pixel is written last
+        frame = np.zeros(H * W)
+        frame[v[order] * W + u[order]] = z[order]
+        x[b] = (np.round(frame * 256.0) / 256.0).reshape(H, W).astype(np.float32)
+    return x, K, E
 
 
 # BASELINE.json configs (index = position in BASELINE.json "configs")

@@ -101,3 +101,37 @@ def generate_multi_channel(lidar_data, lidar_mask, table_size=7, scale_num=4):
     mm = torch.from_numpy(np.ascontiguousarray(m[..., 0])).to(dev)
     outs = _device.generate_multi_channel_device(dd, mm, table_size, scale_num)
     return tuple(None if o is None else o.cpu().numpy()[..., None] for o in outs)
+
+
+def subsample_lidar(sparse_depth, intrinsic, extrinsic, keep_ratio=0.25, n_bins=64):
+    """subsample_Lidar_train.py / subsample_Lidar_val.py: get_all_points -> calculate_angle -> sample(keep_ratio) ->
+    map_points_on_image, in one call (the caller's `* 256 -> uint16` PNG write stays as it is).  sparse_depth [H,W],
+    [H,W,1], [B,H,W] or [B,H,W,1]; intrinsic [3,3] or [B,3,3]; extrinsic (velo->cam) [4,4] or [B,4,4].  Returns float32
+    of the input's shape: the kept pixels hold their input value, the others 0.  Raises np.linalg.LinAlgError for a
+    singular intrinsic / extrinsic and ValueError for a frame without a valid pixel (> 0.1), as the reference does; a
+    frame whose pitch interval is 0 or not finite comes back all zeros, as the reference's NaN labels keep nothing."""
+    import torch
+
+    from . import _lib
+
+    _device.keep_every_of(keep_ratio)  # ValueError before any device work
+    a = _as_f32_frames(sparse_depth)
+    shape = a.shape
+    if a.ndim in (3, 4) and a.shape[-1] == 1:
+        a = a[..., 0]  # [H,W,1] / [B,H,W,1] (a [B,H,W] batch of one-column frames reads as [H,W,1])
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3:
+        raise ValueError("subsample_lidar expects [H,W], [H,W,1], [B,H,W] or [B,H,W,1], got shape %s" % (shape,))
+    dev = _device.default_op().device
+    x = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    out, status = _device.line_subsample_device(x, intrinsic, extrinsic, keep_ratio=keep_ratio, n_bins=n_bins)
+    st = status.cpu().numpy()
+    bad = np.flatnonzero(st & _lib.LINES_SINGULAR)
+    if bad.size:
+        raise np.linalg.LinAlgError("Singular matrix (intrinsic or extrinsic of frame %d)" % bad[0])
+    bad = np.flatnonzero(st & _lib.LINES_NO_POINTS)
+    if bad.size:
+        raise ValueError("zero-size array to reduction operation maximum which has no identity (frame %d has no point "
+                         "with depth > 0.1)" % bad[0])
+    return out.cpu().numpy().reshape(shape)

@@ -186,6 +186,34 @@ int dtfill_png16(const float *x, int B, int H, int W, int pad_top, int use_floor
                  float scale, uint16_t *out, void *stream);
 
 /*
+ * Scan-line subsampling of a projected LiDAR frame: the 32- and 16-line inputs subsample_Lidar_train.py /
+ * subsample_Lidar_val.py build (get_all_points -> calculate_angle -> sample -> map_points_on_image), per frame b:
+ *   a pixel (row v, column u) is VALID iff x > 0.1f (float32 compare: NaN, -inf and (0, 0.1] are not points);
+ *   for a valid pixel, in float64 with d = (double)x:  p_cam = K^-1 [u, v, 1]^T d,  p = (E^-1 [p_cam; 1])[0:3],
+ *     pitch = asin(p.z / |p|)   (K^-1, E^-1: general inverses, partial pivoting, computed on the device);
+ *   pmin, pmax over the frame's valid pixels (NaN if any pitch is NaN, as np.min / np.max), interval = (pmax - pmin) / n_bins;
+ *   label = ceil((pitch - pmin) / interval), not clamped (the minimum has label 0; for a power-of-two n_bins the maximum
+ *     has label n_bins); a valid pixel is KEPT iff label mod keep_every == 0 (keep_every = 1 / keep_ratio: 2 gives the
+ *     reference's 32 lines, 4 its 16).
+ *   out[b] holds x at the kept pixels, bit for bit, and +0.0f everywhere else.  The reference re-projects the kept points
+ *   through the same K and E, which is the identity in exact arithmetic, so nothing is scattered.
+ *   frame_status[b]: DTFILL_LINES_* bits; when any is set, out[b] is all zeros.
+ * x: float32 [B,H,W]; K: float64 [B,3,3] intrinsics; E: float64 [B,4,4] velo->cam extrinsics; out: float32 [B,H,W], may
+ * not alias x; frame_status: int32 [B]; workspace: ws_bytes >= dtfill_line_subsample_workspace_bytes(B,H,W), 256-B
+ * aligned, no initialisation needed, nothing kept between calls.  Asynchronous on `stream`.
+ * Returns DTFILL_ERR_NULL for a NULL pointer, n_bins < 1 or keep_every < 1; DTFILL_ERR_SHAPE for B,H,W < 1, B > 65535 or
+ * B*H*W >= 2^31; DTFILL_ERR_WORKSPACE; all checked before any HIP call.
+ */
+#define DTFILL_LINES_NO_POINTS     1 /* no valid pixel (the reference's np.max raises ValueError) */
+#define DTFILL_LINES_BAD_INTERVAL  2 /* interval 0 or not finite: one point, one pitch, a +inf depth (the reference's NaN
+                                        labels keep nothing) */
+#define DTFILL_LINES_SINGULAR      4 /* K or E singular: a zero pivot (np.linalg.inv raises LinAlgError) */
+size_t dtfill_line_subsample_workspace_bytes(int B, int H, int W);
+int dtfill_line_subsample(const float *x, int B, int H, int W, const double *K, const double *E, int n_bins, int keep_every,
+                          float *out, int32_t *frame_status, void *workspace, size_t ws_bytes, void *stream);
+
+
+/*
  * Error metrics of evaluation.py, one row per frame:
  *   DTFILL_METRICS_KITTI  Result.evaluate, evaluation.py:82-123 (metres -> mm for mse/rmse/mae, -> 1/km for
  *                         irmse/imae; the deltas stay 0 as in the reference);
