@@ -612,6 +612,17 @@ extern "C" int dtfill_fused_prof(unsigned long long *out16, int reset) {
     }
     return 0;
 }
+// the timeline records (g_fused_tl) of the last pass(es) since a reset: F_TL_WAVES x F_TL_EV u64 into out
+extern "C" int dtfill_fused_timeline(unsigned long long *out, int reset) {
+    const size_t n = sizeof(unsigned long long) * F_TL_WAVES * F_TL_EV;
+    if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fused_tl), n) != hipSuccess) return -1;
+    if (reset) {
+        void *d = nullptr;
+        if (hipGetSymbolAddress(&d, HIP_SYMBOL(g_fused_tl)) != hipSuccess || hipMemset(d, 0, n) != hipSuccess) return -1;
+        if (hipDeviceSynchronize() != hipSuccess) return -1;
+    }
+    return 0;
+}
 #endif
 
 #ifdef PTS_PROF

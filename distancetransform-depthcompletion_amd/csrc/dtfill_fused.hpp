@@ -105,17 +105,38 @@ __device__ __forceinline__ u32 mul_u24_opaque(u32 a, u32 b) {
 // one record per wave slot (waves of the grid modulo F_PROF_SLOTS): no atomics contend for a line; the reader sums them
 constexpr int F_PROF_SLOTS = 8192;
 __device__ unsigned long long g_fused_prof[F_PROF_SLOTS][16];
+// Timeline: per wave of the grid (up to F_TL_WAVES), its first F_TL_EV phase changes in order, each one u64
+// = constant-clock time (s_memrealtime, 100 MHz) << 4 | the phase that ENDS there (15: the wave's start); 0 = no entry.
+// The reader bins them into the share of working waves in each phase over time.
+constexpr int F_TL_WAVES = 1 << 16, F_TL_EV = 32;
+__device__ unsigned long long g_fused_tl[F_TL_WAVES][F_TL_EV];
+__device__ __forceinline__ unsigned long long fprof_realtime() {
+    unsigned long long t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+}
 // per wave: t[k] cycles of phase k (P0 load, P1 levels, P1b backward taps, P2 un-slice, P3 hops, P3 epilogue + stores, tail),
 // n[k] counts (waves, levels run, batches, walkers, -, hop trips (two hops each), -, -)
 struct FusedProf {
     unsigned long long t[8] = {}, n[8] = {}, tprev = __builtin_readcyclecounter();
+    int nev = 0;
+    __device__ int wave() const { return (blockIdx.y * gridDim.x + blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6); }
+    __device__ void event(int k) {
+        const unsigned long long rt = fprof_realtime();
+        if ((threadIdx.x & 63) == 0 && wave() < F_TL_WAVES && nev < F_TL_EV) g_fused_tl[wave()][nev] = rt << 4 | (unsigned)k;
+        ++nev;
+    }
+    __device__ FusedProf() { event(15); }
     __device__ void mark(int k) {
         const unsigned long long t_ = __builtin_readcyclecounter();
         t[k] += t_ - tprev;
         tprev = t_;
+        event(k);
     }
     __device__ void flush() {
-        const int slot = ((blockIdx.y * gridDim.x + blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6)) % F_PROF_SLOTS;
+        const int slot = wave() % F_PROF_SLOTS;
         if ((threadIdx.x & 63) == 0)
             for (int k = 0; k < 8; ++k) {
                 atomicAdd(&g_fused_prof[slot][k], t[k]);
@@ -161,10 +182,19 @@ __device__ __forceinline__ bool fused_walk_epilogue(
     const int nval = finfo[b * FI_STRIDE + FI_NVAL];
     const int misaligned = finfo[b * FI_STRIDE + FI_MISALIGNED];
     const float *gbase = misaligned ? vlist + fo : x + fo;
+    // The outputs leave through buffer stores, one descriptor per frame and map (block-uniform): a store the pass does not
+    // make -- an undecided pixel, a cropped row, a map the caller did not ask for (0 records) -- is a store whose offset the
+    // range check drops.  So every batch issues the same stores, branch-free, and the compiler's vmcnt waits for a batch's
+    // gathers are exact: they no longer wait for the label / distance stores issued behind them (in-order vmcnt; with
+    // branches around the stores it has to assume the path without them and wait for all but seven).
     // the depth output may drop the first ep.row0 rows (then frames are H - row0 rows apart)
-    float *od = out_depth ? out_depth + (size_t)b * (H - ep.row0) * W : nullptr, *ot = out_dt ? out_dt + fo : nullptr;
-    const u32 dcrop = (u32)(ep.row0 * W) << 2;  // bytes of a frame's dropped rows
-    int32_t *oi = out_index ? out_index + fo : nullptr;
+    const u32 dcrop = (u32)(ep.row0 * W) << 2;  // bytes of a frame's dropped rows; a pixel of them wraps past the records
+    const u32 fbytes = (u32)(H * W) << 2;
+    const auto rs_d = __builtin_amdgcn_make_buffer_rsrc(out_depth ? out_depth + (size_t)b * (H - ep.row0) * W : nullptr, 0,
+                                                        out_depth ? (int)(fbytes - dcrop) : 0, 0x00020000);
+    const auto rs_t = __builtin_amdgcn_make_buffer_rsrc(out_dt ? out_dt + fo : nullptr, 0, out_dt ? (int)fbytes : 0, 0x00020000);
+    const auto rs_i = __builtin_amdgcn_make_buffer_rsrc(out_index ? out_index + fo : nullptr, 0, out_index ? (int)fbytes : 0, 0x00020000);
+    constexpr u32 OFF_NONE = 0x80000000u;  // past every frame's records (a frame has < 2^26 pixels)
     const char *tab = reinterpret_cast<const char *>(s_tab);
     auto step_of = [&](int c) { return (int)*reinterpret_cast<const short *>(tab + c); };
     const int src_base = wr0 * W + wc0;  // frame offset of window cell (0,0) (may be negative)
@@ -172,13 +202,8 @@ __device__ __forceinline__ bool fused_walk_epilogue(
     bool overflow = false;
     // STREAM (rows of whole 128-byte lines: W % 32 == 0, aligned outputs, tile columns in whole lines): a wave's run of
     // consecutive tile pixels is whole lines, and nothing of the outputs is read again in this pass -- streaming stores
-    // keep them from pushing the inputs out of the caches.  Otherwise the L2 has to merge the partial lines: plain stores.
-    auto put = [](auto *p, auto v) {
-        if constexpr (STREAM)
-            __builtin_nontemporal_store(v, p);
-        else
-            *p = v;
-    };
+    // (nt) keep them from pushing the inputs out of the caches.  Otherwise the L2 has to merge the partial lines: plain stores.
+    auto put = [](__amdgpu_buffer_rsrc_t rs, u32 off, u32 v) { __builtin_amdgcn_raw_buffer_store_b32(v, rs, (int)off, 0, STREAM ? 2 : 0); };
     // A lane walks F_EB pixels of ONE column, rows 8 g .. 8 g + 7 of the tile: slot L = sb + tid is (row group g, column) =
     // divmod(L, tw), so the index arithmetic is done once per slot and the F_EB pixels differ by a row pitch each; a wave's store
     // is still a run of 64 consecutive pixels of a row (two runs where the slots wrap into the next group).
@@ -188,25 +213,15 @@ __device__ __forceinline__ bool fused_walk_epilogue(
     const float inv_tw = 1.0f / (float)tw;
     const u32 w4 = (u32)W << 2;
     float p_val[F_EB];  // the batch whose gathers are in flight
+#pragma unroll
+    for (int e = 0; e < F_EB; ++e) p_val[e] = 0.0f;
     u32 p_opix = 0, p_ok = 0;
-    bool p_full = false;  // wave-uniform: every walker of that batch is stored
-    // p_opix is a BYTE offset (< 2^32: a frame has < 2^26 pixels): scalar base + 32-bit vector offset
+    // p_opix is a BYTE offset (< 2^32: a frame has < 2^26 pixels): descriptor base + 32-bit vector offset
     auto retire = [&]() {
-        if (!od) return;
-        auto st = [&](int e) {
-            const u32 o = p_opix + (u32)e * w4;
-            if constexpr (!EPI)
-                put(reinterpret_cast<float *>(reinterpret_cast<char *>(od) + o), p_val[e]);
-            else if (o >= dcrop)
-                *reinterpret_cast<float *>(reinterpret_cast<char *>(od) + (o - dcrop)) = depth_epilogue(p_val[e], ep);
-        };
-        if (p_full) {
 #pragma unroll
-            for (int e = 0; e < F_EB; ++e) st(e);
-        } else {
-#pragma unroll
-            for (int e = 0; e < F_EB; ++e)
-                if ((p_ok >> e) & 1u) st(e);
+        for (int e = 0; e < F_EB; ++e) {
+            const u32 o = p_opix + (u32)e * w4 - dcrop;
+            put(rs_d, ((p_ok >> e) & 1u) ? o : OFF_NONE, __float_as_uint(EPI ? depth_epilogue(p_val[e], ep) : p_val[e]));
         }
     };
     for (int sb = 0; sb < nslots; sb += NT) {
@@ -298,23 +313,12 @@ __device__ __forceinline__ bool fused_walk_epilogue(
         for (int e = 0; e < F_EB; ++e) p_val[e] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(gbase) + goff[e]);
         p_opix = opix0;
         p_ok = ok;
-        p_full = __all(ok == (1u << F_EB) - 1u);
-        if (oi || ot) {
-            auto st = [&](int e) {
-                const u32 o = opix0 + (u32)e * w4;
-                if (oi) put(reinterpret_cast<int32_t *>(reinterpret_cast<char *>(oi) + o), lab[e]);
-                // L1 distance to the nearest source IS d: |drow| + |dcol| of the two 16-bit halves in one instruction
-                if (ot) put(reinterpret_cast<float *>(reinterpret_cast<char *>(ot) + o),
-                            (float)__builtin_amdgcn_sad_u16((u32)pr[e] << 16 | (u32)pc[e], home0 + ((u32)e << 16), 0u));
-            };
-            if (p_full) {
 #pragma unroll
-                for (int e = 0; e < F_EB; ++e) st(e);
-            } else {
-#pragma unroll
-                for (int e = 0; e < F_EB; ++e)
-                    if ((ok >> e) & 1u) st(e);
-            }
+        for (int e = 0; e < F_EB; ++e) {
+            const u32 o = ((ok >> e) & 1u) ? opix0 + (u32)e * w4 : OFF_NONE;
+            put(rs_i, o, (u32)lab[e]);
+            // L1 distance to the nearest source IS d: |drow| + |dcol| of the two 16-bit halves in one instruction
+            put(rs_t, o, __float_as_uint((float)__builtin_amdgcn_sad_u16((u32)pr[e] << 16 | (u32)pc[e], home0 + ((u32)e << 16), 0u)));
         }
     }
     FPROF(prof.mark(5));
