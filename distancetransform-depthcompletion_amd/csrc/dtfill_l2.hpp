@@ -146,10 +146,11 @@ struct L2Win {
     static constexpr bool BYTE = NONE <= 255;                    // R <= 10: the entries fit a byte
     static constexpr int ESZ = BYTE ? 1 : 2;
     // LDS: entries [NR][256], row bits for the windows [NR][4] x 16 B, the words 4tx-1 .. 4tx+4 [NR][6] x 8 B, the number of
-    // sources before each of them [NR][6] x 4 B, the side bits [NR][4] x 8 B, sqrt table [R^2 + 1]
+    // sources before each of them [NR][6] x 4 B, the side bits [NR][4] x 8 B, sqrt table [R^2 + 1], the tile's handed-on rows
+    // (one bit per row)
     static constexpr size_t OFF_X = (size_t)NR * W2_TW * ESZ, OFF_W = OFF_X + (size_t)NR * 64, OFF_BASE = OFF_W + (size_t)NR * 48,
                             OFF_SIDE = OFF_BASE + (size_t)NR * 24, OFF_SQRT = OFF_SIDE + (size_t)NR * 32,
-                            LDS = OFF_SQRT + (size_t)(R * R + 1) * 4;
+                            OFF_GONE = OFF_SQRT + (size_t)(R * R + 1) * 4, LDS = OFF_GONE + 4;
 };
 
 template <int R>
@@ -188,13 +189,22 @@ __global__ __launch_bounds__(256) void k_l2win(const float *__restrict__ x, cons
     }
     const int ty0 = blockIdx.x / tiles_x;
     // rows k_frame (too far from every row with a source: the sky) or other blocks (too many far pixels) have handed to the
-    // row search: nothing of them is computed, stored or counted here; a tile that holds no other row is done
-    u64 rowgone = 0ull;
-    if (fflag2[b]) {  // (block-uniform; a frame without such rows does not pay for the look)
-        const int l = threadIdx.x & 63, row = ty0 * W2_TH + l;
-        rowgone = __ballot(l < W2_TH && (row >= H || rowfar[(size_t)b * H + min(row, H - 1)] >= w2_row_t(W)));
-        if ((u32)rowgone == 0xFFFFFFFFu) return;  // block-uniform: every wave computes the same mask
+    // row search: nothing of them is computed, stored or counted here; a tile that holds no other row is done.  Other blocks
+    // of this launch mark rows (fflag2, rowfar) while this one runs, so two waves that looked on their own could disagree:
+    // wave 0 looks once and publishes the mask, and every wave goes by that one.  (A row marked after the look is redone whole
+    // by k_l2env all the same: whether this block still stores its part of it does not matter.)
+    u32 *s_gone = reinterpret_cast<u32 *>(lds + C::OFF_GONE);
+    if (threadIdx.x < 64) {
+        u32 gone = 0u;
+        if (__builtin_amdgcn_readfirstlane(fflag2[b])) {  // a frame without such rows does not pay for the look
+            const int l = threadIdx.x, row = ty0 * W2_TH + l;
+            gone = (u32)__ballot(l < W2_TH && (row >= H || rowfar[(size_t)b * H + min(row, H - 1)] >= w2_row_t(W)));
+        }
+        if (threadIdx.x == 0) *s_gone = gone;
     }
+    __syncthreads();
+    const u32 rowgone = *s_gone;
+    if (rowgone == 0xFFFFFFFFu) return;  // block-uniform: one mask for the whole block
     entry_t *s_h = reinterpret_cast<entry_t *>(lds);
     uint4 *s_x = reinterpret_cast<uint4 *>(lds + C::OFF_X);
     u64 *s_w = reinterpret_cast<u64 *>(lds + C::OFF_W);
@@ -274,7 +284,7 @@ __global__ __launch_bounds__(256) void k_l2win(const float *__restrict__ x, cons
                 m = min3u(m, (e[u + dyi] << DB) + (u32)(((dyi - R) * (dyi - R)) << DB | dyi),
                           (e[u + dyi + 1] << DB) + (u32)(((dyi + 1 - R) * (dyi + 1 - R)) << DB | (dyi + 1)));
             best[u] = min(m, (e[u + 2 * R] << DB) + (u32)((R * R) << DB | (2 * R)));
-            far[u] = inw & (y0 + t0 + u < H) & ((best[u] >> DB) > (u32)(R * R)) & !((rowgone >> (t0 + u)) & 1ull);
+            far[u] = inw & (y0 + t0 + u < H) & ((best[u] >> DB) > (u32)(R * R)) & !((rowgone >> (t0 + u)) & 1u);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {  // a pixel with no source within R: counted per row; a few go on k_l2far's list, 32 or more of
@@ -297,7 +307,7 @@ __global__ __launch_bounds__(256) void k_l2win(const float *__restrict__ x, cons
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int i = y0 + t0 + u;
-            S.live[u] = inw & (i < H) & !far[u] & !((rowgone >> (t0 + u)) & 1ull);
+            S.live[u] = inw & (i < H) & !far[u] & !((rowgone >> (t0 + u)) & 1u);
             const u32 d2 = min(best[u] >> DB, (u32)(R * R));  // clamped for the table (a far pixel stores nothing)
             const int dyi = (int)(best[u] & ((1u << DB) - 1u)), dy = dyi - R;
             const int dx2 = max((int)d2 - dy * dy, 0);
