@@ -24,6 +24,8 @@ FLAG_OUTLIER_REMOVAL = 4  # outlier_removal() (data_read.py:103-128) in front of
 LINES_NO_POINTS = 1  # bit: no valid pixel in the frame (DTFILL_LINES_*)
 LINES_BAD_INTERVAL = 2  # bit: the pitch interval is 0 or not finite
 LINES_SINGULAR = 4  # bit: K or E is singular
+READ_NOT_16BIT = 1  # bit: every source value of the frame is <= 255 (DTFILL_READ_*)
+READ_BAD_DIMS = 2  # bit: the frame's dims lie outside [1, hmax] x [1, wmax]; its output is all zeros
 PATHS = {"auto": 0, "general": FLAG_GENERAL_ONLY, "fused": FLAG_FUSED_ONLY}
 
 # every symbol include/dtfill.h declares (tests/test_abi.py checks the .so exports exactly these)
@@ -44,6 +46,8 @@ SYMBOLS = (
     "dtfill_png16",
     "dtfill_line_subsample_workspace_bytes",
     "dtfill_line_subsample",
+    "dtfill_depth_read_workspace_bytes",
+    "dtfill_depth_read",
     "dtfill_metrics_workspace_bytes",
     "dtfill_metrics",
 )
@@ -117,6 +121,10 @@ def load():
     L.dtfill_line_subsample_workspace_bytes.restype = sz
     L.dtfill_line_subsample.argtypes = [vp, ci, ci, ci, vp, vp, ci, ci, vp, vp, vp, sz, vp]
     L.dtfill_line_subsample.restype = ci
+    L.dtfill_depth_read_workspace_bytes.argtypes = [ci, ci, ci]
+    L.dtfill_depth_read_workspace_bytes.restype = sz
+    L.dtfill_depth_read.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, sz, vp]
+    L.dtfill_depth_read.restype = ci
     L.dtfill_metrics_workspace_bytes.argtypes = [ci]
     L.dtfill_metrics_workspace_bytes.restype = sz
     L.dtfill_metrics.argtypes = [vp, vp, ci, ctypes.c_longlong, ci, vp, vp, sz, vp]

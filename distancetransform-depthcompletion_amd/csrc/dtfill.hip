@@ -78,6 +78,7 @@ namespace {
 #include "dtfill_gmc.hpp"
 #include "dtfill_post.hpp"
 #include "dtfill_lines.hpp"
+#include "dtfill_read.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -569,6 +570,32 @@ int dtfill_line_subsample(const float *x, int B, int H, int W, const double *K, 
         k_lines_range<false><<<grid, 256, 0, st>>>(x, W, HW, g.tpb, rec, part);
         k_lines_keep<false><<<grid, 256, 0, st>>>(x, W, HW, n_bins, keep_every, g.tpb, rec, part, out, frame_status);
     }
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+size_t dtfill_depth_read_workspace_bytes(int B, int H, int W) {
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long long)B * H * W >= (1ll << 31)) return 0;
+    return align256((size_t)B * H * sizeof(int)) + align256((size_t)B * W * sizeof(int)) + align256((size_t)B * sizeof(u32));
+}
+
+int dtfill_depth_read(const uint16_t *raw, const int32_t *dims, int B, int hmax, int wmax, int H, int W, float *out,
+                      int32_t *frame_status, void *workspace, size_t ws_bytes, void *stream) {
+    if (!raw || !out || !workspace) return DTFILL_ERR_NULL;
+    const size_t need = dtfill_depth_read_workspace_bytes(B, H, W);
+    if (need == 0 || hmax < 1 || wmax < 1 || (long long)B * hmax * wmax >= (1ll << 31)) return DTFILL_ERR_SHAPE;
+    if (ws_bytes < need || ((uintptr_t)workspace & 255)) return DTFILL_ERR_WORKSPACE;
+    char *base = static_cast<char *>(workspace);
+    int *ry = reinterpret_cast<int *>(base);
+    int *rx = reinterpret_cast<int *>(base + align256((size_t)B * H * sizeof(int)));
+    u32 *fw = reinterpret_cast<u32 *>(base + align256((size_t)B * H * sizeof(int)) + align256((size_t)B * W * sizeof(int)));
+    const int rpb = max(DR_ROWS, (H + 65534) / 65535);
+    const dim3 grid(B, (H + rpb - 1) / rpb);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    k_read_maps<<<B, 128, 0, st>>>(dims, hmax, wmax, H, W, ry, rx, fw);
+    if ((W & 3) == 0 && ((uintptr_t)out & 15) == 0)
+        k_read_gather<true><<<grid, DR_THREADS, 0, st>>>(raw, dims, hmax, wmax, H, W, rpb, ry, rx, fw, out, frame_status);
+    else
+        k_read_gather<false><<<grid, DR_THREADS, 0, st>>>(raw, dims, hmax, wmax, H, W, rpb, ry, rx, fw, out, frame_status);
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 

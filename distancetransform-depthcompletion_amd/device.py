@@ -412,6 +412,51 @@ def line_subsample_device(x, K, E, keep_ratio=0.25, n_bins=64):
     return out, status
 
 
+
+def _read_size(size, what="size"):
+    """PIL's (width, height) -> (H, W) as ints >= 1."""
+    try:
+        W, H = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be (width, height), got %r" % (what, size)) from None
+    if W < 1 or H < 1 or (W, H) != tuple(size):
+        raise ValueError("%s must be two integers >= 1 in PIL's (width, height) order, got %r" % (what, size))
+    return H, W
+
+
+def depth_read_device(raw, dims=None, size=(1216, 352)):
+    """data_read.py:81-99 after the PNG decode, on the device (include/dtfill.h, dtfill_depth_read): the values / 256 and
+    Pillow's NEAREST resize to size = (width, height), PIL's order as data_read.py:96 writes it.  raw: contiguous uint16
+    CUDA tensor [B, hmax, wmax]; dims: (h_b, w_b) per frame as int [B, 2] (numpy, list or tensor; None: every frame
+    hmax x wmax), the padding beyond them is never read.  Returns (out float32 [B, H, W], status int32 [B], bits
+    _lib.READ_*: NOT_16BIT where every value of the frame is <= 255, the reference's assert; BAD_DIMS, with an all-zero
+    frame, for dims outside [1, hmax] x [1, wmax]).  Asynchronous on the current stream; out feeds DtFill.run as it is."""
+    _require_gpu()
+    if raw.dtype != torch.uint16 or not raw.is_cuda or raw.dim() != 3 or not raw.is_contiguous():
+        raise ValueError("raw must be a contiguous uint16 CUDA tensor [B,hmax,wmax]")
+    H, W = _read_size(size)
+    B, hmax, wmax = raw.shape
+    d = None
+    if dims is not None:
+        d = dims if isinstance(dims, torch.Tensor) else torch.from_numpy(np.asarray(dims, dtype=np.int32))
+        d = d.to(device=raw.device, dtype=torch.int32).contiguous()
+        if tuple(d.shape) != (B, 2):
+            raise ValueError("dims must be [B, 2] = [%d, 2], got shape %s" % (B, tuple(d.shape)))
+    L = _lib.load()
+    nbytes = L.dtfill_depth_read_workspace_bytes(B, H, W)
+    if nbytes == 0:
+        _lib.check(-2)
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=raw.device)
+    off = (-ws.data_ptr()) % 256
+    out = torch.empty((B, H, W), dtype=torch.float32, device=raw.device)
+    status = torch.empty((B,), dtype=torch.int32, device=raw.device)
+    with torch.cuda.device(raw.device):
+        _lib.check(L.dtfill_depth_read(raw.data_ptr(), None if d is None else d.data_ptr(), B, hmax, wmax, H, W,
+                                       out.data_ptr(), status.data_ptr(), ws.data_ptr() + off, nbytes,
+                                       torch.cuda.current_stream(raw.device).cuda_stream))
+    return out, status
+
+
 _default_ops = {}
 
 

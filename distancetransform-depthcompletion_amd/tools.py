@@ -3,6 +3,7 @@
 Same names, argument meaning and error behaviour as
   solution_DeepNet/tools.py:7-35      nearest_point, DT_complete_batch
   solution_DeepNet/eval_NYU.py:114-133 nearest_point (threshold 0.001), Distance_Transform
+  data_read.py:81-99                   depth_read (and depth_read_batch for Data_load.read_batch's stack of them)
 but the work is done by libdtfill.so on the current HIP device.  Differences from the reference,
 all widening: DT_complete_batch accepts any HxW (the reference hard-codes 352x1216 in its
 reshapes, tools.py:25,27), and the thresholds the reference writes as literals are keyword
@@ -135,3 +136,95 @@ def subsample_lidar(sparse_depth, intrinsic, extrinsic, keep_ratio=0.25, n_bins=
         raise ValueError("zero-size array to reduction operation maximum which has no identity (frame %d has no point "
                          "with depth > 0.1)" % bad[0])
     return out.cpu().numpy().reshape(shape)
+
+
+KITTI_SIZE = (1216, 352)  # data_read.py:96: PIL's (width, height)
+
+
+def _png_values(a, what):
+    """A decoded PNG frame as the kernel reads it: 2-D, integer values that fit uint16 (TypeError otherwise: the kernel takes
+    16-bit values, where the reference would go on with any int)."""
+    a = np.asarray(a)
+    if a.ndim != 2 or 0 in a.shape:
+        raise ValueError("%s: expected a non-empty 2-D array of decoded PNG values, got shape %s" % (what, a.shape))
+    if a.dtype == np.uint16 or a.dtype == np.uint8:
+        return a
+    if a.dtype.kind not in "iu":
+        raise TypeError("%s: expected integer PNG values, got dtype %s" % (what, a.dtype))
+    if a.min() < 0 or a.max() > 65535:
+        raise TypeError("%s: values in [%d, %d] do not fit uint16" % (what, a.min(), a.max()))
+    return a
+
+
+def _depth_read_frames(frames, size):
+    """The frames (checked by _png_values) -> (float32 [B, H, W, 1] in a page-locked array of its own, status int32 [B]):
+    one padded uint16 staging buffer that carries the dims behind the values, one H2D copy, one dtfill_depth_read, one
+    D2H copy of the result."""
+    import torch
+
+    B = len(frames)
+    if B == 0:
+        raise ValueError("depth_read_batch needs at least one frame")
+    hmax = max(f.shape[0] for f in frames)
+    wmax = max(f.shape[1] for f in frames)
+    if size is None:
+        if any(f.shape != frames[0].shape for f in frames):
+            raise ValueError("size=None keeps the source size, so every frame must have the same shape; got %s"
+                             % sorted({f.shape for f in frames}))
+        H, W = hmax, wmax
+    else:
+        H, W = _device._read_size(size)
+    n = B * hmax * wmax
+    n2 = n + (n & 1)  # the dims start 4-byte aligned
+    stage = _device._host_pool.take((n2 + 4 * B,), np.uint16)
+    raw = stage.array[:n].reshape(B, hmax, wmax)  # the padding is never read: left as it is
+    for b, f in enumerate(frames):
+        raw[b, :f.shape[0], :f.shape[1]] = f
+    stage.array[n2:].view(np.int32).reshape(B, 2)[:] = [f.shape for f in frames]
+    dev = _device.default_op().device
+    with torch.cuda.device(dev):
+        d = torch.empty((n2 + 4 * B,), dtype=torch.uint16, device=dev)
+        d.copy_(stage.tensor, non_blocking=True)
+        out, status = _device.depth_read_device(d[:n].view(B, hmax, wmax), d[n2:].view(torch.int32).view(B, 2), (W, H))
+        host = _device._host_pool.take((B, H, W, 1), np.float32)
+        host.tensor.copy_(out.view(B, H, W, 1), non_blocking=True)
+        st = status.cpu().numpy()  # synchronises: the staging buffer and the result are done with
+    return host.array, st
+
+
+def depth_read(filename):
+    """data_read.py:81-99 (KITTI_demo_loader.depth_read, :404-422, is the same): a 16-bit depth PNG -> float32
+    [352, 1216, 1], the values / 256 NEAREST-resized as Pillow does.  The PNG is decoded on the host, the rest runs on the
+    device.  Raises the reference's AssertionErrors (file missing; every value <= 255) with its messages; values that do
+    not fit uint16 raise TypeError."""
+    import os
+
+    from . import _lib
+
+    assert os.path.exists(filename), "file not found: {}".format(filename)
+    from PIL import Image
+
+    img_file = Image.open(filename)
+    depth_png = _png_values(np.array(img_file), filename)
+    img_file.close()
+    out, st = _depth_read_frames([depth_png], KITTI_SIZE)
+    assert not st[0] & _lib.READ_NOT_16BIT, "np.max(depth_png)={}, path={}".format(np.max(depth_png), filename)
+    return out[0]
+
+
+def depth_read_batch(frames, size=KITTI_SIZE, check=True):
+    """depth_read for a batch: frames is a list of decoded 2-D integer PNG arrays (np.array(Image.open(path))) of any mixed
+    sizes; returns float32 [B, H, W, 1], size = (width, height) as PIL writes it -- np.asarray of the list Data_load.
+    read_batch stacks (data_read.py:166, 172).  size=None keeps the source size, the read_one_val / read_one_test path
+    (data_read.py:215, 261: / 256 without a resize); every frame must then have the same shape.  With check=True an
+    AssertionError names the first frame whose values are all <= 255 (the reference's assert)."""
+    from . import _lib
+
+    frames = [_png_values(f, "frame %d" % b) for b, f in enumerate(frames)]
+    out, st = _depth_read_frames(frames, size)
+    if check:
+        bad = np.flatnonzero(st & _lib.READ_NOT_16BIT)
+        if bad.size:
+            b = int(bad[0])
+            raise AssertionError("np.max(depth_png)={}, frame {}".format(np.max(frames[b]), b))
+    return out

@@ -214,6 +214,29 @@ int dtfill_line_subsample(const float *x, int B, int H, int W, const double *K, 
 
 
 /*
+ * depth_read() of the reference's loader, data_read.py:81-99 (KITTI_demo_loader.depth_read, :404-422, is the same), on the
+ * decoded 16-bit PNG values of B frames; the host keeps the PNG decode.  Frame b holds (h_b, w_b) pixels, every output
+ * frame H x W.  Per frame, in IEEE double (Pillow's NEAREST resize, ImagingScaleAffine's running sum, not a closed form):
+ *   ay = (double)h_b / H;  y = 0.5 * ay;  for i = 0 .. H-1: ry[i] = (int)y (truncation); y += ay   (the same for rx with w_b / W)
+ *   out[b, i, j] = (float)raw[b, ry[i], rx[j]] * 2^-8   (exact, and equal to the reference's float64 value / 256 after
+ *                                                        its PIL mode-F round trip)
+ * Same size in and out is the identity.  An index is clamped to h_b - 1 / w_b - 1, which never binds below 2^26 rows or columns.
+ * raw: uint16 [B, hmax, wmax], row pitch wmax; nothing beyond (h_b, w_b) is read.  dims: int32 [B, 2] holding (h_b, w_b), or
+ * NULL for hmax x wmax everywhere.  out: float32 [B, H, W], may not alias raw.  frame_status: int32 [B] (nullable),
+ * DTFILL_READ_* bits, final when the stream reaches the end of the call.  workspace: ws_bytes >=
+ * dtfill_depth_read_workspace_bytes(B, H, W), 256-B aligned, no initialisation needed, nothing kept between calls.
+ * Asynchronous on `stream`; no allocation.
+ * Returns DTFILL_ERR_NULL for a NULL raw, out or workspace; DTFILL_ERR_SHAPE for B, hmax, wmax, H, W < 1, B > 65535,
+ * B*hmax*wmax >= 2^31 or B*H*W >= 2^31; DTFILL_ERR_WORKSPACE; all checked before any HIP call.
+ */
+#define DTFILL_READ_NOT_16BIT 1 /* every one of the frame's h_b x w_b values is <= 255 (the reference's
+                                   assert np.max(depth_png) > 255, taken before the resize); out[b] is still written */
+#define DTFILL_READ_BAD_DIMS  2 /* dims[b] outside [1, hmax] x [1, wmax]: out[b] is all +0.0 (and the other bit is not set) */
+size_t dtfill_depth_read_workspace_bytes(int B, int H, int W);
+int dtfill_depth_read(const uint16_t *raw, const int32_t *dims, int B, int hmax, int wmax, int H, int W, float *out,
+                      int32_t *frame_status, void *workspace, size_t ws_bytes, void *stream);
+
+/*
  * Error metrics of evaluation.py, one row per frame:
  *   DTFILL_METRICS_KITTI  Result.evaluate, evaluation.py:82-123 (metres -> mm for mse/rmse/mae, -> 1/km for
  *                         irmse/imae; the deltas stay 0 as in the reference);
