@@ -84,8 +84,15 @@ struct DepthEpilogue {
     int use_floor;
     float floor_;
 };
+// The drivers' depth floor np.squeeze(tf.nn.relu(d - 0.9) + 0.9) (eval_NYU.py:205, test.py:133), for the epilogue,
+// k_crop_floor and k_png16: float32 step by step -- (d - 0.9f) + 0.9f is NOT d in float32, so both roundings are kept.  A NaN
+// stays NaN, as max(x, 0) keeps it in TF's relu and in numpy; fmaxf would return the 0 and turn a NaN depth into the floor.
+__device__ __forceinline__ float depth_floor(float d, float floor_) {
+    const float t = __fsub_rn(d, floor_);
+    return __fadd_rn(t < 0.0f ? 0.0f : t, floor_);
+}
 __device__ __forceinline__ float depth_epilogue(float d, const DepthEpilogue &ep) {
-    return ep.use_floor ? __fadd_rn(fmaxf(__fsub_rn(d, ep.floor_), 0.0f), ep.floor_) : d;
+    return ep.use_floor ? depth_floor(d, ep.floor_) : d;
 }
 
 // The pass record: what the kernels of one pass share -- the batch's shape, the input, the outputs and the workspace (carve()

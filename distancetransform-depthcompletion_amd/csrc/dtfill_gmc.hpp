@@ -5,9 +5,12 @@
 // One step of the reference's windowed nearest fill: over the ts x ts window (zero padding, as
 // tf.image.extract_patches(padding='SAME')), s = mask * w with w = ts - |di| - |dj| (net.py:71-81);
 // out = (sum of the inputs at the positions where s equals the window maximum) / (1e-6 + their count)
-// (net.py:91-93).  mask == nullptr: the mask is (data > 0.001f), what the reference feeds to the next step
-// (net.py:95-96).  float32; the sum runs over the taps in row-major order, a new maximum restarts it, so
-// the additions are exactly those of "sum over the selected taps in order".
+// (net.py:91-93).  The maximum runs over all ts^2 taps, padding included, and starts at -inf: any finite mask is
+// legal, negative ones included (a NaN mask tap is never selected).  An input is added only where it is selected;
+// net.py's sum(data * selected) would make every window that holds a +-inf or NaN input NaN (include/dtfill.h).
+// mask == nullptr: the mask is (data > 0.001f), what the reference feeds to the next step (net.py:95-96).
+// float32; the sum runs over the taps in row-major order, a new maximum restarts it, so the additions are exactly
+// those of "sum over the selected taps in order".
 // One block per 16 x 64 tile; data and mask tiles with a (ts-1)/2 halo in LDS.  (GM_TW = 128 fetches a third less -- a staged
 // row segment of 134 floats straddles five 128-byte lines for its four, one of 70 four for two -- and takes the same time on the
 // KITTI crop: the first step is bound by its instructions.  64 divides 1216.)
@@ -168,8 +171,8 @@ __global__ __launch_bounds__(256) void k_gmc7(const float *__restrict__ data, co
         emit(r, c, acc, cnt);
         return false;
     };
-    auto full = [&](int r, int c) {
-        float mx = 0.0f, acc = 0.0f, cnt = 0.0f;
+    auto full = [&](int r, int c) {  // (the maximum starts at -inf: a window of negative weights selects its largest one)
+        float mx = -INFINITY, acc = 0.0f, cnt = 0.0f;
 #pragma unroll
         for (int i = 0; i < 7; ++i) {
 #pragma unroll
@@ -258,8 +261,9 @@ __global__ __launch_bounds__(256) void k_gmc(const float *__restrict__ data, con
         const int r = k / GM_TW, c = k - r * GM_TW;
         const int gi = r0 + r, gj = c0 + c;
         if (gi >= H || gj >= W) continue;
-        float mx = 0.0f, acc = 0.0f, cnt = 0.0f;
-        // pass 1: the window maximum of mask * w (max over exact small products: order does not matter)
+        float mx = -INFINITY, acc = 0.0f, cnt = 0.0f;
+        // pass 1: the window maximum of mask * w over all ts^2 taps, padding included (max over exact small products: order
+        // does not matter; fmaxf skips a NaN product, so a NaN mask tap is never selected)
         for (int i = 0; i < ts; ++i)
             for (int j = 0; j < ts; ++j) {
                 const float w = (float)(ts - abs(i - half) - abs(j - half));

@@ -2,12 +2,6 @@
 // error metrics.  Part of libdtfill.so; included by dtfill.hip inside its anonymous namespace.
 #pragma once
 
-// depth floor of the drivers: np.squeeze(tf.nn.relu(d - 0.9) + 0.9) (eval_NYU.py:205, test.py:133).  Float32
-// step by step -- (d - 0.9f) + 0.9f is NOT d in float32, so the two roundings are kept.
-__device__ __forceinline__ float depth_floor(float d, float floor_) {
-    return __fadd_rn(fmaxf(__fsub_rn(d, floor_), 0.0f), floor_);
-}
-
 // ------------------------------------------------------------------------------------------------
 // k_crop_floor: out[b, i, j] = f(x[b, r0 + i, c0 + j]); f = depth floor if use_floor, identity otherwise.
 // demo.py:292-293 (rows 96: of a KITTI frame), eval_NYU.py:202-205 ([6:234, 8:312] of an NYU frame; the
@@ -26,7 +20,9 @@ __global__ __launch_bounds__(256) void k_crop_floor(const float *__restrict__ x,
 
 // ------------------------------------------------------------------------------------------------
 // k_png16: test.py:133-148.  depth floor, clip to [lo, hi], pad_top copies of the first row on top, * scale,
-// C cast to uint16 (numpy astype).  out is [B, pad_top + H, W].
+// C cast to uint16 (numpy astype).  out is [B, pad_top + H, W].  A NaN depth passes the floor and the clip as NaN
+// (tf.clip_by_value = minimum(maximum(v, lo), hi) keeps it) and is written as 0: converting NaN to an integer is
+// undefined in C++, and numpy's NaN cast is platform-defined.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_png16(const float *__restrict__ x, int H, int W, int pad_top, int use_floor,
                                                float floor_, float lo, float hi, float scale,
@@ -38,16 +34,19 @@ __global__ __launch_bounds__(256) void k_png16(const float *__restrict__ x, int 
     for (int j = blockIdx.x * 256 + threadIdx.x; j < W; j += gridDim.x * 256) {
         float v = src[j];
         if (use_floor) v = depth_floor(v, floor_);
-        v = fminf(fmaxf(v, lo), hi);  // tf.clip_by_value
-        dst[j] = (unsigned short)(int)__fmul_rn(v, scale);
+        v = v < lo ? lo : v;  // tf.clip_by_value, NaN kept (fmaxf / fminf would map it to lo)
+        v = v > hi ? hi : v;
+        dst[j] = v != v ? (unsigned short)0 : (unsigned short)(int)__fmul_rn(v, scale);
     }
 }
 
 // ------------------------------------------------------------------------------------------------
 // Metrics: evaluation.py:82-123 (Result.evaluate, KITTI: metres -> mm / km) and :196-239
 // (Result_NYU.evaluate: no unit change, mae is RELATIVE, + the three delta accuracies).  Per element the
-// float32 operations of the numpy expressions, one rounding each (no contraction); the means accumulate in
-// float64 in a fixed order (numpy: float32 pairwise), so results are reproducible run to run.
+// float32 operations of the numpy expressions, one rounding each; the means accumulate in float64 in a fixed
+// order (numpy: float32 pairwise), so results are reproducible run to run.  No contraction: plain operators
+// under fp contract(off).  (HIP's __fmul_rn / __fsub_rn are plain operators too, so they do NOT keep the
+// compiler's default -ffp-contract=fast-honor-pragmas from fusing 1000 * o - 1000 * t into an FMA.)
 // Stage 1: M_NB blocks per frame write partial sums; stage 2: one wave per frame adds them and finishes.
 // ------------------------------------------------------------------------------------------------
 constexpr int M_NB = 64;   // partial-sum blocks per frame
@@ -57,6 +56,7 @@ constexpr int M_NOUT = 9;  // mse, rmse, mae, irmse, imae, delta1, delta2, delta
 template <int KIND>  // 0 = KITTI (Result), 1 = NYU (Result_NYU)
 __global__ __launch_bounds__(256) void k_metrics_part(const float *__restrict__ output, const float *__restrict__ target,
                                                       long long n, double *__restrict__ part) {
+#pragma clang fp contract(off)
     const int b = blockIdx.y;
     const float *o_ = output + (size_t)b * n, *t_ = target + (size_t)b * n;
     double s[M_NS];
@@ -80,20 +80,20 @@ __global__ __launch_bounds__(256) void k_metrics_part(const float *__restrict__ 
             const float ov = valid ? o[u] : 1.0f, tv = valid ? t[u] : 1.0f;
             float diff, io, it, rel = 0.0f, ratio = 1.0f;
             if (KIND == 0) {
-                diff = fabsf(__fsub_rn(__fmul_rn(1000.0f, ov), __fmul_rn(1000.0f, tv)));  // :89-92
-                io = __frcp_rn(__fmul_rn(0.001f, ov));                                    // :115-116
-                it = __frcp_rn(__fmul_rn(0.001f, tv));
+                diff = fabsf(1000.0f * ov - 1000.0f * tv);  // :89-92
+                io = 1.0f / (0.001f * ov);                  // :115-116
+                it = 1.0f / (0.001f * tv);
             } else {
-                diff = fabsf(__fsub_rn(ov, tv));  // :203-206
-                rel = __fdiv_rn(diff, tv);        // :210 mae = mean(abs_diff / target)
-                ratio = fmaxf(__fdiv_rn(ov, tv), __fdiv_rn(tv, ov));  // :217
-                io = __frcp_rn(ov);               // :232-233
-                it = __frcp_rn(tv);
+                diff = fabsf(ov - tv);  // :203-206
+                rel = diff / tv;        // :210 mae = mean(abs_diff / target)
+                ratio = fmaxf(ov / tv, tv / ov);  // :217
+                io = 1.0f / ov;         // :232-233
+                it = 1.0f / tv;
             }
-            const float idiff = fabsf(__fsub_rn(io, it));
-            s[0] += (double)__fmul_rn(diff, diff);
+            const float idiff = fabsf(io - it);
+            s[0] += (double)(diff * diff);
             s[1] += (double)(KIND == 0 ? diff : rel);
-            s[2] += (double)__fmul_rn(idiff, idiff);
+            s[2] += (double)(idiff * idiff);
             s[3] += (double)idiff;
             if (KIND == 1) {
                 s[4] += (valid && ratio < 1.25f) ? 1.0 : 0.0;  // :218-220

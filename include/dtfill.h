@@ -161,6 +161,11 @@ int dtfill_outlier_removal(const float *x, int B, int H, int W, float *out, void
  * create_weight_matrix, net.py:71-81): the in-network windowed nearest fill.  Step k: over the
  * table_size^2 window (zero padding), s = mask * (table_size - |di| - |dj|); out = sum of the inputs where s
  * equals its window maximum / (1e-6 + their count); the next step's mask is (out > 0.001).
+ * The maximum runs over all table_size^2 taps, the padding's included: any finite mask is legal, negative
+ * values included (a window whose every product is negative selects its largest one); a NaN mask tap is never
+ * selected.  Non-finite data deviates from net.py on purpose: an input is added only where it is selected,
+ * while net.py's sum(data * selected) makes every window that holds a +-inf or NaN input NaN (inf * 0).
+ * Following net.py there would stop a pixel's value from being carried on through the later steps.
  * data, mask: float32 [B,H,W] (the reference's [B,H,W,1]); out2/out3/out4: the reference's lidar_2..4
  * (those beyond scale_num may be NULL); lidar_1 is the input itself.  table_size odd, <= 15; scale_num 1..4.
  * float32; the window sum is accumulated in tap (row-major) order.
@@ -178,7 +183,11 @@ int dtfill_generate_multi_channel(const float *data, const float *mask, int B, i
  * x: float32 [B,H,W]; out: float32 [B, r1-r0, c1-c0], may not alias x.
  *
  * dtfill_png16: test.py:133-148 -- depth floor (if use_floor), clip to [lo, hi] (0, 100), pad_top (96) copies
- * of the first row on top, * scale (256), cast to uint16.  out: uint16 [B, pad_top+H, W].
+ * of the first row on top, * scale (256), cast to uint16.  out: uint16 [B, pad_top+H, W].  Defined for
+ * lo * scale and hi * scale within [0, 65535].
+ *
+ * NaN: the depth floor keeps a NaN depth NaN (relu = max(x, 0), as in TF and numpy), here and in
+ * dtfill_batch_epilogue(); dtfill_png16 clips it to NaN and writes it as 0.
  */
 int dtfill_crop_floor(const float *x, int B, int H, int W, int r0, int r1, int c0, int c1, int use_floor, float floor_,
                       float *out, void *stream);
@@ -244,7 +253,8 @@ int dtfill_depth_read(const uint16_t *raw, const int32_t *dims, int B, int hmax,
  *                         delta1..3 = mean(max(o/t, t/o) < 1.25^k)).
  * Elements with output > 0.01 and target > 0.01 count.  Per element the float32 arithmetic of the numpy
  * expressions; the means accumulate in float64 in a fixed order (numpy: float32 pairwise sums), so a result is
- * reproducible and within ~1e-6 relative of numpy's.  No valid element: NaN (numpy's mean of nothing).
+ * reproducible, within ~1e-13 relative of the exact (math.fsum) mean of those float32 terms, and within ~1e-6
+ * relative of numpy's.  count and delta1..3 are exact.  No valid element: NaN (numpy's mean of nothing).
  * output, target: float32 [B, n] device pointers; out: float64 [B, DTFILL_METRICS_N] device pointer, columns
  * mse, rmse, mae, irmse, imae, delta1, delta2, delta3, count.  workspace: device scratch of at least
  * dtfill_metrics_workspace_bytes(B) bytes.

@@ -119,12 +119,12 @@ def Distance_Transform(lidar, src_thr=0.001, val_thr=0.1):
 def generate_multi_channel(lidar_data, lidar_mask, table_size=7, scale_num=4):
     """net.py:83-122 restated (the in-network windowed nearest fill every model class
     carries, weights from create_weight_matrix net.py:71-81).  TensorFlow is absent here: PARITY UNPINNED.
-    One step: over the table_size^2 window (zero padding, extract_patches padding='SAME'), s = mask * w with
-    w = table_size - |di| - |dj|; the output is the sum of the inputs at the positions where s equals its
-    window maximum, divided by (1e-6 + their count) -- including the all-zero case, where every position
-    (padding too) ties at 0.  The next step's mask is (output > 0.001).  float32 throughout; the window sum
-    is accumulated in tap (row-major) order -- TF's reduction order is unspecified, so against a real TF
-    this is exact only up to float32 summation order.
+    One step (gmc_step): over the table_size^2 window (zero padding, extract_patches padding='SAME'), s = mask * w
+    with w = table_size - |di| - |dj|; the output is the sum of the inputs at the positions where s equals its
+    window maximum over all the taps, divided by (1e-6 + their count) -- including the all-zero case, where every
+    position (padding too) ties at 0, and windows of negative weights, where the largest one wins.  The next step's
+    mask is (output > 0.001).  float32 throughout; the window sum is accumulated in tap (row-major) order -- TF's
+    reduction order is unspecified, so against a real TF this is exact only up to float32 summation order.
     lidar_data, lidar_mask: [B,H,W,1] (or [B,H,W]).  Returns (lidar_1, .., lidar_4) like the reference,
     None for the scales beyond scale_num."""
     data = np.asarray(lidar_data, np.float32)
@@ -132,26 +132,33 @@ def generate_multi_channel(lidar_data, lidar_mask, table_size=7, scale_num=4):
     squeeze_c = data.ndim == 4
     if squeeze_c:
         data, mask = data[..., 0], mask[..., 0]
-    half = (table_size - 1) // 2
     outs = [np.asarray(lidar_data, np.float32)]
     for _ in range(scale_num - 1):
-        B, H, W = data.shape
-        pd = np.pad(data, ((0, 0), (half, half), (half, half)))
-        pm = np.pad(mask, ((0, 0), (half, half), (half, half)))
-        taps = [(i, j, np.float32(table_size - abs(i - half) - abs(j - half))) for i in range(table_size) for j in range(table_size)]
-        mx = np.zeros((B, H, W), np.float32)
-        for i, j, w in taps:
-            mx = np.maximum(mx, pm[:, i : i + H, j : j + W] * w)
-        acc = np.zeros((B, H, W), np.float32)
-        cnt = np.zeros((B, H, W), np.float32)
-        for i, j, w in taps:
-            sel = (pm[:, i : i + H, j : j + W] * w) == mx
-            acc = np.where(sel, (acc + pd[:, i : i + H, j : j + W]).astype(np.float32), acc)
-            cnt = cnt + sel.astype(np.float32)
-        data = (acc / (np.float32(0.000001) + cnt)).astype(np.float32)
+        data = gmc_step(data, mask, table_size)[0]
         mask = (data > np.float32(0.001)).astype(np.float32)
         outs.append(data[..., None] if squeeze_c else data)
     return tuple(outs + [None] * (4 - len(outs)))
+
+
+def gmc_step(data, mask, table_size=7):
+    """One step of generate_multi_channel on [B,H,W] float32 data and mask.  Returns (out, count): count is the number of
+    selected taps per pixel (float32).  The window maximum starts at -inf; np.fmax skips a NaN product, so a NaN mask tap is
+    never selected, as in the kernels."""
+    B, H, W = data.shape
+    half = (table_size - 1) // 2
+    pd = np.pad(data, ((0, 0), (half, half), (half, half)))
+    pm = np.pad(mask, ((0, 0), (half, half), (half, half)))
+    taps = [(i, j, np.float32(table_size - abs(i - half) - abs(j - half))) for i in range(table_size) for j in range(table_size)]
+    mx = np.full((B, H, W), -np.inf, np.float32)
+    for i, j, w in taps:
+        mx = np.fmax(mx, pm[:, i : i + H, j : j + W] * w)
+    acc = np.zeros((B, H, W), np.float32)
+    cnt = np.zeros((B, H, W), np.float32)
+    for i, j, w in taps:
+        sel = (pm[:, i : i + H, j : j + W] * w) == mx
+        acc = np.where(sel, (acc + pd[:, i : i + H, j : j + W]).astype(np.float32), acc)
+        cnt = cnt + sel.astype(np.float32)
+    return (acc / (np.float32(0.000001) + cnt)).astype(np.float32), cnt
 
 
 _DIAMOND7 = np.array([[abs(i - 3) + abs(j - 3) <= 3 for j in range(7)] for i in range(7)])
@@ -221,7 +228,7 @@ def edt_l2(mask):
 # ---- post-fill steps of the drivers and the metrics (8f-3) ----------------------------
 
 def depth_floor(d, floor=0.9):
-    """relu(d - 0.9) + 0.9 on float32, one rounding per step (eval_NYU.py:205, test.py:133)."""
+    """relu(d - 0.9) + 0.9 on float32, one rounding per step (eval_NYU.py:205, test.py:133); np.maximum keeps a NaN."""
     d = np.asarray(d, np.float32)
     f = np.float32(floor)
     return (np.maximum(d - f, np.float32(0.0)) + f).astype(np.float32)
@@ -238,12 +245,14 @@ def nyu_eval_crop(frame):
 
 
 def depth_to_png16(depth, pad_top=96, floor=0.9, lo=0.0, hi=100.0, scale=256.0):
-    """test.py:133-148: depth floor, clip, pad_top copies of row 0 on top, * 256, astype(uint16)."""
+    """test.py:133-148: depth floor, clip, pad_top copies of row 0 on top, * 256, astype(uint16).  A NaN depth stays NaN
+    through the floor and the clip and is written as 0 (numpy's cast of NaN to an integer is platform-defined)."""
     d = depth_floor(np.squeeze(np.asarray(depth, np.float32)), floor)
     d = np.clip(d, np.float32(lo), np.float32(hi))
     top = np.tile(d[0, :], (pad_top, 1)).astype(np.float32)
     d = np.vstack((top, d)) if pad_top else d
-    return (d * np.float32(scale)).astype(np.uint16)
+    d = d * np.float32(scale)
+    return np.where(np.isnan(d), np.float32(0.0), d).astype(np.uint16)
 
 
 def _both_valid(output, target):

@@ -756,7 +756,9 @@ def test_concurrent_streams_and_threads(pkg, oracle):
 
 def test_generate_multi_channel_vs_oracle(pkg, oracle):
     """net.py:83-122.  Same float32 operations in the same order as the restated oracle, so
-    equality is exact (against a real TF the sum order is the only freedom; tolerance 1e-6 relative there)."""
+    equality is exact.  Against a real TF two things differ: the sum order, and windows that hold a +-inf or NaN input,
+    which net.py's sum(data * selected) makes NaN and the product does not (include/dtfill.h).  tests/test_gpu_side_refs.py
+    holds the device against a literal statement of net.py on finite data."""
     rng = np.random.default_rng(21)
     for (B, H, W), ts, sn in [((2, 64, 200), 7, 4), ((1, 256, 1216), 7, 4), ((1, 9, 11), 5, 3), ((3, 5, 4), 3, 2)]:
         x = np.where(rng.random((B, H, W, 1)) < 0.05, rng.uniform(1, 80, (B, H, W, 1)), 0).astype(np.float32)
