@@ -187,17 +187,24 @@ __device__ __forceinline__ bool fused_walk_epilogue(
     // range check drops.  So every batch issues the same stores, branch-free, and the compiler's vmcnt waits for a batch's
     // gathers are exact: they no longer wait for the label / distance stores issued behind them (in-order vmcnt; with
     // branches around the stores it has to assume the path without them and wait for all but seven).
+    // A descriptor's records end with the tile's last row: a slot's rows below the tile (the last row group of a tile whose
+    // height is no multiple of F_EB; still cells of the window, read and walked) are dropped the same way, without a compare.
     // the depth output may drop the first ep.row0 rows (then frames are H - row0 rows apart)
-    const u32 dcrop = (u32)(ep.row0 * W) << 2;  // bytes of a frame's dropped rows; a pixel of them wraps past the records
-    const u32 fbytes = (u32)(H * W) << 2;
+    // bytes of a frame's dropped rows; a pixel of them wraps past the records (the plain instances subtract nothing)
+    const u32 dcrop = EPI ? (u32)(ep.row0 * W) << 2 : 0u;
+    // r0 + th <= H: never past the frame.  (Block-uniform, but a premarked tile's span comes out of LDS: the record counts
+    // are said to be uniform below, or every store is wrapped in a loop over the lanes' descriptors)
+    const u32 tbytes = (u32)((r0 + th) * W) << 2;
+    auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
     const auto rs_d = __builtin_amdgcn_make_buffer_rsrc(out_depth ? out_depth + (size_t)b * (H - ep.row0) * W : nullptr, 0,
-                                                        out_depth ? (int)(fbytes - dcrop) : 0, 0x00020000);
-    const auto rs_t = __builtin_amdgcn_make_buffer_rsrc(out_dt ? out_dt + fo : nullptr, 0, out_dt ? (int)fbytes : 0, 0x00020000);
-    const auto rs_i = __builtin_amdgcn_make_buffer_rsrc(out_index ? out_index + fo : nullptr, 0, out_index ? (int)fbytes : 0, 0x00020000);
-    constexpr u32 OFF_NONE = 0x80000000u;  // past every frame's records (a frame has < 2^26 pixels)
+                                                        uni(out_depth && tbytes > dcrop ? (int)(tbytes - dcrop) : 0), 0x00020000);
+    const auto rs_t = __builtin_amdgcn_make_buffer_rsrc(out_dt ? out_dt + fo : nullptr, 0, uni(out_dt ? (int)tbytes : 0), 0x00020000);
+    const auto rs_i = __builtin_amdgcn_make_buffer_rsrc(out_index ? out_index + fo : nullptr, 0, uni(out_index ? (int)tbytes : 0), 0x00020000);
+    constexpr u32 OFF_NONE = 0x80000000u;  // past every frame's records (a frame has < 2^26 pixels), with up to F_EB rows added too
     const char *tab = reinterpret_cast<const char *>(s_tab);
     auto step_of = [&](int c) { return (int)*reinterpret_cast<const short *>(tab + c); };
     const int src_base = wr0 * W + wc0;  // frame offset of window cell (0,0) (may be negative)
+    const int wrest = W - F_P;           // frame offset of an s_par position: src_base + pos + row * wrest
     const u32 last_px = (u32)(H * W - 1);
     bool overflow = false;
     // STREAM (rows of whole 128-byte lines: W % 32 == 0, aligned outputs, tile columns in whole lines): a wave's run of
@@ -215,18 +222,19 @@ __device__ __forceinline__ bool fused_walk_epilogue(
     float p_val[F_EB];  // the batch whose gathers are in flight
 #pragma unroll
     for (int e = 0; e < F_EB; ++e) p_val[e] = 0.0f;
-    u32 p_opix = 0, p_ok = 0;
-    // p_opix is a BYTE offset (< 2^32: a frame has < 2^26 pixels): descriptor base + 32-bit vector offset
+    // A batch's store offsets are computed once, at its head, and kept in registers: BYTE offsets (< 2^32: a frame has < 2^26
+    // pixels; descriptor base + 32-bit vector offset), OFF_NONE for a pixel that is not stored.  p_o: those of the batch in flight.
+    // OFF_NONE - dcrop is still past every frame's records.
+    u32 p_o[F_EB];
+#pragma unroll
+    for (int e = 0; e < F_EB; ++e) p_o[e] = OFF_NONE;
     auto retire = [&]() {
 #pragma unroll
-        for (int e = 0; e < F_EB; ++e) {
-            const u32 o = p_opix + (u32)e * w4 - dcrop;
-            put(rs_d, ((p_ok >> e) & 1u) ? o : OFF_NONE, __float_as_uint(EPI ? depth_epilogue(p_val[e], ep) : p_val[e]));
-        }
+        for (int e = 0; e < F_EB; ++e) put(rs_d, p_o[e] - dcrop, __float_as_uint(EPI ? depth_epilogue(p_val[e], ep) : p_val[e]));
     };
     for (int sb = 0; sb < nslots; sb += NT) {
         int pos[F_EB], step[F_EB], code[F_EB];  // pos = row * F_P + col: byte index in s_par
-        u32 ok = 0, home0, opix0;   // home0: window row << 16 | window column of the slot's first pixel
+        u32 o[F_EB], home0;   // home0: window row << 16 | window column of the slot's first pixel
         FPROF(prof.mark(5); ++prof.n[2]);
         {
             const int L = sb + (int)threadIdx.x, Lc = min(L, nslots - 1);
@@ -235,17 +243,28 @@ __device__ __forceinline__ bool fused_walk_epilogue(
             const int g = (int)(((float)Lc + 0.5f) * inv_tw);
             const int tc = Lc - __mul24(g, tw), trb = g * F_EB;
             home0 = (u32)(FR + trb) << 16 | (u32)(FR + tc);
-            opix0 = (u32)(__mul24(r0 + trb, W) + c0 + tc) << 2;  // byte offset; 24-bit multiplies are full rate (H, W < 8192)
+            // byte offset; 24-bit multiplies are full rate (H, W < 8192).  A lane without a slot stores nothing
+            u32 op = L < nslots ? (u32)(__mul24(r0 + trb, W) + c0 + tc) << 2 : OFF_NONE;
             const int pos0 = __mul24(FR + trb, F_P) + FR + tc;
-            const int nv = L < nslots ? th - trb : 0;  // the slot's rows inside the tile (the rest: still cells of the window, read and dropped)
+            unsigned long long und = 0;  // lanes with an undecided cell among their eight
 #pragma unroll
             for (int e = 0; e < F_EB; ++e) {
-                const bool valid = e < nv;
                 pos[e] = pos0 + e * F_P;
                 code[e] = s_par[pos[e]];
-                ok |= (valid && code[e] != F_NONE) ? (1u << e) : 0u;
-                // undecidable here: the any-distance kernels take the pixel's row (found again below, off the common path)
-                overflow |= valid && code[e] == F_NONE;
+                und |= __ballot(code[e] == F_NONE);
+                o[e] = code[e] != F_NONE ? op : OFF_NONE;  // (a row below the tile: past the records)
+                // The offset is wanted HERE, in a register, and the next row's as a running add: left alone the compiler
+                // sinks the select below the walk and keeps the eight code bytes and the compares' mask pairs alive instead,
+                // and turns the adds into eight uniform multiples of the pitch (scalar registers the loop does not have).
+                asm volatile("" : "+v"(o[e]), "+v"(op));
+                op += w4;
+            }
+            // undecidable here: the any-distance kernels take the pixel's row (found again below, off the common path).
+            // Wave-uniform and rare: only now does it matter whether the cell is one of the slot's rows inside the tile
+            if (und) {
+                const int nv = L < nslots ? th - trb : 0;
+#pragma unroll
+                for (int e = 0; e < F_EB; ++e) overflow |= e < nv && code[e] == F_NONE;
             }
         }
         // Unconditional hops: sources and undecided cells carry the step (0,0), so a walker that has
@@ -272,22 +291,36 @@ __device__ __forceinline__ bool fused_walk_epilogue(
 #pragma unroll
             for (int e = 0; e < F_EB; ++e) code[e] = s_par[pos[e]];
         }
-        FPROF(prof.mark(4); for (int e = 0; e < F_EB; ++e) prof.n[3] += __popcll(__ballot((ok >> e) & 1u)));
-        int pr[F_EB], pc[F_EB];
-        u32 goff[F_EB];
+        FPROF(prof.mark(4); for (int e = 0; e < F_EB; ++e) prof.n[3] += __popcll(__ballot(o[e] != OFF_NONE)));
+        int pr[F_EB];
+        u32 rc[F_EB], goff[F_EB];  // rc = row << 16 | column of the root in the window
         int lab[F_EB];
+        // a decided chain ends on a source inside the in-image window.  F_RG pixels at a time: their rank records are read
+        // together (independent LDS reads, one wait for the group) and the popcounts follow
+        constexpr int F_RG = 4;
 #pragma unroll
-        for (int e = 0; e < F_EB; ++e) {
-            // a decided chain ends on a source inside the in-image window
+        for (int h = 0; h < F_EB; h += F_RG) {
+            int bp[F_RG], ri[F_RG];
+            uint2 rw[F_RG];
             // pos / F_P by a 24-bit multiply: 196 * 5350 / 2^20 = 1 + 2.3e-5, pos / 196 < 128, so the product is at most 0.003 above
             // the quotient, whose fraction is at most 195 / 196: same integer part (three full-rate instructions with the remainder;
             // the integer division is a quarter-rate v_mul_hi_u32)
             static_assert(F_P == 196 && F_WHM * F_P < (1 << 15), "the reciprocal below is F_P's");
-            pr[e] = (int)(__umul24((u32)pos[e], 5350u) >> 20);
-            pc[e] = pos[e] - __mul24(pr[e], F_P);
-            const int bitpos = sh + pc[e];  // bit index in the row's image-aligned bit string, from word w0
-            const uint2 rw = s_rw[pr[e] * 8 + (bitpos >> 5)];  // {32 source bits, 1 + sources before them in the frame}
-            lab[e] = (int)rw.y + __popc(rw.x & ((1u << (bitpos & 31)) - 1u));
+#pragma unroll
+            for (int k = 0; k < F_RG; ++k) {
+                const int e = h + k;
+                pr[e] = (int)(__umul24((u32)pos[e], 5350u) >> 20);
+                rc[e] = __umul24((u32)pr[e], 65536u - F_P) + (u32)pos[e];  // pos = row * F_P + column: one multiply-add
+                // bits 0..7: the bit index in the row's image-aligned bit string, from word w0 (sh + column < 256);
+                // the row above them does not matter to the two bit-field extracts
+                bp[k] = (int)(rc[e] + (u32)sh);
+                ri[k] = pr[e] * 8 + (int)__builtin_amdgcn_ubfe((u32)bp[k], 5u, 3u);
+            }
+#pragma unroll
+            for (int k = 0; k < F_RG; ++k) rw[k] = s_rw[ri[k]];  // {32 source bits, 1 + sources before them in the frame}
+            // the bits below the pixel's: v_bfe_u32 takes the low five bits of its width operand
+#pragma unroll
+            for (int k = 0; k < F_RG; ++k) lab[h + k] = (int)rw[k].y + __popc(__builtin_amdgcn_ubfe(rw[k].x, 0u, (u32)bp[k]));
         }
         // depth_list[label-1] (tools.py:26).  A decided pixel has label >= 1, so the numpy wrap of index -1
         // cannot occur here.  Masks agree (block-uniform): the label-th value is x at the source, and
@@ -296,14 +329,19 @@ __device__ __forceinline__ bool fused_walk_epilogue(
         // out of range reads garbage at worst).
         if (!misaligned) {
 #pragma unroll
-            for (int e = 0; e < F_EB; ++e) goff[e] = min((u32)(src_base + __mul24(pr[e], W) + pc[e]), last_px) << 2;  // byte offset
+            for (int e = 0; e < F_EB; ++e) {
+                u32 t = (u32)(__mul24(pr[e], wrest) + pos[e]);
+                asm("" : "+v"(t));  // one multiply-add, one add-shift: an instruction reads one scalar register, summed the other way round they are three
+                goff[e] = min((t + (u32)src_base) << 2, last_px << 2);  // byte offset
+            }
         } else {
             bool bad = false;
+            const int nv = th + FR - (int)(home0 >> 16);  // the slot's rows inside the tile (a lane without a slot: no offsets at all)
 #pragma unroll
             for (int e = 0; e < F_EB; ++e) {
                 const int idx = lab[e] - 1;
                 const bool oob = idx >= nval;
-                bad |= ((ok >> e) & 1u) && oob;
+                bad |= o[e] != OFF_NONE && e < nv && oob;
                 goff[e] = (oob ? 0u : min((u32)idx, last_px)) << 2;
             }
             if (bad && out_depth) atomicOr(frame_status + b, DTFILL_FRAME_INDEX_ERROR);
@@ -311,14 +349,12 @@ __device__ __forceinline__ bool fused_walk_epilogue(
         retire();  // the previous batch: its gathers had the whole walk above to arrive
 #pragma unroll
         for (int e = 0; e < F_EB; ++e) p_val[e] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(gbase) + goff[e]);
-        p_opix = opix0;
-        p_ok = ok;
 #pragma unroll
         for (int e = 0; e < F_EB; ++e) {
-            const u32 o = ((ok >> e) & 1u) ? opix0 + (u32)e * w4 : OFF_NONE;
-            put(rs_i, o, (u32)lab[e]);
+            p_o[e] = o[e];
+            put(rs_i, o[e], (u32)lab[e]);
             // L1 distance to the nearest source IS d: |drow| + |dcol| of the two 16-bit halves in one instruction
-            put(rs_t, o, __float_as_uint((float)__builtin_amdgcn_sad_u16((u32)pr[e] << 16 | (u32)pc[e], home0 + ((u32)e << 16), 0u)));
+            put(rs_t, o[e], __float_as_uint((float)__builtin_amdgcn_sad_u16(rc[e], home0 + ((u32)e << 16), 0u)));
         }
     }
     FPROF(prof.mark(5));
