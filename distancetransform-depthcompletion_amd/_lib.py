@@ -42,6 +42,8 @@ SYMBOLS = (
     "dtfill_pass_stats",
     "dtfill_outlier_removal",
     "dtfill_generate_multi_channel",
+    "dtfill_demo_multi_channel_workspace_bytes",
+    "dtfill_demo_multi_channel",
     "dtfill_crop_floor",
     "dtfill_png16",
     "dtfill_line_subsample_workspace_bytes",
@@ -113,6 +115,10 @@ def load():
     L.dtfill_outlier_removal.restype = ci
     L.dtfill_generate_multi_channel.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp]
     L.dtfill_generate_multi_channel.restype = ci
+    L.dtfill_demo_multi_channel_workspace_bytes.argtypes = [ci, ci, ci, ci]
+    L.dtfill_demo_multi_channel_workspace_bytes.restype = sz
+    L.dtfill_demo_multi_channel.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, sz, vp]
+    L.dtfill_demo_multi_channel.restype = ci
     L.dtfill_crop_floor.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp, vp]
     L.dtfill_crop_floor.restype = ci
     L.dtfill_png16.argtypes = [vp, ci, ci, ci, ci, ci, cf, cf, cf, cf, vp, vp]

@@ -76,6 +76,7 @@ namespace {
 #include "dtfill_l2.hpp"
 #include "dtfill_outlier.hpp"
 #include "dtfill_gmc.hpp"
+#include "dtfill_gmcv.hpp"
 #include "dtfill_post.hpp"
 #include "dtfill_lines.hpp"
 #include "dtfill_read.hpp"
@@ -389,6 +390,28 @@ inline LinesGrid lines_grid(int H, int W) {
     return LinesGrid{tpb, (T + tpb - 1) / tpb};
 }
 
+namespace {
+// dtfill_demo_multi_channel: out_1, then one launch per step (raws: the two workspace frames the raw steps alternate between)
+template <int FORM>
+void gmcv_launch(const float *lidar, const float *rgb, int C, int B, int H, int W, int ts, int scale_num, float sr,
+                        float *const *outs, float *const *raws, hipStream_t st) {
+    const size_t n = (size_t)B * H * W;
+    const int tx = (W + GM_TW - 1) / GM_TW, ty = (H + GM_TH - 1) / GM_TH;
+    const u32 ntiles = (u32)((size_t)tx * ty * B);  // (< 2^31: a tile holds a pixel)
+    const u32 grid = min(ntiles, 1u << 22);
+    k_gmcv_first<FORM><<<(unsigned)min((n + 255) / 256, (size_t)1 << 16), 256, 0, st>>>(lidar, rgb, C, n, sr, outs[0]);
+    const float *src = lidar;
+    for (int k = 1; k < scale_num; ++k) {
+        float *raw = k + 1 < scale_num ? raws[(k - 1) & 1] : nullptr;  // stored only if a later step reads it
+        if (ts == 7)
+            k_gmcv7<FORM><<<grid, 256, 0, st>>>(src, rgb, C, H, W, tx, ty, ntiles, sr, raw, outs[k]);
+        else
+            k_gmcv<FORM><<<grid, 256, 0, st>>>(src, rgb, C, H, W, ts, tx, ty, ntiles, sr, raw, outs[k]);
+        src = raw;
+    }
+}
+}  // namespace
+
 extern "C" {
 
 int dtfill_abi_version(void) { return DTFILL_ABI_VERSION; }
@@ -477,6 +500,47 @@ int dtfill_generate_multi_channel(const float *data, const float *mask, int B, i
         src = outs[k];
         msk = nullptr;  // the next step's mask is (previous output > 0.001)
     }
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+// B * H * W * ch < 2^31 for positive arguments, by division: the product itself may not fit 64 bits
+static bool gmcv_count_ok(int B, int H, int W, int ch) {
+    return B >= 1 && H >= 1 && W >= 1 && ch >= 1 && B <= 0x7fffffff / H / W / ch;
+}
+
+size_t dtfill_demo_multi_channel_workspace_bytes(int B, int H, int W, int scale_num) {
+    if (!gmcv_count_ok(B, H, W, 1) || scale_num < 1 || scale_num > 4) return 0;
+    // raw_k for the steps a later step reads (k = 2 .. scale_num - 1), at most two frames alive at a time
+    return (size_t)min(2, max(0, scale_num - 2)) * align256((size_t)B * H * W * sizeof(float));
+}
+
+int dtfill_demo_multi_channel(const float *lidar, const float *rgb, int C, int B, int H, int W, int table_size, int scale_num,
+                              float scale_range, float *out1, float *out2, float *out3, float *out4, void *workspace,
+                              size_t ws_bytes, void *stream) {
+    if (!lidar) return DTFILL_ERR_NULL;
+    if (table_size < 1 || (table_size & 1) == 0 || (table_size - 1) / 2 > GM_MAXHALF || scale_num < 1 || scale_num > 4)
+        return DTFILL_ERR_SHAPE;
+    if (!(scale_range != 0.0f) || !isfinite(scale_range) || (rgb && C < 1) || B < 1 || H < 1 || W < 1) return DTFILL_ERR_SHAPE;
+    if (!rgb) C = 0;
+    if (C >= 0x7fffffff || !gmcv_count_ok(B, H, W, C + 1)) return DTFILL_ERR_SHAPE;
+    float *outs[4] = {out1, out2, out3, out4};
+    for (int k = 0; k < scale_num; ++k)
+        if (!outs[k]) return DTFILL_ERR_NULL;
+    const size_t need = dtfill_demo_multi_channel_workspace_bytes(B, H, W, scale_num);
+    if (need && !workspace) return DTFILL_ERR_NULL;
+    if (need && (ws_bytes < need || ((uintptr_t)workspace & 255))) return DTFILL_ERR_WORKSPACE;
+    float *raws[2] = {nullptr, nullptr};  // raw_2 and raw_3, where a later step reads them
+    if (need) raws[0] = static_cast<float *>(workspace);
+    if (scale_num == 4) raws[1] = reinterpret_cast<float *>(static_cast<char *>(workspace) + need / 2);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    bool al16 = true;  // the one-store pixel of the three-channel image form needs 16-byte aligned outputs
+    for (int k = 0; k < scale_num; ++k) al16 &= ((uintptr_t)outs[k] & 15) == 0;
+    if (!rgb)
+        gmcv_launch<GV_PLAIN>(lidar, nullptr, 0, B, H, W, table_size, scale_num, scale_range, outs, raws, st);
+    else if (C == 3 && al16)
+        gmcv_launch<GV_RGB3>(lidar, rgb, C, B, H, W, table_size, scale_num, scale_range, outs, raws, st);
+    else
+        gmcv_launch<GV_RGBC>(lidar, rgb, C, B, H, W, table_size, scale_num, scale_range, outs, raws, st);
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 

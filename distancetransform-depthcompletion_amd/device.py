@@ -299,6 +299,39 @@ def generate_multi_channel_device(data, mask, table_size=7, scale_num=4):
     return tuple([data] + outs + [None] * (4 - scale_num))
 
 
+def demo_multi_channel_device(lidar, rgb=None, table_size=7, scale_range=90.0, scale_num=4):
+    """demo.py:108-149 (rgb None) / :151-198 on the device (include/dtfill.h, dtfill_demo_multi_channel).  lidar: contiguous
+    float32 CUDA tensor [B,H,W]; rgb: contiguous float32 CUDA tensor [B,H,W,C] or None.  Returns (out_1, .., out_4) with None
+    beyond scale_num: [B,H,W] = raw_k / scale_range without rgb, [B,H,W,C+1] = concat(rgb, raw_k / scale_range) /
+    scale_range with it.  Asynchronous on the current stream."""
+    _require_gpu()
+    if lidar.dtype != torch.float32 or not lidar.is_cuda or lidar.dim() != 3 or not lidar.is_contiguous():
+        raise ValueError("lidar must be a contiguous float32 CUDA tensor [B,H,W]")
+    B, H, W = lidar.shape
+    C = 0
+    if rgb is not None:
+        if rgb.dtype != torch.float32 or not rgb.is_cuda or rgb.dim() != 4 or not rgb.is_contiguous():
+            raise ValueError("rgb must be a contiguous float32 CUDA tensor [B,H,W,C]")
+        if tuple(rgb.shape[:3]) != (B, H, W) or rgb.device != lidar.device:
+            raise ValueError("rgb must hold lidar's frames: [%d,%d,%d,C] on %s" % (B, H, W, lidar.device))
+        C = rgb.shape[3]
+    if scale_num not in (1, 2, 3, 4):
+        raise ValueError("scale_num must be 1, 2, 3 or 4, got %r" % (scale_num,))
+    L = _lib.load()
+    nbytes = L.dtfill_demo_multi_channel_workspace_bytes(B, H, W, scale_num)
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=lidar.device)
+    off = (-ws.data_ptr()) % 256
+    shape = (B, H, W) if rgb is None else (B, H, W, C + 1)
+    outs = [torch.empty(shape, dtype=torch.float32, device=lidar.device) for _ in range(scale_num)]
+    ptrs = [o.data_ptr() for o in outs] + [None] * (4 - scale_num)
+    with torch.cuda.device(lidar.device):
+        _lib.check(L.dtfill_demo_multi_channel(lidar.data_ptr(), None if rgb is None else rgb.data_ptr(), C, B, H, W,
+                                               int(table_size), int(scale_num), float(scale_range), *ptrs,
+                                               ws.data_ptr() + off, nbytes,
+                                               torch.cuda.current_stream(lidar.device).cuda_stream))
+    return tuple(outs + [None] * (4 - scale_num))
+
+
 def _check_frames(t, what):
     if t.dtype != torch.float32 or not t.is_cuda or t.dim() != 3 or not t.is_contiguous():
         raise ValueError("%s must be a contiguous float32 CUDA tensor [B,H,W]" % what)

@@ -174,6 +174,53 @@ int dtfill_generate_multi_channel(const float *data, const float *mask, int B, i
                                   int scale_num, float *out2, float *out3, float *out4, void *stream);
 
 /*
+ * generate_multi_channel() and generate_multi_channel_with_image() of the reference's demo driver,
+ * solution_DeepNet/demo.py:108-149 and :151-198 (weights create_weight_matrix, demo.py:65-75): what demo.py runs with its
+ * default --model_type DT.  Not the net.py form above: the weights are powers of ten, the selection runs on data * w (the
+ * data is its own mask, nothing is re-masked between the steps, so a farther but larger depth can beat a nearer one),
+ * the divisor counts the non-zero selected inputs, and every output is divided by scale_range.
+ *
+ * lidar: float32 [B,H,W].  ts = table_size (odd, 1..15), raw_1 = lidar.  Step k (2..scale_num), per pixel, in float32:
+ *   taps   the ts x ts window over the zero-padded frame, as tf.image.extract_patches(padding='SAME') reads it, in
+ *          row-major order;
+ *   w      (float)10^(ts - |di| - |dj|): the double 10^e (exact for e <= 22) rounded to float32 once (exact for
+ *          e <= 10; 10^11 .. 10^15 are not);
+ *   p      d * w, one rounded multiply, contracted into nothing;
+ *   mx     the maximum of p over all ts^2 taps; padding taps count, with p = 0;
+ *   sel    p == mx;
+ *   sum    the float32 sum of d over the selected taps in tap order, starting from +0 (unselected taps may add +0: the
+ *          only trace is a -0 sum coming out as +0; the two compare equal, here and in every later step);
+ *   cnt    the number of selected taps with d != 0: it is 0 exactly when mx == 0;
+ *   raw_k  sum / (1e-6f + (float)cnt); an all-zero window gives 0 / 1e-6 = 0.
+ * The next step reads raw_k.  Outputs for k = 1..scale_num, sr = scale_range:
+ *   rgb == NULL   out_k float32 [B,H,W]     = raw_k / sr
+ *   rgb given     out_k float32 [B,H,W,C+1]: channels 0..C-1 = rgb / sr; channel C = (raw_k / sr) / sr, both roundings
+ *                 kept -- demo.py:172-173 divides the lidar channel, :198 the concatenated tensor again.  rgb: float32
+ *                 [B,H,W,C], channel-last.
+ * Every division is an IEEE-rounded division, not a multiply by a reciprocal.
+ * Defined for finite inputs with |d| * 10^ts finite.  Beyond that: a NaN product is never selected, and an input is added
+ * only where it is selected (demo.py's reduce_sum(data * selected) would make every window that holds a +-inf or NaN
+ * input NaN; the same deliberate deviation as dtfill_generate_multi_channel's); nothing faults.
+ * TensorFlow's reduce_sum does not document its summation order and the reference could not be run where this was
+ * written, so "tap order" is this library's contract, not a measured property of the reference: with one selected tap
+ * (the common case) every order gives the same bits; with more, TensorFlow may differ in the last place.
+ *
+ * out1..out4: those beyond scale_num may be NULL; none may alias lidar or rgb.  workspace: at least
+ * dtfill_demo_multi_channel_workspace_bytes(B,H,W,scale_num) bytes (at most two [B,H,W] float frames for the raw
+ * intermediates a later step reads; 0 for scale_num <= 2, when workspace may be NULL), 256-B aligned, the caller's, no
+ * initialisation needed, nothing kept between calls.  Asynchronous on `stream`.
+ * Returns, all checked before any HIP call: DTFILL_ERR_NULL for a NULL lidar, a NULL required output or a NULL workspace
+ * where one is needed; DTFILL_ERR_SHAPE for an even table_size or one outside 1..15, scale_num outside 1..4, scale_range
+ * zero or not finite, rgb given with C < 1, B, H or W < 1, or B*H*W*(C+1) >= 2^31 (C = 0 without rgb);
+ * DTFILL_ERR_WORKSPACE for a workspace that is too small or not aligned.
+ */
+size_t dtfill_demo_multi_channel_workspace_bytes(int B, int H, int W, int scale_num); /* 0 on a bad shape */
+int dtfill_demo_multi_channel(const float *lidar, const float *rgb /* nullable */, int C, int B, int H, int W,
+                              int table_size, int scale_num, float scale_range,
+                              float *out1, float *out2, float *out3, float *out4,
+                              void *workspace, size_t ws_bytes, void *stream);
+
+/*
  * What the reference's drivers do with a filled frame.
  *
  * dtfill_crop_floor: out[b, i, j] = f(x[b, r0+i, c0+j]) for rows [r0, r1), columns [c0, c1); f is the depth
