@@ -24,6 +24,10 @@ def __getattr__(name):
 
         mod = importlib.import_module(__name__ + ".device")
         return mod if name == "device" else getattr(mod, name)
+    if name == "autograd":  # the differentiable net.py form, <package>.autograd.generate_multi_channel (imports torch too)
+        import importlib
+
+        return importlib.import_module(__name__ + ".autograd")
     raise AttributeError(name)
 
 

@@ -42,6 +42,8 @@ SYMBOLS = (
     "dtfill_pass_stats",
     "dtfill_outlier_removal",
     "dtfill_generate_multi_channel",
+    "dtfill_generate_multi_channel_backward_workspace_bytes",
+    "dtfill_generate_multi_channel_backward",
     "dtfill_demo_multi_channel_workspace_bytes",
     "dtfill_demo_multi_channel",
     "dtfill_crop_floor",
@@ -115,6 +117,10 @@ def load():
     L.dtfill_outlier_removal.restype = ci
     L.dtfill_generate_multi_channel.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp]
     L.dtfill_generate_multi_channel.restype = ci
+    L.dtfill_generate_multi_channel_backward_workspace_bytes.argtypes = [ci, ci, ci, ci]
+    L.dtfill_generate_multi_channel_backward_workspace_bytes.restype = sz
+    L.dtfill_generate_multi_channel_backward.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.dtfill_generate_multi_channel_backward.restype = ci
     L.dtfill_demo_multi_channel_workspace_bytes.argtypes = [ci, ci, ci, ci]
     L.dtfill_demo_multi_channel_workspace_bytes.restype = sz
     L.dtfill_demo_multi_channel.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, sz, vp]

@@ -77,6 +77,7 @@ namespace {
 #include "dtfill_outlier.hpp"
 #include "dtfill_gmc.hpp"
 #include "dtfill_gmcv.hpp"
+#include "dtfill_gmcb.hpp"
 #include "dtfill_post.hpp"
 #include "dtfill_lines.hpp"
 #include "dtfill_read.hpp"
@@ -541,6 +542,55 @@ int dtfill_demo_multi_channel(const float *lidar, const float *rgb, int C, int B
         gmcv_launch<GV_RGB3>(lidar, rgb, C, B, H, W, table_size, scale_num, scale_range, outs, raws, st);
     else
         gmcv_launch<GV_RGBC>(lidar, rgb, C, B, H, W, table_size, scale_num, scale_range, outs, raws, st);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+size_t dtfill_generate_multi_channel_backward_workspace_bytes(int B, int H, int W, int scale_num) {
+    if (!gmcv_count_ok(B, H, W, 1) || scale_num < 1 || scale_num > 4) return 0;
+    // G_k for the steps whose transpose feeds another one (k = 2 .. scale_num - 1)
+    return (size_t)min(2, max(0, scale_num - 2)) * align256((size_t)B * H * W * sizeof(float));
+}
+
+int dtfill_generate_multi_channel_backward(const float *mask, const float *out2, const float *out3, int B, int H, int W,
+                                           int table_size, int scale_num, const float *g1, const float *g2, const float *g3,
+                                           const float *g4, float *grad_data, void *workspace, size_t ws_bytes, void *stream) {
+    if (!mask || !grad_data) return DTFILL_ERR_NULL;
+    if (table_size < 1 || (table_size & 1) == 0 || (table_size - 1) / 2 > GM_MAXHALF || scale_num < 1 || scale_num > 4)
+        return DTFILL_ERR_SHAPE;
+    if (!gmcv_count_ok(B, H, W, 1)) return DTFILL_ERR_SHAPE;
+    if ((scale_num >= 3 && !out2) || (scale_num == 4 && !out3)) return DTFILL_ERR_NULL;
+    const size_t need = dtfill_generate_multi_channel_backward_workspace_bytes(B, H, W, scale_num);
+    if (need && !workspace) return DTFILL_ERR_NULL;
+    if (need && (ws_bytes < need || ((uintptr_t)workspace & 255))) return DTFILL_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t n = (size_t)B * H * W;
+    const float *gs[4] = {g1, g2, g3, g4}, *fwds[3] = {nullptr, out2, out3};
+    const int half = (table_size - 1) / 2;
+    const size_t lds = ((size_t)2 * (GM_TH + 2 * half) * (GM_TW + 2 * half) + (size_t)(GM_TH + 4 * half) * (GM_TW + 4 * half)) * sizeof(float);
+    const int tx = (W + GM_TW - 1) / GM_TW, ty = (H + GM_TH - 1) / GM_TH;
+    const u32 ntiles = (u32)((size_t)tx * ty * B);  // (< 2^31: a tile holds a pixel)
+    const u32 grid = min(ntiles, 1u << 22);
+    // G_k = g_k + A_k^T G_(k+1), from the last step down; `up` is G_(k+1), NULL while it is all zero.  A zero G_(k+1) makes
+    // the transpose sum +0 everywhere, so G_k = g_k + (+0): g_k itself but for its -0.0, which no later sum can tell from
+    // +0.0 (a window's c_p enters only an addition to a sum that started from +0).  Such a step is not launched: the next
+    // one reads g_k in place of G_k.  Only grad_data itself is written as g_1 + (+0).
+    const float *up = gs[scale_num - 1];
+    int frames = 0;
+    for (int k = scale_num - 1; k >= 1; --k) {
+        if (!up) {
+            up = gs[k - 1];
+            continue;
+        }
+        float *dst = k == 1 ? grad_data : reinterpret_cast<float *>(static_cast<char *>(workspace) + (size_t)(frames++ & 1) * (need / 2));
+        const float *msk = k == 1 ? mask : nullptr;
+        if (table_size == 7)
+            k_gmcb<7><<<grid, 256, lds, st>>>(msk, fwds[k - 1], up, gs[k - 1], H, W, 7, tx, ty, ntiles, dst);
+        else
+            k_gmcb<0><<<grid, 256, lds, st>>>(msk, fwds[k - 1], up, gs[k - 1], H, W, table_size, tx, ty, ntiles, dst);
+        up = dst;
+    }
+    if (up != grad_data)  // no step stored it: scale_num 1 (g_1 as it is), or every later gradient NULL (g_1 + (+0))
+        k_gmcb_first<<<(unsigned)min((n + 255) / 256, (size_t)1 << 16), 256, 0, st>>>(up, n, scale_num > 1, grad_data);
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 

@@ -299,6 +299,53 @@ def generate_multi_channel_device(data, mask, table_size=7, scale_num=4):
     return tuple([data] + outs + [None] * (4 - scale_num))
 
 
+_gmcb_ws = {}  # (device index, stream) -> the backward's workspace: calls on one stream are ordered, so they can share it
+
+
+def _gmcb_workspace(device, nbytes):
+    """A 256-byte aligned pointer to at least nbytes of scratch on `device`, kept for the current stream and grown on demand."""
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+    ws = _gmcb_ws.get(key)
+    if ws is None or ws.numel() < nbytes + 256:
+        ws = _gmcb_ws[key] = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+    return ws.data_ptr() + (-ws.data_ptr()) % 256
+
+
+def generate_multi_channel_backward_device(mask, out2, out3, grads, table_size=7, scale_num=4):
+    """The backward of generate_multi_channel_device (include/dtfill.h, dtfill_generate_multi_channel_backward): the gradient
+    with respect to data.  mask: the forward's; out2, out3: the forward's lidar_2 and lidar_3 (needed for scale_num >= 3 and
+    4, None otherwise is fine); grads: the gradients of (lidar_1, .., lidar_4), a 4-sequence, None for a zero gradient.  All
+    contiguous float32 CUDA tensors [B,H,W] on one device.  Returns a new tensor; asynchronous on the current stream."""
+    _require_gpu()
+    if scale_num not in (1, 2, 3, 4):
+        raise ValueError("scale_num must be 1, 2, 3 or 4, got %r" % (scale_num,))
+    grads = tuple(grads)
+    if len(grads) != 4:
+        raise ValueError("grads must hold four gradients (None for a zero one), got %d" % len(grads))
+    need = (("mask", mask, True), ("out2", out2, scale_num >= 3), ("out3", out3, scale_num == 4))
+    named = need + tuple(("grads[%d]" % k, g, False) for k, g in enumerate(grads))
+    for what, t, required in named:
+        if t is None:
+            if required:
+                raise ValueError("%s is needed for scale_num %d" % (what, scale_num))
+            continue
+        if t.dtype != torch.float32 or not t.is_cuda or t.dim() != 3 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float32 CUDA tensor [B,H,W]" % what)
+        if t.shape != mask.shape or t.device != mask.device:
+            raise ValueError("%s must have mask's shape and device" % what)
+    B, H, W = mask.shape
+    L = _lib.load()
+    ptr = lambda t: None if t is None else t.data_ptr()
+    out = torch.empty_like(mask)
+    with torch.cuda.device(mask.device):
+        nbytes = L.dtfill_generate_multi_channel_backward_workspace_bytes(B, H, W, scale_num)
+        ws = _gmcb_workspace(mask.device, nbytes) if nbytes else None
+        _lib.check(L.dtfill_generate_multi_channel_backward(
+            mask.data_ptr(), ptr(out2), ptr(out3), B, H, W, int(table_size), int(scale_num), *[ptr(g) for g in grads],
+            out.data_ptr(), ws, nbytes, torch.cuda.current_stream(mask.device).cuda_stream))
+    return out
+
+
 def demo_multi_channel_device(lidar, rgb=None, table_size=7, scale_range=90.0, scale_num=4):
     """demo.py:108-149 (rgb None) / :151-198 on the device (include/dtfill.h, dtfill_demo_multi_channel).  lidar: contiguous
     float32 CUDA tensor [B,H,W]; rgb: contiguous float32 CUDA tensor [B,H,W,C] or None.  Returns (out_1, .., out_4) with None

@@ -174,6 +174,51 @@ int dtfill_generate_multi_channel(const float *data, const float *mask, int B, i
                                   int scale_num, float *out2, float *out3, float *out4, void *stream);
 
 /*
+ * The backward pass of dtfill_generate_multi_channel(): the gradient of a loss with respect to `data`, given its gradients
+ * with respect to lidar_1..4.  In the reference the operator sits inside the trained graph: with if_correct its input is the
+ * output of four learned convolutions (net.py:469-486), its outputs feed the encoder (net.py:489), and the gradient is cut
+ * only when joint_train is off (net.py:491-496).  tf.equal, tf.cast and tf.greater have no gradient, so the selection of a
+ * step and the re-masking between the steps (net.py:95-96) are constants, every step is a fixed sparse linear map A_k of its
+ * input, and the backward applies the transposes.  It needs the masks and the forward outputs, never the data.  The mask
+ * receives no gradient.
+ *
+ * One forward step, input d, mask m, ts = table_size, w(t) = ts - |di| - |dj| (as above):
+ *   mx_p  = max over all ts^2 taps t of m[p+t] * w(t); padding taps count, with product 0; a NaN product is never selected;
+ *   sel_p(t) = (m[p+t] * w(t) == mx_p);  cnt_p = the number of selected taps;
+ *   out_p = sum_t sel_p(t) * d[p+t] / (1e-6f + cnt_p).
+ * Its transpose applied to an upstream gradient G, for an in-image pixel q, in float32:
+ *   c_p      = G_p / (1e-6f + (float)cnt_p), one IEEE division per p;
+ *   (A^T G)_q = the sum, starting from +0, over the in-image p with |p - q|_inf <= (ts-1)/2, in ascending raster order of
+ *              p, of c_p where m[q] * w(q - p) == mx_p.
+ * A c_p is added only where it is selected (as the forward adds an input only where it is selected): a non-finite G_p does
+ * not spread to pixels that did not select it.  Gradient sent to padding taps is dropped.  "Ascending raster order of p" is
+ * this library's contract, as the forward's tap order is: TensorFlow's own order is not documented, and where one window
+ * selects a pixel every order gives the same bits.
+ *
+ * The whole call: g1..g4 are the gradients of lidar_1..4 (lidar_1 is the data itself), m_1 = mask, m_k = (lidar_k > 0.001f)
+ * for k >= 2, derived from out2 / out3 while they are read, never stored.  For scale_num 4
+ *   G_3 = g3 + A_3^T g4;  G_2 = g2 + A_2^T G_3;  grad_data = g1 + A_1^T G_2,
+ * each + one float32 add of g_k and the finished transpose sum; shorter chains for scale_num 3 and 2; scale_num 1 gives
+ * grad_data = g1.  A NULL g_k is a zero gradient and adds nothing (scale_num 1 with a NULL g1: all +0).  grad_data is
+ * always fully overwritten.
+ *
+ * mask: float32 [B,H,W], the forward's.  out2, out3: the forward's lidar_2 and lidar_3, needed where a later step's mask
+ * derives from them (out2 for scale_num >= 3, out3 for scale_num 4; NULL otherwise is fine).  g1..g4: float32 [B,H,W], each
+ * nullable.  grad_data: float32 [B,H,W], may not alias any input.  workspace: at least
+ * dtfill_generate_multi_channel_backward_workspace_bytes(B,H,W,scale_num) bytes (at most two [B,H,W] float frames, G_3 and
+ * G_2; 0 for scale_num <= 2, when workspace may be NULL), 256-B aligned, the caller's, no initialisation needed, nothing kept
+ * between calls.  Asynchronous on `stream`; no allocation; no atomics, so two calls give the same bits.
+ * Returns, all checked before any HIP call: DTFILL_ERR_NULL for a NULL mask, a NULL grad_data, a NULL required out_k or a NULL
+ * workspace where one is needed; DTFILL_ERR_SHAPE for an even table_size or one outside 1..15, scale_num outside 1..4, B, H
+ * or W < 1, or B*H*W >= 2^31; DTFILL_ERR_WORKSPACE for a workspace that is too small or not aligned.
+ */
+size_t dtfill_generate_multi_channel_backward_workspace_bytes(int B, int H, int W, int scale_num); /* 0 on a bad shape */
+int dtfill_generate_multi_channel_backward(const float *mask, const float *out2, const float *out3,
+                                           int B, int H, int W, int table_size, int scale_num,
+                                           const float *g1, const float *g2, const float *g3, const float *g4, /* each nullable */
+                                           float *grad_data, void *workspace, size_t ws_bytes, void *stream);
+
+/*
  * generate_multi_channel() and generate_multi_channel_with_image() of the reference's demo driver,
  * solution_DeepNet/demo.py:108-149 and :151-198 (weights create_weight_matrix, demo.py:65-75): what demo.py runs with its
  * default --model_type DT.  Not the net.py form above: the weights are powers of ten, the selection runs on data * w (the
