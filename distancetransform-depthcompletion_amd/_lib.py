@@ -21,6 +21,7 @@ FRAME_GENERAL_PATH = 2  # bit, informational
 FLAG_GENERAL_ONLY = 1
 FLAG_FUSED_ONLY = 2
 FLAG_OUTLIER_REMOVAL = 4  # outlier_removal() (data_read.py:103-128) in front of the predicates
+FLAG_SEPARATE_FRAME = 8  # l1_cv: the frame facts in a k_frame launch of their own (tests, A/B timing); same results
 LINES_NO_POINTS = 1  # bit: no valid pixel in the frame (DTFILL_LINES_*)
 LINES_BAD_INTERVAL = 2  # bit: the pitch interval is 0 or not finite
 LINES_SINGULAR = 4  # bit: K or E is singular

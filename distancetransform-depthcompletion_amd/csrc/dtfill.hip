@@ -20,13 +20,16 @@
 // Every hop lowers d by exactly the hop's L1 length, so a chain ends on a NEAREST source of its start pixel, and
 // everything that decides label(q) lies inside the L1 ball of radius d(q) around q.
 //
-// Kernels of one l1_cv pass (seven launches):
+// Kernels of one l1_cv pass (six launches; seven with a k_frame launch of its own, see run_l1):
 //   k_mask     source / value bit words + per-row prefix popcounts                    reads x once
-//              (16-byte or dword row loads; with the outlier filter a second launch redoes the frames with a negative value)
-//   k_frame    per-frame row-count scan -> compaction ranks; frame facts; the row structure (first source row, rows too far
+//              (16-byte or dword row loads; with the outlier filter a second launch redoes the frames with a negative value);
+//              clears the per-pass flags that later blocks only raise
+//   k_frame    (frame_facts + frame_publish: block 0 of every frame in k_fused's launch, or a launch of its own)
+//              per-frame row-count scan -> compaction ranks; frame facts; the row structure (first source row, rows too far
 //              from every source row) and with it WHO takes which rows of the frame; value list when the source and value masks
 //              of a frame differ; the source list of a frame that holds a handful
-//   k_fused    dense frames (halo 16 or 32 per frame): one workgroup per (tile + halo) window, bit-sliced: the
+//   k_fused    every window block first works out the facts of its own frame from the row counts (frame_facts, the same
+//              definition), so that it waits for no other block.  Dense frames (halo 16 or 32 per frame): one workgroup per (tile + halo) window, bit-sliced: the
 //              level-synchronous form of the identity on bit planes held in registers, byte codes un-sliced into LDS,
 //              lock-step chain walk, rank lookup, depth gather and the three output stores.  Hands a ROW on when one of its
 //              pixels is farther than the halo from every source.
@@ -159,6 +162,9 @@ bool shape_ok(int B, int H, int W) {
            (long long)B * H * W < (1ll << 31);  // B is a grid dimension; pixel indices are 32-bit
 }
 
+// l1_cv: frames of up to DTFILL_FRAME_RIDE_MAX_H rows have their facts worked out inside k_fused's launch (run_l1)
+static_assert(DTFILL_FRAME_RIDE_MAX_H <= F_RIDE_HMAX, "the facts of a riding frame lie in k_fused's ring memory");
+
 // kernel_ms slots of dtfill_batch_timed, in launch order
 enum { S1_MASK, S1_FRAME, S1_FUSED, S1_COLT, S1_ROWS, S1_FIN, S1_TIESX, NK_L1 };
 const char *const kNamesL1[NK_L1] = {"k_mask", "k_frame", "k_fused", "k_colT", "k_rows", "k_fin", "k_tiesx"};
@@ -172,10 +178,14 @@ struct Marks {
     hipEvent_t *ev;
     int k = 0;
     bool ok = true;
+    unsigned idle = 0;  // bit k: nothing was launched in slot k
     void at(int slot) {
         ok = ok && hipGetLastError() == hipSuccess;
         if (ev)
-            for (; k <= slot; ++k) (void)hipEventRecord(ev[k], st);
+            for (; k <= slot; ++k) {
+                if (k < slot) idle |= 1u << k;
+                (void)hipEventRecord(ev[k], st);
+            }
     }
 };
 
@@ -217,14 +227,18 @@ bool launch_colT(const Pass &p, const SkyArgs &sky, hipStream_t st) {
     return ok;
 }
 
-int run_l1(Pass p, unsigned flags, hipStream_t st, hipEvent_t *ev) {
+int run_l1(Pass p, unsigned flags, hipStream_t st, hipEvent_t *ev, unsigned *idle) {
     const int B = p.B, H = p.H, W = p.W;
     const bool general_only = flags & DTFILL_FLAG_GENERAL_ONLY;
     const bool fused_only = flags & DTFILL_FLAG_FUSED_ONLY;
     Marks m{st, ev};
+    // The frame facts: every window block of k_fused works out its own frame's, and the first block of a frame publishes them
+    // for the later launches (six launches).  A launch of its own (seven) where there is no window launch, on request, and for
+    // tall frames: every window block scans all H row counts (DTFILL_FRAME_RIDE_MAX_H: DESIGN.md section 4).
+    const bool ride = !general_only && !(flags & DTFILL_FLAG_SEPARATE_FRAME) && H <= DTFILL_FRAME_RIDE_MAX_H;
+    p.ride = ride;
     m.at(S1_MASK);
     launch_mask(p, flags, st);
-    m.at(S1_FRAME);
     // geometry of the window kernel's two tilings (k_frame pre-marks whole tile rows)
     auto tiling = [&](int R) {
             const int THM = F_WHM - 2 * R, TWM = F_WWM - 2 * R;
@@ -248,7 +262,11 @@ int run_l1(Pass p, unsigned flags, hipStream_t st, hipEvent_t *ev) {
     // k_sky takes the distances of its two base rows from the distance map: without one from the caller, the scratch frame
     float *const out_dt_caller = p.out_dt;
     if (rowflags && !p.out_dt) p.out_dt = p.dscratch;
-    k_frame<<<B, 256, 0, st>>>(p, (general_only ? 1 : 0) | (rowflags ? 4 | 8 : 0), t16.nty, t32.nty);
+    const int mode = (general_only ? 1 : 0) | (rowflags ? 4 | 8 : 0);
+    if (!ride) {
+        m.at(S1_FRAME);  // (else the slot reads 0 ms)
+        k_frame<<<B, 256, 0, st>>>(p, mode, t16.nty, t32.nty);
+    }
     m.at(S1_FUSED);
     if (!general_only) {
         // dense frames: the window kernel, halo 16 or 32 per frame (k_frame's route).  It hands rows on (fflag2, rowfar) when a
@@ -257,10 +275,12 @@ int run_l1(Pass p, unsigned flags, hipStream_t st, hipEvent_t *ev) {
         auto line = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 127) == 0; };
         const bool stream = (W & 31) == 0 && (t16.TW & 31) == 0 && (t32.TW & 31) == 0 && line(p.out_depth) && line(p.out_dt) &&
                             line(p.out_index);
-        const dim3 fg(B, max(t16.ntiles, t32.ntiles));  // frames along x: a frame's tiles beyond its own tiling (they exit) come last
+        // frames along x: a frame's tiles beyond its own tiling (they exit) come last
+        const dim3 fg(B, max(t16.ntiles, t32.ntiles));
         // the depth epilogue is a template parameter (no streaming stores with it): each instance holds two bodies, not four
         (epi ? k_fused<false, true> : stream ? k_fused<true, false> : k_fused<false, false>)<<<fg, F_NT, 0, st>>>(p.x, p.srcbits, p.wpre_s, p.rowbase_s, p.finfo, p.vlist, H, W, p.Wd, t16, t32,
-                                                                      p.out_depth, p.out_dt, p.out_index, p.route, p.fflag2, p.rowfar, p.status, p.ep);
+                                                                      p.out_depth, p.out_dt, p.out_index, p.route, p.fflag2, p.rowfar, p.status, p.ep,
+                                                                      frame_args(p, mode, t16.nty, t32.nty, ride, min(t16.ntiles, t32.ntiles)));
     }
     m.at(S1_COLT);
     if (!fused_only) {
@@ -315,10 +335,11 @@ int run_l1(Pass p, unsigned flags, hipStream_t st, hipEvent_t *ev) {
         }
     }
     m.at(NK_L1);
+    if (idle) *idle = m.idle;
     return m.ok ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 
-int run_l2(const Pass &p, unsigned flags, hipStream_t st, hipEvent_t *ev) {
+int run_l2(const Pass &p, unsigned flags, hipStream_t st, hipEvent_t *ev, unsigned *idle) {
     const int B = p.B, H = p.H, W = p.W;
     Marks m{st, ev};
     m.at(S2_MASK);
@@ -360,12 +381,14 @@ int run_l2(const Pass &p, unsigned flags, hipStream_t st, hipEvent_t *ev) {
                                                                        p.status);
     }
     m.at(NK_L2);
+    if (idle) *idle = m.idle;
     return m.ok ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 
-int run(const Pass &p, int metric, unsigned flags, void *stream, hipEvent_t *ev) {
+// idle (with ev): bit k = slot k's kernel was not launched in this pass
+int run(const Pass &p, int metric, unsigned flags, void *stream, hipEvent_t *ev, unsigned *idle = nullptr) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return metric == DTFILL_METRIC_L2 ? run_l2(p, flags, st, ev) : run_l1(p, flags, st, ev);
+    return metric == DTFILL_METRIC_L2 ? run_l2(p, flags, st, ev, idle) : run_l1(p, flags, st, ev, idle);
 }
 
 int check_args(const float *x, int B, int H, int W, int metric, float *out_depth, float *out_dt,
@@ -618,9 +641,13 @@ int dtfill_batch_timed(const float *x, int B, int H, int W, float src_thr, float
             while (k-- > 0) (void)hipEventDestroy(ev[k]);  // nothing created so far is left behind
             return DTFILL_ERR_NO_DEVICE;
         }
-    rc = run(make_pass(x, B, H, W, src_thr, val_thr, out_depth, out_dt, out_index, frame_status, workspace), metric, flags, stream, ev);
+    unsigned idle = 0;
+    rc = run(make_pass(x, B, H, W, src_thr, val_thr, out_depth, out_dt, out_index, frame_status, workspace), metric, flags, stream, ev, &idle);
     (void)hipEventSynchronize(ev[nk]);
-    for (int k = 0; k < nk; ++k) (void)hipEventElapsedTime(&kernel_ms[k], ev[k], ev[k + 1]);
+    for (int k = 0; k < nk; ++k) {
+        (void)hipEventElapsedTime(&kernel_ms[k], ev[k], ev[k + 1]);
+        if (idle >> k & 1u) kernel_ms[k] = 0.0f;  // (two events back to back are still some microseconds apart)
+    }
     for (int k = 0; k <= nk; ++k) (void)hipEventDestroy(ev[k]);
     return rc;
 }

@@ -6,15 +6,19 @@ constexpr int BIG = 1 << 20;       // in-register "infinite" distance
 constexpr int INF16 = 0xFFFF;      // stored "infinite" distance in the uint16 scan arrays
 constexpr int MAX_HW_SUM = 8192;   // cv2's Q16 INIT_DIST0 = INT_MAX>>2 caps distances at 8191
 
-// frame facts written by k_frame: int32[FI_STRIDE] per frame
+// frame facts as the frame's publishing block stores them (frame_publish: k_frame, or the first block of the frame in k_fused's launch):
+// int32[FI_STRIDE] per frame
 constexpr int FI_NSRC = 0, FI_NVAL = 1, FI_MISALIGNED = 2, FI_DLB = 3;  // DLB: lower bound of the largest distance (empty rows)
-constexpr int FI_NUNRES = 4;  // tie pixels k_fin handed to k_tiesx (zeroed by k_frame)
-constexpr int FI_SKY = 5;     // l1_cv: rows [0, FI_SKY) hold no source and lie above every source: k_sky's (0: none, or called off)
-constexpr int FI_SKY0 = 6;    // ... as k_frame set it.  k_fused calls the sky off (FI_SKY = 0) when it has to hand on one of the two rows
-                              // k_sky would start from (FI_SKY0, FI_SKY0 + 1): the sky's rows then count as flagged 1
+constexpr int FI_NUNRES = 4;  // tie pixels k_fin handed to k_tiesx (zeroed by the publishing block)
+constexpr int FI_SKY = 5;     // l1_cv: rows [0, FI_SKY) hold no source and lie above every source: k_sky's (0: none) ...
+constexpr int SKY_OFF = 0x40000000;  // ... unless this bit is set in it: k_fused calls the sky off when it has to hand on one of the two
+                              // rows k_sky would start from (FI_SKY, FI_SKY + 1): the sky's rows then count as flagged 1.  The
+                              // publishing block and the window blocks may run in one launch: the word starts clear (k_mask) and
+                              // both OR into it.  Readers: sky_rows()
 constexpr int FI_TR0 = 7;     // l1_cv, a window kernel's frame: the first row of its tiling (the rows above are the sky's: the tile rows split
                               // the rest evenly, so that no tile row is spent on rows that are not the window's)
 constexpr int FI_STRIDE = 8;
+constexpr int ROUTE_UNKNOWN = -0x7FFFFFFF - 1;  // route[b] from k_mask until the frame's facts are published (reads as "no window")
 constexpr int ROUTE_POINTS = -1;  // route[b]: l2, at most L2_PTS_MAX sources in the frame (k_l2pts)
 constexpr int L2_PTS_MAX = 512;
 constexpr int W2_R16 = 10, W2_R32 = 15;  // l2: window radius of k_l2win for the frames k_frame routes 16 / 32
@@ -104,6 +108,7 @@ struct Pass {
     int B, H, W;
     int Wd, Wp;          // 64-pixel words per row; bytes per row of a bit plane (Wd * 8)
     int nb, ctp;         // 32-row bands per frame, columns per row of ct
+    int ride;            // l1_cv: the frame facts are worked out in k_fused's launch (k_mask then clears what that launch only raises)
     size_t plane_bytes;  // bytes of one plane
     const float *x;
     float src_thr, val_thr;
@@ -133,6 +138,12 @@ struct Pass {
     float *vlist;
     PtsSrc *ptslist;     // k_frame -> k_pts: the sources of a frame that has a handful (l1_cv, ROUTE_POINTS)
 };
+
+// the rows [0, n) of frame b that are k_sky's: FI_SKY unless the window kernel called the sky off
+__device__ __forceinline__ int sky_rows(const int *__restrict__ finfo, int b) {
+    const int v = finfo[b * FI_STRIDE + FI_SKY];
+    return (v & SKY_OFF) ? 0 : v;
+}
 
 // row flag f of a frame whose sky is / is not k_sky's: is the row one of the any-distance kernels'?
 __device__ __forceinline__ bool row_is_anydist(u32 f, int sky_live) { return f == 1u || (f == 2u && !sky_live); }

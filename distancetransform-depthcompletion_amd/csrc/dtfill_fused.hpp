@@ -171,7 +171,7 @@ __device__ __forceinline__ bool fused_walk_epilogue(
     const u8 *__restrict__ s_par, const short *__restrict__ s_tab, const uint2 *__restrict__ s_rw, int b, int H,
     int W, int th, int tw, int r0, int c0, int wr0, int wc0, int sh, const float *__restrict__ x,
     const float *__restrict__ vlist,
-    int *__restrict__ finfo, float *__restrict__ out_depth, float *__restrict__ out_dt,
+    int *__restrict__ finfo, int nval, int misaligned, int sky0, float *__restrict__ out_depth, float *__restrict__ out_dt,
     int32_t *__restrict__ out_index, int *__restrict__ frame_status, const DepthEpilogue ep, u32 *__restrict__ rowflag
     FPROF(, FusedProf &prof)) {
     // ---- P3: tile pixels: walk to the source, d, rank -> label, gather, store.  Each lane walks F_EB
@@ -179,8 +179,7 @@ __device__ __forceinline__ bool fused_walk_epilogue(
     // F_EB global gathers in flight together.
     // Frame bases are block-uniform (scalar registers); per pixel only 32-bit in-frame offsets are computed.
     const size_t fo = (size_t)b * H * W;
-    const int nval = finfo[b * FI_STRIDE + FI_NVAL];
-    const int misaligned = finfo[b * FI_STRIDE + FI_MISALIGNED];
+    // (nval, misaligned, sky0: the frame's FI_NVAL, FI_MISALIGNED, FI_SKY -- block-uniform)
     const float *gbase = misaligned ? vlist + fo : x + fo;
     // The outputs leave through buffer stores, one descriptor per frame and map (block-uniform): a store the pass does not
     // make -- an undecided pixel, a cropped row, a map the caller did not ask for (0 records) -- is a store whose offset the
@@ -369,9 +368,9 @@ __device__ __forceinline__ bool fused_walk_epilogue(
             for (int tr = g * F_EB; tr < min(g * F_EB + F_EB, th); ++tr)
                 if (s_par[__mul24(FR + tr, F_P) + FR + tc] == F_NONE) {
                     rowflag[(size_t)b * H + r0 + tr] = 1u;  // same-value race
-                    // one of the two rows k_sky starts from: the any-distance kernels take the sky's rows as well
-                    const int s0 = finfo[b * FI_STRIDE + FI_SKY0];
-                    if (s0 > 0 && (r0 + tr == s0 || r0 + tr == s0 + 1)) finfo[b * FI_STRIDE + FI_SKY] = 0;
+                    // one of the two rows k_sky starts from: the any-distance kernels take the sky's rows as well (the sky is
+                    // called off by a bit ORed into FI_SKY: the frame's publishing block may be ORing the rows into it in this very launch)
+                    if (sky0 > 0 && (r0 + tr == sky0 || r0 + tr == sky0 + 1)) atomicOr(&finfo[b * FI_STRIDE + FI_SKY], SKY_OFF);
                 }
         }
     }
@@ -385,7 +384,8 @@ struct FusedTiles {
 };
 
 template <int FR, bool EPI, bool STREAM>
-__device__ __forceinline__ void fused_body(bool premarked,
+__device__ __forceinline__ void fused_body(int tile, bool premarked, int tbase, int nval, int misaligned, int sky0, const u32 *__restrict__ s_bs,
+    const u32 *__restrict__ s_far,
     const float *__restrict__ x, const u64 *__restrict__ srcbits, const u16 *__restrict__ wpre_s,
     const u32 *__restrict__ rowbase_s, int *__restrict__ finfo, const float *__restrict__ vlist,
     int H, int W, int Wd, int nty, int TW, int tiles_x, float *__restrict__ out_depth,
@@ -395,9 +395,10 @@ __device__ __forceinline__ void fused_body(bool premarked,
     const int tid = threadIdx.x;
     // (frames along x, tiles along y: the tiles beyond a frame's own tiling, which exit, are dispatched after every working block)
     const int b = blockIdx.x;
-    const int ty = blockIdx.y / tiles_x, tx = blockIdx.y - ty * tiles_x;
-    // the tile rows split the rows from FI_TR0 on evenly (k_frame: 0, or the first source row under a sky)
-    const int tbase = finfo[b * FI_STRIDE + FI_TR0];
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    // the tile rows split the rows from tbase = FI_TR0 on evenly (frame_facts: 0, or the first source row under a sky)
+    // s_bs, s_far (LDS, inside the ring's memory; null when a k_frame launch went before): the frame's rank bases per row and
+    // its pre-marked rows as bits, as this block's own frame_facts left them -- else rowbase_s and rowfar say the same
     const int TH = (H - tbase + nty - 1) / nty;
     int r0 = tbase + ty * TH;
     const int c0 = tx * TW;
@@ -405,16 +406,17 @@ __device__ __forceinline__ void fused_body(bool premarked,
     const int tw = min(TW, W - c0);
     if (th <= 0) return;  // block-uniform
     if (premarked) {
-        // k_frame handed rows of this frame to the any-distance kernels up front (the empty sky): the tile shrinks to the span
+        // rows of this frame were handed to the any-distance kernels up front (the empty sky): the tile shrinks to the span
         // of its rows that are still this kernel's; a tile without any is done.  (A row another block marks meanwhile is
         // redone whole as well: whether this block still stores its part of it does not matter.)
         const u32 *rowflag = rowfar + (size_t)b * H;
+        auto mine = [&](int i) { return s_far ? ((s_far[i >> 5] >> (i & 31)) & 1u) == 0u : rowflag[i] == 0u; };
         if (tid == 0) {
             s_any[0][0] = 0xFFFFFFFFu;
             s_any[0][1] = 0u;
         }
         __syncthreads();
-        if (tid < th && rowflag[r0 + tid] == 0u) {
+        if (tid < th && mine(r0 + tid)) {
             atomicMin(&s_any[0][0], (u32)tid);
             atomicMax(&s_any[0][1], (u32)tid + 1u);
         }
@@ -453,7 +455,7 @@ __device__ __forceinline__ void fused_body(bool premarked,
             if (rowin && kk < 4 && w >= 0 && w < Wd) {
                 const size_t wi = ((size_t)b * H + gi) * Wd + w;
                 sb = srcbits[wi];
-                rk = rowbase_s[(size_t)b * H + gi] + wpre_s[wi];
+                rk = (s_bs ? s_bs[gi] : rowbase_s[(size_t)b * H + gi]) + wpre_s[wi];
             }
             g[2 * k] = (u32)sb;
             g[2 * k + 1] = (u32)(sb >> 32);
@@ -487,6 +489,7 @@ __device__ __forceinline__ void fused_body(bool premarked,
         }
     }
     // level 0: E_0 = L_0 = sources; zero the rest of the ring (levels "-1,-2,-3", the guard rows, the pads)
+    if (s_bs) __syncthreads();  // block-uniform: everybody has read the frame facts that lie in the ring's memory
     for (int k = tid; k < F_RING; k += F_NT) s_ring[k] = 0;
     if (tid < 64) {
         const int hi = tid >> 3, lo = tid & 7;
@@ -657,7 +660,7 @@ __device__ __forceinline__ void fused_body(bool premarked,
     FPROF(prof.mark(3));
 
     const bool overflow = fused_walk_epilogue<FR, F_NT, EPI, STREAM>(s_par, s_tab, s_rw, b, H, W, th, tw, r0, c0, wr0, wc0, sh, x, vlist,
-                                                        finfo, out_depth, out_dt, out_index, frame_status, ep, rowfar FPROF(, prof));
+                                                        finfo, nval, misaligned, sky0, out_depth, out_dt, out_index, frame_status, ep, rowfar FPROF(, prof));
     if (overflow && (threadIdx.x & 63) == 0) {  // wave-uniform
         // 1: the rows marked in rowflag, 2: the whole frame.  Same-value race: every writer of a frame stores the same value,
         // the any-distance kernels read it after this kernel
@@ -667,23 +670,30 @@ __device__ __forceinline__ void fused_body(bool premarked,
     FPROF(prof.mark(6); prof.flush());
 }
 
-// k_fused: one launch for both halos.  route[b] (k_frame): 16 / 32 = the halo that is expected to decide every pixel of
+// k_fused: one launch for both halos.  route (frame_facts): 16 / 32 = the halo that is expected to decide every pixel of
 // frame b (source density, runs of source-free rows), 0 = the any-distance kernels take the frame.  The grid is
 // sized for the halo-32 tiling (more, smaller tiles); blocks beyond a frame's own tiling exit.  A tile pixel that turns out
 // to be farther than the halo from every source is not stored: its ROW is handed to the any-distance kernels (rowflag,
 // fflag = 1; frame_status), which redo exactly those rows -- the empty sky of a LiDAR frame, a hole in a dense one.
+// fa.ride: no k_frame launch went before.  Every window block works out the facts of its frame itself (frame_facts: one round
+// trip for the frame's row counts, then LDS), and the first block of every frame also publishes them for the later launches
+// (frame_publish).  No block waits for another.  Else route, finfo, rowbase_s and rowfar are read as k_frame stored them.
 // the block's LDS: one buffer, carved here
 constexpr size_t F_OFF_RW = (sizeof(u32) * F_RING + 15) & ~(size_t)15, F_OFF_TAB = F_OFF_RW + sizeof(uint2) * F_WHM * 8, F_OFF_ANY = F_OFF_TAB + sizeof(short) * 64,
                  F_LDS_OWN = F_OFF_ANY + sizeof(u32) * 2 * (F_NT / 64);
 constexpr size_t F_LDS = F_LDS_OWN;
+// frames of up to this many rows can ride: their facts (FrameScratch, then two rank bases per row) lie in the ring's memory
+constexpr int F_RIDE_HMAX = (int)((sizeof(u32) * F_RING - sizeof(FrameScratch)) / (2 * sizeof(u32)));
+static_assert(sizeof(FrameScratch) % 4 == 0 && F_NT == 256, "frame_facts runs on the window kernel's 256 threads");
 
 template <bool STREAM, bool EPI>
 __global__ __launch_bounds__(F_NT, 4) void k_fused(
     const float *__restrict__ x, const u64 *__restrict__ srcbits, const u16 *__restrict__ wpre_s,
-    const u32 *__restrict__ rowbase_s, int *__restrict__ finfo, const float *__restrict__ vlist,
+    const u32 *__restrict__ rowbase_s, int *__restrict__ finfo, float *vlist /* written here in a frame whose masks differ */,
     int H, int W, int Wd, FusedTiles t16, FusedTiles t32, float *__restrict__ out_depth,
     float *__restrict__ out_dt, int32_t *__restrict__ out_index,
-    const int *__restrict__ route, int *__restrict__ fflag, u32 *__restrict__ rowfar, int *__restrict__ frame_status, const DepthEpilogue ep) {
+    int *__restrict__ route, int *__restrict__ fflag, u32 *__restrict__ rowfar, int *__restrict__ frame_status, const DepthEpilogue ep,
+    const FrameArgs fa) {
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[F_LDS];
     u32 *s_ring = reinterpret_cast<u32 *>(s_raw);  // later: s_par bytes
     // per window row, the eight image-aligned 32-pixel half words it touches: {source bits, 1 + sources before them
@@ -691,17 +701,70 @@ __global__ __launch_bounds__(F_NT, 4) void k_fused(
     uint2 *s_rw = reinterpret_cast<uint2 *>(s_raw + F_OFF_RW);
     short *s_tab = reinterpret_cast<short *>(s_raw + F_OFF_TAB);  // s_par displacement of the step enc (0 for the codes that are no step)
     u32(*s_any)[F_NT / 64] = reinterpret_cast<u32(*)[F_NT / 64]>(s_raw + F_OFF_ANY);  // per wave: did level t produce anything (double-buffered by level parity)
-    const int rt = route[blockIdx.x];        // block-uniform
+    const int b = blockIdx.x, tile = blockIdx.y;
+    int rt, tbase, nval, misaligned, sky0;  // block-uniform
+    const u32 *s_bs = nullptr, *s_far = nullptr;
+    if (fa.ride) {
+        // A block beyond the tiling with fewer tiles (fa.ntmin of them) works only in a frame of the other tiling: most such
+        // blocks exit.  They are dispatched long after the frame's first block, which has published the route by then (clear
+        // since k_mask): a look at it saves them the facts.  Not seen yet (or not visible here): the facts say the same.
+        // ONE look per block: the word changes during this launch, so every wave looking for itself could see something else,
+        // and a block must stay or leave whole (thread 0 looks, everybody reads its answer behind a barrier; the slot is not
+        // written again before the barriers of frame_facts)
+        if (tile >= fa.ntmin) {  // block-uniform
+            if (threadIdx.x == 0) s_any[0][0] = (u32)__hip_atomic_load(&route[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __syncthreads();
+            const int seen = (int)s_any[0][0];
+            const int rs = seen > 0 ? (seen & 0xFF) : 0;
+            if (seen != ROUTE_UNKNOWN && !((rs == 16 && tile < t16.ntiles) || (rs == 32 && tile < t32.ntiles))) return;  // block-uniform
+        }
+        FrameScratch &sc = *reinterpret_cast<FrameScratch *>(s_raw);
+        u32 *bs = reinterpret_cast<u32 *>(s_raw + sizeof(FrameScratch)), *bv = bs + H;
+        u32 *gs = fa.rowbase_s + (size_t)b * H, *gv = fa.rowbase_v + (size_t)b * H;
+        const bool pub = tile == 0;  // the frame's first block also publishes the facts for the later launches
+        const FrameFacts ff = frame_facts(fa.rowcnt_s + (size_t)b * H, fa.rowcnt_v + (size_t)b * H, H, W, fa.mode, fa.nty16, fa.nty32, sc, pub,
+                                          [&](int i, u32 base_s, u32 base_v) {
+                                              bs[i] = base_s;
+                                              bv[i] = base_v;
+                                              if (pub) {
+                                                  gs[i] = base_s;
+                                                  gv[i] = base_v;
+                                              }
+                                          });
+        // The two masks of the frame differ somewhere (rare): its depths are gathered from the value list, which the
+        // frame's first block writes in this very launch -- and no block waits for another.  So every working window
+        // block of such a frame writes the whole list itself first (the same values from every writer).  Its own stores
+        // are visible to its gathers: the barrier in front of the ring's zeroing lies between them.
+        if (pub)
+            frame_publish(ff, sc, b, fa.x, fa.valbits, fa.wpre_v, fa.srcbits, fa.wpre_s, fa.ptslist, H, W, Wd, gs, gv, finfo, vlist,
+                          fflag, route, frame_status, fa.mode, fa.negflag, rowfar, true);
+        else if (ff.misaligned && out_depth && ((ff.r == 16 && tile < t16.ntiles) || (ff.r == 32 && tile < t32.ntiles)))
+            value_list(b, fa.x, fa.valbits, fa.wpre_v, H, W, Wd, vlist, [&](int i) { return bv[i]; });
+        auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
+        rt = uni(ff.route);
+        tbase = uni(ff.tr0);
+        nval = uni(ff.nval);
+        misaligned = uni(ff.misaligned);
+        sky0 = uni(ff.sky);
+        s_bs = bs;
+        s_far = sc.far[ff.plane];
+    } else {
+        rt = route[b];
+        tbase = finfo[b * FI_STRIDE + FI_TR0];
+        nval = finfo[b * FI_STRIDE + FI_NVAL];
+        misaligned = finfo[b * FI_STRIDE + FI_MISALIGNED];
+        sky0 = finfo[b * FI_STRIDE + FI_SKY] & ~SKY_OFF;  // (another block may have called the sky off already)
+    }
     if (rt == ROUTE_POINTS) return;  // a frame with a handful of sources: k_pts's tiles ride in k_fin's launch (dtfill_pts.hpp)
     const int r = rt > 0 ? (rt & 0xFF) : 0;
     const bool pre = rt > 0 && (rt & ROUTE_PREMARK);
     // EPI (a depth epilogue: ep.row0 != 0 || ep.use_floor) is chosen on the host: the plain pass runs code compiled without it
 #define FUSED_CALL(FR_, T_)                                                                                        \
-    fused_body<FR_, EPI, STREAM>(pre, x, srcbits, wpre_s, rowbase_s, finfo, vlist, H, W, Wd, T_.nty, T_.TW, T_.tiles_x, out_depth, out_dt, \
+    fused_body<FR_, EPI, STREAM>(tile, pre, tbase, nval, misaligned, sky0, s_bs, s_far, x, srcbits, wpre_s, rowbase_s, finfo, vlist, H, W, Wd, T_.nty, T_.TW, T_.tiles_x, out_depth, out_dt, \
                           out_index, fflag, rowfar, frame_status, ep, s_ring, s_rw, s_tab, s_any)
-    if (r == 16 && (int)blockIdx.y < t16.ntiles)
+    if (r == 16 && tile < t16.ntiles)
         FUSED_CALL(16, t16);
-    else if (r == 32 && (int)blockIdx.y < t32.ntiles)
+    else if (r == 32 && tile < t32.ntiles)
         FUSED_CALL(32, t32);
 #undef FUSED_CALL
 }

@@ -165,9 +165,9 @@ __device__ __forceinline__ void stats_body(const int *__restrict__ route, const 
             } else if (r == 0)
                 ++any;
         } else if (r > 0) {
-            if (f == 2u && finfo[b * FI_STRIDE + FI_SKY] > 0) ++sky; else if (f == 0u) ++win; else ++any;
+            if (f == 2u && sky_rows(finfo, b) > 0) ++sky; else if (f == 0u) ++win; else ++any;
         } else if (r == 0) {
-            if (f == 2u && finfo[b * FI_STRIDE + FI_SKY] > 0) ++sky; else ++any;
+            if (f == 2u && sky_rows(finfo, b) > 0) ++sky; else ++any;
         }
     }
     __shared__ int s[3];

@@ -5,7 +5,7 @@
 // ------------------------------------------------------------------------------------------------
 // k_mask: one wave per image row.  Source predicate exactly as tools.py:8, mask = (1.0 - x) > thr (1 = fill, 0 = source);
 // value predicate as tools.py:22, x > thr.  Per 64-pixel word: the two bit words and the row-local exclusive popcount; per
-// row: totals (+ "masks differ" in bit 31).  A row is read in chunks of 256 pixels = four words, a batch of chunks in flight:
+// row: totals (+ "masks differ" in bit 31), and the row's and the frame's per-pass flags cleared.  A row is read in chunks of 256 pixels = four words, a batch of chunks in flight:
 //   VEC (W % 4 == 0, 16-byte aligned frames): a lane reads 4 consecutive pixels in one load; its four predicate bits form a
 //        nibble, and the 16 lanes of a DPP row combine theirs into one word.
 //   !VEC: a lane reads pixel 64 q + lane of each of the chunk's four words q; word q is a ballot.
@@ -60,7 +60,8 @@ template <int OM, bool VEC>
 __device__ __forceinline__ void mask_body(const float *__restrict__ x, int H, int W, int Wd, float src_thr, float val_thr,
                                           u64 *__restrict__ srcbits, u64 *__restrict__ valbits, u16 *__restrict__ wpre_s,
                                           u16 *__restrict__ wpre_v, u32 *__restrict__ rowcnt_s, u32 *__restrict__ rowcnt_v,
-                                          int *__restrict__ negflag) {
+                                          int *__restrict__ negflag, u32 *__restrict__ rowfar, int *__restrict__ fflag2,
+                                          int *__restrict__ frame_status, int *__restrict__ finfo, int *__restrict__ route, bool clear) {
     __shared__ u16 s_list[OM ? 4 : 1][OM ? M4_NC * 256 : 1];
     __shared__ u32 s_drop[OM ? 4 : 1][OM ? M4_NC * 8 : 1];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -158,83 +159,114 @@ __device__ __forceinline__ void mask_body(const float *__restrict__ x, int H, in
     if (lane == 0) {
         rowcnt_s[(size_t)b * H + i] = run_s;
         rowcnt_v[(size_t)b * H + i] = run_v | (mis ? 0x80000000u : 0u);
+        // clear (a pass whose frame facts are worked out in k_fused's launch): what the frame's publishing block
+        // (frame_publish) and the window blocks both raise in that one launch starts clear here: the row flags, the frame's
+        // any-distance flag, its status, "the sky is called off" and the route.  The raisers only ever set bits.  (With a
+        // k_frame launch of its own that kernel stores all of them, as it always did.)
+        if (clear) rowfar[(size_t)b * H + i] = 0u;
+        if (clear && i == 0) {
+            fflag2[b] = 0;
+            frame_status[b] = DTFILL_FRAME_OK;
+            finfo[b * FI_STRIDE + FI_SKY] = 0;
+            route[b] = ROUTE_UNKNOWN;  // (k_fused's late blocks look at it before the facts are published)
+        }
     }
     if (OM == 1 && __any(neg) && lane == 0) negflag[b] = 1;  // this frame is redone by the exhaustive launch
 }
 template <int OM, bool VEC>
 __global__ __launch_bounds__(256) void k_mask(const Pass p) {
     mask_body<OM, VEC>(p.x, p.H, p.W, p.Wd, p.src_thr, p.val_thr, p.srcbits, p.valbits, p.wpre_s, p.wpre_v, p.rowcnt_s, p.rowcnt_v,
-                       p.negflag);
+                       p.negflag, p.rowfar, p.fflag2, p.status, p.finfo, p.route, p.ride != 0);
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_frame: one workgroup per frame.  Exclusive scan of the row counts = raster rank of the first
-// source / value pixel of every row: cv2's label init (k=1; every zero pixel gets k++) and numpy's
-// boolean compaction x[with_value] (tools.py:24).  The value list is only materialised when the two
-// masks differ somewhere in the frame.
+// The frame facts: everything a pass decides per frame, a pure function of the frame's row counts (k_mask), H, W, mode and
+// the two tilings' tile rows.  Exclusive scan of the row counts = raster rank of the first source / value pixel of every row:
+// cv2's label init (k=1; every zero pixel gets k++) and numpy's boolean compaction x[with_value] (tools.py:24).
+//   frame_facts    works them out for a block of 256 threads and leaves the row structure in LDS (FrameScratch); every
+//                  row's two rank bases go to the caller's sink.  Called by the block that publishes a frame (k_frame, or
+//                  the first block of the frame in k_fused's launch) and by every window block of k_fused for its own frame: ONE
+//                  definition, so a window block and the published state always agree.
+//   frame_publish  stores what later launches read: finfo, route, the row flags, fflag2, the frame status, the source list
+//                  of a k_pts frame, the value list when the two masks of a frame differ somewhere.  The row flags, fflag2,
+//                  the status and FI_SKY start clear (k_mask) and are only raised here: the window blocks of the same
+//                  launch raise them too.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void frame_body(const float *__restrict__ x, const u64 *__restrict__ valbits,
-                                           const u16 *__restrict__ wpre_v, const u64 *__restrict__ srcbits,
-                                           const u16 *__restrict__ wpre_s, PtsSrc *__restrict__ ptslist,
-                                           const u32 *__restrict__ rowcnt_s, const u32 *__restrict__ rowcnt_v, int H, int W, int Wd,
-                                           u32 *__restrict__ rowbase_s, u32 *__restrict__ rowbase_v, int *__restrict__ finfo,
-                                           float *__restrict__ vlist, int *__restrict__ fflag2, int *__restrict__ route,
-                                           int *__restrict__ frame_status, int mode, int *__restrict__ negflag,
-                                           u32 *__restrict__ rowfar, int nty16, int nty32) {
+struct FrameScratch {
+    u32 empty[256];   // bit i: row i holds no source (the rows past H count as empty)
+    u32 far[2][256];  // bit i: row i >= r0 and vd(i) > PM16 / > PM32; after the tile-row culling: the chosen halo's pre-marked rows
+    u16 ptrow[L2_PTS_MAX];  // rows that hold a source (for the source list of a k_pts frame)
+    u32 ws[2][4], wv[2][4];  // the waves' totals of a batch of 256 rows, double-buffered by batch parity: one barrier per batch
+    int mis, dlb, nfar[2], r0, bandmax, nrow;
+};
+struct FrameFacts {
+    int r;           // the route without ROUTE_PREMARK: 16, 32, 0 or ROUTE_POINTS
+    int route;       // ... as route[b] holds it
+    int r0;          // the first row that holds a source (H: none)
+    int sky;         // rows [0, sky) are k_sky's (0: none)
+    int tr0;         // the first row of the window kernel's tiling
+    int nsrc, nval, misaligned, dlb;
+    int plane;       // which of FrameScratch::far holds the frame's pre-marked rows
+    bool flags, sky_ok, any1, anygone;
+    // the row flag of row i (l1_cv: 0 = the window kernel's, 1 = the any-distance kernels', 2 = k_sky's; l2: L2_ROW_GONE)
+    __device__ __forceinline__ u32 rowflag(const FrameScratch &sc, int i, bool l2) const {
+        const u32 farbit = (sc.far[plane][i >> 5] >> (i & 31)) & 1u;
+        u32 f = 0u;
+        if (flags && r > 0) f = i < r0 && sky_ok ? (sky ? 2u : 1u) : farbit;
+        if (l2 && r > 0 && farbit) f = L2_ROW_GONE;  // (a frame without sources is not routed to a window)
+        return f;
+    }
+};
+
+// cs_, cv_: the frame's row counts; sink(i, bs, bv): the rank bases of row i < H; list: the rows that hold a source are wanted
+// in sc.ptrow / sc.nrow (the publishing block's, for the source list of a k_pts frame)
+template <class Sink>
+__device__ __forceinline__ FrameFacts frame_facts(const u32 *__restrict__ cs_, const u32 *__restrict__ cv_, int H, int W, int mode,
+                                                  int nty16, int nty32, FrameScratch &sc, bool list, Sink sink) {
     const bool force_general = mode & 1;  // every frame takes the any-distance kernels (tests)
     const bool l2 = mode & 2;             // l2: the window kernel's cost does not grow with the distances it meets
     const bool premark = mode & 4;        // l1_cv without a depth epilogue: rows too far from every source row are handed on up front
     const bool pts_ok = mode & 8;         // l1_cv: a frame with a handful of sources may go to k_pts
-    __shared__ u32 s_ws[4], s_wv[4];
-    __shared__ int s_mis, s_dlb;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const u32 *cs_ = rowcnt_s + (size_t)b * H, *cv_ = rowcnt_v + (size_t)b * H;
-    u32 *bs_ = rowbase_s + (size_t)b * H, *bv_ = rowbase_v + (size_t)b * H;
-    __shared__ u32 s_empty[256];   // bit i: row i holds no source (the rows past H count as empty)
-    __shared__ u32 s_far[2][256];  // bit i: row i >= r0 and vd(i) > PM16 / > PM32
-    __shared__ int s_nfar[2], s_r0, s_route, s_bandmax, s_nrow;
-    __shared__ u16 s_ptrow[L2_PTS_MAX];  // rows that hold a source (for the source list of a k_pts frame)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int Hp = (H + 63) & ~63;
+    // the counts of the first 256 rows are on their way before anything else; every later batch while the one before is scanned
+    u32 ncs = tid < H ? cs_[tid] : 0u, ncv = tid < H ? cv_[tid] : 0u;
     if (tid == 0) {
-        s_mis = 0;
-        s_dlb = 0;
-        s_r0 = H;
-        s_bandmax = 0;
-        s_nrow = 0;
+        sc.mis = 0;
+        sc.dlb = 0;
+        sc.r0 = H;
+        sc.bandmax = 0;
+        sc.nrow = 0;
     }
-    if (tid < 2) s_nfar[tid] = 0;
-    for (int w = tid + (Hp >> 5); w < 256; w += 256) s_empty[w] = 0xFFFFFFFFu;
+    if (tid < 2) sc.nfar[tid] = 0;
+    for (int w = tid + (Hp >> 5); w < 256; w += 256) sc.empty[w] = 0xFFFFFFFFu;
     __syncthreads();
     u32 run_s = 0, run_v = 0;
     int mis = 0;
     for (int base = 0; base < Hp; base += 256) {
         const int i = base + tid;
-        u32 cs = 0, cv = 0;
-        if (i < H) {
-            cs = cs_[i];
-            cv = cv_[i];
-            mis |= (int)(cv >> 31);
-            cv &= 0x7FFFFFFFu;
-        }
+        u32 cs = ncs, cv = ncv;
+        ncs = i + 256 < H ? cs_[i + 256] : 0u;
+        ncv = i + 256 < H ? cv_[i + 256] : 0u;
+        mis |= (int)(cv >> 31);
+        cv &= 0x7FFFFFFFu;
         {
             // the same pass over the row counts: "row has no source" as bits (a wave holds 64 consecutive rows: two whole words per
             // ballot, no atomics), the first row with a source, the most sources in a band of 32 rows (k_pts's tiles are that high)
             const u64 has = __ballot(cs != 0u), bal = ~has;
             if (lane == 0 && i < Hp) {
-                s_empty[i >> 5] = (u32)bal;
-                s_empty[(i >> 5) + 1] = (u32)(bal >> 32);
-                if (has) atomicMin(&s_r0, i + __ffsll((long long)has) - 1);
+                sc.empty[i >> 5] = (u32)bal;
+                sc.empty[(i >> 5) + 1] = (u32)(bal >> 32);
+                if (has) atomicMin(&sc.r0, i + __ffsll((long long)has) - 1);
             }
-            u32 c = cs;
-#pragma unroll
-            for (int o = 1; o < 32; o <<= 1) c += (u32)__shfl_xor((int)c, o);
-            if ((lane & 31) == 0 && c) atomicMax(&s_bandmax, (int)c);
             // ... and the rows that hold a source, listed (in any order; at most L2_PTS_MAX matter: a frame with more of them
             // is no k_pts frame)
-            int at = 0;
-            if (lane == 0 && has) at = atomicAdd(&s_nrow, __popcll(has));
-            at = __builtin_amdgcn_readfirstlane(at) + (int)__builtin_amdgcn_mbcnt_hi((u32)(has >> 32), __builtin_amdgcn_mbcnt_lo((u32)has, 0u));
-            if (cs != 0u && at < L2_PTS_MAX) s_ptrow[at] = (u16)i;
+            if (list) {  // block-uniform
+                int at = 0;
+                if (lane == 0 && has) at = atomicAdd(&sc.nrow, __popcll(has));
+                at = __builtin_amdgcn_readfirstlane(at) + (int)__builtin_amdgcn_mbcnt_hi((u32)(has >> 32), __builtin_amdgcn_mbcnt_lo((u32)has, 0u));
+                if (cs != 0u && at < L2_PTS_MAX) sc.ptrow[at] = (u16)i;
+            }
         }
         u32 is = cs, iv = cv;
 #pragma unroll
@@ -245,30 +277,33 @@ __device__ __forceinline__ void frame_body(const float *__restrict__ x, const u6
                 iv += tv;
             }
         }
+        {
+            // the two bands of 32 rows a wave holds, off the inclusive scan: lanes 0..31 end in lane 31, the rest is the other band
+            const u32 half = (u32)__shfl((int)is, 31);
+            if (lane == 31 && is) atomicMax(&sc.bandmax, (int)is);
+            if (lane == 63 && is != half) atomicMax(&sc.bandmax, (int)(is - half));
+        }
+        const int par = (base >> 8) & 1;
         if (lane == 63) {
-            s_ws[wave] = is;
-            s_wv[wave] = iv;
+            sc.ws[par][wave] = is;
+            sc.wv[par][wave] = iv;
         }
         __syncthreads();
         u32 ps = 0, pv = 0, ts = 0, tv = 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (k < wave) {
-                ps += s_ws[k];
-                pv += s_wv[k];
+                ps += sc.ws[par][k];
+                pv += sc.wv[par][k];
             }
-            ts += s_ws[k];
-            tv += s_wv[k];
+            ts += sc.ws[par][k];
+            tv += sc.wv[par][k];
         }
-        if (i < H) {
-            bs_[i] = run_s + ps + is - cs;
-            bv_[i] = run_v + pv + iv - cv;
-        }
+        if (i < H) sink(i, run_s + ps + is - cs, run_v + pv + iv - cv);
         run_s += ts;
         run_v += tv;
-        __syncthreads();
     }
-    if (mis) atomicOr(&s_mis, 1);
+    if (mis) atomicOr(&sc.mis, 1);
     // Row structure of the frame (l1_cv uses all of it, l2 only FI_DLB):
     //   r0     the first row that holds a source.  The rows above it -- the empty sky of a LiDAR frame -- need no search at all:
     //          every source is below them, so cv2's backward sweep alone decides them, row by row from the two rows beneath
@@ -280,13 +315,13 @@ __device__ __forceinline__ void frame_body(const float *__restrict__ x, const u6
     // "Row has no source" as bits in LDS (H <= 8191 -> 256 words); the rows past H count as empty.
     // (a frame in which every row holds a source -- the common dense one -- has vd = 0 everywhere: nothing to search)
     bool someempty = false;
-    for (int w = tid; w <= (H - 1) >> 5; w += 256) someempty |= (s_empty[w] & (w == (H - 1) >> 5 ? (2u << ((H - 1) & 31)) - 1u : 0xFFFFFFFFu)) != 0u;
+    for (int w = tid; w <= (H - 1) >> 5; w += 256) someempty |= (sc.empty[w] & (w == (H - 1) >> 5 ? (2u << ((H - 1) & 31)) - 1u : 0xFFFFFFFFu)) != 0u;
     someempty = __syncthreads_or(someempty);
     if (!someempty) {
-        s_far[0][tid] = s_far[1][tid] = 0u;
+        sc.far[0][tid] = sc.far[1][tid] = 0u;
     } else {
         int dlb = 0;
-        const int lastw = (H - 1) >> 5, r0 = s_r0;
+        const int lastw = (H - 1) >> 5, r0 = sc.r0;
         for (int base = 0; base < Hp; base += 256) {
             const int i = base + tid;
             int vd = 0;
@@ -294,14 +329,14 @@ __device__ __forceinline__ void frame_body(const float *__restrict__ x, const u6
                 int up = BIG, dn = BIG;  // distance to the nearest row with a source at or above / at or below row i
                 {
                     int w = i >> 5;
-                    u32 m = ~s_empty[w] & ((2u << (i & 31)) - 1u);
-                    while (!m && w > 0) m = ~s_empty[--w];
+                    u32 m = ~sc.empty[w] & ((2u << (i & 31)) - 1u);
+                    while (!m && w > 0) m = ~sc.empty[--w];
                     if (m) up = i - (w * 32 + 31 - __clz((int)m));
                 }
                 {
                     int w = i >> 5;
-                    u32 m = ~s_empty[w] & ~((1u << (i & 31)) - 1u);
-                    while (!m && w < lastw) m = ~s_empty[++w];
+                    u32 m = ~sc.empty[w] & ~((1u << (i & 31)) - 1u);
+                    while (!m && w < lastw) m = ~sc.empty[++w];
                     if (m) dn = w * 32 + __ffs((int)m) - 1 - i;
                 }
                 vd = min(up, dn);
@@ -310,23 +345,28 @@ __device__ __forceinline__ void frame_body(const float *__restrict__ x, const u6
             // l2: the rows farther from every row with a source than the window kernel's radius (no pixel of them has a source in its window)
             const u64 f16 = __ballot(i < H && (l2 ? vd > W2_R16 : (i >= r0 && vd > PM16))), f32 = __ballot(i < H && (l2 ? vd > W2_R32 : (i >= r0 && vd > PM32)));
             if (lane == 0 && i < Hp) {
-                s_far[0][i >> 5] = (u32)f16;
-                s_far[0][(i >> 5) + 1] = (u32)(f16 >> 32);
-                s_far[1][i >> 5] = (u32)f32;
-                s_far[1][(i >> 5) + 1] = (u32)(f32 >> 32);
-                if (f16) atomicAdd(&s_nfar[0], __popcll(f16));
-                if (f32) atomicAdd(&s_nfar[1], __popcll(f32));
+                sc.far[0][i >> 5] = (u32)f16;
+                sc.far[0][(i >> 5) + 1] = (u32)(f16 >> 32);
+                sc.far[1][i >> 5] = (u32)f32;
+                sc.far[1][(i >> 5) + 1] = (u32)(f32 >> 32);
+                if (f16) atomicAdd(&sc.nfar[0], __popcll(f16));
+                if (f32) atomicAdd(&sc.nfar[1], __popcll(f32));
             }
         }
 #pragma unroll
         for (int o = 32; o; o >>= 1) dlb = max(dlb, __shfl_xor(dlb, o));
-        if (lane == 0 && dlb) atomicMax(&s_dlb, dlb);
+        if (lane == 0 && dlb) atomicMax(&sc.dlb, dlb);
     }
     __syncthreads();
-    const int misaligned = s_mis;
-    const int r0 = s_r0;
-    const bool sky_ok = premark && r0 >= SKY_MIN && r0 <= SKY_MAX && r0 < H;  // rows [0, r0) can be k_sky's
-    if (tid == 0) {
+    FrameFacts ff;
+    ff.misaligned = sc.mis;
+    ff.dlb = sc.dlb;
+    ff.nsrc = (int)run_s;
+    ff.nval = (int)run_v;
+    const int r0 = ff.r0 = sc.r0;
+    const bool sky_ok = ff.sky_ok = premark && r0 >= SKY_MIN && r0 <= SKY_MAX && r0 < H;  // rows [0, r0) can be k_sky's
+    int r;
+    {  // (every thread for itself, from what the barrier above made visible: no thread waits for another's decision)
         // Which kernel family takes the frame -- a speed heuristic, never a correctness condition (the window kernels hand on
         // every row in which they meet a pixel they cannot decide).  With source density p the chance that a pixel has no
         // source within L1 distance R is about (1-p)^(2 R^2 + 2 R + 1); if the frame is expected to hold such pixels all
@@ -340,7 +380,7 @@ __device__ __forceinline__ void frame_body(const float *__restrict__ x, const u6
         auto fits = [&](int R, int nfar) {
             const long long ball = 2 * R * R + 2 * R + 1;
             if (l2) return (long long)run_s * ball >= 14ll * H * W;
-            if (!premark) return (long long)run_s * ball >= 14ll * H * W && s_dlb <= R;
+            if (!premark) return (long long)run_s * ball >= 14ll * H * W && sc.dlb <= R;
             const int rest = H - (sky_ok ? r0 : 0) - nfar;
             return rest > 0 && (long long)run_s * ball >= 14ll * rest * W;
         };
@@ -350,50 +390,20 @@ __device__ __forceinline__ void frame_body(const float *__restrict__ x, const u6
         const bool points = l2 && !force_general && run_s > 0 && run_s <= (u32)L2_PTS_MAX;
         // l1_cv, a handful of sources and too thin for a window: k_pts (per tile, the sources whose cells reach it).  Not when they
         // crowd into one band of rows: its tiles would look at all of them for every pixel.
-        const bool points1 = !l2 && pts_ok && run_s > 0 && run_s <= (u32)L2_PTS_MAX && s_bandmax <= PTS_BAND_MAX;
-        const int window = fits(16, s_nfar[0]) ? 16 : fits(32, s_nfar[1]) ? 32 : 0;
-        s_route = force_general ? 0 : points ? ROUTE_POINTS : window ? window : points1 ? ROUTE_POINTS : 0;
+        const bool points1 = !l2 && pts_ok && run_s > 0 && run_s <= (u32)L2_PTS_MAX && sc.bandmax <= PTS_BAND_MAX;
+        const int window = fits(16, sc.nfar[0]) ? 16 : fits(32, sc.nfar[1]) ? 32 : 0;
+        r = force_general ? 0 : points ? ROUTE_POINTS : window ? window : points1 ? ROUTE_POINTS : 0;
     }
-    __syncthreads();
-    const int r = s_route;
-    if (!l2 && r == ROUTE_POINTS) {
-        // the frame's sources in raster order (index = label - 1), for k_pts
-        PtsSrc *list = ptslist + (size_t)b * L2_PTS_MAX;
-        const float *xf = x + (size_t)b * H * W;
-        // an item = one 64-pixel word of a row that holds a source (the rows were listed above); a word's sources go to their
-        // raster ranks.  Eight items per step, and everything an item needs before its depths is loaded at once (this block alone
-        // works on the frame: the chain of dependent loads is what the step costs)
-        constexpr int NQ = 8;
-        const int nitems = min(s_nrow, L2_PTS_MAX) * Wd;
-        for (int it0 = tid; it0 < nitems; it0 += 256 * NQ) {
-            u64 sb[NQ];
-            u32 k[NQ];
-            int row[NQ], w[NQ];
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const int it = min(it0 + 256 * q, nitems - 1);
-                row[q] = s_ptrow[it / Wd];
-                w[q] = it % Wd;
-                const size_t at = ((size_t)b * H + row[q]) * Wd + w[q];
-                sb[q] = it0 + 256 * q < nitems ? srcbits[at] : 0ull;
-                k[q] = bs_[row[q]] + wpre_s[at];  // (this block wrote bs_ above, before a barrier)
-            }
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                u64 m = sb[q];
-                while (m) {
-                    const int j = w[q] * 64 + __ffsll((long long)m) - 1;
-                    m &= m - 1;
-                    list[k[q]++] = PtsSrc{(u32)row[q] << 16 | (u32)j, xf[(size_t)row[q] * W + j]};  // ... with its depth
-                }
-            }
-        }
-    }
-    const bool flags = !l2 && premark && r >= 0;  // this frame's rows carry flags
+    ff.r = r;
+    const bool flags = ff.flags = !l2 && premark && r >= 0;  // this frame's rows carry flags
     // k_sky starts from rows r0 and r0 + 1 as the window kernel leaves them (it runs beside the first any-distance kernel): a
     // frame that is not a window kernel's, or whose row r0 / r0 + 1 is handed on up front, keeps its sky with the other rows
     bool sky = sky_ok && r > 0;
-    u32 *far = s_far[r == 32 ? 1 : 0];
+    ff.plane = r == 32 ? 1 : 0;
+    u32 *far = sc.far[ff.plane];
+    ff.any1 = false;
+    // (a frame in which every row holds a source has no far row, no sky and nothing to cull)
+    if (someempty) {  // block-uniform
     if (flags && r > 0) {
         // a tile row of the window kernel that is left with only a few rows is not worth its windows: all of it goes to the
         // any-distance kernels.  One thread per tile row, whole words at a time.
@@ -415,56 +425,171 @@ __device__ __forceinline__ void frame_body(const float *__restrict__ x, const u6
     }
     __syncthreads();
     if (sky && (((far[r0 >> 5] >> (r0 & 31)) & 1u) || (r0 + 1 < H && ((far[(r0 + 1) >> 5] >> ((r0 + 1) & 31)) & 1u)))) sky = false;
-    // per row: l1_cv: 0 = the window kernel's, 1 = the any-distance kernels' (pre-marked here, or set by k_fused when it meets
-    // a pixel farther than its halo), 2 = k_sky's; l2: far pixels k_l2win counted
+    // some row carries flag 1: the rows above r0 when their sky is not k_sky's, or a pre-marked row (far holds no bit of a
+    // row above r0 then, and none of a row past H ever)
     bool one = false;
-    for (int i = tid; i < H; i += 256) {
-        u32 f = 0u;
-        if (flags && r > 0) f = i < r0 && sky_ok ? (sky ? 2u : 1u) : (far[i >> 5] >> (i & 31)) & 1u;
-        if (l2 && r > 0 && ((far[i >> 5] >> (i & 31)) & 1u)) f = L2_ROW_GONE;  // (a frame without sources is not routed to a window)
-        one |= f == 1u;
-        rowfar[(size_t)b * H + i] = f;
+    if (flags && r > 0) {
+        one = sky_ok && !sky;
+        for (int w = tid; w <= (H - 1) >> 5; w += 256) one |= far[w] != 0u;
     }
-    const bool any1 = __syncthreads_or(one);
-    const bool anygone = l2 && r > 0 && s_nfar[r == 32 ? 1 : 0] > 0;  // l2: rows for k_colT + k_l2env from the start
+    ff.any1 = __syncthreads_or(one);
+    }
+    ff.sky = (flags && sky) ? r0 : 0;
+    ff.tr0 = (flags && r > 0 && sky_ok) ? r0 : 0;
+    ff.anygone = l2 && r > 0 && sc.nfar[ff.plane] > 0;  // l2: rows for k_colT + k_l2env from the start
+    const bool marked = flags && r > 0 && (ff.sky > 0 || ff.any1);
+    ff.route = marked ? (r | ROUTE_PREMARK) : r;
+    return ff;
+}
+
+// The compacted value list of a frame whose two masks differ somewhere (rare): x at the value pixels, in raster order.
+// bv(i): the rank base of row i's values.  One block of 256 threads writes the whole list.
+template <class Base>
+__device__ __forceinline__ void value_list(int b, const float *__restrict__ x, const u64 *__restrict__ valbits,
+                                           const u16 *__restrict__ wpre_v, int H, int W, int Wd, float *__restrict__ vlist, Base bv) {
+    const float *xf = x + (size_t)b * H * W;
+    float *vl = vlist + (size_t)b * H * W;
+    const int nwords = H * Wd;
+    for (int w = threadIdx.x; w < nwords; w += 256) {
+        u64 vb = valbits[(size_t)b * nwords + w];
+        const int i = w / Wd, j0 = (w - i * Wd) * 64;
+        u32 k = bv(i) + wpre_v[(size_t)b * nwords + w];
+        while (vb) {
+            const int bit = __ffsll((long long)vb) - 1;
+            vb &= vb - 1;
+            vl[k++] = xf[(size_t)i * W + j0 + bit];
+        }
+    }
+}
+
+// what the later launches read of frame b (bs_: the frame's rowbase_s, which this block's sink has stored before a barrier)
+__device__ __forceinline__ void frame_publish(const FrameFacts &ff, const FrameScratch &sc, int b, const float *__restrict__ x,
+                                              const u64 *__restrict__ valbits, const u16 *__restrict__ wpre_v,
+                                              const u64 *__restrict__ srcbits, const u16 *__restrict__ wpre_s,
+                                              PtsSrc *__restrict__ ptslist, int H, int W, int Wd, const u32 *bs_, const u32 *bv_,
+                                              int *__restrict__ finfo, float *__restrict__ vlist, int *__restrict__ fflag2,
+                                              int *__restrict__ route, int *__restrict__ frame_status, int mode,
+                                              int *__restrict__ negflag, u32 *__restrict__ rowfar, bool raise) {
+    // raise: the window blocks of this very launch raise rowfar, fflag2, the status and FI_SKY's SKY_OFF bit too (all clear since k_mask):
+    // only what is non-zero is stored, flags by atomicOr.  Else (k_frame) every word is stored.
+    const bool l2 = mode & 2;
+    const int tid = threadIdx.x, r = ff.r;
+    // the route first: k_fused's late blocks look at it (they exit at once in a frame that is not their tiling's)
+    if (tid == 0) __hip_atomic_store(&route[b], ff.route, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!l2 && r == ROUTE_POINTS) {
+        // the frame's sources in raster order (index = label - 1), for k_pts
+        PtsSrc *list = ptslist + (size_t)b * L2_PTS_MAX;
+        const float *xf = x + (size_t)b * H * W;
+        // an item = one 64-pixel word of a row that holds a source (the rows were listed above); a word's sources go to their
+        // raster ranks.  Eight items per step, and everything an item needs before its depths is loaded at once (this block alone
+        // works on the frame: the chain of dependent loads is what the step costs)
+        constexpr int NQ = 8;
+        const int nitems = min(sc.nrow, L2_PTS_MAX) * Wd;
+        for (int it0 = tid; it0 < nitems; it0 += 256 * NQ) {
+            u64 sb[NQ];
+            u32 k[NQ];
+            int row[NQ], w[NQ];
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const int it = min(it0 + 256 * q, nitems - 1);
+                row[q] = sc.ptrow[it / Wd];
+                w[q] = it % Wd;
+                const size_t at = ((size_t)b * H + row[q]) * Wd + w[q];
+                sb[q] = it0 + 256 * q < nitems ? srcbits[at] : 0ull;
+                k[q] = bs_[row[q]] + wpre_s[at];  // (this block wrote bs_ before a barrier)
+            }
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                u64 m = sb[q];
+                while (m) {
+                    const int j = w[q] * 64 + __ffsll((long long)m) - 1;
+                    m &= m - 1;
+                    list[k[q]++] = PtsSrc{(u32)row[q] << 16 | (u32)j, xf[(size_t)row[q] * W + j]};  // ... with its depth
+                }
+            }
+        }
+    }
+    // per row: l1_cv: 0 = the window kernel's, 1 = the any-distance kernels' (pre-marked here, or set by k_fused when it meets
+    // a pixel farther than its halo), 2 = k_sky's; l2: far pixels k_l2win counted.  (Clear since k_mask.)
+    for (int i = tid; i < H; i += 256) {
+        const u32 f = ff.rowflag(sc, i, l2);
+        if (f || !raise) rowfar[(size_t)b * H + i] = f;  // (1: the window kernel may store the same)
+    }
     if (tid == 0) {
-        finfo[b * FI_STRIDE + FI_NSRC] = (int)run_s;
-        finfo[b * FI_STRIDE + FI_NVAL] = (int)run_v;
-        finfo[b * FI_STRIDE + FI_MISALIGNED] = misaligned;
-        finfo[b * FI_STRIDE + FI_DLB] = s_dlb;
+        finfo[b * FI_STRIDE + FI_NSRC] = ff.nsrc;
+        finfo[b * FI_STRIDE + FI_NVAL] = ff.nval;
+        finfo[b * FI_STRIDE + FI_MISALIGNED] = ff.misaligned;
+        finfo[b * FI_STRIDE + FI_DLB] = ff.dlb;
         finfo[b * FI_STRIDE + FI_NUNRES] = 0;
-        finfo[b * FI_STRIDE + FI_SKY] = finfo[b * FI_STRIDE + FI_SKY0] = (flags && sky) ? r0 : 0;
-        finfo[b * FI_STRIDE + FI_TR0] = (flags && r > 0 && sky_ok) ? r0 : 0;
-        const bool marked = flags && r > 0 && (sky || any1);
-        route[b] = marked ? (r | ROUTE_PREMARK) : r;
+        if (!raise)
+            finfo[b * FI_STRIDE + FI_SKY] = ff.sky;
+        else if (ff.sky)
+            atomicOr(&finfo[b * FI_STRIDE + FI_SKY], ff.sky);
+        finfo[b * FI_STRIDE + FI_TR0] = ff.tr0;
         negflag[b] = 0;  // k_mask's "this frame holds a negative value": consumed before this kernel, reset for the next pass
         const bool general = r == 0;
         // 2: the any-distance kernels take the whole frame; 1: the rows flagged 1 (pre-marked here, or by k_fused, or (l2) by
         // k_l2win when it hands a row of far pixels on); 0: nothing for them
         // 3 (l1_cv, ROUTE_POINTS): k_pts takes the frame, of the any-distance kernels only k_tiesx has something to do
-        fflag2[b] = (!l2 && r == ROUTE_POINTS) ? 3 : general ? 2 : ((flags && any1) || anygone) ? 1 : 0;
-        frame_status[b] = (general || r == ROUTE_POINTS || marked) ? DTFILL_FRAME_GENERAL_PATH : DTFILL_FRAME_OK;
-    }
-    if (misaligned) {
-        // rare path: scatter x at value pixels into the compacted value list
-        const float *xf = x + (size_t)b * H * W;
-        float *vl = vlist + (size_t)b * H * W;
-        const int nwords = H * Wd;
-        for (int w = tid; w < nwords; w += 256) {
-            u64 vb = valbits[(size_t)b * nwords + w];
-            const int i = w / Wd, j0 = (w - i * Wd) * 64;
-            u32 k = bv_[i] + wpre_v[(size_t)b * nwords + w];
-            while (vb) {
-                const int bit = __ffsll((long long)vb) - 1;
-                vb &= vb - 1;
-                vl[k++] = xf[(size_t)i * W + j0 + bit];
-            }
+        const int f2 = (!l2 && r == ROUTE_POINTS) ? 3 : general ? 2 : ((ff.flags && ff.any1) || ff.anygone) ? 1 : 0;
+        const int st = (general || r == ROUTE_POINTS || (ff.route > 0 && (ff.route & ROUTE_PREMARK))) ? DTFILL_FRAME_GENERAL_PATH : DTFILL_FRAME_OK;
+        if (!raise) {
+            fflag2[b] = f2;
+            frame_status[b] = st;
+        } else {
+            // k_fused stores fflag2 = 1 in a window frame whose rows carry flags, where f2 is 0 or 1, and 2 in a window frame
+            // under a depth epilogue, where f2 is 0 (no row flags): the OR never mixes two different non-zero values
+            if (f2) atomicOr(&fflag2[b], f2);
+            if (st) atomicOr(&frame_status[b], st);
         }
     }
+    // (this block wrote bv_ before a barrier)
+    if (ff.misaligned) value_list(b, x, valbits, wpre_v, H, W, Wd, vlist, [&](int i) { return bv_[i]; });
 }
+
+// What the publishing block of a frame needs beside the pass's shape (k_frame unpacks the pass record into it, k_fused's
+// launch carries it: its blocks read the row counts, mode and the two nty from it, a frame's first block all of it)
+struct FrameArgs {
+    const float *x;
+    const u64 *valbits, *srcbits;
+    const u16 *wpre_v, *wpre_s;
+    PtsSrc *ptslist;
+    const u32 *rowcnt_s, *rowcnt_v;
+    u32 *rowbase_s, *rowbase_v;
+    int *negflag;
+    int mode, nty16, nty32;
+    int ride;   // k_fused: its window blocks work the frame facts out themselves, block 0 of a frame publishes them
+    int ntmin;  // ... the number of tiles of the tiling with fewer of them: the blocks from there on look at route[b] first
+};
+__host__ __device__ inline FrameArgs frame_args(const Pass &p, int mode, int nty16, int nty32, int ride, int ntmin) {
+    return FrameArgs{p.x, p.valbits, p.srcbits, p.wpre_v, p.wpre_s, p.ptslist, p.rowcnt_s, p.rowcnt_v, p.rowbase_s, p.rowbase_v,
+                     p.negflag, mode, nty16, nty32, ride, ntmin};
+}
+
+// one block of 256 threads: the facts of frame b, published
+__device__ __forceinline__ void frame_body(int b, const float *__restrict__ x, const u64 *__restrict__ valbits,
+                                           const u16 *__restrict__ wpre_v, const u64 *__restrict__ srcbits,
+                                           const u16 *__restrict__ wpre_s, PtsSrc *__restrict__ ptslist,
+                                           const u32 *__restrict__ rowcnt_s, const u32 *__restrict__ rowcnt_v, int H, int W, int Wd,
+                                           u32 *__restrict__ rowbase_s, u32 *__restrict__ rowbase_v, int *__restrict__ finfo,
+                                           float *__restrict__ vlist, int *__restrict__ fflag2, int *__restrict__ route,
+                                           int *__restrict__ frame_status, int mode, int *__restrict__ negflag,
+                                           u32 *__restrict__ rowfar, int nty16, int nty32, FrameScratch &sc) {
+    u32 *bs_ = rowbase_s + (size_t)b * H, *bv_ = rowbase_v + (size_t)b * H;
+    const FrameFacts ff = frame_facts(rowcnt_s + (size_t)b * H, rowcnt_v + (size_t)b * H, H, W, mode, nty16, nty32, sc, true,
+                                      [&](int i, u32 bs, u32 bv) {
+                                          bs_[i] = bs;
+                                          bv_[i] = bv;
+                                      });
+    frame_publish(ff, sc, b, x, valbits, wpre_v, srcbits, wpre_s, ptslist, H, W, Wd, bs_, bv_, finfo, vlist, fflag2, route, frame_status,
+                  mode, negflag, rowfar, false);
+}
+// k_frame: one workgroup per frame, in a launch of its own (the l2 pass, the forced any-distance path, frames taller than
+// FRAME_RIDE_MAX_H, DTFILL_FLAG_SEPARATE_FRAME; else k_fused's blocks do the same in its launch)
 __global__ __launch_bounds__(256) void k_frame(const Pass p, int mode, int nty16, int nty32) {
-    frame_body(p.x, p.valbits, p.wpre_v, p.srcbits, p.wpre_s, p.ptslist, p.rowcnt_s, p.rowcnt_v, p.H, p.W, p.Wd, p.rowbase_s, p.rowbase_v,
-               p.finfo, p.vlist, p.fflag2, p.route, p.status, mode, p.negflag, p.rowfar, nty16, nty32);
+    __shared__ FrameScratch sc;
+    frame_body(blockIdx.x, p.x, p.valbits, p.wpre_v, p.srcbits, p.wpre_s, p.ptslist, p.rowcnt_s, p.rowcnt_v, p.H, p.W, p.Wd, p.rowbase_s,
+               p.rowbase_v, p.finfo, p.vlist, p.fflag2, p.route, p.status, mode, p.negflag, p.rowfar, nty16, nty32, sc);
 }
 
 // label of the source at (i, j): 1 + number of sources before it in raster order

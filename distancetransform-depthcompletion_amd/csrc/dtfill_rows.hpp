@@ -280,7 +280,7 @@ __device__ __forceinline__ void rows_body(
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwv = blockDim.x >> 6;
     if (ff == 1) {    // only near a row k_fused could not finish
         const int rr = i - R_MARGIN + lane;
-        const int sky_live = finfo_sky[b * FI_STRIDE + FI_SKY];
+        const int sky_live = sky_rows(finfo_sky, b);
         if (!__any(lane <= 2 * R_MARGIN && rr >= 0 && rr < H && row_is_anydist(rowflag[(size_t)b * H + rr], sky_live))) return;
     }
     const int band = i >> 5, r = i & 31;
@@ -594,7 +594,7 @@ __device__ __forceinline__ void fin_body(
     u32 coremask = 0xFFFFFFFFu;
     if (ff == 1) {
         const int l = tid & 63;
-        const int sky_live = finfo[b * FI_STRIDE + FI_SKY];
+        const int sky_live = sky_rows(finfo, b);
         coremask = (u32)__ballot(l < Q_TH && r0 + l < H && row_is_anydist(rowflag[(size_t)b * H + min(r0 + l, H - 1)], sky_live));
         if (!coremask) return;  // block-uniform: every wave computes the same mask
     }
@@ -902,7 +902,7 @@ __device__ __forceinline__ void tiesx_body(const u8 *__restrict__ unres, int Wp,
         for (int step = 0; step < H * W; ++step) {  // every step ends on a pixel nearer to the sources
             const u32 pi = p / (u32)W, pj = p - pi * (u32)W;
             // a row that was not redone holds k_fused's finished pixels (and no "unresolved" bits of this pass)
-            const bool redone = ff != 1 || row_is_anydist(rowflag[rowb + pi], finfo[b * FI_STRIDE + FI_SKY]);
+            const bool redone = ff != 1 || row_is_anydist(rowflag[rowb + pi], sky_rows(finfo, b));
             const u32 open = (unres[(rowb + pi) * Wp + (pj >> 3)] >> (pj & 7u)) & 1u;
             const u32 nx = xptr[fo + p];  // meaningful only if open
             if (!redone || !open) break;

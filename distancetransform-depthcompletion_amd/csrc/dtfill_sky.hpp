@@ -34,7 +34,7 @@ __host__ __device__ inline size_t sky_lds(int span) { return (size_t)((span + 7)
 __device__ __forceinline__ void sky_body(unsigned char *s_sky, const int *__restrict__ finfo, int H, int W, const float *dt_src, float *out_dt,
                                          float *out_depth, int32_t *out_index, int strip, int rowgroup, int b) {
     const int tid = threadIdx.x, NT = blockDim.x;  // (at least SKY_NT threads: the host sees to it)
-    const int r0 = finfo[b * FI_STRIDE + FI_SKY];
+    const int r0 = sky_rows(finfo, b);
     const int i0 = rowgroup * SKY_RG;
     if (r0 <= 0 || r0 >= H || i0 >= r0) return;  // block-uniform: no sky in this frame (or called off), or not this far down
     const int i1 = min(i0 + SKY_RG, r0);

@@ -65,7 +65,7 @@ class DtFill:
 
     # -- the op --------------------------------------------------------------------------------
     def run(self, x, src_thr=0.1, val_thr=0.1, want=WANT_ALL, timed=False, path="auto", depth_rows_from=0, depth_floor=None,
-            outlier_removal=False):
+            outlier_removal=False, separate_frame=False):
         """x: float32 CUDA tensor [B,H,W] (contiguous).  Returns a dict of device tensors
         (views of buffers owned by this object, overwritten by the next call) for the names in
         `want`, plus "status" (int32 [B], bit set of _lib.FRAME_*).  Asynchronous on the current
@@ -74,7 +74,8 @@ class DtFill:
         post-fill steps folded into the depth stores (demo.py:292-293 rows 96:, eval_NYU.py:205
         relu(d - 0.9) + 0.9): "depth" is then [B, H - depth_rows_from, W]; l1_cv only.  outlier_removal: the loader's filter
         (data_read.py:103-128, 168-169) in front of the predicates -- the pass equals run(outlier_removal_device(x)) without
-        the filtered map being written."""
+        the filtered map being written.  separate_frame: l1_cv, the frame facts in a k_frame launch of their own instead of inside
+        the window kernel's launch (_lib.FLAG_SEPARATE_FRAME: tests and A/B timing; the results are the same)."""
         if x.dtype != torch.float32 or not x.is_cuda or x.dim() != 3 or not x.is_contiguous():
             raise ValueError("x must be a contiguous float32 CUDA tensor [B,H,W]")
         B, H, W = x.shape
@@ -97,7 +98,7 @@ class DtFill:
                 ptr("depth"), ptr("dt"), ptr("index"), o["status"].data_ptr(),
                 self._ws.data_ptr() + self._ws_off, self._ws_bytes, stream,
             ]
-            flags = _lib.PATHS[path] | (_lib.FLAG_OUTLIER_REMOVAL if outlier_removal else 0)
+            flags = _lib.PATHS[path] | (_lib.FLAG_OUTLIER_REMOVAL if outlier_removal else 0) | (_lib.FLAG_SEPARATE_FRAME if separate_frame else 0)
             if timed:
                 nk = self.lib.dtfill_num_kernels(self.metric)
                 ms = (ctypes.c_float * nk)()

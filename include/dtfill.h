@@ -69,6 +69,12 @@ extern "C" {
    dtfill_outlier_removal() followed by dtfill_batch() on its output, without the filtered map ever being written:
    a removed pixel stops being a source / value, the surviving ones are gathered from x.  Needs H, W >= 4. */
 #define DTFILL_FLAG_OUTLIER_REMOVAL 4u
+/* ... and one that changes only how the l1_cv pass is launched, for tests and A/B timing: the frame facts in a k_frame launch
+   of their own in front of the window kernel (seven launches) instead of inside the window kernel's launch (six; the
+   default for frames of up to DTFILL_FRAME_RIDE_MAX_H rows).  Results are identical; dtfill_batch_timed() reports a k_frame
+   slot only then (0 ms otherwise). */
+#define DTFILL_FLAG_SEPARATE_FRAME 8u
+#define DTFILL_FRAME_RIDE_MAX_H 512
 
 int dtfill_abi_version(void);
 const char *dtfill_strerror(int code);
