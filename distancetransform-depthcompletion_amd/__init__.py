@@ -24,7 +24,7 @@ def __getattr__(name):
 
         mod = importlib.import_module(__name__ + ".device")
         return mod if name == "device" else getattr(mod, name)
-    if name == "autograd":  # the differentiable net.py form, <package>.autograd.generate_multi_channel (imports torch too)
+    if name == "autograd":  # <package>.autograd.generate_multi_channel (net.py form) and .train_loss (imports torch too)
         import importlib
 
         return importlib.import_module(__name__ + ".autograd")

@@ -55,11 +55,17 @@ SYMBOLS = (
     "dtfill_depth_read",
     "dtfill_metrics_workspace_bytes",
     "dtfill_metrics",
+    "dtfill_train_loss_workspace_bytes",
+    "dtfill_train_loss",
+    "dtfill_train_loss_backward",
 )
 STATS = ("all", "window", "anydist", "sky", "points", "colt")  # DTFILL_STATS_*
 METRICS_KITTI = 0
 METRICS_NYU = 1
 METRICS_COLUMNS = ("mse", "rmse", "mae", "irmse", "imae", "delta1", "delta2", "delta3", "count")
+LOSS_KITTI = 0
+LOSS_NYU = 1
+LOSS_COLUMNS = ("main", "aux", "n_gt", "n_in", "S_main", "S_aux")
 
 _lib = None
 
@@ -142,6 +148,12 @@ def load():
     L.dtfill_metrics_workspace_bytes.restype = sz
     L.dtfill_metrics.argtypes = [vp, vp, ci, ctypes.c_longlong, ci, vp, vp, sz, vp]
     L.dtfill_metrics.restype = ci
+    L.dtfill_train_loss_workspace_bytes.argtypes = [ci, ci, ci]
+    L.dtfill_train_loss_workspace_bytes.restype = sz
+    L.dtfill_train_loss.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, ci, ci, ci, ci, vp, vp, sz, vp]
+    L.dtfill_train_loss.restype = ci
+    L.dtfill_train_loss_backward.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+    L.dtfill_train_loss_backward.restype = ci
     _lib = L
     return L
 

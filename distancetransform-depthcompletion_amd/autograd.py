@@ -1,4 +1,5 @@
-"""generate_multi_channel() of the reference's models (solution_DeepNet/net.py:83-122) as a differentiable torch operator.
+"""The reference's in-graph pieces around the network as differentiable torch operators: generate_multi_channel() of its models
+(solution_DeepNet/net.py:83-122) and the objective of its training step (solution_DeepNet/train.py:210-251, train_loss below).
 
 In the reference the windowed fill sits inside the trained graph: with if_correct its input is the output of four learned
 convolutions (net.py:469-486), its outputs feed the encoder (net.py:489), and the gradient is cut only when joint_train is
@@ -46,3 +47,44 @@ def generate_multi_channel(data, mask, table_size=7, scale_num=4):
         return (data, None, None, None)
     steps = _WindowSteps.apply(data, mask.detach(), int(table_size), int(scale_num))
     return (data,) + tuple(steps) + (None,) * (4 - scale_num)
+
+
+class _TrainLoss(torch.autograd.Function):
+    """(main, aux) of train.py:240-249 as 0-d float32 tensors; aux only with a correction."""
+
+    @staticmethod
+    def forward(ctx, pred, correction, gt, lidar, cfg):
+        stats = device.train_loss_device(pred, gt, lidar, correction, **cfg)
+        ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None: nothing is computed for it
+        ctx.cfg = cfg
+        ctx.save_for_backward(pred, correction, gt, lidar, stats)
+        # fresh tensors, not two views of one: the caller may go on in place (total = main; total += aux)
+        main = stats[0].to(torch.float32)
+        return (main, stats[1].to(torch.float32)) if correction is not None else (main,)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_main, g_aux=None):
+        pred, correction, gt, lidar, stats = ctx.saved_tensors
+        want_pred = ctx.needs_input_grad[0] and g_main is not None
+        want_corr = ctx.needs_input_grad[1] and g_aux is not None
+        if not (want_pred or want_corr):
+            return None, None, None, None, None
+        scalar = lambda g: None if g is None else g.to(torch.float32).contiguous()
+        # pred's gradient needs neither the correction nor the LiDAR; they ride along only where the correction's is asked for
+        grad_pred, grad_corr = device.train_loss_backward_device(
+            pred, gt, stats, scalar(g_main), scalar(g_aux), lidar if want_corr else None, correction if want_corr else None,
+            want_pred=want_pred, want_correction=want_corr, **ctx.cfg)
+        return grad_pred, grad_corr, None, None, None
+
+
+def train_loss(pred, gt, lidar=None, correction=None, dataset="KITTI", gt_thr=None, in_thr=None, rows=None, cols=None):
+    """train.py:215-249 on contiguous float32 CUDA tensors [B,H,W]: pred = depth_predicted, correction = lidar_correction (with
+    --correct, together with lidar), gt and lidar the loader's frames after the driver's row crop.  dataset and the overrides
+    as device.train_loss_device.  Returns (main, aux), 0-d float32 tensors, aux None without a correction; train.py:251's
+    total = main + aux is the caller's add, so autograd splits the upstream gradient by itself.  Differentiable in pred and
+    correction only, once; an unused output costs nothing in the backward; no host synchronisation in either direction."""
+    cfg = dict(dataset=dataset, gt_thr=gt_thr, in_thr=in_thr, rows=rows, cols=cols)
+    lidar = None if lidar is None else lidar.detach()
+    out = _TrainLoss.apply(pred, correction, gt.detach(), lidar, cfg)
+    return (out[0], out[1]) if correction is not None else (out[0], None)

@@ -60,6 +60,7 @@
 #include <stdint.h>
 #include <math.h>
 #include <stdlib.h>
+#include <initializer_list>
 #include <type_traits>
 #include "../../include/dtfill.h"
 
@@ -82,6 +83,7 @@ namespace {
 #include "dtfill_gmcv.hpp"
 #include "dtfill_gmcb.hpp"
 #include "dtfill_post.hpp"
+#include "dtfill_loss.hpp"
 #include "dtfill_lines.hpp"
 #include "dtfill_read.hpp"
 
@@ -614,6 +616,75 @@ int dtfill_generate_multi_channel_backward(const float *mask, const float *out2,
     }
     if (up != grad_data)  // no step stored it: scale_num 1 (g_1 as it is), or every later gradient NULL (g_1 + (+0))
         k_gmcb_first<<<(unsigned)min((n + 255) / 256, (size_t)1 << 16), 256, 0, st>>>(up, n, scale_num > 1, grad_data);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+// the checks the two loss entry points share; whether every pointer and the count allow the 16-byte loads
+static int loss_check(const float *pred, const float *corr, const float *gt, const float *lidar, int B, int H, int W, int kind,
+                      int r0, int r1, int c0, int c1) {
+    if (!pred || !gt || (corr && !lidar)) return DTFILL_ERR_NULL;
+    if (!gmcv_count_ok(B, H, W, 1)) return DTFILL_ERR_SHAPE;
+    if (r0 < 0 || r1 > H || r0 >= r1 || c0 < 0 || c1 > W || c0 >= c1) return DTFILL_ERR_SHAPE;
+    if (kind != DTFILL_LOSS_KITTI && kind != DTFILL_LOSS_NYU) return DTFILL_ERR_METRIC;
+    return DTFILL_OK;
+}
+static bool loss_vec(size_t n, std::initializer_list<const void *> ptrs) {
+    uintptr_t bits = (uintptr_t)(n & 3);
+    for (const void *p : ptrs) bits |= (uintptr_t)p & 15;
+    return bits == 0;
+}
+
+size_t dtfill_train_loss_workspace_bytes(int B, int H, int W) {
+    if (!gmcv_count_ok(B, H, W, 1)) return 0;
+    const size_t nb = (size_t)loss_blocks((size_t)B * H * W);
+    return align256(nb * 2 * sizeof(double)) + align256(nb * 2 * sizeof(u32));
+}
+
+int dtfill_train_loss(const float *pred, const float *corr, const float *gt, const float *lidar, int B, int H, int W, int kind,
+                      float gt_thr, float in_thr, int r0, int r1, int c0, int c1, double *stats, void *workspace,
+                      size_t ws_bytes, void *stream) {
+    if (!stats || !workspace) return DTFILL_ERR_NULL;
+    const int rc = loss_check(pred, corr, gt, lidar, B, H, W, kind, r0, r1, c0, c1);
+    if (rc != DTFILL_OK) return rc;
+    if (ws_bytes < dtfill_train_loss_workspace_bytes(B, H, W) || ((uintptr_t)workspace & 255)) return DTFILL_ERR_WORKSPACE;
+    const size_t n = (size_t)B * H * W;
+    const int nb = loss_blocks(n);
+    double *part_s = static_cast<double *>(workspace);
+    u32 *part_n = reinterpret_cast<u32 *>(static_cast<char *>(workspace) + align256((size_t)nb * 2 * sizeof(double)));
+    const LossWindow w{H, W, r0, r1, c0, c1};
+    const bool win = r0 != 0 || r1 != H || c0 != 0 || c1 != W;
+    const bool vec = loss_vec(n, {pred, corr, gt, corr ? lidar : nullptr});
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // (aux, win, vec) -> the instantiation; lidar is not passed on without corr, so it is never read
+    auto launch = [&](auto a, auto wn, auto v) {
+        k_loss_part<decltype(a)::value, decltype(wn)::value, decltype(v)::value><<<nb, 256, 0, st>>>(
+            pred, corr, gt, corr ? lidar : nullptr, n, w, gt_thr, in_thr, part_s, part_n);
+    };
+    auto pick_v = [&](auto a, auto wn) { vec ? launch(a, wn, std::true_type{}) : launch(a, wn, std::false_type{}); };
+    auto pick_w = [&](auto a) { win ? pick_v(a, std::true_type{}) : pick_v(a, std::false_type{}); };
+    corr ? pick_w(std::true_type{}) : pick_w(std::false_type{});
+    k_loss_final<<<1, 64, 0, st>>>(part_s, part_n, nb, kind, corr ? 1 : 0, stats);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+int dtfill_train_loss_backward(const float *pred, const float *corr, const float *gt, const float *lidar, int B, int H, int W,
+                               int kind, float gt_thr, float in_thr, int r0, int r1, int c0, int c1, const double *stats,
+                               const float *g_main, const float *g_aux, float *grad_pred, float *grad_corr, void *stream) {
+    if (!stats || (!grad_pred && !grad_corr) || (grad_corr && !corr)) return DTFILL_ERR_NULL;
+    const int rc = loss_check(pred, corr, gt, lidar, B, H, W, kind, r0, r1, c0, c1);
+    if (rc != DTFILL_OK) return rc;
+    const size_t n = (size_t)B * H * W;
+    const LossWindow w{H, W, r0, r1, c0, c1};
+    const bool win = r0 != 0 || r1 != H || c0 != 0 || c1 != W;
+    const bool vec = loss_vec(n, {pred, corr, gt, corr ? lidar : nullptr, grad_pred, grad_corr});
+    const unsigned grid = (unsigned)min((n + L_CHUNK - 1) / L_CHUNK, (size_t)L_BWD_MAXB);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    auto launch = [&](auto wn, auto v) {
+        k_loss_bwd<decltype(wn)::value, decltype(v)::value><<<grid, 256, 0, st>>>(
+            pred, corr, gt, corr ? lidar : nullptr, n, w, kind, gt_thr, in_thr, stats, g_main, g_aux, grad_pred, grad_corr);
+    };
+    auto pick_v = [&](auto wn) { vec ? launch(wn, std::true_type{}) : launch(wn, std::false_type{}); };
+    win ? pick_v(std::true_type{}) : pick_v(std::false_type{});
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 

@@ -303,12 +303,12 @@ def generate_multi_channel_device(data, mask, table_size=7, scale_num=4):
 _gmcb_ws = {}  # (device index, stream) -> the backward's workspace: calls on one stream are ordered, so they can share it
 
 
-def _gmcb_workspace(device, nbytes):
+def _gmcb_workspace(device, nbytes, cache=_gmcb_ws):
     """A 256-byte aligned pointer to at least nbytes of scratch on `device`, kept for the current stream and grown on demand."""
     key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-    ws = _gmcb_ws.get(key)
+    ws = cache.get(key)
     if ws is None or ws.numel() < nbytes + 256:
-        ws = _gmcb_ws[key] = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+        ws = cache[key] = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
     return ws.data_ptr() + (-ws.data_ptr()) % 256
 
 
@@ -438,6 +438,79 @@ def metrics_device(output, target, kind="kitti"):
         _lib.check(L.dtfill_metrics(output.data_ptr(), target.data_ptr(), B, n, kinds[kind], out.data_ptr(),
                                     ws.data_ptr(), nbytes, torch.cuda.current_stream(output.device).cuda_stream))
     return out
+
+
+LOSS_PRESETS = {  # dataset -> (kind, gt_thr, in_thr, rows, cols) of train.py:215-216, :244 and :220-221, :242
+    "KITTI": (_lib.LOSS_KITTI, 0.1, 0.1, None, None),
+    "NYU": (_lib.LOSS_NYU, 0.0001, 0.001, (6, 228), (8, 304)),
+}
+_loss_ws = {}  # (device index, stream) -> the forward's partial sums, shared like _gmcb_ws
+
+
+def _loss_args(pred, gt, lidar, correction, dataset, gt_thr, in_thr, rows, cols):
+    """The checked C arguments both loss entry points share: (pointers, B, H, W, kind, gt_thr, in_thr, r0, r1, c0, c1)."""
+    _require_gpu()
+    if dataset not in LOSS_PRESETS:
+        raise ValueError("dataset must be 'KITTI' or 'NYU', got %r" % (dataset,))
+    if (lidar is None) != (correction is None):
+        raise ValueError("lidar and correction come together (train.py's --correct) or not at all")
+    for what, t in (("pred", pred), ("gt", gt), ("lidar", lidar), ("correction", correction)):
+        if t is None:
+            continue
+        _check_frames(t, what)
+        if t.shape != pred.shape or t.device != pred.device:
+            raise ValueError("%s must have pred's shape and device" % what)
+    kind, gthr, ithr, prows, pcols = LOSS_PRESETS[dataset]
+    B, H, W = pred.shape
+    r0, r1 = (prows or (0, H)) if rows is None else rows
+    c0, c1 = (pcols or (0, W)) if cols is None else cols
+    if not (0 <= r0 < r1 <= H and 0 <= c0 < c1 <= W):
+        raise ValueError("empty or out-of-frame window rows=%s cols=%s of a %dx%d frame" % ((r0, r1), (c0, c1), H, W))
+    ptrs = (pred.data_ptr(), None if correction is None else correction.data_ptr(), gt.data_ptr(),
+            None if lidar is None else lidar.data_ptr())
+    return ptrs + (B, H, W, kind, float(gthr if gt_thr is None else gt_thr), float(ithr if in_thr is None else in_thr),
+                   int(r0), int(r1), int(c0), int(c1))
+
+
+def train_loss_device(pred, gt, lidar=None, correction=None, dataset="KITTI", gt_thr=None, in_thr=None, rows=None, cols=None):
+    """The objective of train.py:210-251 (include/dtfill.h, dtfill_train_loss).  pred, gt and, with --correct, lidar and
+    correction: contiguous float32 CUDA tensors [B,H,W].  dataset "KITTI": thresholds 0.1 / 0.1, whole frame, no root; "NYU":
+    1e-4 / 1e-3, rows (6,228), cols (8,304), root; gt_thr, in_thr, rows and cols override the preset.  Returns the float64 CUDA
+    tensor [6] = main, aux, n_gt, n_in, S_main, S_aux (_lib.LOSS_COLUMNS).  Asynchronous on the current stream, no host sync."""
+    args = _loss_args(pred, gt, lidar, correction, dataset, gt_thr, in_thr, rows, cols)
+    L = _lib.load()
+    stats = torch.empty(len(_lib.LOSS_COLUMNS), dtype=torch.float64, device=pred.device)
+    with torch.cuda.device(pred.device):
+        nbytes = L.dtfill_train_loss_workspace_bytes(*args[4:7])
+        ws = _gmcb_workspace(pred.device, nbytes, _loss_ws)
+        _lib.check(L.dtfill_train_loss(*args, stats.data_ptr(), ws, nbytes, torch.cuda.current_stream(pred.device).cuda_stream))
+    return stats
+
+
+def train_loss_backward_device(pred, gt, stats, g_main=None, g_aux=None, lidar=None, correction=None, dataset="KITTI",
+                               gt_thr=None, in_thr=None, rows=None, cols=None, want_pred=True, want_correction=None):
+    """The gradients of g_main * main + g_aux * aux (include/dtfill.h, dtfill_train_loss_backward).  stats: what
+    train_loss_device returned for the same arguments; g_main, g_aux: float32 CUDA scalars (one element), None for a zero
+    gradient.  Returns (grad_pred, grad_corr): new tensors, None for one that was not asked for (want_correction defaults to
+    "correction is given").  Asynchronous on the current stream, no host sync."""
+    args = _loss_args(pred, gt, lidar, correction, dataset, gt_thr, in_thr, rows, cols)
+    want_correction = correction is not None if want_correction is None else want_correction
+    if want_correction and correction is None:
+        raise ValueError("a gradient for correction needs correction")
+    if not (want_pred or want_correction):
+        raise ValueError("no gradient asked for")
+    if stats.dtype != torch.float64 or stats.device != pred.device or stats.numel() != len(_lib.LOSS_COLUMNS) or not stats.is_contiguous():
+        raise ValueError("stats must be train_loss_device's float64 [6] tensor on pred's device")
+    for what, g in (("g_main", g_main), ("g_aux", g_aux)):
+        if g is not None and (g.dtype != torch.float32 or g.device != pred.device or g.numel() != 1):
+            raise ValueError("%s must be a float32 scalar on pred's device" % what)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    grad_pred = torch.empty_like(pred) if want_pred else None
+    grad_corr = torch.empty_like(pred) if want_correction else None
+    with torch.cuda.device(pred.device):
+        _lib.check(_lib.load().dtfill_train_loss_backward(*args, stats.data_ptr(), ptr(g_main), ptr(g_aux), ptr(grad_pred),
+                                                          ptr(grad_corr), torch.cuda.current_stream(pred.device).cuda_stream))
+    return grad_pred, grad_corr
 
 
 def keep_every_of(keep_ratio):

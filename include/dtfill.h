@@ -364,6 +364,61 @@ size_t dtfill_metrics_workspace_bytes(int B);
 int dtfill_metrics(const float *output, const float *target, int B, long long n, int kind, double *out, void *workspace,
                    size_t ws_bytes, void *stream);
 
+/*
+ * The objective of the reference's training step, solution_DeepNet/train.py:210-251, and its gradient: the masked squared
+ * error of the prediction and, with --correct, the squared-plus-absolute error of the corrected LiDAR, each divided by a
+ * count taken over the whole batch.  pred, corr: the network's depth_predicted and lidar_correction; gt, lidar: the loader's
+ * frames after the driver's row crop (train.py:211-212); all float32 [B,H,W].
+ *   m  = gt > gt_thr              train.py:215 (KITTI 0.1) / :220 (NYU 0.0001)
+ *   mi = m && lidar > in_thr      train.py:216 (0.1) / :221 (0.001), :227
+ *   n_gt = |m|, n_in = |mi|, over the batch and the WHOLE frame                                        (:224, :228)
+ *   S_main = sum of (pred - gt)^2 over m inside rows [r0, r1) x columns [c0, c1)                       (:240)
+ *   S_aux  = sum of (corr - gt)^2 + |corr - gt| over mi, always the whole frame                        (:248)
+ *   main = S_main / n_gt (DTFILL_LOSS_KITTI, :244, window 0,H,0,W) or sqrt(S_main / n_gt) (DTFILL_LOSS_NYU, :242, window
+ *          6,228,8,304: the sum runs over the window, the count over the frame, as the reference has it)
+ *   aux  = S_aux / n_in                                                                                (:249)
+ * total = main + aux (:251) is the caller's add.  Both compares are float32 compares, so a NaN is in no mask; the masks are
+ * derived while the inputs are read and never stored.
+ * Per element float32, one rounding per operation, nothing contracted: t = pred - gt, e = t * t; u = corr - gt,
+ * a = u * u + fabsf(u).  A term is added only where its mask (and, for e, the window) selects it, so a non-finite pred or
+ * corr at an unselected pixel leaves no trace: the same deliberate deviation from the reference's x * mask as
+ * dtfill_generate_multi_channel's.  S_main and S_aux accumulate in float64 in an order that is a function of B*H*W alone (no
+ * atomics; neither the pointers' alignment nor the window changes it): two calls give the same bits, within n_terms * 2^-53
+ * relative of the exact sum of those float32 terms.  TensorFlow sums in float32 in an order it does not document, so the order
+ * is this library's contract, not a property of the reference.  n_gt and n_in are exact.
+ * stats: DEVICE double[DTFILL_LOSS_N] = main, aux, n_gt, n_in, S_main, S_aux; the divisions and the root in double; an empty
+ * mask gives 0 / 0 = NaN, like the reference.  corr == NULL (no --correct): aux, n_in and S_aux are +0 and lidar is not read.
+ * workspace: at least dtfill_train_loss_workspace_bytes(B,H,W) bytes, 256-B aligned, the caller's, no initialisation needed,
+ * nothing kept between calls.
+ *
+ * dtfill_train_loss_backward: the gradients of g_main * main + g_aux * aux, in float32 (2 * t is exact):
+ *   k_main = (float)(g_main / n_gt)  (KITTI)  or  (float)(g_main / ((2 * main) * n_gt))  (NYU: main == 0 gives 0 * inf = NaN)
+ *   k_aux  = (float)(g_aux / n_in)
+ *   grad_pred = (2 * t) * k_main where m inside the window, +0.0f elsewhere
+ *   grad_corr = (2 * u + sgn(u)) * k_aux where mi, +0.0f elsewhere; sgn(0) = 0; one rounded add, one rounded multiply
+ * The divisions are in double, from stats (what dtfill_train_loss wrote for the same arguments) and the DEVICE float scalars
+ * g_main and g_aux, and are rounded to float32 once.  A NULL g_* is a zero gradient: that output is all +0.  grad_pred and
+ * grad_corr: float32 [B,H,W], each nullable but not both, always fully overwritten, may alias no input.  gt and lidar get no
+ * gradient.
+ *
+ * Both calls are asynchronous on `stream`, read stats and g_* on the device, and neither synchronises nor allocates.
+ * Returns, all checked before any HIP call: DTFILL_ERR_NULL for a NULL pred, gt or stats, a NULL workspace, corr without lidar,
+ * grad_corr without corr, or both gradients NULL; DTFILL_ERR_SHAPE for B, H or W < 1, B*H*W >= 2^31, or a window that is empty
+ * or not inside the frame; DTFILL_ERR_METRIC for an unknown kind; DTFILL_ERR_WORKSPACE for a workspace that is too small or
+ * not aligned.
+ */
+#define DTFILL_LOSS_KITTI 0 /* main = S_main / n_gt        train.py:244 */
+#define DTFILL_LOSS_NYU   1 /* main = sqrt(S_main / n_gt)  train.py:242 */
+#define DTFILL_LOSS_N 6     /* stats columns: main, aux, n_gt, n_in, S_main, S_aux */
+size_t dtfill_train_loss_workspace_bytes(int B, int H, int W); /* 0 on a bad shape */
+int dtfill_train_loss(const float *pred, const float *corr /* nullable */, const float *gt,
+                      const float *lidar /* nullable iff corr is */, int B, int H, int W, int kind, float gt_thr, float in_thr,
+                      int r0, int r1, int c0, int c1, double *stats, void *workspace, size_t ws_bytes, void *stream);
+int dtfill_train_loss_backward(const float *pred, const float *corr, const float *gt, const float *lidar, int B, int H, int W,
+                               int kind, float gt_thr, float in_thr, int r0, int r1, int c0, int c1, const double *stats,
+                               const float *g_main, const float *g_aux /* device scalars, each nullable */,
+                               float *grad_pred, float *grad_corr /* each nullable, not both */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
