@@ -1,4 +1,4 @@
-// dtfill_common.hpp -- constants, tap tables and small device helpers shared by every kernel
+// dtfill_common.hpp -- constants, the tap table (dtfill_taps.hpp) and small device helpers shared by every kernel
 // Part of libdtfill.so; included by dtfill.hip inside its anonymous namespace (one translation unit).
 #pragma once
 
@@ -36,22 +36,33 @@ constexpr int PM16 = 8, PM32 = 16;
 constexpr int SKY_MAX = 320;  // ... and up to this many (k_sky's blocks stage r0 + 260 columns in LDS, in k_colT's launch)
 constexpr int SKY_MIN = 9;  // rows above the first source row are k_sky's from this many on (fewer: within every window's reach)
 
-// cv2 tap order (OpenCV 3.4 distanceTransformEx_5x5), forward taps 0..7; backward tap t is the
-// NEGATED forward tap t with the same weight.  Parent code = t | (backward ? 8 : 0).
-#define TAP_DI(t) ((t) < 2 ? -2 : (t) < 7 ? -1 : 0)
-#define TAP_DJ(t) ((t) == 0 ? -1 : (t) == 1 ? 1 : (t) == 2 ? -2 : (t) == 3 ? -1 : (t) == 4 ? 0 : (t) == 5 ? 1 : (t) == 6 ? 2 : -1)
-#define TAP_W(t) ((t) < 3 ? 3 : (t) == 3 ? 2 : (t) == 4 ? 1 : (t) == 5 ? 2 : (t) == 6 ? 3 : 1)
-constexpr u32 TAP_DI_NIB = 0x21111100u;  // nibble t = di(t) + 2
-constexpr u32 TAP_DJ_NIB = 0x14321031u;  // nibble t = dj(t) + 2
+// the l1_cv parent rule's tap table (offsets, weights, parent codes, step encoding, tap_decode): stated once, there
+#include "dtfill_taps.hpp"
 
-__device__ __forceinline__ void tap_decode(int code, int &di, int &dj) {
-    const int sh = (code & 7) * 4;
-    di = (int)((TAP_DI_NIB >> sh) & 15u) - 2;
-    dj = (int)((TAP_DJ_NIB >> sh) & 15u) - 2;
-    if (code & 8) {
-        di = -di;
-        dj = -dj;
+// a[0..2] = a 32-pixel word a[1] of a row of bits with its left / right neighbour words: the word shifted so that
+// result[c] = row[c + DJ].  The caller passes a pointer into an array (a 3-word row, or row + i of a 5-word row with i <= 2):
+// all three words must lie inside it -- nothing here can check that.
+template <int DJ>
+__device__ __forceinline__ u32 row_shift(const u32 *a) {
+    if (DJ == 0) return a[1];
+    if (DJ > 0) return __builtin_amdgcn_alignbit(a[2], a[1], DJ);
+    return __builtin_amdgcn_alignbit(a[1], a[0], 32 + DJ);
+}
+
+// the pixels (of 32) with (d(r) + WGT) mod 8 == d(q) mod 8, on the bit planes x0..x2 of d(r) and b0..b2 of d(q).  d is an exact
+// L1 distance field, so for a tap of weight WGT <= 3 |d(r) - d(q)| <= WGT and d(r) + WGT - d(q) lies in [0, 6]: zero iff zero mod 8.
+template <int WGT>
+__device__ __forceinline__ u32 dist_match(u32 x0, u32 x1, u32 x2, u32 b0, u32 b1, u32 b2) {
+    static_assert(WGT >= 1 && WGT <= 3, "a tap's weight");
+    u32 s0, s1, s2;  // (d(r) + WGT) mod 8
+    if (WGT == 1) {
+        s0 = ~x0; s1 = x1 ^ x0; s2 = x2 ^ (x1 & x0);
+    } else if (WGT == 2) {
+        s0 = x0; s1 = ~x1; s2 = x2 ^ x1;
+    } else {
+        s0 = ~x0; s1 = ~(x1 ^ x0); s2 = x2 ^ (x1 | x0);
     }
+    return ~((s0 ^ b0) | (s1 ^ b1) | (s2 ^ b2));
 }
 
 // outlier_removal() (dtfill_outlier.hpp) as k_outlier and k_mask both apply it: cv2's reflect-101 border ...

@@ -41,55 +41,40 @@ static_assert(F_WWM == 32 * F_NWD, "window width must be six words");
 static_assert(F_RING * 4 >= F_WHM * F_P + 256 * 8, "s_par and the un-slicing table must fit in the ring's memory");
 static_assert((F_WHM * F_P) % 8 == 0 && F_WHM * F_P >= 4 * (1 + 4 * F_RPLANE), "the table is 8-byte aligned and lies behind the planes of P1b");
 
-#define ENC_F(t) (((TAP_DI(t) + 2) << 3) | (TAP_DJ(t) + 2))
-
-// a[0..4] = the lane's three words a[1..3] with their left / right neighbour words; word i (0..2) of the
-// row shifted so that result[c] = row[c + DJ]
-template <int DJ>
-__device__ __forceinline__ u32 hshift(const u32 (&a)[5], int i) {
-    if (DJ == 0) return a[i + 1];
-    if (DJ > 0) return __builtin_amdgcn_alignbit(a[i + 2], a[i + 1], DJ);
-    return __builtin_amdgcn_alignbit(a[i + 1], a[i], 32 + DJ);
-}
-
-// one tap of the first-match chain: cand = shift(src, DJ); winners get the bits of ENC in the code planes
-template <int DJ, int ENC>
+// One forward tap T (dtfill_taps.hpp) of the first-match chain.  src = the live pixels of the level BACK levels back, in the
+// window row ROW below the lane's, with their neighbour words (src[1..3] = the lane's three words): what the call site loaded
+// must be what the table says.  cand = shift(src, dj); the winners get the bits of the step encoding in the code planes.
+template <int T, int ROW, int BACK>
 __device__ __forceinline__ void tap_step(const u32 (&src)[5], u32 (&taken)[F_HW], u32 (&C)[6][F_HW]) {
+    static_assert(T >= 0 && T < 8 && ROW == code_di(T) && BACK == code_weight(T), "tap T reads row r + di of level t - weight");
 #pragma unroll
     for (int i = 0; i < F_HW; ++i) {
-        const u32 cand = hshift<DJ>(src, i);
+        const u32 cand = row_shift<code_dj(T)>(src + i);
         const u32 sel = cand & ~taken[i];
         taken[i] |= cand;
 #pragma unroll
         for (int j = 0; j < 6; ++j)
-            if (ENC & (1 << j)) C[j][i] |= sel;
+            if (code_enc(T) & (1 << j)) C[j][i] |= sel;
     }
 }
 
-// one BACKWARD tap, evaluated after the level loop for all levels at once: the candidate r = q + (row, DJ) matches
-// iff it is decided and d(r) + WGT == d(q).  Only d mod 8 is kept (planes a0..a2 / b0..b2): d is an exact L1
-// distance field, so |d(r) - d(q)| <= WGT <= 3 and d(r) + WGT - d(q) lies in [0, 6]: zero iff zero mod 8.
-template <int DJ, int WGT, int ENC>
+// One BACKWARD tap (parent code T | 8), evaluated after the level loop for all levels at once: the candidate r = q + (ROW, dj)
+// matches iff it is decided (dv) and d(r) + weight == d(q).  Only d mod 8 is kept (planes a0..a2 / b0..b2: dist_match).
+template <int T, int ROW>
 __device__ __forceinline__ void bwd_tap(const u32 (&a0)[5], const u32 (&a1)[5], const u32 (&a2)[5], const u32 (&dv)[5],
                                         const u32 (&b0)[F_HW], const u32 (&b1)[F_HW], const u32 (&b2)[F_HW],
                                         u32 (&taken)[F_HW], u32 (&C)[6][F_HW]) {
+    constexpr int CODE = T | 8, DJ = code_dj(CODE);
+    static_assert(T >= 0 && T < 8 && ROW == code_di(CODE), "backward tap T reads row r - di");
 #pragma unroll
     for (int i = 0; i < F_HW; ++i) {
-        const u32 x0 = hshift<DJ>(a0, i), x1 = hshift<DJ>(a1, i), x2 = hshift<DJ>(a2, i);
-        u32 s0, s1, s2;  // (d(r) + WGT) mod 8
-        if (WGT == 1) {
-            s0 = ~x0; s1 = x1 ^ x0; s2 = x2 ^ (x1 & x0);
-        } else if (WGT == 2) {
-            s0 = x0; s1 = ~x1; s2 = x2 ^ x1;
-        } else {
-            s0 = ~x0; s1 = ~(x1 ^ x0); s2 = x2 ^ (x1 | x0);
-        }
-        const u32 m = ~((s0 ^ b0[i]) | (s1 ^ b1[i]) | (s2 ^ b2[i])) & hshift<DJ>(dv, i);
+        const u32 m = dist_match<code_weight(CODE)>(row_shift<DJ>(a0 + i), row_shift<DJ>(a1 + i), row_shift<DJ>(a2 + i), b0[i], b1[i], b2[i]) &
+                      row_shift<DJ>(dv + i);
         const u32 sel = m & ~taken[i];
         taken[i] |= m;
 #pragma unroll
         for (int j = 0; j < 6; ++j)
-            if (ENC & (1 << j)) C[j][i] |= sel;
+            if (code_enc(CODE) & (1 << j)) C[j][i] |= sel;
     }
 }
 
@@ -533,29 +518,30 @@ __device__ __forceinline__ void fused_body(int tile, bool premarked, int tbase, 
 #pragma unroll
             for (int i = 0; i < F_HW; ++i) {
                 Ddn[i] |= e1d[i + 1];
-                const u32 dil = hshift<1>(dd, i) | hshift<-1>(dd, i) | Dup[i] | Ddn[i];
+                const u32 dil = row_shift<1>(dd + i) | row_shift<-1>(dd + i) | Dup[i] | Ddn[i];
                 Et[i] = dil & ~D[i] & M[i];
                 taken[i] = ~Et[i];
                 nonempty |= Et[i] != 0;
             }
         }
-        // forward taps in cv2 order; the candidates are live pixels of levels t-3, t-2, t-1
+        // forward taps in cv2 order; the candidates are live pixels of levels t-3, t-2, t-1.  tap_step<T, row, levels back>: the
+        // last two name what was loaded into its argument and are checked against the table
         ring_load5(s_ring, s3, 1, r + 0, wb, nb);  // L_{t-3}, row r-2
-        tap_step<-1, ENC_F(0)>(nb, taken, C);
-        tap_step<1, ENC_F(1)>(nb, taken, C);
+        tap_step<0, -2, 3>(nb, taken, C);
+        tap_step<1, -2, 3>(nb, taken, C);
         {
             u32 l3[5], l2[5];
             ring_load5(s_ring, s3, 1, r + 1, wb, l3);  // L_{t-3}, row r-1
             ring_load5(s_ring, s2, 1, r + 1, wb, l2);  // L_{t-2}, row r-1
             ring_load5(s_ring, s1, 1, r + 1, wb, nb);  // L_{t-1}, row r-1
-            tap_step<-2, ENC_F(2)>(l3, taken, C);
-            tap_step<-1, ENC_F(3)>(l2, taken, C);
-            tap_step<0, ENC_F(4)>(nb, taken, C);
-            tap_step<1, ENC_F(5)>(l2, taken, C);
-            tap_step<2, ENC_F(6)>(l3, taken, C);
+            tap_step<2, -1, 3>(l3, taken, C);
+            tap_step<3, -1, 2>(l2, taken, C);
+            tap_step<4, -1, 1>(nb, taken, C);
+            tap_step<5, -1, 2>(l2, taken, C);
+            tap_step<6, -1, 3>(l3, taken, C);
         }
         ring_load5(s_ring, s1, 1, r + 2, wb, l1);  // L_{t-1}, this row
-        tap_step<-1, ENC_F(7)>(l1, taken, C);
+        tap_step<7, 0, 1>(l1, taken, C);
         {
             const u32 m0 = (t & 1) ? 0xFFFFFFFFu : 0u, m1 = (t & 2) ? 0xFFFFFFFFu : 0u, m2 = (t & 4) ? 0xFFFFFFFFu : 0u;
 #pragma unroll
@@ -615,18 +601,19 @@ __device__ __forceinline__ void fused_body(int tile, bool premarked, int tbase, 
             ring_load5(s_ring, 1, 0, row, wb, a2);
             ring_load5(s_ring, 1, 1, row, wb, dv);
         };
-        // negated offsets of the cv2 taps, same order: (+2,+1) (+2,-1) (+1,+2) (+1,+1) (+1,0) (+1,-1) (+1,-2) (0,+1)
+        // the negated cv2 taps, same order; bwd_tap<T, row>: the row that row4 loaded, checked against the table.  (Taps 5 and 6
+        // never win and stay all the same: see fin_body, dtfill_rows.hpp.)
         row4(r + 4);
-        bwd_tap<1, 3, 36 - ENC_F(0)>(a0, a1, a2, dv, P0, P1, P2, taken, C);
-        bwd_tap<-1, 3, 36 - ENC_F(1)>(a0, a1, a2, dv, P0, P1, P2, taken, C);
+        bwd_tap<0, 2>(a0, a1, a2, dv, P0, P1, P2, taken, C);
+        bwd_tap<1, 2>(a0, a1, a2, dv, P0, P1, P2, taken, C);
         row4(r + 3);
-        bwd_tap<2, 3, 36 - ENC_F(2)>(a0, a1, a2, dv, P0, P1, P2, taken, C);
-        bwd_tap<1, 2, 36 - ENC_F(3)>(a0, a1, a2, dv, P0, P1, P2, taken, C);
-        bwd_tap<0, 1, 36 - ENC_F(4)>(a0, a1, a2, dv, P0, P1, P2, taken, C);
-        bwd_tap<-1, 2, 36 - ENC_F(5)>(a0, a1, a2, dv, P0, P1, P2, taken, C);
-        bwd_tap<-2, 3, 36 - ENC_F(6)>(a0, a1, a2, dv, P0, P1, P2, taken, C);
+        bwd_tap<2, 1>(a0, a1, a2, dv, P0, P1, P2, taken, C);
+        bwd_tap<3, 1>(a0, a1, a2, dv, P0, P1, P2, taken, C);
+        bwd_tap<4, 1>(a0, a1, a2, dv, P0, P1, P2, taken, C);
+        bwd_tap<5, 1>(a0, a1, a2, dv, P0, P1, P2, taken, C);
+        bwd_tap<6, 1>(a0, a1, a2, dv, P0, P1, P2, taken, C);
         row4(r + 2);
-        bwd_tap<1, 1, 36 - ENC_F(7)>(a0, a1, a2, dv, P0, P1, P2, taken, C);
+        bwd_tap<7, 0>(a0, a1, a2, dv, P0, P1, P2, taken, C);
     }
 
     // ---- P2: un-slice the code planes of this half row into bytes (2 * enc), 8 pixels per step: a byte of a plane goes

@@ -465,30 +465,31 @@ __device__ __forceinline__ void pts_body(unsigned char *__restrict__ s_raw, cons
             const int qrow = trow + 2;
             const u32 b0 = s_pl[0][qrow][tw + 1], b1 = s_pl[1][qrow][tw + 1], b2 = s_pl[2][qrow][tw + 1];
             const u32 qlive = s_pl[3][qrow][tw + 1];
+            // (the same sixteen taps as fin_body: dtfill_rows.hpp)
             u32 takenF = ~(mytie & qlive), takenB = ~(mytie & ~qlive);
             u32 a0[3], a1[3], a2[3], lv[3], vd[3];
             ld3(0, qrow - 2, a0); ld3(1, qrow - 2, a1); ld3(2, qrow - 2, a2); ld3(3, qrow - 2, lv); ld3(5, qrow - 2, vd);
-            rule_tap<-1, 3, true, 0>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
-            rule_tap<+1, 3, true, 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
+            rule_tap<0, -2>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
+            rule_tap<1, -2>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
             ld3(0, qrow - 1, a0); ld3(1, qrow - 1, a1); ld3(2, qrow - 1, a2); ld3(3, qrow - 1, lv); ld3(5, qrow - 1, vd);
-            rule_tap<-2, 3, true, 2>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
-            rule_tap<-1, 2, true, 3>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
-            rule_tap<0, 1, true, 4>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
-            rule_tap<+1, 2, true, 5>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
-            rule_tap<+2, 3, true, 6>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
-            u32 z0[3], z1[3], z2[3], zv[3];
+            rule_tap<2, -1>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
+            rule_tap<3, -1>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
+            rule_tap<4, -1>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
+            rule_tap<5, -1>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
+            rule_tap<6, -1>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
+            u32 z0[3], z1[3], z2[3], zv[3];  // this row: last forward tap now, last backward tap at the end
             ld3(0, qrow, z0); ld3(1, qrow, z1); ld3(2, qrow, z2); ld3(3, qrow, lv); ld3(5, qrow, zv);
-            rule_tap<-1, 1, true, 7>(z0, z1, z2, lv, zv, b0, b1, b2, takenF, C);
+            rule_tap<7, 0>(z0, z1, z2, lv, zv, b0, b1, b2, takenF, C);
             ld3(0, qrow + 2, a0); ld3(1, qrow + 2, a1); ld3(2, qrow + 2, a2); ld3(5, qrow + 2, vd);
-            rule_tap<+1, 3, false, 8 | 0>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
-            rule_tap<-1, 3, false, 8 | 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
+            rule_tap<8 | 0, 2>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
+            rule_tap<8 | 1, 2>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
             ld3(0, qrow + 1, a0); ld3(1, qrow + 1, a1); ld3(2, qrow + 1, a2); ld3(5, qrow + 1, vd);
-            rule_tap<+2, 3, false, 8 | 2>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
-            rule_tap<+1, 2, false, 8 | 3>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
-            rule_tap<0, 1, false, 8 | 4>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
-            rule_tap<-1, 2, false, 8 | 5>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
-            rule_tap<-2, 3, false, 8 | 6>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
-            rule_tap<+1, 1, false, 8 | 7>(z0, z1, z2, lv, zv, b0, b1, b2, takenB, C);
+            rule_tap<8 | 2, 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
+            rule_tap<8 | 3, 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
+            rule_tap<8 | 4, 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
+            rule_tap<8 | 5, 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
+            rule_tap<8 | 6, 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
+            rule_tap<8 | 7, 0>(z0, z1, z2, lv, zv, b0, b1, b2, takenB, C);
             // the tap codes stay bit-sliced: a hop reads its four bits out of the word's planes (only tie pixels' codes are ever
             // read: a chain stops on the first pixel that is none)
             s_code[trow * WW + tw] = make_uint4(C[0], C[1], C[2], C[3]);

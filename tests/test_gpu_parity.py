@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from guarded import poison_op
-from helpers import digest, labels_from_nearest, load_cases, load_l2_cases
+from helpers import digest, labels_from_nearest, load_cases, load_l2_cases, tap_cover_batches
 
 pytestmark = pytest.mark.gpu
 CASES, DIGESTS = load_cases()
@@ -575,6 +575,11 @@ def test_l1_frames_with_a_handful_of_sources(gpu_op, oracle):
         for k, ref in (("index", lbl), ("dt", dt), ("depth", depth)):
             if k in want:
                 assert np.array_equal(got[k], ref), (want, k)
+    # every parent code that can win, among the tie pixels of frames that are k_pts's (and on the any-distance kernels)
+    a, _ = tap_cover_batches()
+    assert_equal_to_oracle(oracle, gpu_op, a, paths=("auto",))
+    assert gpu_op.pass_stats()["points"] > 0
+    assert_equal_to_oracle(oracle, gpu_op, a, paths=("general",))
 
 
 def test_extreme_shapes_vs_oracle(gpu_op, oracle):
@@ -880,6 +885,15 @@ def test_tie_regions_and_long_tie_chains(gpu_op, oracle):
         y[2, H // 3, W // 3] = 2.0
         y[2, H // 3 - 5, W // 3 + 5] = 3.0
         assert_equal_to_oracle(oracle, gpu_op, y, paths=("general",))
+    # every parent code that can win, among the tie pixels of the any-distance kernels and over all pixels of the window kernel
+    _, b = tap_cover_batches()
+    assert_equal_to_oracle(oracle, gpu_op, b, paths=("general",))
+    depth, dt, lbl, status = oracle.fill_batch(b)
+    got = run(gpu_op, b, path="fused")
+    stats = gpu_op.pass_stats()
+    assert stats["window"] == stats["all"] > 0 and not got["general"].any(), stats
+    assert np.array_equal(got["dt"], dt) and np.array_equal(got["index"], lbl) and np.array_equal(got["status"], status)
+    assert (status == 0).all() and np.array_equal(got["depth"], depth)
 
 
 def test_input_pointer_alignment_does_not_matter(gpu_op, oracle):
