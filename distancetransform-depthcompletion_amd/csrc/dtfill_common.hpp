@@ -1,4 +1,5 @@
-// dtfill_common.hpp -- constants, the tap table (dtfill_taps.hpp) and small device helpers shared by every kernel
+// dtfill_common.hpp -- constants, the tap table (dtfill_taps.hpp), the depth index rule (dtfill_index.hpp) and small device
+// helpers shared by every kernel
 // Part of libdtfill.so; included by dtfill.hip inside its anonymous namespace (one translation unit).
 #pragma once
 
@@ -38,6 +39,8 @@ constexpr int SKY_MIN = 9;  // rows above the first source row are k_sky's from 
 
 // the l1_cv parent rule's tap table (offsets, weights, parent codes, step encoding, tap_decode): stated once, there
 #include "dtfill_taps.hpp"
+// numpy's index rule for depth_list[label - 1] (depth_index, depth_index_pos): stated once, there
+#include "dtfill_index.hpp"
 
 // a[0..2] = a 32-pixel word a[1] of a row of bits with its left / right neighbour words: the word shifted so that
 // result[c] = row[c + DJ].  The caller passes a pointer into an array (a 3-word row, or row + i of a 5-word row with i <= 2):

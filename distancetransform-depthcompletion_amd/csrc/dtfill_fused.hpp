@@ -306,9 +306,8 @@ __device__ __forceinline__ bool fused_walk_epilogue(
 #pragma unroll
             for (int k = 0; k < F_RG; ++k) lab[h + k] = (int)rw[k].y + __popc(__builtin_amdgcn_ubfe(rw[k].x, 0u, (u32)bp[k]));
         }
-        // depth_list[label-1] (tools.py:26).  A decided pixel has label >= 1, so the numpy wrap of index -1
-        // cannot occur here.  Masks agree (block-uniform): the label-th value is x at the source, and
-        // label <= nsrc = nval.  Masks differ: an index past the value list is numpy's IndexError.
+        // depth_list[label - 1].  A decided pixel has label >= 1: depth_index_pos (dtfill_index.hpp).  Masks agree
+        // (block-uniform): the label-th value is x at the source, and label <= nsrc = nval: nothing to test.
         // The min only makes sure that a logic error could never become a wild global access (an LDS index
         // out of range reads garbage at worst).
         if (!misaligned) {
@@ -323,10 +322,9 @@ __device__ __forceinline__ bool fused_walk_epilogue(
             const int nv = th + FR - (int)(home0 >> 16);  // the slot's rows inside the tile (a lane without a slot: no offsets at all)
 #pragma unroll
             for (int e = 0; e < F_EB; ++e) {
-                const int idx = lab[e] - 1;
-                const bool oob = idx >= nval;
-                bad |= o[e] != OFF_NONE && e < nv && oob;
-                goff[e] = (oob ? 0u : min((u32)idx, last_px)) << 2;
+                const DepthIndex di = depth_index_pos(lab[e], nval);
+                bad |= o[e] != OFF_NONE && e < nv && !di.ok;
+                goff[e] = (di.ok ? min((u32)di.idx, last_px) : 0u) << 2;
             }
             if (bad && out_depth) atomicOr(frame_status + b, DTFILL_FRAME_INDEX_ERROR);
         }

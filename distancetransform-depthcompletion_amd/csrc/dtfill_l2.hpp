@@ -1,5 +1,6 @@
 // dtfill_l2.hpp -- the exact Euclidean transform (l2 metric): k_l2win (dense frames), k_l2rest (far pixels, rows of far pixels, sparse frames)
 // Part of libdtfill.so; included by dtfill.hip inside its anonymous namespace (one translation unit).
+// Every depth gather here takes its index from depth_index / depth_index_pos (dtfill_index.hpp).
 #pragma once
 
 // ------------------------------------------------------------------------------------------------
@@ -317,9 +318,9 @@ __global__ __launch_bounds__(256) void k_l2win(const float *__restrict__ x, cons
             const int sc = ((s_side[yy * 4 + wv] >> lane) & 1ull) ? j + dx : j - dx;
             const int c = min(max((sc >> 6) - (tx * 4 - 1), 0), 5);
             S.label[u] = source_rank(s_base[yy * 6 + c], s_w[yy * 6 + c], sc);
-            // depth_list[label - 1] with numpy's index semantics (tools.py:26): the label is >= 1 here
-            S.gok[u] = S.label[u] - 1 < nval;
-            goff[u] = misaligned ? S.label[u] - 1 : (i + dy) * W + sc;
+            const DepthIndex di = depth_index_pos(S.label[u], nval);  // a source's rank: the label is >= 1
+            S.gok[u] = di.ok;
+            goff[u] = misaligned ? di.idx : (i + dy) * W + sc;
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) S.dep[u] = (out_depth && S.live[u] && S.gok[u]) ? gsrc[goff[u]] : nanf("");
@@ -536,12 +537,10 @@ __device__ __forceinline__ void l2env_row(const float *__restrict__ x, const uin
         }
         if (out_depth) {
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {  // depth_list[label - 1] with numpy's index semantics (tools.py:26)
-                int idx = label[u] - 1;
-                if (idx < 0) idx += nval;
-                const bool ok = idx >= 0 && idx < nval;
-                dep[u] = ok ? gsrc[misaligned ? idx : q[u]] : nanf("");
-                index_error |= in[u] && !ok;
+            for (int u = 0; u < 4; ++u) {
+                const DepthIndex di = depth_index(label[u], nval);
+                dep[u] = di.ok ? gsrc[misaligned ? di.idx : q[u]] : nanf("");
+                index_error |= in[u] && !di.ok;
             }
         }
 #pragma unroll
@@ -659,12 +658,10 @@ __device__ __forceinline__ void l2sky_row(const float *__restrict__ x, const uin
         }
         if (out_depth) {
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {  // depth_list[label - 1] with numpy's index semantics (tools.py:26)
-                int idx = label[u] - 1;
-                if (idx < 0) idx += nval;
-                const bool ok = idx >= 0 && idx < nval;
-                dep[u] = (in[u] && ok) ? gsrc[misaligned ? idx : q[u]] : nanf("");
-                index_error |= in[u] && !ok;
+            for (int u = 0; u < 4; ++u) {
+                const DepthIndex di = depth_index(label[u], nval);
+                dep[u] = (in[u] && di.ok) ? gsrc[misaligned ? di.idx : q[u]] : nanf("");
+                index_error |= in[u] && !di.ok;
             }
         }
 #pragma unroll
@@ -764,13 +761,13 @@ __device__ __forceinline__ void l2pts_tile(const float *__restrict__ x, const u3
     float dep[NP];
     bool index_error = false;
 #pragma unroll
-    for (int u = 0; u < NP; ++u) {  // depth_list[label - 1] (tools.py:26): the label is >= 1 here
+    for (int u = 0; u < NP; ++u) {
         const u32 rc = (u32)best[u];
         const int q = (int)(rc >> 16) * W + (int)(rc & 0xFFFFu);
-        const bool ok = (int)bidx[u] < nval;
+        const DepthIndex di = depth_index_pos((int)bidx[u] + 1, nval);  // label = list index + 1 >= 1
         const bool in = i0 + u < H && j < W;
-        dep[u] = (out_depth && in && ok) ? gsrc[misaligned ? (int)bidx[u] : q] : nanf("");
-        index_error |= in && !ok;
+        dep[u] = (out_depth && in && di.ok) ? gsrc[misaligned ? di.idx : q] : nanf("");
+        index_error |= in && !di.ok;
     }
 #pragma unroll
     for (int u = 0; u < NP; ++u) {

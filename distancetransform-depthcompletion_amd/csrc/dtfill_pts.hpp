@@ -1,8 +1,8 @@
 // dtfill_pts.hpp -- pts_body ("k_pts"): l1_cv frames with a handful of sources (the NYU sampling patterns), one kernel from the source
 // list to the three outputs
 // Part of libdtfill.so; included by dtfill.hip inside its anonymous namespace (one translation unit), after dtfill_rows.hpp
-// (the bit-sliced parent rule rule_tap, the tile geometry Q_* and fin_body, the other half of the k_fin kernel at the end of this
-// file, are defined there).
+// (the bit-sliced parent rule tie_word_rule, the hand-off hand_on_append, the tile geometry Q_* and fin_body, the other half of the
+// k_fin kernel at the end of this file, are defined there).
 #pragma once
 
 // ------------------------------------------------------------------------------------------------
@@ -398,7 +398,7 @@ __device__ __forceinline__ void pts_body(unsigned char *__restrict__ s_raw, cons
     PTS_MARK(2);
     __syncthreads();
     PTS_MARK(3);
-    // the depths phase 3 left out (see depth_now there): depth_list[label - 1] (tools.py:26) from LDS, for the wave's pixels that
+    // the depths phase 3 left out (see depth_now there): depth_list[label - 1] from LDS, for the wave's pixels that
     // are no tie pixels (those follow their chain below)
     if (dp_f && !wave_idle && (misaligned || nw > 64 || H + W > 8100)) {  // wave-uniform
         const int j = wc0 + lane;
@@ -408,7 +408,7 @@ __device__ __forceinline__ void pts_body(unsigned char *__restrict__ s_raw, cons
             const u32 v = s_src[32 * wr + row + 2][2 + 64 * wcol + lane];
             if (j < W && !((v >> 13) & 1u)) {
                 const u32 idx = v & 511u;
-                bad |= misaligned && (int)idx >= nval;  // (the list holds NaN there)
+                bad |= misaligned && !depth_index_pos((int)idx + 1, nval).ok;  // label = idx + 1 >= 1 (the list holds NaN there)
                 dp_f[i * W + j] = __uint_as_float(s_rc[idx]);
             }
         }
@@ -465,31 +465,7 @@ __device__ __forceinline__ void pts_body(unsigned char *__restrict__ s_raw, cons
             const int qrow = trow + 2;
             const u32 b0 = s_pl[0][qrow][tw + 1], b1 = s_pl[1][qrow][tw + 1], b2 = s_pl[2][qrow][tw + 1];
             const u32 qlive = s_pl[3][qrow][tw + 1];
-            // (the same sixteen taps as fin_body: dtfill_rows.hpp)
-            u32 takenF = ~(mytie & qlive), takenB = ~(mytie & ~qlive);
-            u32 a0[3], a1[3], a2[3], lv[3], vd[3];
-            ld3(0, qrow - 2, a0); ld3(1, qrow - 2, a1); ld3(2, qrow - 2, a2); ld3(3, qrow - 2, lv); ld3(5, qrow - 2, vd);
-            rule_tap<0, -2>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
-            rule_tap<1, -2>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
-            ld3(0, qrow - 1, a0); ld3(1, qrow - 1, a1); ld3(2, qrow - 1, a2); ld3(3, qrow - 1, lv); ld3(5, qrow - 1, vd);
-            rule_tap<2, -1>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
-            rule_tap<3, -1>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
-            rule_tap<4, -1>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
-            rule_tap<5, -1>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
-            rule_tap<6, -1>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
-            u32 z0[3], z1[3], z2[3], zv[3];  // this row: last forward tap now, last backward tap at the end
-            ld3(0, qrow, z0); ld3(1, qrow, z1); ld3(2, qrow, z2); ld3(3, qrow, lv); ld3(5, qrow, zv);
-            rule_tap<7, 0>(z0, z1, z2, lv, zv, b0, b1, b2, takenF, C);
-            ld3(0, qrow + 2, a0); ld3(1, qrow + 2, a1); ld3(2, qrow + 2, a2); ld3(5, qrow + 2, vd);
-            rule_tap<8 | 0, 2>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
-            rule_tap<8 | 1, 2>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
-            ld3(0, qrow + 1, a0); ld3(1, qrow + 1, a1); ld3(2, qrow + 1, a2); ld3(5, qrow + 1, vd);
-            rule_tap<8 | 2, 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
-            rule_tap<8 | 3, 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
-            rule_tap<8 | 4, 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
-            rule_tap<8 | 5, 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
-            rule_tap<8 | 6, 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
-            rule_tap<8 | 7, 0>(z0, z1, z2, lv, zv, b0, b1, b2, takenB, C);
+            tie_word_rule(ld3, qrow, b0, b1, b2, qlive, mytie, C);
             // the tap codes stay bit-sliced: a hop reads its four bits out of the word's planes (only tie pixels' codes are ever
             // read: a chain stops on the first pixel that is none)
             s_code[trow * WW + tw] = make_uint4(C[0], C[1], C[2], C[3]);
@@ -498,7 +474,6 @@ __device__ __forceinline__ void pts_body(unsigned char *__restrict__ s_raw, cons
         __syncthreads();
         // every tie pixel of this word hops along the tap codes until it stands on a pixel that is no tie pixel and takes that
         // pixel's source; a chain that leaves the tile while still on tie pixels, or runs longer than Q_HOPS, goes to k_tiesx
-        auto is_tie = [&](int r, int c) -> bool { return (s_pl[4][r + 2][(c + 32) >> 5] >> ((c + 32) & 31)) & 1u; };
         u32 m = mytie;  // (a tie bit is only ever set inside the image)
         while (m) {
             const int bit = __ffs((int)m) - 1;
@@ -514,7 +489,7 @@ __device__ __forceinline__ void pts_body(unsigned char *__restrict__ s_raw, cons
                 tap_decode((int)(((cw4.x >> sb) & 1u) | ((cw4.y >> sb) & 1u) << 1 | ((cw4.z >> sb) & 1u) << 2 | ((cw4.w >> sb) & 1u) << 3), di, dj);
                 er += di;
                 ec += dj;
-                if (!is_tie(er, ec)) {
+                if (!tile_is_tie(s_pl[4], er, ec)) {
                     open = false;
                     break;
                 }
@@ -527,39 +502,14 @@ __device__ __forceinline__ void pts_body(unsigned char *__restrict__ s_raw, cons
             } else {
                 const u32 idx = s_src[min(max(er, -2), TH + 1) + 2][min(max(ec, -2), TW + 1) + 2] & 511u;
                 if (ix_f) ix_f[pix] = (int32_t)idx + 1;
-                bad |= misaligned && (int)idx >= nval;
+                bad |= misaligned && !depth_index_pos((int)idx + 1, nval).ok;
                 if (dp_f) dp_f[pix] = __uint_as_float(s_rc[idx]);
             }
         }
         PTS_MARK(5);
-        // the handed-on pixels join the frame's list: block-wide count, ONE atomic, then every thread writes its own
-        const int cu = __popc(umask);
-        int incl = cu;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(incl, off);
-            if (lane >= off) incl += t;
-        }
-        if (lane == 63) s_cnt[wave] = (u32)incl;
-        __syncthreads();
-        int pre = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < Q_NT / 64; ++w) {
-            pre += w < wave ? (int)s_cnt[w] : 0;
-            all += (int)s_cnt[w];
-        }
-        if (all) {  // block-uniform
-            __syncthreads();
-            if (tid == 0) s_cnt[0] = (u32)atomicAdd(&finfo[b * FI_STRIDE + FI_NUNRES], all);
-            __syncthreads();
-            u32 o = s_cnt[0] + (u32)(pre + incl - cu);
-            u32 mm = umask;
-            while (mm) {
-                const int k = __ffs((int)mm) - 1;
-                mm &= mm - 1;
-                xlist[fo + o++] = (u32)(gi * W + c0 + tw * 32 + k);
-            }
-        }
+        // the handed-on pixels join the frame's list (bit k: pixel k of this thread's word)
+        hand_on_append(umask, lane, wave, tid, s_cnt, finfo + b * FI_STRIDE, xlist + fo,
+                       [&](int k) { return (u32)(gi * W + c0 + tw * 32 + k); });
     }
     if (tin) reinterpret_cast<u32 *>(unres + ((size_t)b * H + gi) * Wp)[gw] = umask;
     PTS_MARK(6);

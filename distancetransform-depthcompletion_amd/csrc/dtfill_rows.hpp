@@ -1,5 +1,7 @@
 // dtfill_rows.hpp -- k_colT, k_rows, k_fin, k_tiesx: the any-distance path of the l1_cv pass (argmin scans)
 // Part of libdtfill.so; included by dtfill.hip inside its anonymous namespace (one translation unit).
+// Stated once here for fin_body and pts_body (dtfill_pts.hpp): tie_word_rule (the sixteen taps of the parent rule in cv2's order for
+// one 32-pixel word), tile_is_tie, hand_on_append (open chains join the frame's list for k_tiesx).
 #pragma once
 
 // ================================================================================================
@@ -515,8 +517,8 @@ __global__ __launch_bounds__(MAXT, MAXT == 256 ? 4 : 1) void k_rows(  // MULTI: 
 //      (one nearest source, or a source) and take over that pixel's source (k_rows left every pixel's nearest
 //      source in column kmin in spix).  A chain that leaves the tile while still on tie pixels records where it
 //      goes on (xptr, the "unresolved" plane, the frame's list) for k_tiesx.
-//   4. label = 1 + raster rank of the source (cv2's label init), depth = depth_list[label - 1] with numpy's index
-//      rules (tools.py:24-26); three loads + a gather per pixel, eight pixels' worth in flight per thread.
+//   4. label = 1 + raster rank of the source (cv2's label init), depth = depth_list[label - 1] (depth_index:
+//      dtfill_index.hpp); three loads + a gather per pixel, eight pixels' worth in flight per thread.
 // ------------------------------------------------------------------------------------------------
 constexpr int Q_TH = 32, Q_TW = 256;
 constexpr int Q_NT = 256;
@@ -551,6 +553,87 @@ __device__ __forceinline__ void step_tap(const u32 (&C)[4], u32 mytie, u32 (&E)[
 #pragma unroll
     for (int j = 0; j < 6; ++j)
         if (code_enc(CODE) & (1 << j)) E[j] |= sel;
+}
+
+// The parent rule for one 32-pixel word, the ONE place where the order of the sixteen taps is written down ("first match wins" rests
+// on it): the word's tie pixels mytie (planes b0..b2 = d mod 8, qlive) get their parent codes, bit-sliced, in C.  ld3(p, row, o)
+// gives words w - 1, w, w + 1 of plane p (0..2: d mod 8, 3: live, 5: in the image) in row `row` of the caller's window; the word
+// itself sits in row qrow.  Callers: fin_body (below), pts_body (dtfill_pts.hpp).
+template <class Ld3>
+__device__ __forceinline__ void tie_word_rule(Ld3 ld3, int qrow, u32 b0, u32 b1, u32 b2, u32 qlive, u32 mytie, u32 (&C)[4]) {
+    // cv2 tap order, forward taps for the live pixels, the negated taps in the same order for the others: rule_tap<CODE, row>,
+    // the row being the one whose planes were just loaded (checked against the table).  The two chains are independent
+    // (live / non-live pixels), each keeps its order.
+    u32 takenF = ~(mytie & qlive), takenB = ~(mytie & ~qlive);
+    u32 a0[3], a1[3], a2[3], lv[3], vd[3];
+    ld3(0, qrow - 2, a0); ld3(1, qrow - 2, a1); ld3(2, qrow - 2, a2); ld3(3, qrow - 2, lv); ld3(5, qrow - 2, vd);
+    rule_tap<0, -2>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
+    rule_tap<1, -2>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
+    ld3(0, qrow - 1, a0); ld3(1, qrow - 1, a1); ld3(2, qrow - 1, a2); ld3(3, qrow - 1, lv); ld3(5, qrow - 1, vd);
+    rule_tap<2, -1>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
+    rule_tap<3, -1>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
+    rule_tap<4, -1>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
+    rule_tap<5, -1>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
+    rule_tap<6, -1>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
+    u32 z0[3], z1[3], z2[3], zv[3];  // this row: last forward tap now, last backward tap at the end
+    ld3(0, qrow, z0); ld3(1, qrow, z1); ld3(2, qrow, z2); ld3(3, qrow, lv); ld3(5, qrow, zv);
+    rule_tap<7, 0>(z0, z1, z2, lv, zv, b0, b1, b2, takenF, C);
+    ld3(0, qrow + 2, a0); ld3(1, qrow + 2, a1); ld3(2, qrow + 2, a2); ld3(5, qrow + 2, vd);
+    rule_tap<8 | 0, 2>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
+    rule_tap<8 | 1, 2>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
+    ld3(0, qrow + 1, a0); ld3(1, qrow + 1, a1); ld3(2, qrow + 1, a2); ld3(5, qrow + 1, vd);
+    rule_tap<8 | 2, 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
+    rule_tap<8 | 3, 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
+    rule_tap<8 | 4, 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
+    // (codes 13 and 14 never win: where (+1, -1) or (+1, -2) matches, d(q + (1, 0)) can only be d(q) - 1, so code 12 matches too
+    // and comes first -- 0 wins in 60 random frames of 96 x 160 at source densities from 0.2 % to 30 %.  They stay: the rule is
+    // cv2's as it stands.)
+    rule_tap<8 | 5, 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
+    rule_tap<8 | 6, 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
+    rule_tap<8 | 7, 0>(z0, z1, z2, lv, zv, b0, b1, b2, takenB, C);
+}
+
+// is tile pixel (r, c) -- rows -2 .. TH + 1, columns -32 .. TW + 31 -- a tie pixel?  tie = the window's tie plane s_pl[4] (word 0 of a
+// row is the left ring's, row 0 is tile row -2)
+template <int RS>
+__device__ __forceinline__ bool tile_is_tie(const u32 (*tie)[RS], int r, int c) {
+    return (tie[r + 2][(c + 32) >> 5] >> ((c + 32) & 31)) & 1u;
+}
+
+// The hand-off of open chains to k_tiesx: the block's handed-on pixels (bit k of a thread's umask; pix_of(k) is that pixel's frame
+// index) join the frame's list xl_f = xlist + fo -- block-wide count, ONE atomic on the frame's FI_NUNRES, then every thread writes
+// its own.  Call it from all Q_NT threads (both callers sit under the block-uniform any_tie): one barrier always, two more when
+// the block hands anything on.  s_cnt: a word per wave, free to overwrite.
+template <class PixOf>
+__device__ __forceinline__ void hand_on_append(u32 umask, int lane, int wave, int tid, u32 *s_cnt, int *__restrict__ finfo_b,
+                                               u32 *__restrict__ xl_f, PixOf pix_of) {
+    const int cu = __popc(umask);
+    int incl = cu;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int t = __shfl_up(incl, off);
+        if (lane >= off) incl += t;
+    }
+    if (lane == 63) s_cnt[wave] = (u32)incl;
+    __syncthreads();
+    int pre = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < Q_NT / 64; ++w) {
+        pre += w < wave ? (int)s_cnt[w] : 0;
+        all += (int)s_cnt[w];
+    }
+    if (all) {  // block-uniform
+        __syncthreads();
+        if (tid == 0) s_cnt[0] = (u32)atomicAdd(&finfo_b[FI_NUNRES], all);
+        __syncthreads();
+        u32 o = s_cnt[0] + (u32)(pre + incl - cu);
+        u32 m = umask;
+        while (m) {
+            const int k = __ffs((int)m) - 1;
+            m &= m - 1;
+            xl_f[o++] = pix_of(k);
+        }
+    }
 }
 
 // LDS of a k_fin block (carved from the kernel's buffer: the kernel, in dtfill_pts.hpp, also runs k_pts's tiles)
@@ -647,36 +730,7 @@ __device__ __forceinline__ void fin_body(
             const int qrow = trow + 2;
             const u32 b0 = s_pl[0][qrow][tw + 1], b1 = s_pl[1][qrow][tw + 1], b2 = s_pl[2][qrow][tw + 1];
             const u32 qlive = s_pl[3][qrow][tw + 1];
-            // cv2 tap order, forward taps for the live pixels, the negated taps in the same order for the others: rule_tap<CODE, row>,
-            // the row being the one whose planes were just loaded (checked against the table).  The two chains are independent
-            // (live / non-live pixels), each keeps its order.
-            u32 takenF = ~(mytie & qlive), takenB = ~(mytie & ~qlive);
-            u32 a0[3], a1[3], a2[3], lv[3], vd[3];
-            ld3(0, qrow - 2, a0); ld3(1, qrow - 2, a1); ld3(2, qrow - 2, a2); ld3(3, qrow - 2, lv); ld3(5, qrow - 2, vd);
-            rule_tap<0, -2>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
-            rule_tap<1, -2>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
-            ld3(0, qrow - 1, a0); ld3(1, qrow - 1, a1); ld3(2, qrow - 1, a2); ld3(3, qrow - 1, lv); ld3(5, qrow - 1, vd);
-            rule_tap<2, -1>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
-            rule_tap<3, -1>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
-            rule_tap<4, -1>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
-            rule_tap<5, -1>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
-            rule_tap<6, -1>(a0, a1, a2, lv, vd, b0, b1, b2, takenF, C);
-            u32 z0[3], z1[3], z2[3], zv[3];  // this row: last forward tap now, last backward tap at the end
-            ld3(0, qrow, z0); ld3(1, qrow, z1); ld3(2, qrow, z2); ld3(3, qrow, lv); ld3(5, qrow, zv);
-            rule_tap<7, 0>(z0, z1, z2, lv, zv, b0, b1, b2, takenF, C);
-            ld3(0, qrow + 2, a0); ld3(1, qrow + 2, a1); ld3(2, qrow + 2, a2); ld3(5, qrow + 2, vd);
-            rule_tap<8 | 0, 2>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
-            rule_tap<8 | 1, 2>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
-            ld3(0, qrow + 1, a0); ld3(1, qrow + 1, a1); ld3(2, qrow + 1, a2); ld3(5, qrow + 1, vd);
-            rule_tap<8 | 2, 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
-            rule_tap<8 | 3, 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
-            rule_tap<8 | 4, 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
-            // (codes 13 and 14 never win: where (+1, -1) or (+1, -2) matches, d(q + (1, 0)) can only be d(q) - 1, so code 12 matches too
-            // and comes first -- 0 wins in 60 random frames of 96 x 160 at source densities from 0.2 % to 30 %.  They stay: the rule is
-            // cv2's as it stands.)
-            rule_tap<8 | 5, 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
-            rule_tap<8 | 6, 1>(a0, a1, a2, lv, vd, b0, b1, b2, takenB, C);
-            rule_tap<8 | 7, 0>(z0, z1, z2, lv, zv, b0, b1, b2, takenB, C);
+            tie_word_rule(ld3, qrow, b0, b1, b2, qlive, mytie, C);
             // every tie pixel's step code, still bit-sliced: tap t was chosen where the code planes spell t
             {
                 E[1] = E[4] = ~mytie;
@@ -730,7 +784,6 @@ __device__ __forceinline__ void fin_body(
     // with the pixel where it goes on (that pixel's own chain is shorter: k_tiesx follows such links to their end).
     u32 esp[NRW][4];
     u32 umask = 0;  // bit 4 * it + u: handed to k_tiesx
-    auto is_tie = [&](int r, int c) -> bool { return (s_pl[4][r + 2][(c + 32) >> 5] >> ((c + 32) & 31)) & 1u; };
 #pragma unroll
     for (int it = 0; it < NRW; ++it) {
         const int rr = ewave + (Q_NT / 64) * it;
@@ -741,14 +794,14 @@ __device__ __forceinline__ void fin_body(
         for (int u = 0; u < 4; ++u) {
             const u32 bb = (b4 >> (8 * u)) & 63u;
             int er = rr + (int)(bb >> 3) - 2, ec = elane * 4 + u + (int)(bb & 7u) - 2;  // one hop (none: step (0, 0))
-            if (bb != 18u && ((inm >> u) & 1u) && is_tie(er, ec)) {  // rare: a chain of more than one hop
+            if (bb != 18u && ((inm >> u) & 1u) && tile_is_tie(s_pl[4], er, ec)) {  // rare: a chain of more than one hop
                 bool open = true;
                 for (int hop = 1; hop < Q_HOPS; ++hop) {
                     if (er < 0 || er >= Q_TH || ec < 0 || ec >= Q_TW) break;  // a tie pixel of another tile: no step here
                     const u32 b2 = s_byte[er][ec] & 63u;
                     er += (int)(b2 >> 3) - 2;
                     ec += (int)(b2 & 7u) - 2;
-                    if (!is_tie(er, ec)) {
+                    if (!tile_is_tie(s_pl[4], er, ec)) {
                         open = false;
                         break;
                     }
@@ -767,34 +820,10 @@ __device__ __forceinline__ void fin_body(
         }
     }
     if (any_tie) {
-        // the handed-on pixels join the frame's list: block-wide count, ONE atomic, then every thread writes its own
-        const int cu = __popc(umask);
-        int incl = cu;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(incl, off);
-            if (elane >= off) incl += t;
-        }
-        if (elane == 63) s_cnt[ewave] = (u32)incl;
-        __syncthreads();  // also: s_unres is complete
-        int pre = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < Q_NT / 64; ++w) {
-            pre += w < ewave ? (int)s_cnt[w] : 0;
-            all += (int)s_cnt[w];
-        }
-        if (all) {  // block-uniform
-            __syncthreads();
-            if (tid == 0) s_cnt[0] = (u32)atomicAdd(&finfo[b * FI_STRIDE + FI_NUNRES], all);
-            __syncthreads();
-            u32 o = s_cnt[0] + (u32)(pre + incl - cu);
-            u32 m = umask;
-            while (m) {
-                const int k = __ffs((int)m) - 1;
-                m &= m - 1;
-                xlist[fo + o++] = (u32)((r0 + ewave + (Q_NT / 64) * (k >> 2)) * W + col + (k & 3));
-            }
-        }
+        // the handed-on pixels join the frame's list (bit 4 * it + u: row ewave + waves * it, column col + u); its first barrier
+        // also completes s_unres
+        hand_on_append(umask, elane, ewave, tid, s_cnt, finfo + b * FI_STRIDE, xlist + fo,
+                       [&](int k) { return (u32)((r0 + ewave + (Q_NT / 64) * (k >> 2)) * W + col + (k & 3)); });
     }
     if (tin) reinterpret_cast<u32 *>(unres + (rowb + gi) * Wp)[gw] = s_unres[tid];
     // label from the source's rank record, depth = depth_list[label - 1] = x[source] when the masks agree: two gathers per pixel,
@@ -821,17 +850,15 @@ __device__ __forceinline__ void fin_body(
         const u32 pixb = ((u32)min(r0 + rr, H - 1) * (u32)W + (u32)col) << 2;
 #pragma unroll
         for (int u = 0; u < 4; ++u) lab[it][u] = ((nonem >> (4 * it + u)) & 1u) ? 0 : lab[it][u];
-        if (dp_f && (misaligned || ((nonem >> (4 * it)) & 15u))) {  // rare: numpy's index rules (tools.py:26)
+        if (dp_f && (misaligned || ((nonem >> (4 * it)) & 15u))) {  // rare: everything but "masks agree, the pixel has a source"
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const bool none = (nonem >> (4 * it + u)) & 1u;
-                int idx = lab[it][u] - 1;
-                if (idx < 0) idx += nval;  // numpy: index -1 wraps to the last element
-                const bool oob = idx < 0 || idx >= nval;
-                bad |= oob && ((inm >> u) & 1u);
+                const DepthIndex di = depth_index(lab[it][u], nval);
+                bad |= !di.ok && ((inm >> u) & 1u);
                 // label 0 with agreeing masks means nval == nsrc == 0: out of bounds; so an in-bounds gather of a
                 // source-less frame reads the value list
-                val[it][u] = oob ? nanf("") : ((misaligned || none) ? vl_f[idx] : val[it][u]);
+                val[it][u] = !di.ok ? nanf("") : ((misaligned || none) ? vl_f[di.idx] : val[it][u]);
             }
         }
         const bool kept = pixb >= dcrop;  // wave-uniform: a wave holds one row
