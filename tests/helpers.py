@@ -39,6 +39,12 @@ def labels_from_nearest(x, near, src_thr=0.1):
     return np.where(near.ravel() >= 0, rank[np.maximum(near.ravel(), 0)], 0).reshape(x.shape).astype(np.int32)
 
 
+def dt_bits(dt):
+    """A distance map as uint32 bit patterns: an l2 dt is sqrtf (correctly rounded) of the exact integer d2 on the device, in the
+    oracle and in numpy alike, so two of them are compared for equality of every bit (+inf included), not within a tolerance."""
+    return np.ascontiguousarray(dt, np.float32).view(np.uint32)
+
+
 TAP_CODES = tuple(range(13)) + (15,)  # the parent codes that can win (13 and 14 never do: code 12 matches wherever they match)
 
 

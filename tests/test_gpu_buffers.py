@@ -6,7 +6,7 @@ mode -- run wherever an offset is not 0), starts filled with an impossible value
 starts as zero, 0xFF, random bytes or the state a pass over a different input on the other path left.  After every call:
 every guard is intact (the workspace's tail guard sits right behind dtfill_workspace_bytes() bytes), x is bit-for-bit
 unchanged, no requested output still holds poison, and every output equals the oracle (depth on the frames without
-IndexError; l2 dt at rtol 1e-6, everything else exact).
+IndexError; everything exact, an l2 dt as sqrtf of the exact integer bit for bit).
 
 Workspace regions of one pass (include/dtfill.h promises no initialisation contract): who writes each region a later kernel
 of the same pass reads.  Audited before these tests first ran; no region is read as an index or a count before this pass
@@ -36,6 +36,7 @@ import numpy as np
 import pytest
 
 from guarded import KINDS, GuardedBuffer, is_poison, other_input, poison, poison_output
+from helpers import dt_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -120,7 +121,7 @@ def guarded_pass(L, xh, metric=0, flags=0, want=ALL, status=True, offs=None, epi
 
 
 def assert_pass_equals_oracle(out, ref, metric, flags, want, epi=None, what=""):
-    """Outputs of guarded_pass against oracle.fill_batch: exact (l2 dt at rtol 1e-6), no poison left; with FUSED_ONLY the
+    """Outputs of guarded_pass against oracle.fill_batch: exact (an l2 dt bit for bit), no poison left; with FUSED_ONLY the
     frames that carry DTFILL_FRAME_GENERAL_PATH are left undefined by contract and not compared."""
     depth, dt, idx, status = ref
     B = dt.shape[0]
@@ -142,7 +143,7 @@ def assert_pass_equals_oracle(out, ref, metric, flags, want, epi=None, what=""):
         got = out["dt"][keep]
         assert not is_poison(got, "dt").any(), "%s: dt poison left" % what
         if metric == 1:
-            assert np.allclose(got, dt[keep], rtol=1e-6, atol=0) and np.array_equal(np.isinf(got), np.isinf(dt[keep])), what
+            assert np.array_equal(dt_bits(got), dt_bits(dt[keep])) and np.array_equal(np.isinf(got), np.isinf(dt[keep])), what
         else:
             assert np.array_equal(got, dt[keep]), "%s: dt differs at %d px" % (what, (got != dt[keep]).sum())
     if "depth" in want:

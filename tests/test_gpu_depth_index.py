@@ -16,13 +16,14 @@ Cases, from F (source values in (0.95, 10)) and the thresholds (source, value):
   (f) no source, no value            zeros                              (0.1, 0.1)    IndexError
 (a), (b), (e), (f) run as ONE batch: only (f)'s frame may carry the status bit there, so a bit raised on the wrong frame shows.
 The comparison is assert_equal_to_oracle's / assert_l2_equal_to_oracle's (test_gpu_parity.py): index and status exact on every
-frame, dt exact (l1_cv) or at rtol 1e-6 (l2), depth on the frames with status 0, outputs and workspace poisoned first."""
+frame, dt exact (l2: sqrtf of the exact integer, bit for bit), depth on the frames with status 0, outputs and workspace poisoned first."""
 import itertools
 
 import numpy as np
 import pytest
 
 from guarded import poison_op
+from helpers import dt_bits
 
 pytestmark = pytest.mark.gpu
 _POISON = itertools.count(9300)
@@ -68,7 +69,7 @@ def compare(oracle, op, metric, x, st, vt, path, want_status):
     assert not bad.any(), "%s: index differs at %d px, first %s" % (what, bad.sum(), np.argwhere(bad)[:3].tolist())
     assert np.array_equal(got["status"][done] & 1, status[done]), "%s: status %s, want %s" % (what, got["status"].tolist(), status.tolist())
     if metric == "l2":
-        assert np.allclose(got["dt"][done], dt[done], rtol=1e-6, atol=0), "%s: distance differs" % what
+        assert np.array_equal(dt_bits(got["dt"][done]), dt_bits(dt[done])), "%s: distance differs" % what
         assert np.array_equal(np.isinf(got["dt"][done]), np.isinf(dt[done])), what
     else:
         assert np.array_equal(got["dt"][done], dt[done]), "%s: distance map differs" % what

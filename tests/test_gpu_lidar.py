@@ -65,7 +65,7 @@ def assert_matches(metric, got, ref, want=ALL, what=""):
         if metric == "l1_cv":
             assert np.array_equal(bits(got["dt"]), bits(dt)), "%s: distance map differs" % what
         else:
-            assert np.allclose(got["dt"], dt, rtol=1e-6, atol=0), "%s: l2 distance differs" % what
+            assert np.array_equal(bits(got["dt"]), bits(dt)), "%s: l2 distance differs" % what
             assert np.array_equal(np.isinf(got["dt"]), np.isinf(dt)), what
     if "depth" in want:
         assert np.array_equal(got["status"] & 1, status), "%s: IndexError frames differ: %s vs %s" % (what, got["status"] & 1, status)

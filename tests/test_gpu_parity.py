@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from guarded import poison_op
-from helpers import digest, labels_from_nearest, load_cases, load_l2_cases, tap_cover_batches
+from helpers import digest, dt_bits, labels_from_nearest, load_cases, load_l2_cases, tap_cover_batches
 
 pytestmark = pytest.mark.gpu
 CASES, DIGESTS = load_cases()
@@ -265,9 +265,9 @@ def test_tile_seams_and_halo_boundary(gpu_op, oracle):
 
 def test_l2_metric_vs_oracle(pkg, oracle):
     """The `l2` mode (exact Euclidean transform, ties -> smallest raster index of the source):
-    index map and squared distances bit-exact (the float distance is sqrtf of an exact integer,
-    compared at rtol 1e-6, inside the 1e-5 BASELINE.json's north_star allows), depth gathered
-    through the same value-list glue."""
+    index map and distances bit-exact (the float distance is sqrtf of an exact integer, correctly
+    rounded on both sides: every bit of it is compared), depth gathered through the same
+    value-list glue."""
     import torch
 
     op = pkg.device.DtFill(device="cuda:0", metric="l2")
@@ -292,7 +292,7 @@ def test_l2_metric_vs_oracle(pkg, oracle):
         torch.cuda.synchronize()
         got = {k: v.cpu().numpy() for k, v in res.items()}
         assert np.array_equal(got["index"], idx), "l2 index map differs: %d px" % (got["index"] != idx).sum()
-        assert np.allclose(got["dt"], dt, rtol=1e-6, atol=0), "l2 distance differs"
+        assert np.array_equal(dt_bits(got["dt"]), dt_bits(dt)), "l2 distance differs"
         assert np.array_equal(np.isinf(got["dt"]), np.isinf(dt))
         assert np.array_equal(got["status"] & 1, status)
         ok = status == 0
@@ -312,7 +312,8 @@ def _run_l2(pkg, x, path="auto"):
 @pytest.mark.parametrize("path", ("auto", "general"))
 def test_l2_scipy_pinned_cases(pkg, path):
     """The l2 mode against fixtures written from scipy.ndimage.distance_transform_edt (tests/golden/make_golden_l2.py; north_star:
-    index map bit-exact, distance within 1e-5 relative): squared distances are scipy's, the index is the canonical one
+    index map bit-exact; the distance, which north_star allows 1e-5 relative, is held to sqrt of the fixture's integer d2 in
+    float32, bit for bit): squared distances are scipy's, the index is the canonical one
     (smallest raster index among the equidistant sources, pinned by brute force when the fixtures were made).  Both kernel
     families (window + far list; column distances + envelope search / tile search)."""
     for name, c in L2_CASES.items():
@@ -321,8 +322,7 @@ def test_l2_scipy_pinned_cases(pkg, path):
             assert np.isinf(got["dt"]).all() and (got["index"] == 0).all(), name
             continue
         assert np.array_equal(got["index"][0], labels_from_nearest(c["x"], c["near"])), name
-        want = np.sqrt(c["d2"].astype(np.float64))
-        assert np.allclose(got["dt"][0], want, rtol=1e-5, atol=0), name  # tolerance of BASELINE.json's north_star
+        assert np.array_equal(dt_bits(got["dt"][0]), dt_bits(np.sqrt(c["d2"].astype(np.float32)))), name
         src = c["x"] >= 0.9
         assert np.array_equal(got["depth"][0], c["x"].ravel()[c["near"].ravel()].reshape(c["x"].shape)) or not src.any(), name
 
@@ -355,13 +355,13 @@ def test_l2_full_size_properties(pkg, oracle):
     idx = res["index"].cpu().numpy()
     dt = res["dt"].cpu().numpy()
     depth, dt0, idx0, _ = oracle.fill_batch(x[:1], metric="l2")
-    assert np.array_equal(idx[0], idx0[0]) and np.allclose(dt[0], dt0[0], rtol=1e-6)
+    assert np.array_equal(idx[0], idx0[0]) and np.array_equal(dt_bits(dt[0]), dt_bits(dt0[0]))
     assert np.array_equal(res["depth"].cpu().numpy()[0], depth[0])
     ii, jj = np.indices(x.shape[1:])
     for b in range(1, 4):
         pos = np.argwhere(x[b] >= 0.9)
         d2 = (ii - pos[idx[b] - 1, 0]) ** 2 + (jj - pos[idx[b] - 1, 1]) ** 2
-        assert np.allclose(np.sqrt(d2.astype(np.float32)), dt[b], rtol=1e-6)
+        assert np.array_equal(dt_bits(np.sqrt(d2.astype(np.float32))), dt_bits(dt[b]))
 
 
 def test_rows_handed_on_by_the_window_kernel(gpu_op, oracle):
@@ -426,7 +426,7 @@ def assert_l2_equal_to_oracle(oracle, op2, x, st=0.1, vt=0.1, paths=("auto", "ge
         got = {k: v.cpu().numpy() for k, v in res.items()}
         bad = got["index"] != idx
         assert not bad.any(), "l2 %s: index differs at %d px, first %s" % (path, bad.sum(), np.argwhere(bad)[:3].tolist())
-        assert np.allclose(got["dt"], dt, rtol=1e-6, atol=0), "l2 %s: distance differs" % path
+        assert np.array_equal(dt_bits(got["dt"]), dt_bits(dt)), "l2 %s: distance differs" % path
         assert np.array_equal(np.isinf(got["dt"]), np.isinf(dt))
         assert np.array_equal(got["status"] & 1, status)
         ok = status == 0
@@ -638,7 +638,7 @@ def test_random_fuzz_both_metrics(pkg, gpu_op, oracle):
         res = op2.run(torch.from_numpy(x).to("cuda:0"), st, vt)
         torch.cuda.synchronize()
         assert np.array_equal(res["index"].cpu().numpy(), idx)
-        assert np.allclose(res["dt"].cpu().numpy(), dt, rtol=1e-6, atol=0)
+        assert np.array_equal(dt_bits(res["dt"].cpu().numpy()), dt_bits(dt))
 
 
 def test_outlier_removal_vs_oracle(pkg, oracle):
@@ -708,7 +708,7 @@ def test_outlier_removal_fused_into_the_predicates(pkg, gpu_op, oracle):
                 torch.cuda.synchronize()
                 got = {k: v.cpu().numpy() for k, v in res.items()}
                 assert np.array_equal(got["index"], idx), (metric, path, B, H, W)
-                assert np.allclose(got["dt"], dt, rtol=1e-6, atol=0) if metric == "l2" else np.array_equal(got["dt"], dt)
+                assert np.array_equal(dt_bits(got["dt"]), dt_bits(dt)) if metric == "l2" else np.array_equal(got["dt"], dt)
                 ok = status == 0
                 assert np.array_equal(got["status"] & 1, status) and np.array_equal(got["depth"][ok], depth[ok], equal_nan=True)
     # values that are not sources (misaligned enumerations) + the reference-named entry point
