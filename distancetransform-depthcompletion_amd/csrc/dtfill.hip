@@ -49,10 +49,12 @@
 //   k_tiesx    the few tie pixels whose chain crosses tiles or runs longer: follows the recorded links
 // l2 pass (exact Euclidean, canonical tie-break; dtfill_l2.hpp): k_mask, k_frame, then
 //   k_l2win<R> dense frames: (2R+1)^2 windows straight from the bit words, packed-key minimum over the window rows
-//   k_l2far    the odd far pixel of a dense frame, half a wave each
-//   k_colT     vertical distances per column, for sparse frames and for rows of far pixels (the empty sky)
-//   k_l2env    sparse frames: lower envelope of parabolas searched by monotone bisection; rows of far pixels of a dense frame
-//              (the sky): a window in the column distances; frames with a handful of sources: tiles over the source list
+//   k_l2far    the odd far pixel of a dense frame, half a wave each (l2far_list, l2far_pixel)
+//   k_colT     vertical distances per column, for sparse frames and for rows of far pixels (the empty sky); its column words
+//              are read through col_dist (dtfill_rows.hpp), by the l2 row searches as l2_column
+//   k_l2env    sparse frames: lower envelope of parabolas searched by monotone bisection (l2env_row); rows of far pixels of a
+//              dense frame (the sky): a window in the column distances (l2sky_row); frames with a handful of sources: tiles
+//              over the source list (l2pts_tile)
 //
 // No MFMA anywhere: this path is compare/min/index work (DESIGN.md "Roofline").
 
@@ -349,16 +351,17 @@ int run_l2(const Pass &p, unsigned flags, hipStream_t st, hipEvent_t *ev, unsign
     m.at(S2_FRAME);
     k_frame<<<B, 256, 0, st>>>(p, ((flags & DTFILL_FLAG_GENERAL_ONLY) ? 1 : 0) | 2, 0, 0);
     m.at(S2_WIN16);
-    // dense frames (k_frame's route 16 / 32): windows of 15 x 15 / 31 x 31 around every pixel, the few pixels with no source
+    // dense frames (k_frame's route 16 / 32): windows of 21 x 21 / 31 x 31 around every pixel, the few pixels with no source
     // that near one by one
     const int ttx = (W + W2_TW - 1) / W2_TW, tty = (H + W2_TH - 1) / W2_TH;
-    k_l2win<W2_R16><<<dim3(ttx * tty, B), 256, L2Win<W2_R16>::LDS, st>>>(
-        p.x, p.srcbits, p.wpre_s, p.rowbase_s, p.finfo, p.vlist, p.xlist, p.route, 16, p.rowfar, p.fflag2, H, W, p.Wd, ttx, p.out_depth, p.out_dt,
-        p.out_index, p.status);
+    auto win = [&](auto radius, int want_route) {
+        constexpr int R = decltype(radius)::value;
+        k_l2win<R><<<dim3(ttx * tty, B), 256, L2Win<R>::LDS, st>>>(p.x, p.srcbits, p.wpre_s, p.rowbase_s, p.finfo, p.vlist, p.xlist, p.route, want_route,
+                                                                   p.rowfar, p.fflag2, H, W, p.Wd, ttx, p.out_depth, p.out_dt, p.out_index, p.status);
+    };
+    win(std::integral_constant<int, W2_R16>{}, 16);
     m.at(S2_WIN32);
-    k_l2win<W2_R32><<<dim3(ttx * tty, B), 256, L2Win<W2_R32>::LDS, st>>>(
-        p.x, p.srcbits, p.wpre_s, p.rowbase_s, p.finfo, p.vlist, p.xlist, p.route, 32, p.rowfar, p.fflag2, H, W, p.Wd, ttx, p.out_depth, p.out_dt,
-        p.out_index, p.status);
+    win(std::integral_constant<int, W2_R32>{}, 32);
     m.at(S2_FAR);
     // one wave per listed pixel: enough blocks per frame for ~16 k waves in the batch
     k_l2far<<<dim3(min(256, max(16, 4096 / B)), B), 256, 0, st>>>(p);
@@ -369,18 +372,20 @@ int run_l2(const Pass &p, unsigned flags, hipStream_t st, hipEvent_t *ev, unsign
     // the rows, one wave each; then the 32 x 32 tiles of the frames with a handful of sources, one wave each
     const size_t wave_lds = max(max(l2env_lds(W), (size_t)L2_PTS_MAX * 8), (size_t)(W + 2 * L2S_R) * 8);
     const int ntile = ((H + PT_T - 1) / PT_T) * ((W + PT_T - 1) / PT_T);
+    auto env = [&](auto waves, int tpw) {  // waves per block, tiles per wave
+        constexpr int WPB = decltype(waves)::value;
+        const int nrowblk = (H + WPB - 1) / WPB;
+        k_l2env<WPB><<<dim3(B, nrowblk + (ntile + WPB * tpw - 1) / (WPB * tpw)), 64 * WPB, WPB * wave_lds, st>>>(
+            p.x, p.ct, p.ctp, p.nb, p.rec, p.Wd, p.finfo, p.vlist, p.route, p.rowfar, p.srclist(), H, W, nrowblk, wave_lds, tpw, p.out_depth,
+            p.out_dt, p.out_index, p.status);
+    };
     if (4 * wave_lds <= 64 * 1024) {
-        const int nrowblk = (H + 3) / 4;
-        k_l2env<4><<<dim3(B, nrowblk + (ntile + 3) / 4), 256, 4 * wave_lds, st>>>(p.x, p.ct, p.ctp, p.nb, p.rec, p.Wd, p.finfo, p.vlist, p.route,
-                                                                                  p.rowfar, p.srclist(), H, W, nrowblk, wave_lds, 1, p.out_depth,
-                                                                                  p.out_dt, p.out_index, p.status);
+        env(std::integral_constant<int, 4>{}, 1);
     } else {
         if (wave_lds > 48 * 1024)  // rows wider than ~4900 pixels (set per call: the attribute belongs to the current device)
             m.ok = m.ok && hipFuncSetAttribute(reinterpret_cast<const void *>(k_l2env<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                (int)l2env_lds(8192)) == hipSuccess;
-        k_l2env<1><<<dim3(B, H + (ntile + 7) / 8), 64, wave_lds, st>>>(p.x, p.ct, p.ctp, p.nb, p.rec, p.Wd, p.finfo, p.vlist, p.route, p.rowfar,
-                                                                       p.srclist(), H, W, H, wave_lds, 8, p.out_depth, p.out_dt, p.out_index,
-                                                                       p.status);
+        env(std::integral_constant<int, 1>{}, 8);
     }
     m.at(NK_L2);
     if (idle) *idle = m.idle;

@@ -1,7 +1,40 @@
-// dtfill_l2.hpp -- the exact Euclidean transform (l2 metric): k_l2win (dense frames), k_l2rest (far pixels, rows of far pixels, sparse frames)
+// dtfill_l2.hpp -- the exact Euclidean transform (l2 metric): k_l2win (dense frames), k_l2far (their far pixels), k_l2env (rows of
+// far pixels, sparse frames, frames with a handful of sources)
 // Part of libdtfill.so; included by dtfill.hip inside its anonymous namespace (one translation unit).
-// Every depth gather here takes its index from depth_index / depth_index_pos (dtfill_index.hpp).
+// Stated once here: L2Frame (what a frame's outputs and depth list are: k_l2win and the far pixels of k_l2far gather
+// through it, with the index from depth_index / depth_index_pos of dtfill_index.hpp) and l2_column (a column word of k_colT
+// as a candidate of the row searches).
 #pragma once
+
+// ------------------------------------------------------------------------------------------------
+// The frame an l2 body works on, built once per kernel from its positional parameters: where its outputs go, and what its depth
+// list is -- depth_list[k] is vlist[k] when the frame's source and value masks differ (misaligned); else the k-th value IS its
+// source pixel's own depth and is read from x there.
+// ------------------------------------------------------------------------------------------------
+struct L2Frame {
+    int b, H, W;
+    size_t fo;                  // the frame's first pixel in the batch: b * H * W
+    float *out_depth, *out_dt;  // the pass's outputs (null: not wanted); this frame's pixels start at fo
+    int32_t *out_index;
+    int *status;                // the frame's status word
+    int nval, misaligned;       // FI_NVAL, FI_MISALIGNED
+    const float *gsrc;          // the gather base: the frame's slice of vlist (misaligned) or of x
+    // where depth_list[di.idx] of a pixel whose nearest source is the frame's pixel src_pixel stands in gsrc ...
+    __device__ __forceinline__ int at(const DepthIndex di, int src_pixel) const { return misaligned ? di.idx : src_pixel; }
+    // ... and the gather: NaN for a pixel that is not ok -- outside the image, not this body's, or its index out of bounds
+    // (numpy's IndexError: the body collects !di.ok of the pixels it stores for raise(), once per thread after its stores)
+    __device__ __forceinline__ float depth(int at, bool ok) const { return ok ? gsrc[at] : nanf(""); }
+    __device__ __forceinline__ void raise(bool index_error) const {
+        if (out_depth && index_error) atomicOr(status, DTFILL_FRAME_INDEX_ERROR);
+    }
+};
+__device__ __forceinline__ L2Frame l2_frame(const float *__restrict__ x, const float *__restrict__ vlist, const int *__restrict__ finfo,
+                                            int b, int H, int W, float *__restrict__ out_depth, float *__restrict__ out_dt,
+                                            int32_t *__restrict__ out_index, int *__restrict__ frame_status) {
+    const size_t fo = (size_t)b * H * W;
+    const int nval = finfo[b * FI_STRIDE + FI_NVAL], misaligned = finfo[b * FI_STRIDE + FI_MISALIGNED];
+    return L2Frame{b, H, W, fo, out_depth, out_dt, out_index, frame_status + b, nval, misaligned, misaligned ? vlist + fo : x + fo};
+}
 
 // ------------------------------------------------------------------------------------------------
 // l2 metric, dense frames: k_l2win<R>.  The squared distance separates, d2(i,j) = min_y (y-i)^2 + hx(y,j)^2 with hx the
@@ -87,14 +120,10 @@ __device__ __forceinline__ void l2far_row(const u64 *__restrict__ row, int Wd, i
 // Two pixels per wave: lanes 0-31 search for pixel (i, j) of their half, lanes 32-63 for theirs (the two may be the same
 // pixel); lane l of a half takes the rows i - (base + l) and i + (base + l), base advancing by 32.  The first lane of each
 // half stores the three outputs.
-__device__ __forceinline__ void l2far_pixel(const float *__restrict__ x, const u64 *__restrict__ srcbits,
-                                            const u16 *__restrict__ wpre_s, const u32 *__restrict__ rowbase_s,
-                                            const float *__restrict__ vlist, int b, int H, int W, int Wd, int i, int j,
-                                            int nval, int misaligned, float *__restrict__ out_depth,
-                                            float *__restrict__ out_dt, int32_t *__restrict__ out_index,
-                                            int *__restrict__ frame_status) {
+__device__ __forceinline__ void l2far_pixel(const L2Frame &f, const u64 *__restrict__ srcbits,
+                                            const u16 *__restrict__ wpre_s, const u32 *__restrict__ rowbase_s, int Wd, int i, int j) {
     const int hl = threadIdx.x & 31;
-    const size_t fo = (size_t)b * H * W;
+    const int b = f.b, H = f.H, W = f.W;
     u32 bestd2 = 0xFFFFFFFFu, bestrc = 0xFFFFFFFFu;
     for (int base = 0; base < H; base += 32) {       // a routed frame has sources: the loop ends with a finite best
         // base^2 == bestd2 may still hold a smaller source row; the wave goes on while either half has rows to look at
@@ -132,9 +161,13 @@ __device__ __forceinline__ void l2far_pixel(const float *__restrict__ x, const u
             label = source_rank(rowbase_s[(size_t)b * H + srow] + wpre_s[w], srcbits[w], scol);
             dist = sqrtf((float)bestd2);
         }
-        if (out_index) out_index[fo + p] = label;
-        if (out_dt) out_dt[fo + p] = dist;
-        if (out_depth) out_depth[fo + p] = gather_depth(x + fo, vlist + fo, label, q, nval, misaligned, frame_status + b);
+        if (f.out_index) f.out_index[f.fo + p] = label;
+        if (f.out_dt) f.out_dt[f.fo + p] = dist;
+        if (f.out_depth) {
+            const DepthIndex di = depth_index(label, f.nval);
+            f.raise(!di.ok);
+            f.out_depth[f.fo + p] = f.depth(f.at(di, q), di.ok);
+        }
     }
 }
 
@@ -214,8 +247,8 @@ __global__ __launch_bounds__(256) void k_l2win(const float *__restrict__ x, cons
     float *s_sqrt = reinterpret_cast<float *>(lds + C::OFF_SQRT);
     const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
     const int y0 = ty * W2_TH, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const size_t fo = (size_t)b * H * W;
-    const int nval = finfo[b * FI_STRIDE + FI_NVAL], misaligned = finfo[b * FI_STRIDE + FI_MISALIGNED];
+    const L2Frame f = l2_frame(x, vlist, finfo, b, H, W, out_depth, out_dt, out_index, frame_status);
+    const size_t fo = f.fo;
     for (int t = tid; t < NR * 6; t += 256) {
         const int yy = t / 6, c = t - yy * 6;
         const int y = y0 - R + yy, wd = tx * 4 - 1 + c;
@@ -262,7 +295,6 @@ __global__ __launch_bounds__(256) void k_l2win(const float *__restrict__ x, cons
     __syncthreads();
     const int j = tx * W2_TW + tid;
     const bool inw = j < W;
-    const float *gsrc = misaligned ? vlist + fo : x + fo;
     bool index_error = false;
     // phase 2, four rows per step, software-pipelined: the depth gathers of step g are in flight while step g + 1 is
     // computed; a step's stores follow one step later.  key = (hx^2 + dy^2) << DB | (dy + R)
@@ -318,12 +350,12 @@ __global__ __launch_bounds__(256) void k_l2win(const float *__restrict__ x, cons
             const int sc = ((s_side[yy * 4 + wv] >> lane) & 1ull) ? j + dx : j - dx;
             const int c = min(max((sc >> 6) - (tx * 4 - 1), 0), 5);
             S.label[u] = source_rank(s_base[yy * 6 + c], s_w[yy * 6 + c], sc);
-            const DepthIndex di = depth_index_pos(S.label[u], nval);  // a source's rank: the label is >= 1
+            const DepthIndex di = depth_index_pos(S.label[u], f.nval);  // a source's rank: the label is >= 1
             S.gok[u] = di.ok;
-            goff[u] = misaligned ? di.idx : (i + dy) * W + sc;
+            goff[u] = f.at(di, (i + dy) * W + sc);
         }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) S.dep[u] = (out_depth && S.live[u] && S.gok[u]) ? gsrc[goff[u]] : nanf("");
+        for (int u = 0; u < 4; ++u) S.dep[u] = f.depth(goff[u], out_depth && S.live[u] && S.gok[u]);
     };
     auto store = [&](int t0, const Step &S) {
 #pragma unroll
@@ -346,20 +378,16 @@ __global__ __launch_bounds__(256) void k_l2win(const float *__restrict__ x, cons
         prev = cur;
     }
     store(W2_TH - 4, prev);
-    if (out_depth && index_error) atomicOr(frame_status + b, DTFILL_FRAME_INDEX_ERROR);
+    f.raise(index_error);
 }
 
 // ------------------------------------------------------------------------------------------------
 // The far pixels k_l2win put on the frame's list, one wave per pixel (l2far_pixel); run by k_l2far.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void l2far_list(const float *__restrict__ x, const u64 *__restrict__ srcbits,
-                                           const u16 *__restrict__ wpre_s, const u32 *__restrict__ rowbase_s,
-                                           const int *__restrict__ finfo, const float *__restrict__ vlist,
-                                           const u32 *__restrict__ xlist, const u32 *__restrict__ rowfar, int b, int blk, int nblk,
-                                           int H, int W, int Wd, float *__restrict__ out_depth, float *__restrict__ out_dt,
-                                           int32_t *__restrict__ out_index, int *__restrict__ frame_status) {
-    const int n = finfo[b * FI_STRIDE + FI_NUNRES];
-    const int nval = finfo[b * FI_STRIDE + FI_NVAL], misaligned = finfo[b * FI_STRIDE + FI_MISALIGNED];
+__device__ __forceinline__ void l2far_list(const L2Frame &f, const u64 *__restrict__ srcbits, const u16 *__restrict__ wpre_s,
+                                           const u32 *__restrict__ rowbase_s, int n /* FI_NUNRES */, const u32 *__restrict__ xlist,
+                                           const u32 *__restrict__ rowfar, int blk, int nblk, int Wd) {
+    const int b = f.b, H = f.H, W = f.W;
     const int lane = threadIdx.x & 63;
     const u32 t = w2_row_t(W);
     // the list is dealt out to the waves entry by entry (neighbours on the list are neighbours in the frame and cost alike); a
@@ -376,8 +404,7 @@ __device__ __forceinline__ void l2far_list(const float *__restrict__ x, const u6
             const int l1 = keep ? __ffsll((long long)keep) - 1 : l0;
             keep &= keep - 1;  // (0 stays 0)
             const int pp = __shfl(p, lane < 32 ? l0 : l1), i = pp / W;
-            l2far_pixel(x, srcbits, wpre_s, rowbase_s, vlist, b, H, W, Wd, i, pp - i * W, nval, misaligned, out_depth, out_dt, out_index,
-                        frame_status);
+            l2far_pixel(f, srcbits, wpre_s, rowbase_s, Wd, i, pp - i * W);
         }
     }
 }
@@ -415,70 +442,50 @@ __device__ __forceinline__ void l2env_merge(L2Cand &best, int off) {
 }
 
 __host__ __device__ constexpr size_t l2env_lds(int W) { return ((size_t)W * 10 + 15) & ~(size_t)15; }  // LDS of one row's search
-// NW waves per image row.  k_l2env uses NW = 1: the per-level bookkeeping is per wave, so one wave per row costs the fewest
-// instructions (a 256-thread block per row measured 1.8 x the time on whole sparse frames); NW = 4 shortens a single row's
-// chain and pays when only a few rows are searched.
-template <int NW>
-__device__ __forceinline__ void l2env_sync() {
-    if (NW == 1)
-        __builtin_amdgcn_wave_barrier();  // one wave: its LDS operations complete in order
-    else
-        __syncthreads();
+// Column k of image row i as the row searches take it: the column word of k_colT (col_dist, dtfill_rows.hpp) -> whether the
+// column holds a source at all, its vertical distance g, and the candidate {g^2, source row << 16 | k}.
+struct L2Col {
+    bool has;
+    u32 g;
+    uint2 cv;
+};
+__device__ __forceinline__ L2Col l2_column(const uint2 w, int i, int k) {
+    const ColDist cd = col_dist(w.x, w.y, i & 31);
+    const u32 m = min(cd.gu, cd.gd);  // on a vertical tie the upper source (the smaller raster index)
+    return L2Col{m < (u32)MAX_HW_SUM, m, make_uint2(m * m, (u32)(cd.gd < cd.gu ? i + (int)m : i - (int)m) << 16 | (u32)k)};
 }
-template <int NW>
+// One wave per image row: the per-level bookkeeping is per wave, so a row that is one wave's costs the fewest instructions.
 __device__ __forceinline__ void l2env_row(const float *__restrict__ x, const uint2 *__restrict__ ct, int CTP, int nb,
                                           const uint4 *__restrict__ rec, int Wd, const int *__restrict__ finfo,
                                           const float *__restrict__ vlist, int H, int W, int b, int i,
                                           float *__restrict__ out_depth, float *__restrict__ out_dt,
                                           int32_t *__restrict__ out_index, int *__restrict__ frame_status,
-                                          unsigned char *s_env, u32 *s_wcnt) {
-    constexpr int NT = 64 * NW;
+                                          unsigned char *s_env) {
     uint2 *s_c = reinterpret_cast<uint2 *>(s_env);               // [W] the columns with a source, in column order: {g^2, row << 16 | column}
     u16 *s_own = reinterpret_cast<u16 *>(s_env + (size_t)W * 8);  // [W] owner of every solved pixel (index into s_c)
-    const int tid = NW == 1 ? (int)(threadIdx.x & 63) : (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int lane = threadIdx.x & 63;
     const size_t fo = (size_t)b * H * W;
-    int c = 0;  // uniform over the row's waves
+    int c = 0;  // wave-uniform
     {
-        const int band = i >> 5, r = i & 31;
-        const uint2 *crow = ct + ((size_t)b * nb + band) * CTP;
-        const u32 upmask = (2u << r) - 1u;
-        for (int k0 = 0; k0 < W; k0 += NT) {
-            const int k = k0 + tid;
-            bool has = false;
-            uint2 cv = make_uint2(0u, 0u);
-            if (k < W) {
-                const uint2 w = crow[k];
-                const u32 gu = min(ffbh_u32(w.x & upmask) + (u32)(r - 31), (w.y & 0xFFFFu) + (u32)r);
-                const u32 gd = min(ffbl_b32(w.x >> r), (w.y >> 16) + (u32)(31 - r));
-                const u32 m = min(gu, gd);  // on a vertical tie the upper source (the smaller raster index)
-                has = m < (u32)MAX_HW_SUM;
-                cv = make_uint2(m * m, (u32)(gd < gu ? i + (int)m : i - (int)m) << 16 | (u32)k);
-            }
-            const u64 bal = __ballot(has);
-            int off = c, tot = __popcll(bal);
-            if (NW > 1) {
-                if (lane == 0) s_wcnt[wv] = (u32)tot;
-                l2env_sync<NW>();
-                tot = 0;
-                for (int w = 0; w < NW; ++w) {
-                    if (w < wv) off += (int)s_wcnt[w];
-                    tot += (int)s_wcnt[w];
-                }
-            }
-            if (has) s_c[off + (int)__builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0u))] = cv;
-            c += tot;
-            if (NW > 1) l2env_sync<NW>();
+        const uint2 *crow = ct + ((size_t)b * nb + (i >> 5)) * CTP;
+        for (int k0 = 0; k0 < W; k0 += 64) {
+            const int k = k0 + lane;
+            L2Col col = {false, 0u, make_uint2(0u, 0u)};
+            if (k < W) col = l2_column(crow[k], i, k);
+            const u64 bal = __ballot(col.has);
+            if (col.has) s_c[c + (int)__builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0u))] = col.cv;
+            c += __popcll(bal);
         }
     }
-    l2env_sync<NW>();
+    __builtin_amdgcn_wave_barrier();
     if (c > 0) {
         // a level: nq queries j = (2m + 1) s, each between the owners of its solved neighbours; G lanes per query
         auto level = [&](int nq, int s, bool ends) {
             int lg = 6;  // log2 G: G = threads / (nq rounded up to a power of two), at most a wave, at least one lane per query
-            while (lg > 0 && (nq << lg) > NT) --lg;
-            const int G = 1 << lg, per = NT >> lg, gl = lane & (G - 1);
+            while (lg > 0 && (nq << lg) > 64) --lg;
+            const int G = 1 << lg, per = 64 >> lg, gl = lane & (G - 1);
             for (int m0 = 0; m0 < nq; m0 += per) {
-                const int m = m0 + (tid >> lg);
+                const int m = m0 + (lane >> lg);
                 const bool act = m < nq;
                 const int j = ends ? (m ? W - 1 : 0) : (2 * m + 1) * s;
                 L2Cand best = {0xFFFFFFFFu, 0xFFFFFFFFu};
@@ -497,7 +504,7 @@ __device__ __forceinline__ void l2env_row(const float *__restrict__ x, const uin
                 for (int o = G >> 1; o; o >>= 1) l2env_merge(best, o);
                 if (act && gl == 0) s_own[j] = (u16)(best.lo & 0xFFFFu);
             }
-            l2env_sync<NW>();
+            __builtin_amdgcn_wave_barrier();
         };
         level(W > 1 ? 2 : 1, 0, true);  // pixels 0 and W-1 over every column
         int s = 1;
@@ -510,14 +517,14 @@ __device__ __forceinline__ void l2env_row(const float *__restrict__ x, const uin
     const int nval = finfo[b * FI_STRIDE + FI_NVAL], misaligned = finfo[b * FI_STRIDE + FI_MISALIGNED];
     const float *gsrc = misaligned ? vlist + fo : x + fo;
     bool index_error = false;
-    for (int j0 = 0; j0 < W; j0 += 4 * NT) {  // four pixels per lane and step: their gathers are in flight together
+    for (int j0 = 0; j0 < W; j0 += 256) {  // four pixels per lane and step: their gathers are in flight together
         int q[4], label[4], sr[4], sc[4];
         float dist[4], dep[4];
         bool in[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             sr[u] = sc[u] = 0;
-            const int j = j0 + NT * u + tid;
+            const int j = j0 + 64 * u + lane;
             in[u] = j < W;
             q[u] = i * W + min(j, W - 1);
             dist[u] = INFINITY;
@@ -545,7 +552,7 @@ __device__ __forceinline__ void l2env_row(const float *__restrict__ x, const uin
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const size_t o = fo + (size_t)i * W + j0 + NT * u + tid;
+            const size_t o = fo + (size_t)i * W + j0 + 64 * u + lane;
             if (in[u]) {  // whole 256-byte runs per store instruction, never read again in this pass: streaming stores
                 if (out_index) __builtin_nontemporal_store((int32_t)label[u], &out_index[o]);
                 if (out_dt) __builtin_nontemporal_store(dist[u], &out_dt[o]);
@@ -578,18 +585,12 @@ __device__ __forceinline__ void l2sky_row(const float *__restrict__ x, const uin
     const size_t fo = (size_t)b * H * W;
     u32 gmin = 0xFFFFFFFFu;
     {
-        const int band = i >> 5, r = i & 31;
-        const uint2 *crow = ct + ((size_t)b * nb + band) * CTP;
-        const u32 upmask = (2u << r) - 1u;
+        const uint2 *crow = ct + ((size_t)b * nb + (i >> 5)) * CTP;
         if (lane < 2 * L2S_R) s_col[lane < L2S_R ? lane - L2S_R : W + lane - L2S_R] = make_uint2(0x7FFFFFFFu, 0xFFFFFFFFu);
         for (int k = lane; k < W; k += 64) {
-            const uint2 w = crow[k];
-            const u32 gu = min(ffbh_u32(w.x & upmask) + (u32)(r - 31), (w.y & 0xFFFFu) + (u32)r);
-            const u32 gd = min(ffbl_b32(w.x >> r), (w.y >> 16) + (u32)(31 - r));
-            const u32 m = min(gu, gd);  // on a vertical tie the upper source (the smaller raster index)
-            const bool has = m < (u32)MAX_HW_SUM;
-            s_col[k] = make_uint2(has ? m * m : 0x7FFFFFFFu, (u32)(gd < gu ? i + (int)m : i - (int)m) << 16 | (u32)k);
-            gmin = min(gmin, has ? m : 0xFFFFFFFFu);
+            const L2Col col = l2_column(crow[k], i, k);
+            s_col[k] = make_uint2(col.has ? col.cv.x : 0x7FFFFFFFu, col.cv.y);
+            gmin = min(gmin, col.has ? col.g : 0xFFFFFFFFu);
         }
 #pragma unroll
         for (int o = 32; o; o >>= 1) gmin = min(gmin, (u32)__shfl_xor((int)gmin, o));
@@ -682,8 +683,8 @@ __device__ __forceinline__ void l2sky_row(const float *__restrict__ x, const uin
 __global__ __launch_bounds__(256) void k_l2far(const Pass p) {
     const int b = blockIdx.y;
     if (p.route[b] != 0)
-        l2far_list(p.x, p.srcbits, p.wpre_s, p.rowbase_s, p.finfo, p.vlist, p.xlist, p.rowfar, b, (int)blockIdx.x, (int)gridDim.x, p.H, p.W,
-                   p.Wd, p.out_depth, p.out_dt, p.out_index, p.status);
+        l2far_list(l2_frame(p.x, p.vlist, p.finfo, b, p.H, p.W, p.out_depth, p.out_dt, p.out_index, p.status), p.srcbits, p.wpre_s,
+                   p.rowbase_s, p.finfo[b * FI_STRIDE + FI_NUNRES], p.xlist, p.rowfar, (int)blockIdx.x, (int)gridDim.x, p.Wd);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -784,9 +785,9 @@ __device__ __forceinline__ void l2pts_tile(const float *__restrict__ x, const u3
 // ------------------------------------------------------------------------------------------------
 // k_l2env: what the window kernels left, one WAVE per unit of work (the waves of a block share nothing but the launch).
 // Blocks [0, nrowblk): rows -- every row of a route-0 frame, and the rows of a window-kernel frame in which k_l2win counted
-// too many far pixels (l2env_row: one wave per row costs the fewest instructions -- the per-level bookkeeping is per wave --
-// and leaves the most rows in flight per CU).  The blocks behind them: the 32 x 32 tiles of the frames with a handful of
-// sources (l2pts_tile).
+// too many far pixels (l2env_row, l2sky_row: a wave per row leaves the most rows in flight per CU).  The blocks behind them:
+// the 32 x 32 tiles of the frames with a handful of sources (l2pts_tile).  The three bodies keep positional parameters and
+// their own reads of the frame's depth list: k_l2env has no register to spare for a frame context.
 // ------------------------------------------------------------------------------------------------
 template <int WPB>  // waves per block, each on a unit of its own: 4 while four rows' LDS fit 64 KB (W <= 1638), else 1
 __global__ __launch_bounds__(64 * WPB, 5) void k_l2env(const float *__restrict__ x, const uint2 *__restrict__ ct, int CTP, int nb,
@@ -815,7 +816,7 @@ __global__ __launch_bounds__(64 * WPB, 5) void k_l2env(const float *__restrict__
     const int i = blk * WPB + wv;
     if (i >= H) return;
     if (r == 0)  // a sparse frame: few columns hold a source, the distances are large -- the envelope search
-        l2env_row<1>(x, ct, CTP, nb, rec, Wd, finfo, vlist, H, W, b, i, out_depth, out_dt, out_index, frame_status, lds, nullptr);
+        l2env_row(x, ct, CTP, nb, rec, Wd, finfo, vlist, H, W, b, i, out_depth, out_dt, out_index, frame_status, lds);
     else if (r > 0 && rowfar[(size_t)b * H + i] >= w2_row_t(W))  // a row of far pixels of a dense frame (the sky): the window in column distances
         l2sky_row(x, ct, CTP, nb, rec, Wd, finfo, vlist, H, W, b, i, out_depth, out_dt, out_index, frame_status, lds);
 }

@@ -596,16 +596,3 @@ __global__ __launch_bounds__(256) void k_frame(const Pass p, int mode, int nty16
 __device__ __forceinline__ int source_rank(u32 base, u64 word, int j) {
     return (int)base + __popcll(word & ((1ull << (j & 63)) - 1ull)) + 1;
 }
-
-// gather depth_list[label - 1] (depth_index: dtfill_index.hpp)
-__device__ __forceinline__ float gather_depth(const float *__restrict__ xf, const float *__restrict__ vlf,
-                                              int label, int src_pixel, int nval, int misaligned,
-                                              int *frame_status_b) {
-    const DepthIndex di = depth_index(label, nval);
-    if (!di.ok) {
-        atomicOr(frame_status_b, DTFILL_FRAME_INDEX_ERROR);
-        return nanf("");
-    }
-    if (misaligned) return vlf[di.idx];
-    return xf[src_pixel];  // masks agree: the label-th value IS the source pixel's own depth
-}

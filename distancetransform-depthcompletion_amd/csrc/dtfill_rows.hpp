@@ -1,7 +1,8 @@
 // dtfill_rows.hpp -- k_colT, k_rows, k_fin, k_tiesx: the any-distance path of the l1_cv pass (argmin scans)
 // Part of libdtfill.so; included by dtfill.hip inside its anonymous namespace (one translation unit).
 // Stated once here for fin_body and pts_body (dtfill_pts.hpp): tie_word_rule (the sixteen taps of the parent rule in cv2's order for
-// one 32-pixel word), tile_is_tie, hand_on_append (open chains join the frame's list for k_tiesx).
+// one 32-pixel word), tile_is_tie, hand_on_append (open chains join the frame's list for k_tiesx); for rows_body and the l2 row
+// searches (dtfill_l2.hpp): col_dist, the one reader of the column words k_colT writes.
 #pragma once
 
 // ================================================================================================
@@ -175,6 +176,18 @@ __device__ __forceinline__ u32 ffbl_b32(u32 v) {  // position of the lowest set 
     asm("v_ffbl_b32 %0, %1" : "=v"(r) : "v"(v));
     return r;
 }
+// The column word k_colT writes -- {bits: the band's source bits of the column, ud: distance above | distance below << 16} -- read
+// for row r of the band (0..31): the distance from that row to the column's nearest source at or above it (gu) and at or below
+// it (gd).  Branch-free: v_ffbh / v_ffbl give 0xFFFFFFFF for "no bit", which loses the unsigned min against the carried distance;
+// a side without a source comes out >= GBIG.  The one reader of the format: rows_body and l2_column (dtfill_l2.hpp) go by it.
+struct ColDist {
+    u32 gu, gd;
+};
+__device__ __forceinline__ ColDist col_dist(u32 bits, u32 ud, int r) {
+    const u32 upmask = (2u << r) - 1u;  // band rows 0..r (r = 31: all)
+    return ColDist{min(ffbh_u32(bits & upmask) + (u32)(r - 31), (ud & 0xFFFFu) + (u32)r),
+                   min(ffbl_b32(bits >> r), (ud >> 16) + (u32)(31 - r))};
+}
 // uniform base + 32-bit BYTE offset: the form that needs no 64-bit vector address arithmetic
 template <typename T>
 __device__ __forceinline__ T ld_off(const void *base, u32 byte_off) {
@@ -303,17 +316,14 @@ __device__ __forceinline__ void rows_body(
     const u32 fo = (u32)b * (u32)(H * W);  // < 2^31 (shape_ok)
     __syncthreads();  // s_bits is zero
     // six keys per column: {all sources, prefer the smallest column | all, prefer the largest | sources at or above
-    // this row} x {left scan (value - column), right scan (value + column)}.  Branch-free: v_ffbh / v_ffbl give
-    // 0xFFFFFFFF for "no bit", which loses the unsigned min against the carried distance.
+    // this row} x {left scan (value - column), right scan (value + column)}.
     u32 Lmin[PPL], Lmax[PPL], LU[PPL], Rmin[PPL], Rmax[PPL], RU[PPL];
     {
-        const u32 upmask = (2u << r) - 1u;  // band rows 0..r (r = 31: all)
         const u32 kbase = (u32)(K_OFF - idx0);
 #pragma unroll
         for (int q = 0; q < PPL; ++q) {
-            const u32 gu = min(ffbh_u32(T[q] & upmask) + (u32)(r - 31), (UD[q] & 0xFFFFu) + (u32)r);
-            const u32 gd = min(ffbl_b32(T[q] >> r), (UD[q] >> 16) + (u32)(31 - r));
-            const u32 g = min(gu, gd);
+            const ColDist cd = col_dist(T[q], UD[q], r);
+            const u32 gu = cd.gu, gd = cd.gd, g = min(gu, gd);
             // flags of the column: bit 0 = its nearest source is below this row, bit 1 = above and below tie
             // (gu == gd != 0; two "no source" distances r + GBIG and 31 - r + GBIG are never equal)
             const u32 t = gd - gu;
