@@ -58,6 +58,8 @@ SYMBOLS = (
     "dtfill_train_loss_workspace_bytes",
     "dtfill_train_loss",
     "dtfill_train_loss_backward",
+    "dtfill_fill_backward_workspace_bytes",
+    "dtfill_fill_backward",
 )
 STATS = ("all", "window", "anydist", "sky", "points", "colt")  # DTFILL_STATS_*
 METRICS_KITTI = 0
@@ -154,6 +156,10 @@ def load():
     L.dtfill_train_loss.restype = ci
     L.dtfill_train_loss_backward.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
     L.dtfill_train_loss_backward.restype = ci
+    L.dtfill_fill_backward_workspace_bytes.argtypes = [ci, ci, ci]
+    L.dtfill_fill_backward_workspace_bytes.restype = sz
+    L.dtfill_fill_backward.argtypes = [vp, vp, vp, ci, ci, ci, cf, vp, vp, vp, sz, vp]
+    L.dtfill_fill_backward.restype = ci
     _lib = L
     return L
 

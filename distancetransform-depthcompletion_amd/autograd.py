@@ -1,5 +1,6 @@
 """The reference's in-graph pieces around the network as differentiable torch operators: generate_multi_channel() of its models
-(solution_DeepNet/net.py:83-122) and the objective of its training step (solution_DeepNet/train.py:210-251, train_loss below).
+(solution_DeepNet/net.py:83-122), the objective of its training step (solution_DeepNet/train.py:210-251, train_loss below), and
+the exact fill itself (tools.py:13-35, fill below), which the reference could only run in numpy outside the graph.
 
 In the reference the windowed fill sits inside the trained graph: with if_correct its input is the output of four learned
 convolutions (net.py:469-486), its outputs feed the encoder (net.py:489), and the gradient is cut only when joint_train is
@@ -88,3 +89,44 @@ def train_loss(pred, gt, lidar=None, correction=None, dataset="KITTI", gt_thr=No
     lidar = None if lidar is None else lidar.detach()
     out = _TrainLoss.apply(pred, correction, gt.detach(), lidar, cfg)
     return (out[0], out[1]) if correction is not None else (out[0], None)
+
+
+class _Fill(torch.autograd.Function):
+    """(depth, dt, index, status) of DtFill.run in tensors of the call's own; depth alone carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, x, src_thr, val_thr, metric):
+        with torch.cuda.device(x.device):
+            op = device.default_op(metric)
+        B = x.shape[0] if x.dim() == 3 else 0  # (run raises for anything but [B,H,W])
+        # the operator's own buffers are overwritten by its next call: these are not
+        out = dict(depth=torch.empty_like(x), dt=torch.empty_like(x), index=torch.empty_like(x, dtype=torch.int32),
+                   status=torch.empty((B,), dtype=torch.int32, device=x.device))
+        op.run(x, src_thr, val_thr, out=out)
+        ctx.set_materialize_grads(False)  # an unused depth arrives as None: nothing is launched for it
+        ctx.val_thr = val_thr
+        ctx.save_for_backward(x, out["index"])
+        ctx.mark_non_differentiable(out["dt"], out["index"], out["status"])
+        return out["depth"], out["dt"], out["index"], out["status"]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_depth, g_dt=None, g_index=None, g_status=None):
+        if g_depth is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        x, index = ctx.saved_tensors
+        grad_x, _ = device.fill_backward_device(x, index, g_depth.to(torch.float32).contiguous(), ctx.val_thr)
+        return grad_x, None, None, None
+
+
+def fill(x, src_thr=0.1, val_thr=0.1, metric="l1_cv"):
+    """The exact fill depth = depth_list[lbl - 1] (tools.py:13-35, eval_NYU.py:120-133) as a differentiable operator, for the place
+    where net.py:155 has the windowed generate_multi_channel behind the learned correction of net.py:136-153.  x: contiguous
+    float32 CUDA tensor [B,H,W].  Returns (depth, dt, index, status) as DtFill.run gives them, in tensors of their own.
+    Differentiable in x through depth only, once; dt, index and status are marked non-differentiable.  The predicates and the
+    labels are constants of the differentiation: the backward (include/dtfill.h, dtfill_fill_backward) sends the gradient of
+    every pixel that read depth_list[k] to the k-th valued pixel, bitwise reproducibly; a frame whose status carries
+    _lib.FRAME_INDEX_ERROR gets a zero gradient.  With depth unused nothing is launched in the backward; no host
+    synchronisation in either direction.  The depth epilogue (row crop, floor) and outlier_removal stay out: they compose as
+    torch ops, or as this package's device functions on a detached input, on either side."""
+    return _Fill.apply(x, float(src_thr), float(val_thr), metric)

@@ -88,6 +88,7 @@ namespace {
 #include "dtfill_loss.hpp"
 #include "dtfill_lines.hpp"
 #include "dtfill_read.hpp"
+#include "dtfill_fillb.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -836,6 +837,57 @@ int dtfill_metrics(const float *output, const float *target, int B, long long n,
         k_metrics_part<1><<<dim3(M_NB, B), 256, 0, st>>>(output, target, n, part);
         k_metrics_final<1><<<B, 64, 0, st>>>(part, M_NB, out);
     }
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+// The workspace of dtfill_fill_backward, 256-byte aligned pieces; with ws = nullptr only the total is worked out.
+static FbWs fb_carve(void *ws, int B, int H, int W, size_t *total) {
+    const size_t N = (size_t)B * H * W, Wd = (size_t)(W + 63) / 64, NR = (size_t)B * H;
+    char *base = static_cast<char *>(ws);
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        char *r = base ? base + off : nullptr;
+        off += align256(bytes);
+        return r;
+    };
+    FbWs c{};
+    c.Wd = (int)Wd;
+    c.tsum = (long long *)take(N * 8);
+    c.ebias = (u32 *)take(N * 4);
+    c.flags = (u32 *)take(N * 4);
+    c.valbits = (u64 *)take(NR * Wd * 8);
+    c.rowcnt = (u32 *)take(NR * 4);
+    c.rowbase = (u32 *)take(NR * 4);
+    c.nval = (u32 *)take((size_t)B * 4);
+    c.err = (u32 *)take((size_t)B * 4);
+    if (total) *total = off;
+    return c;
+}
+
+size_t dtfill_fill_backward_workspace_bytes(int B, int H, int W) {
+    if (!shape_ok(B, H, W)) return 0;
+    size_t total = 0;
+    fb_carve(nullptr, B, H, W, &total);
+    return total;
+}
+
+int dtfill_fill_backward(const float *x, const int32_t *index, const float *grad_depth, int B, int H, int W, float val_thr,
+                         float *grad_x, int32_t *frame_status, void *workspace, size_t ws_bytes, void *stream) {
+    if (!x || !index || !grad_depth || !grad_x || !workspace) return DTFILL_ERR_NULL;
+    if (!shape_ok(B, H, W)) return DTFILL_ERR_SHAPE;
+    if (ws_bytes < dtfill_fill_backward_workspace_bytes(B, H, W) || ((uintptr_t)workspace & 255)) return DTFILL_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const FbWs ws = fb_carve(workspace, B, H, W, nullptr);
+    const size_t HW = (size_t)H * W;
+    const dim3 rows((H + 3) / 4, B);
+    k_fb_count<<<rows, 256, 0, st>>>(x, H, W, val_thr, ws);
+    // blocks that share a frame's clearing: one per 4096 pixels, at most 64
+    k_fb_scan<<<dim3((unsigned)min((HW + 4095) / 4096, (size_t)64), B), 256, 0, st>>>(H, HW, ws);
+    const int sx = (W + 63) / 64, nstrips = sx * ((H + FB_TH - 1) / FB_TH);
+    const dim3 strips((nstrips + 3) / 4, B);
+    k_fb_acc<0><<<strips, 256, 0, st>>>(index, grad_depth, H, W, sx, nstrips, ws);
+    k_fb_acc<1><<<strips, 256, 0, st>>>(index, grad_depth, H, W, sx, nstrips, ws);
+    k_fb_out<<<rows, 256, 0, st>>>(H, W, ws, grad_x, frame_status);
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 

@@ -65,7 +65,7 @@ class DtFill:
 
     # -- the op --------------------------------------------------------------------------------
     def run(self, x, src_thr=0.1, val_thr=0.1, want=WANT_ALL, timed=False, path="auto", depth_rows_from=0, depth_floor=None,
-            outlier_removal=False, separate_frame=False):
+            outlier_removal=False, separate_frame=False, out=None):
         """x: float32 CUDA tensor [B,H,W] (contiguous).  Returns a dict of device tensors
         (views of buffers owned by this object, overwritten by the next call) for the names in
         `want`, plus "status" (int32 [B], bit set of _lib.FRAME_*).  Asynchronous on the current
@@ -75,7 +75,9 @@ class DtFill:
         relu(d - 0.9) + 0.9): "depth" is then [B, H - depth_rows_from, W]; l1_cv only.  outlier_removal: the loader's filter
         (data_read.py:103-128, 168-169) in front of the predicates -- the pass equals run(outlier_removal_device(x)) without
         the filtered map being written.  separate_frame: l1_cv, the frame facts in a k_frame launch of their own instead of inside
-        the window kernel's launch (_lib.FLAG_SEPARATE_FRAME: tests and A/B timing; the results are the same)."""
+        the window kernel's launch (_lib.FLAG_SEPARATE_FRAME: tests and A/B timing; the results are the same).  out: a dict of the
+        caller's own tensors, name -> contiguous tensor of that output's shape and dtype on this device ("depth", "dt", "index",
+        "status"), written in place of this object's buffers and returned: tensors no later call overwrites."""
         if x.dtype != torch.float32 or not x.is_cuda or x.dim() != 3 or not x.is_contiguous():
             raise ValueError("x must be a contiguous float32 CUDA tensor [B,H,W]")
         B, H, W = x.shape
@@ -85,12 +87,22 @@ class DtFill:
             self._ensure(B, H, W)
             o = self._out
             epi = depth_rows_from != 0 or depth_floor is not None
+            if out is not None:
+                for name, t in out.items():
+                    if name not in o:
+                        raise ValueError("out: no output named %r" % (name,))
+                    shape = (B, H - depth_rows_from, W) if name == "depth" else tuple(o[name].shape)
+                    if t.dtype != o[name].dtype or t.device != self.device or tuple(t.shape) != shape or not t.is_contiguous():
+                        raise ValueError("out[%r] must be a contiguous %s tensor of shape %s on %s" % (name, o[name].dtype, shape, self.device))
             if epi:
                 if timed or not (0 <= depth_rows_from < H):
                     raise ValueError("depth epilogue: 0 <= depth_rows_from < H, and not with timed=True")
                 if getattr(self, "_crop", None) is None or self._crop.shape != (B, H - depth_rows_from, W):
                     self._crop = torch.empty((B, H - depth_rows_from, W), dtype=torch.float32, device=self.device)
-                o = dict(o, depth=self._crop)
+                if out is None or "depth" not in out:
+                    o = dict(o, depth=self._crop)
+            if out is not None:
+                o = dict(o, **out)
             ptr = lambda name: o[name].data_ptr() if name in want else None
             stream = torch.cuda.current_stream(self.device).cuda_stream
             args = [
@@ -511,6 +523,38 @@ def train_loss_backward_device(pred, gt, stats, g_main=None, g_aux=None, lidar=N
         _lib.check(_lib.load().dtfill_train_loss_backward(*args, stats.data_ptr(), ptr(g_main), ptr(g_aux), ptr(grad_pred),
                                                           ptr(grad_corr), torch.cuda.current_stream(pred.device).cuda_stream))
     return grad_pred, grad_corr
+
+
+_fillb_ws = {}  # (device index, stream) -> the fill backward's accumulators, shared like _gmcb_ws
+
+
+def fill_backward_device(x, index, grad_depth, val_thr=0.1):
+    """The backward of the exact fill depth = depth_list[index - 1] (include/dtfill.h, dtfill_fill_backward): the gradient with
+    respect to x.  x: the forward's input; index: its "index" output (either metric); grad_depth: the gradient of its "depth"
+    output.  x, grad_depth: contiguous float32 CUDA tensors [B,H,W]; index: contiguous int32, same shape and device.  Returns
+    (grad_x, status): new tensors, status int32 [B] with _lib.FRAME_INDEX_ERROR for a frame whose gather would have raised (its
+    gradient is all zeros).  Asynchronous on the current stream, no host synchronisation."""
+    _require_gpu()
+    _check_frames(x, "x")
+    _check_frames(grad_depth, "grad_depth")
+    if index.dtype != torch.int32 or not index.is_cuda or index.dim() != 3 or not index.is_contiguous():
+        raise ValueError("index must be a contiguous int32 CUDA tensor [B,H,W]")
+    for what, t in (("index", index), ("grad_depth", grad_depth)):
+        if t.shape != x.shape or t.device != x.device:
+            raise ValueError("%s must have x's shape and device" % what)
+    B, H, W = x.shape
+    L = _lib.load()
+    nbytes = L.dtfill_fill_backward_workspace_bytes(B, H, W)
+    if nbytes == 0:
+        _lib.check(-2)
+    grad_x = torch.empty_like(x)
+    status = torch.empty((B,), dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        ws = _gmcb_workspace(x.device, nbytes, _fillb_ws)
+        _lib.check(L.dtfill_fill_backward(x.data_ptr(), index.data_ptr(), grad_depth.data_ptr(), B, H, W, float(val_thr),
+                                          grad_x.data_ptr(), status.data_ptr(), ws, nbytes,
+                                          torch.cuda.current_stream(x.device).cuda_stream))
+    return grad_x, status
 
 
 def keep_every_of(keep_ratio):

@@ -419,6 +419,48 @@ int dtfill_train_loss_backward(const float *pred, const float *corr, const float
                                const float *g_main, const float *g_aux /* device scalars, each nullable */,
                                float *grad_pred, float *grad_corr /* each nullable, not both */, void *stream);
 
+/*
+ * The backward pass of the exact fill out_depth = depth_list[lbl - 1] (tools.py:22-26): the gradient of a loss with respect to
+ * x, given its gradient with respect to out_depth.  The reference runs this gather in numpy outside the graph; here it can sit
+ * behind a learned correction.  x and index are dtfill_batch()'s input and out_index (either metric: a label means the same
+ * thing in both).  The predicates and the labels are constants of the differentiation, so the backward is the gather transposed
+ * literally: the k-th VALUED pixel receives the gradient of every pixel that read depth_list[k] -- not the nearest source,
+ * wherever the source and the value predicate disagree.  Per frame:
+ *   the value list is the pixels with x > val_thr in raster order; n its length, v_k the pixel of its k-th entry;
+ *   idx(p) = index[p] - 1, and idx(p) += n if it is negative: numpy's wrap, so label 0 in a frame with a non-empty value list
+ *     addresses the LAST value;
+ *   if any pixel's idx falls outside [0, n) -- n == 0, or a label larger than n -- the frame is an index-error frame: grad_x is
+ *     +0.0 everywhere in it and frame_status[b] = DTFILL_FRAME_INDEX_ERROR; otherwise frame_status[b] = 0.  The call derives
+ *     this itself, it does not take the forward's status, and any 32-bit content of index is memory-safe;
+ *   otherwise grad_x[v_k] = S(C_k) for the cell C_k = {grad_depth[p] : idx(p) = k}, and +0.0 at every pixel outside the list.
+ *
+ * The cell sum S(C), defined so that it does not depend on the order of the additions:
+ *   an empty cell, or one whose terms are all +-0: +0.0;
+ *   a cell with any NaN term, or with both +inf and -inf: the quiet NaN 0x7FC00000;
+ *   otherwise a cell with any +inf: +inf; with any -inf: -inf;
+ *   otherwise E = the largest true binary exponent floor(log2 |g|) over the cell's non-zero terms (a subnormal counts by its
+ *     true exponent), q = E - 37;
+ *   every term becomes the integer t = rint(g * 2^-q), round half to even: exact for every term within 14 binades of the
+ *     largest; |t| < 2^38;
+ *   T = the sum of the t in integers (no int64 overflow: H + W - 2 < 8192 keeps a frame below 2^24.001 pixels);
+ *   S = ldexpf(f32(T), q), f32(T) the single round-to-nearest-even conversion of the integer, the scaling IEEE (exact unless
+ *     it lands in the subnormal range or overflows); T = 0 gives +0.0.
+ * So |S - exact sum| <= |C| * 2^(E-38) + 2^-24 * |exact sum| + 2^-149, and [1e8, 1, -1e8] gives 1.0 where a float32 running
+ * sum gives 0.0.  The accumulators are integers (a max, an OR, a 64-bit add, all by atomics): two calls give the same bits.
+ *
+ * x, grad_depth, grad_x: float32 [B,H,W]; index: int32 [B,H,W]; grad_x is always fully overwritten and may alias no input;
+ * frame_status: int32 [B], nullable.  workspace: at least dtfill_fill_backward_workspace_bytes(B,H,W) bytes, 256-B aligned,
+ * the caller's, no initialisation needed (the kernels clear what they accumulate into), nothing kept between calls.
+ * Asynchronous on `stream`; no allocation, no host synchronisation.
+ * Returns, all checked before any HIP call: DTFILL_ERR_NULL for a NULL x, index, grad_depth, grad_x or workspace;
+ * DTFILL_ERR_SHAPE for dtfill_batch()'s shape rule; DTFILL_ERR_WORKSPACE for a workspace that is too small or not aligned;
+ * then DTFILL_ERR_LAUNCH if a launch failed.
+ */
+size_t dtfill_fill_backward_workspace_bytes(int B, int H, int W); /* 0 on a bad shape; the forward's shape rule */
+int dtfill_fill_backward(const float *x, const int32_t *index, const float *grad_depth, int B, int H, int W,
+                         float val_thr, float *grad_x, int32_t *frame_status /* nullable */,
+                         void *workspace, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
