@@ -18,6 +18,7 @@ METRICS = {"l1_cv": METRIC_L1_CV, "l2": METRIC_L2}
 FRAME_OK = 0
 FRAME_INDEX_ERROR = 1  # bit
 FRAME_GENERAL_PATH = 2  # bit, informational
+FRAME_NO_SOURCE = 4  # bit (nearest_gather): the frame has no source pixel
 FLAG_GENERAL_ONLY = 1
 FLAG_FUSED_ONLY = 2
 FLAG_OUTLIER_REMOVAL = 4  # outlier_removal() (data_read.py:103-128) in front of the predicates
@@ -60,6 +61,10 @@ SYMBOLS = (
     "dtfill_train_loss_backward",
     "dtfill_fill_backward_workspace_bytes",
     "dtfill_fill_backward",
+    "dtfill_nearest_gather_workspace_bytes",
+    "dtfill_nearest_gather",
+    "dtfill_nearest_gather_backward_workspace_bytes",
+    "dtfill_nearest_gather_backward",
 )
 STATS = ("all", "window", "anydist", "sky", "points", "colt")  # DTFILL_STATS_*
 METRICS_KITTI = 0
@@ -160,6 +165,14 @@ def load():
     L.dtfill_fill_backward_workspace_bytes.restype = sz
     L.dtfill_fill_backward.argtypes = [vp, vp, vp, ci, ci, ci, cf, vp, vp, vp, sz, vp]
     L.dtfill_fill_backward.restype = ci
+    L.dtfill_nearest_gather_workspace_bytes.argtypes = [ci, ci, ci]
+    L.dtfill_nearest_gather_workspace_bytes.restype = sz
+    L.dtfill_nearest_gather.argtypes = [vp, vp, vp, ci, ci, ci, ci, cf, vp, vp, vp, vp, sz, vp]
+    L.dtfill_nearest_gather.restype = ci
+    L.dtfill_nearest_gather_backward_workspace_bytes.argtypes = [ci, ci, ci, ci]
+    L.dtfill_nearest_gather_backward_workspace_bytes.restype = sz
+    L.dtfill_nearest_gather_backward.argtypes = [vp, vp, vp, ci, ci, ci, ci, cf, vp, vp, vp, sz, vp]
+    L.dtfill_nearest_gather_backward.restype = ci
     _lib = L
     return L
 

@@ -130,3 +130,51 @@ def fill(x, src_thr=0.1, val_thr=0.1, metric="l1_cv"):
     synchronisation in either direction.  The depth epilogue (row crop, floor) and outlier_removal stay out: they compose as
     torch ops, or as this package's device functions on a detached input, on either side."""
     return _Fill.apply(x, float(src_thr), float(val_thr), metric)
+
+
+class _FillValues(torch.autograd.Function):
+    """(filled, dt, index, pixel, status) of DtFill.run(x) and the nearest gather of values; filled alone carries a gradient,
+    and only to values."""
+
+    @staticmethod
+    def forward(ctx, x, values, src_thr, metric):
+        with torch.cuda.device(x.device):
+            op = device.default_op(metric)
+        # the operator's own buffers are overwritten by its next call: these are not
+        out = dict(dt=torch.empty_like(x), index=torch.empty_like(x, dtype=torch.int32))
+        op.run(x, src_thr, 0.1, want=("dt", "index"), out=out)
+        filled, pixel, status = device.nearest_gather_device(x, out["index"], values, src_thr)
+        ctx.set_materialize_grads(False)  # an unused filled arrives as None: nothing is launched for it
+        ctx.src_thr = src_thr
+        ctx.save_for_backward(x, out["index"])
+        ctx.mark_non_differentiable(out["dt"], out["index"], pixel, status)
+        return filled, out["dt"], out["index"], pixel, status
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_filled, g_dt=None, g_index=None, g_pixel=None, g_status=None):
+        if g_filled is None or not ctx.needs_input_grad[1]:
+            return None, None, None, None
+        x, index = ctx.saved_tensors
+        grad_values, _ = device.nearest_gather_backward_device(x, index, g_filled.to(torch.float32).contiguous(), ctx.src_thr)
+        return None, grad_values, None, None
+
+
+def fill_values(x, values, src_thr=0.1, metric="l1_cv"):
+    """The exact fill with the sources decided by one tensor and the payload read from another: every pixel of `filled` holds
+    `values` at the pixel's nearest source of x (include/dtfill.h, dtfill_nearest_gather).  This is the exact fill for the place
+    where net.py:131-155 has the windowed one: there the mask comes from the raw LiDAR, valued_mask = input_lidar > 0.1, and the
+    values from the learned correction lidar_correct, so the recipe is
+        filled, dt, index, pixel, status = fill_values(input_lidar, lidar_correct)
+    A pixel of x is a source iff NOT((1.0f - x) > src_thr) in float32 (DtFill's source predicate: with src_thr = 0.1 that is
+    x above about 0.9, or NaN, where the reference's mask is x > 0.1; the two agree on LiDAR in metres, whose returns lie beyond 1 m).
+    x: contiguous float32 CUDA tensor [B,H,W], a constant; values: [B,C,H,W] with 1 <= C <= 64, or [B,H,W] as C = 1 (filled
+    then comes back [B,H,W]).  Returns (filled, dt, index, pixel, status): dt and index as DtFill.run(x) gives them, pixel int32
+    [B,H,W] the flat pixel row*W + col of the nearest source (-1 in a frame without one, where filled is +0.0), status the
+    gather's (_lib.FRAME_NO_SOURCE, _lib.FRAME_INDEX_ERROR), all in tensors of the call's own.  Differentiable in values through
+    filled only, once; dt, index, pixel and status are marked non-differentiable.  The backward (dtfill_nearest_gather_backward)
+    sends the gradient of every pixel to the source it read, bitwise reproducibly; with filled unused nothing is launched.  No
+    host synchronisation in either direction."""
+    squeeze = values.dim() == 3
+    out = _FillValues.apply(x.detach(), values.unsqueeze(1) if squeeze else values, float(src_thr), metric)
+    return (out[0].squeeze(1) if squeeze else out[0],) + tuple(out[1:])

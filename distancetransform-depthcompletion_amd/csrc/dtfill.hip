@@ -89,6 +89,7 @@ namespace {
 #include "dtfill_lines.hpp"
 #include "dtfill_read.hpp"
 #include "dtfill_fillb.hpp"
+#include "dtfill_near.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -441,6 +442,60 @@ void gmcv_launch(const float *lidar, const float *rgb, int C, int B, int H, int 
             k_gmcv<FORM><<<grid, 256, 0, st>>>(src, rgb, C, H, W, ts, tx, ty, ntiles, sr, raw, outs[k]);
         src = raw;
     }
+}
+
+// The workspace of dtfill_nearest_gather (nacc = 0: with spix) and of its backward (nacc = min(C, NG_CH) sets of accumulators),
+// 256-byte aligned pieces; with ws = nullptr only the total is worked out.
+NgWs ng_carve(void *ws, int B, int H, int W, int nacc, size_t *total) {
+    const size_t N = (size_t)B * H * W, Wd = (size_t)(W + 63) / 64, NR = (size_t)B * H;
+    char *base = static_cast<char *>(ws);
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        char *r = base ? base + off : nullptr;
+        off += align256(bytes);
+        return r;
+    };
+    NgWs c{};
+    c.Wd = (int)Wd;
+    c.N = N;
+    if (nacc) {
+        c.tsum = (long long *)take(nacc * N * 8);
+        c.ebias = (u32 *)take(nacc * N * 4);
+        c.flags = (u32 *)take(nacc * N * 4);
+    } else {
+        c.spix = (u32 *)take(N * 4);
+    }
+    c.srcbits = (u64 *)take(NR * Wd * 8);
+    c.rowcnt = (u32 *)take(NR * 4);
+    c.rowbase = (u32 *)take(NR * 4);
+    c.nsrc = (u32 *)take((size_t)B * 4);
+    c.status = (int32_t *)take((size_t)B * 4);
+    if (total) *total = off;
+    return c;
+}
+
+template <int PX>
+void ng_launch_gather(dim3 grid, hipStream_t st, const int32_t *index, const u32 *values, int C, size_t HW, const NgWs &ws,
+                             u32 *out_values, int32_t *out_pixel, int32_t *status) {
+    if (out_values && out_pixel)
+        k_ng_gather<PX, true, true><<<grid, 256, 0, st>>>(index, values, C, HW, ws, out_values, out_pixel, status);
+    else if (out_pixel)
+        k_ng_gather<PX, true, false><<<grid, 256, 0, st>>>(index, values, C, HW, ws, out_values, out_pixel, status);
+    else
+        k_ng_gather<PX, false, true><<<grid, 256, 0, st>>>(index, values, C, HW, ws, out_values, out_pixel, status);
+}
+
+// One round of the backward: NC channels from channel c0 on.
+template <int NC>
+void ngb_round(hipStream_t st, const int32_t *index, const float *grad_out, float *grad_values, int C, int c0, int B, int H,
+                      int W, const NgWs &ws, int32_t *status) {
+    const size_t HW = (size_t)H * W, cp = (size_t)C * HW;
+    const int sx = (W + 63) / 64, nstrips = sx * ((H + FB_TH - 1) / FB_TH);
+    const dim3 strips((nstrips + 3) / 4, B), rows((H + 3) / 4, B);
+    const float *g = grad_out + (size_t)c0 * HW;
+    k_ngb_acc<0, NC><<<strips, 256, 0, st>>>(index, g, cp, H, W, sx, nstrips, c0 == 0, ws, status);
+    k_ngb_acc<1, NC><<<strips, 256, 0, st>>>(index, g, cp, H, W, sx, nstrips, false, ws, status);
+    k_ngb_out<NC><<<rows, 256, 0, st>>>(H, W, cp, c0 + NC < C, ws, grad_values + (size_t)c0 * HW);
 }
 }  // namespace
 
@@ -888,6 +943,66 @@ int dtfill_fill_backward(const float *x, const int32_t *index, const float *grad
     k_fb_acc<0><<<strips, 256, 0, st>>>(index, grad_depth, H, W, sx, nstrips, ws);
     k_fb_acc<1><<<strips, 256, 0, st>>>(index, grad_depth, H, W, sx, nstrips, ws);
     k_fb_out<<<rows, 256, 0, st>>>(H, W, ws, grad_x, frame_status);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+size_t dtfill_nearest_gather_workspace_bytes(int B, int H, int W) {
+    if (!shape_ok(B, H, W)) return 0;
+    size_t total = 0;
+    ng_carve(nullptr, B, H, W, 0, &total);
+    return total;
+}
+
+int dtfill_nearest_gather(const float *x, const int32_t *index, const float *values, int C, int B, int H, int W, float src_thr,
+                          float *out_values, int32_t *out_pixel, int32_t *frame_status, void *workspace, size_t ws_bytes,
+                          void *stream) {
+    if (!x || !index || !workspace || (!out_values && !out_pixel) || (!values != !out_values)) return DTFILL_ERR_NULL;
+    if (!shape_ok(B, H, W) || C < 0 || C > DTFILL_NEAR_MAX_C || (C == 0 && values)) return DTFILL_ERR_SHAPE;
+    if (ws_bytes < dtfill_nearest_gather_workspace_bytes(B, H, W) || ((uintptr_t)workspace & 255)) return DTFILL_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const NgWs ws = ng_carve(workspace, B, H, W, 0, nullptr);
+    int32_t *status = frame_status ? frame_status : ws.status;
+    const size_t HW = (size_t)H * W;
+    const dim3 rows((H + 3) / 4, B);
+    k_ng_count<<<rows, 256, 0, st>>>(x, H, W, src_thr, ws);
+    k_ng_scan<0><<<dim3(1, B), 256, 0, st>>>(H, HW, 0, ws, status);
+    k_ng_list<<<rows, 256, 0, st>>>(H, W, ws);
+    const u32 *vin = reinterpret_cast<const u32 *>(values);  // the payload moves as bits
+    u32 *vout = reinterpret_cast<u32 *>(out_values);
+    const bool vec = (W & 3) == 0 && (((uintptr_t)index | (uintptr_t)out_values | (uintptr_t)out_pixel) & 15) == 0;
+    if (vec)
+        ng_launch_gather<4>(dim3((unsigned)((HW / 4 + 255) / 256), B), st, index, vin, C, HW, ws, vout, out_pixel, status);
+    else
+        ng_launch_gather<1>(dim3((unsigned)((HW + 255) / 256), B), st, index, vin, C, HW, ws, vout, out_pixel, status);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+size_t dtfill_nearest_gather_backward_workspace_bytes(int B, int H, int W, int C) {
+    if (!shape_ok(B, H, W) || C < 1 || C > DTFILL_NEAR_MAX_C) return 0;
+    size_t total = 0;
+    ng_carve(nullptr, B, H, W, min(C, NG_CH), &total);
+    return total;
+}
+
+int dtfill_nearest_gather_backward(const float *x, const int32_t *index, const float *grad_out, int C, int B, int H, int W,
+                                   float src_thr, float *grad_values, int32_t *frame_status, void *workspace, size_t ws_bytes,
+                                   void *stream) {
+    if (!x || !index || !grad_out || !grad_values || !workspace) return DTFILL_ERR_NULL;
+    if (!shape_ok(B, H, W) || C < 1 || C > DTFILL_NEAR_MAX_C) return DTFILL_ERR_SHAPE;
+    if (ws_bytes < dtfill_nearest_gather_backward_workspace_bytes(B, H, W, C) || ((uintptr_t)workspace & 255))
+        return DTFILL_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int nacc = min(C, NG_CH);
+    const NgWs ws = ng_carve(workspace, B, H, W, nacc, nullptr);
+    int32_t *status = frame_status ? frame_status : ws.status;
+    const size_t HW = (size_t)H * W;
+    k_ng_count<<<dim3((H + 3) / 4, B), 256, 0, st>>>(x, H, W, src_thr, ws);
+    // blocks that share a frame's clearing: one per 4096 pixels, at most 64
+    k_ng_scan<1><<<dim3((unsigned)min((HW + 4095) / 4096, (size_t)64), B), 256, 0, st>>>(H, HW, nacc, ws, status);
+    static_assert(NG_CH == 2, "the rounds below are of two channels and, for an odd C, a last one of one");
+    int c0 = 0;
+    for (; c0 + 2 <= C; c0 += 2) ngb_round<2>(st, index, grad_out, grad_values, C, c0, B, H, W, ws, status);
+    if (c0 < C) ngb_round<1>(st, index, grad_out, grad_values, C, c0, B, H, W, ws, status);
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 

@@ -557,6 +557,82 @@ def fill_backward_device(x, index, grad_depth, val_thr=0.1):
     return grad_x, status
 
 
+_near_ws = {}  # (device index, stream) -> the nearest gather's workspace (forward and backward), shared like _gmcb_ws
+
+
+def _check_near(x, index, payload, what):
+    """The argument checks of the two nearest-gather calls (fill_backward_device's): x float32 [B,H,W], index int32 of x's
+    shape, payload None or float32 [B,C,H,W] with x's frames, all contiguous CUDA tensors on x's device."""
+    _check_frames(x, "x")
+    if index.dtype != torch.int32 or not index.is_cuda or index.dim() != 3 or not index.is_contiguous():
+        raise ValueError("index must be a contiguous int32 CUDA tensor [B,H,W]")
+    if index.shape != x.shape or index.device != x.device:
+        raise ValueError("index must have x's shape and device")
+    if payload is None:
+        return 0
+    if payload.dtype != torch.float32 or not payload.is_cuda or payload.dim() != 4 or not payload.is_contiguous():
+        raise ValueError("%s must be a contiguous float32 CUDA tensor [B,C,H,W]" % what)
+    if payload.shape[0] != x.shape[0] or payload.shape[2:] != x.shape[1:] or payload.device != x.device:
+        raise ValueError("%s must have x's frames [B,C,H,W] and device" % what)
+    C = payload.shape[1]
+    if not 1 <= C <= 64:
+        raise ValueError("%s must have 1 to 64 channels, got %d" % (what, C))
+    return C
+
+
+def nearest_gather_device(x, index, values=None, src_thr=0.1, want_pixel=True):
+    """Label -> source pixel (include/dtfill.h, dtfill_nearest_gather).  x: the tensor that decides the sources, NOT((1 - x) >
+    src_thr); index: DtFill.run(x)'s "index" (either metric); values: None or [B,C,H,W], the channels to fill from the nearest
+    source.  x, values: contiguous float32 CUDA tensors; index: contiguous int32 of x's shape [B,H,W], all on one device.
+    Returns (filled or None, pixel or None, status): filled [B,C,H,W] holds values' bits at the nearest source (+0.0 where the
+    label names none), pixel int32 [B,H,W] the source's flat pixel row*W + col (-1 where none), status int32 [B] the bits
+    _lib.FRAME_NO_SOURCE and _lib.FRAME_INDEX_ERROR.  New tensors; asynchronous on the current stream, no host
+    synchronisation."""
+    C = _check_near(x, index, values, "values")
+    if values is None and not want_pixel:
+        raise ValueError("nothing to compute: values is None and want_pixel is False")
+    _require_gpu()
+    B, H, W = x.shape
+    L = _lib.load()
+    nbytes = L.dtfill_nearest_gather_workspace_bytes(B, H, W)
+    if nbytes == 0:
+        _lib.check(-2)
+    filled = torch.empty_like(values) if values is not None else None
+    pixel = torch.empty_like(index) if want_pixel else None
+    status = torch.empty((B,), dtype=torch.int32, device=x.device)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(x.device):
+        ws = _gmcb_workspace(x.device, nbytes, _near_ws)
+        _lib.check(L.dtfill_nearest_gather(x.data_ptr(), index.data_ptr(), ptr(values), C, B, H, W, float(src_thr), ptr(filled),
+                                           ptr(pixel), status.data_ptr(), ws, nbytes,
+                                           torch.cuda.current_stream(x.device).cuda_stream))
+    return filled, pixel, status
+
+
+def nearest_gather_backward_device(x, index, grad_out, src_thr=0.1):
+    """The backward of nearest_gather_device with respect to values (include/dtfill.h, dtfill_nearest_gather_backward): every
+    source pixel receives, per channel, the cell sum of grad_out over the pixels whose label names it; every other pixel +0.0.
+    x, index: as in the forward; grad_out: contiguous float32 CUDA tensor [B,C,H,W].  Returns (grad_values, status): new
+    tensors, bitwise reproducible.  Asynchronous on the current stream, no host synchronisation."""
+    if grad_out is None:
+        raise ValueError("grad_out must be a contiguous float32 CUDA tensor [B,C,H,W]")
+    C = _check_near(x, index, grad_out, "grad_out")
+    _require_gpu()
+    B, H, W = x.shape
+    L = _lib.load()
+    nbytes = L.dtfill_nearest_gather_backward_workspace_bytes(B, H, W, C)
+    if nbytes == 0:
+        _lib.check(-2)
+    grad_values = torch.empty_like(grad_out)
+    status = torch.empty((B,), dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        ws = _gmcb_workspace(x.device, nbytes, _near_ws)
+        _lib.check(L.dtfill_nearest_gather_backward(x.data_ptr(), index.data_ptr(), grad_out.data_ptr(), C, B, H, W, float(src_thr),
+                                                    grad_values.data_ptr(), status.data_ptr(), ws, nbytes,
+                                                    torch.cuda.current_stream(x.device).cuda_stream))
+    return grad_values, status
+
+
 def keep_every_of(keep_ratio):
     """1 / keep_ratio as the integer the kernel takes (sample()'s `label % (1.0 / keep_ratio) == 0`): 0.5 -> 2 (the
     reference's 32-line input), 0.25 -> 4 (16 lines).  ValueError unless 1 / keep_ratio is an integer >= 1."""

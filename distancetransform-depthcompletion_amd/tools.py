@@ -58,6 +58,43 @@ def DT_complete_batch(lidar_batch, src_thr=0.1, val_thr=0.1, first_row=0, floor=
     return np.expand_dims(out["depth"], axis=-1)  # already a fresh float32 array
 
 
+def nearest_source(x, values=None, src_thr=0.1, metric="l1_cv"):
+    """The nearest-source pixel map, and any channels filled from it (include/dtfill.h, dtfill_nearest_gather).  x: squeezed
+    like nearest_point's argument, to one frame [H,W] or to a batch [B,H,W]; a pixel is a source iff NOT((1 - x) > src_thr) in
+    float32.  Returns (dt, pixel): the distance map and, int32, the flat pixel row*W + col of every pixel's nearest source (-1
+    in a frame without one) -- with metric="l2" the raveled scipy.ndimage.distance_transform_edt(return_indices=True), ties to
+    the smallest raster index.  values: float32, [H,W] or [C,H,W] for a frame, [B,H,W] or [B,C,H,W] for a batch; then
+    (dt, pixel, filled), filled of values' shape with values' bits at the nearest source and +0.0 where there is none."""
+    import torch
+
+    a = np.squeeze(_as_f32_frames(x))
+    if a.ndim not in (2, 3):
+        raise ValueError("nearest_source expects an array squeezable to [H,W] or [B,H,W], got shape %s" % (np.shape(x),))
+    batch = a.ndim == 3
+    a = a if batch else a[None]
+    B, H, W = a.shape
+    v = None
+    if values is not None:
+        v = np.asarray(values)
+        if v.dtype != np.float32:
+            raise TypeError("values must be float32 (they are copied as bits), got dtype %s" % v.dtype)
+        lead = v.shape[:-2]
+        if v.shape[-2:] != (H, W) or (lead not in ((B,), ) and not (len(lead) == 2 and lead[0] == B) if batch else len(lead) > 1):
+            raise ValueError("values of shape %s do not go with frames of shape %s" % (v.shape, np.shape(x)))
+        v = v.reshape(B, -1, H, W)
+    op = _device.default_op(metric)
+    xd = torch.from_numpy(np.ascontiguousarray(a)).to(op.device)
+    res = op.run(xd, src_thr=src_thr, val_thr=0.1, want=("dt", "index"))
+    vd = None if v is None else torch.from_numpy(np.ascontiguousarray(v)).to(op.device)
+    filled, pixel, _ = _device.nearest_gather_device(xd, res["index"], vd, src_thr)
+    dt, pixel = res["dt"].cpu().numpy(), pixel.cpu().numpy()
+    if not batch:
+        dt, pixel = dt[0], pixel[0]
+    if v is None:
+        return dt, pixel
+    return dt, pixel, filled.cpu().numpy().reshape(np.shape(values))
+
+
 def Distance_Transform(lidar, src_thr=0.001, val_thr=0.1, floor=None):
     """eval_NYU.py:120-133 (src_thr=0.001 as eval_NYU.py:115; the notebooks use 0.1).
     One frame squeezable to [H,W]; the result keeps the input's dtype like the reference.

@@ -55,6 +55,7 @@ extern "C" {
                                        a label addresses past the value list, or label 0 (no source in
                                        the frame) with an empty value list.  out_depth of that frame is
                                        then unspecified; out_dt / out_index are still exact. */
+#define DTFILL_FRAME_NO_SOURCE    4 /* dtfill_nearest_gather[_backward]: the frame has no source pixel */
 #define DTFILL_FRAME_GENERAL_PATH 2 /* informational (l1_cv): the frame, or some of its rows, was computed outside the LDS
                                        window kernel -- by the any-distance kernels (sparse frame, rows with a pixel
                                        farther than the halo from every source), k_sky (the rows above every source)
@@ -460,6 +461,61 @@ size_t dtfill_fill_backward_workspace_bytes(int B, int H, int W); /* 0 on a bad 
 int dtfill_fill_backward(const float *x, const int32_t *index, const float *grad_depth, int B, int H, int W,
                          float val_thr, float *grad_x, int32_t *frame_status /* nullable */,
                          void *workspace, size_t ws_bytes, void *stream);
+
+/*
+ * Label -> source pixel: any channels filled from the nearest source, and the nearest-source pixel map itself.  A label of
+ * dtfill_batch()'s out_index is a raster rank among the frame's sources (either metric: a label means the same thing in both);
+ * this call turns it back into the source's pixel and copies C channels of a second tensor from there.  So the sources are
+ * decided by one tensor (x) and the payload is read from another (values): the exact fill behind a learned correction
+ * (net.py:131-155: the mask from input_lidar, the values from lidar_correct), many channels behind one dtfill_batch() pass, and
+ * what scipy.ndimage.distance_transform_edt(return_indices=True) returns (the l2 metric).  Per frame b:
+ *   the source list is the pixels with NOT((1.0f - x) > src_thr), evaluated in float32, in raster order: dtfill_batch()'s
+ *     source predicate, a NaN is a source; m its length, s_k the flat pixel row*W + col of its k-th entry;
+ *   a pixel p with L = index[b][p], 1 <= L <= m: out_pixel[b][p] = s_{L-1}, and out_values[b][c][p] has the bits of
+ *     values[b][c][s_{L-1}] for every channel c: a copy, so NaN payloads, -0.0 and subnormals come through unchanged;
+ *   L == 0 (dtfill_batch()'s label in a frame without a source): out_pixel = -1 and out_values = +0.0.  There is no numpy wrap
+ *     here: that belongs to depth_list[lbl - 1], which dtfill_batch()'s out_depth keeps reproducing;
+ *   L < 0 or L > m: that pixel gets -1 / +0.0 and the frame's status DTFILL_FRAME_INDEX_ERROR.  The rule is per pixel, the
+ *     frame's other pixels are served, and any 32-bit content of index is memory-safe, INT32_MIN and INT32_MAX included;
+ *   frame_status[b] = (m == 0 ? DTFILL_FRAME_NO_SOURCE : 0) | (a label outside [0, m] ? DTFILL_FRAME_INDEX_ERROR : 0).
+ * With DTFILL_FLAG_OUTLIER_REMOVAL in the forward the x to pass is the filtered one (dtfill_outlier_removal()'s output): the
+ * labels count the sources the forward saw.
+ *
+ * x: float32 [B,H,W]; index, out_pixel: int32 [B,H,W]; values, out_values: float32 [B,C,H,W], 0 <= C <= DTFILL_NEAR_MAX_C.
+ * values and out_values are NULL together, out_pixel may be NULL, not both outputs; with C == 0 values and out_values are NULL
+ * and the call produces the pixel map alone.  Every output given is fully overwritten and may alias no input.
+ * frame_status: int32 [B], nullable.  workspace: at least dtfill_nearest_gather_workspace_bytes(B,H,W) bytes, 256-B aligned,
+ * the caller's, no initialisation needed, nothing kept between calls.  Asynchronous on `stream`; no allocation, no host
+ * synchronisation.
+ * Returns, all checked before any HIP call: DTFILL_ERR_NULL for a NULL x, index or workspace, both outputs NULL, or exactly one
+ * of values / out_values NULL; DTFILL_ERR_SHAPE for dtfill_batch()'s shape rule, C outside [0, DTFILL_NEAR_MAX_C], or C == 0
+ * with values; DTFILL_ERR_WORKSPACE for a workspace that is too small or not aligned; then DTFILL_ERR_LAUNCH if a launch failed.
+ */
+#define DTFILL_NEAR_MAX_C 64
+size_t dtfill_nearest_gather_workspace_bytes(int B, int H, int W); /* 0 on a bad shape; the forward's shape rule */
+int dtfill_nearest_gather(const float *x, const int32_t *index, const float *values /* nullable */, int C,
+                          int B, int H, int W, float src_thr,
+                          float *out_values /* nullable */, int32_t *out_pixel /* nullable */,
+                          int32_t *frame_status /* nullable */, void *workspace, size_t ws_bytes, void *stream);
+
+/*
+ * The backward of dtfill_nearest_gather() with respect to values, given the gradient with respect to out_values.  x and index
+ * are constants of the differentiation, so it is the gather transposed literally, with the source list, m and s_k as above:
+ *   grad_values[b][c][s_k] = S({grad_out[b][c][p] : index[b][p] - 1 == k}) for every source, S the cell sum stated at
+ *     dtfill_fill_backward() (integer accumulators: the same bits on every run), and +0.0 at every pixel that is not a source;
+ *   labels outside [1, m] contribute nowhere; the status is the forward's, derived here again.
+ * grad_out, grad_values: float32 [B,C,H,W], 1 <= C <= DTFILL_NEAR_MAX_C; grad_values is fully overwritten and may alias no
+ * input.  workspace: at least dtfill_nearest_gather_backward_workspace_bytes(B,H,W,C) bytes, 256-B aligned, no initialisation
+ * needed.  The channels run in rounds that share one set of accumulators, so that size is non-decreasing in C and for every C
+ * no larger than its value at C = 4.  Asynchronous on `stream`; no allocation, no host synchronisation.
+ * Returns, all checked before any HIP call: DTFILL_ERR_NULL for a NULL x, index, grad_out, grad_values or workspace;
+ * DTFILL_ERR_SHAPE for dtfill_batch()'s shape rule or C outside [1, DTFILL_NEAR_MAX_C]; DTFILL_ERR_WORKSPACE; then
+ * DTFILL_ERR_LAUNCH if a launch failed.
+ */
+size_t dtfill_nearest_gather_backward_workspace_bytes(int B, int H, int W, int C); /* 0 on a bad shape */
+int dtfill_nearest_gather_backward(const float *x, const int32_t *index, const float *grad_out, int C,
+                                   int B, int H, int W, float src_thr, float *grad_values,
+                                   int32_t *frame_status /* nullable */, void *workspace, size_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }
