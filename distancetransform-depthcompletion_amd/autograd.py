@@ -8,6 +8,11 @@ off (net.py:491-496).  generate_multi_channel() here is that operator on CUDA te
 dtfill_generate_multi_channel, backward by dtfill_generate_multi_channel_backward (include/dtfill.h states both).
 Differentiable in `data` only, once: tf.equal / tf.cast / tf.greater give the mask no gradient, and there is no double
 backward.  joint_train = False is the caller's .detach() on the input.
+
+Threads and streams: every operator here may be called from several host threads on one stream and on several streams at once.
+The cached pieces (device.default_op's operator, the backward workspaces) are per stream, and one call's launches are enqueued
+under that piece's lock, so they stay contiguous on their stream; the outputs are the call's own tensors.  No lock is held
+across a host synchronisation: there is none.
 """
 import torch
 from torch.autograd.function import once_differentiable

@@ -4,7 +4,9 @@
 workspace + output set per (B, H, W) so that repeated calls (the reference calls the op once per
 frame in a loop, demo.py:268-290 / eval_NYU.py:138-195) allocate nothing.
 """
+import contextlib
 import ctypes
+import threading
 
 import numpy as np
 import torch
@@ -29,6 +31,16 @@ class DtFill:
     Parameters mirror the literals of the reference: src_thr is the 0.1 of tools.py:8 (0.001 in
     eval_NYU.py:115), val_thr the 0.1 of tools.py:22; metric "l1_cv" is the reference's
     cv2.DIST_L1 / mask 5 / DIST_LABEL_PIXEL transform.
+
+    Threads and streams.  One pass in flight at a time per object: the workspace, the output buffers and the staging buffers
+    are this object's, so a second pass may start only where it is ordered behind the first -- on the same stream, or behind an
+    event of it.  Host threads that share an object serialise on its lock instead of corrupting it: run() holds the lock from
+    the buffer check to the last launch (one pass's launches stay contiguous on their stream), run_numpy() from the staging copy
+    to the stream synchronisation (the staging buffers and the returned frames are one caller's).  The tensors run() returns
+    without `out=` are still overwritten by the next pass, another thread's included: threads that share an object pass `out=`
+    or use run_numpy().  The buffers belong to the stream that was current when they were allocated; a pass on another stream
+    records itself on them (Tensor.record_stream), so that dropping or reshaping the object while that pass is in flight does
+    not hand their memory out again before the pass is done.
     """
 
     def __init__(self, device=None, metric="l1_cv"):
@@ -41,9 +53,17 @@ class DtFill:
         self._shape = None
         self._ws = None
         self._out = None
+        self._crop = None
+        self._dev_in = None
+        self._home = {}  # buffer attribute -> the stream it was allocated under
+        self._lock = threading.RLock()
 
     # -- buffers -------------------------------------------------------------------------------
     def _ensure(self, B, H, W):
+        with self._lock:
+            self._ensure_locked(B, H, W)
+
+    def _ensure_locked(self, B, H, W):
         if self._shape == (B, H, W):
             return
         nbytes = self.lib.dtfill_workspace_bytes(B, H, W, self.metric)
@@ -59,6 +79,17 @@ class DtFill:
             "status": torch.empty((B,), dtype=torch.int32, device=self.device),
         }
         self._shape = (B, H, W)
+        self._home["_ws"] = self._home["_out"] = torch.cuda.current_stream(self.device).cuda_stream
+
+    def _on_stream(self, stream):
+        """Before a pass on `stream` (holding the lock): every buffer of this object that was allocated under another stream
+        records the pass, so that the caching allocator keeps its memory until the pass is done."""
+        for name in ("_ws", "_out", "_crop", "_dev_in"):
+            if self._home.get(name) == stream.cuda_stream:  # (a buffer somebody else put there has no home: it records)
+                continue
+            buf = getattr(self, name)
+            for t in (buf.values() if isinstance(buf, dict) else () if buf is None else (buf,)):
+                t.record_stream(stream)
 
     def workspace_bytes(self, B, H, W):
         return int(self.lib.dtfill_workspace_bytes(B, H, W, self.metric))
@@ -81,10 +112,10 @@ class DtFill:
         if x.dtype != torch.float32 or not x.is_cuda or x.dim() != 3 or not x.is_contiguous():
             raise ValueError("x must be a contiguous float32 CUDA tensor [B,H,W]")
         B, H, W = x.shape
-        with torch.cuda.device(x.device):
+        with torch.cuda.device(x.device), self._lock:
             if x.device != self.device:
                 raise ValueError("x lives on %s, operator on %s" % (x.device, self.device))
-            self._ensure(B, H, W)
+            self._ensure_locked(B, H, W)
             o = self._out
             epi = depth_rows_from != 0 or depth_floor is not None
             if out is not None:
@@ -97,14 +128,17 @@ class DtFill:
             if epi:
                 if timed or not (0 <= depth_rows_from < H):
                     raise ValueError("depth epilogue: 0 <= depth_rows_from < H, and not with timed=True")
-                if getattr(self, "_crop", None) is None or self._crop.shape != (B, H - depth_rows_from, W):
+                if self._crop is None or self._crop.shape != (B, H - depth_rows_from, W):
                     self._crop = torch.empty((B, H - depth_rows_from, W), dtype=torch.float32, device=self.device)
+                    self._home["_crop"] = torch.cuda.current_stream(self.device).cuda_stream
                 if out is None or "depth" not in out:
                     o = dict(o, depth=self._crop)
             if out is not None:
                 o = dict(o, **out)
             ptr = lambda name: o[name].data_ptr() if name in want else None
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+            current = torch.cuda.current_stream(self.device)
+            self._on_stream(current)
+            stream = current.cuda_stream
             args = [
                 x.data_ptr(), B, H, W, float(src_thr), float(val_thr), self.metric,
                 ptr("depth"), ptr("dt"), ptr("index"), o["status"].data_ptr(),
@@ -128,20 +162,25 @@ class DtFill:
 
     def upload(self, xh):
         """Host frames [B,H,W] (any real dtype / strides) -> this operator's float32 device input buffer, asynchronously on the
-        current stream: a small thread pool copies the caller's pageable array into pinned staging memory a few frames at a
-        time (numpy releases the GIL inside the copy), every chunk's DMA starting as soon as its copy is done."""
+        current stream (the staging buffer is this object's: a caller that shares the object with other threads holds its lock
+        until the copy has run, as run_numpy does): a small thread pool copies the caller's pageable array into pinned staging
+        memory a few frames at a time (numpy releases the GIL inside the copy), every chunk's DMA starting as soon as its copy
+        is done."""
         B, H, W = xh.shape
-        self._ensure(B, H, W)
-        if getattr(self, "_pin_shape", None) != (B, H, W):
-            self._pin_in = torch.empty((B, H, W), dtype=torch.float32).pin_memory()
-            self._dev_in = torch.empty((B, H, W), dtype=torch.float32, device=self.device)
-            self._pin_status = torch.empty((B,), dtype=torch.int32).pin_memory()
-            self._pin_shape = (B, H, W)
         nchunk = min(B, 8)
         cuts = [B * c // nchunk for c in range(nchunk + 1)]
-        pin_in = self._pin_in.numpy()
         pool = _copy_pool()
-        with torch.cuda.device(self.device):
+        with torch.cuda.device(self.device), self._lock:
+            self._ensure_locked(B, H, W)
+            current = torch.cuda.current_stream(self.device)
+            if getattr(self, "_pin_shape", None) != (B, H, W):
+                self._pin_in = torch.empty((B, H, W), dtype=torch.float32).pin_memory()
+                self._dev_in = torch.empty((B, H, W), dtype=torch.float32, device=self.device)
+                self._pin_status = torch.empty((B,), dtype=torch.int32).pin_memory()
+                self._pin_shape = (B, H, W)
+                self._home["_dev_in"] = current.cuda_stream
+            self._on_stream(current)
+            pin_in = self._pin_in.numpy()
             stage = [pool.submit(np.copyto, pin_in[cuts[c]:cuts[c + 1]], xh[cuts[c]:cuts[c + 1]], "same_kind") for c in range(nchunk)]
             for c in range(nchunk):
                 stage[c].result()  # (one pass: gathers strided input, casts if needed)
@@ -150,9 +189,10 @@ class DtFill:
 
     def pass_stats(self):
         """Which kernel family owned how many pixels in the last run() of this operator (dtfill_pass_stats): dict of ints."""
-        B, H, W = self._shape
         out = torch.zeros(len(_lib.STATS), dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
+        with torch.cuda.device(self.device), self._lock:
+            B, H, W = self._shape
+            self._on_stream(torch.cuda.current_stream(self.device))
             _lib.check(self.lib.dtfill_pass_stats(self._ws.data_ptr() + self._ws_off, self._ws_bytes, B, H, W, self.metric, out.data_ptr(),
                                                   torch.cuda.current_stream(self.device).cuda_stream))
         return dict(zip(_lib.STATS, [int(v) for v in out.cpu().tolist()]))
@@ -172,7 +212,9 @@ class DtFill:
         if xh.ndim != 3:
             raise ValueError("x must be [B,H,W]")
         B, H, W = xh.shape
-        with torch.cuda.device(self.device):
+        # the lock from the staging copy to the synchronisation: the pinned staging buffer, the device input, the outputs and the
+        # status buffer are this call's until its last DMA has landed
+        with torch.cuda.device(self.device), self._lock:
             stream = torch.cuda.current_stream(self.device)
             dev_in = self.upload(xh)
             res = self.run(dev_in, src_thr, val_thr, want, depth_rows_from=depth_rows_from, depth_floor=depth_floor,
@@ -312,16 +354,34 @@ def generate_multi_channel_device(data, mask, table_size=7, scale_num=4):
     return tuple([data] + outs + [None] * (4 - scale_num))
 
 
-_gmcb_ws = {}  # (device index, stream) -> the backward's workspace: calls on one stream are ordered, so they can share it
+class _Scratch:
+    """(device index, stream) -> one scratch tensor for one entry point's workspace, grown on demand, and the lock that goes with
+    it.  Calls on one stream are ordered, so they can share the scratch -- as long as one call's launches are contiguous in the
+    stream: hold() keeps the entry's lock while the caller enqueues, so a second host thread on the same stream enqueues its call
+    behind this one's last launch, not between two of them.  The lock is held across the enqueue only, never across a host
+    synchronisation.  Another stream has another entry: its calls run beside these in scratch of their own."""
+
+    def __init__(self):
+        self._entries = {}
+        self._lock = threading.Lock()
+
+    @contextlib.contextmanager
+    def hold(self, device, nbytes):
+        """A 256-byte aligned pointer to at least nbytes of scratch on `device`, the current stream's, for one call's enqueue."""
+        key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+        with self._lock:
+            entry = self._entries.get(key)
+            if entry is None:
+                entry = self._entries[key] = [threading.Lock(), None]
+        with entry[0]:
+            ws = entry[1]
+            if ws is None or ws.numel() < nbytes + 256:
+                # (the tensor it replaces goes back to this stream's pool, behind the launches that still use it)
+                ws = entry[1] = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+            yield ws.data_ptr() + (-ws.data_ptr()) % 256
 
 
-def _gmcb_workspace(device, nbytes, cache=_gmcb_ws):
-    """A 256-byte aligned pointer to at least nbytes of scratch on `device`, kept for the current stream and grown on demand."""
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-    ws = cache.get(key)
-    if ws is None or ws.numel() < nbytes + 256:
-        ws = cache[key] = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-    return ws.data_ptr() + (-ws.data_ptr()) % 256
+_gmcb_ws = _Scratch()  # the backward's workspace
 
 
 def generate_multi_channel_backward_device(mask, out2, out3, grads, table_size=7, scale_num=4):
@@ -352,10 +412,10 @@ def generate_multi_channel_backward_device(mask, out2, out3, grads, table_size=7
     out = torch.empty_like(mask)
     with torch.cuda.device(mask.device):
         nbytes = L.dtfill_generate_multi_channel_backward_workspace_bytes(B, H, W, scale_num)
-        ws = _gmcb_workspace(mask.device, nbytes) if nbytes else None
-        _lib.check(L.dtfill_generate_multi_channel_backward(
-            mask.data_ptr(), ptr(out2), ptr(out3), B, H, W, int(table_size), int(scale_num), *[ptr(g) for g in grads],
-            out.data_ptr(), ws, nbytes, torch.cuda.current_stream(mask.device).cuda_stream))
+        with (_gmcb_ws.hold(mask.device, nbytes) if nbytes else contextlib.nullcontext()) as ws:
+            _lib.check(L.dtfill_generate_multi_channel_backward(
+                mask.data_ptr(), ptr(out2), ptr(out3), B, H, W, int(table_size), int(scale_num), *[ptr(g) for g in grads],
+                out.data_ptr(), ws, nbytes, torch.cuda.current_stream(mask.device).cuda_stream))
     return out
 
 
@@ -456,7 +516,7 @@ LOSS_PRESETS = {  # dataset -> (kind, gt_thr, in_thr, rows, cols) of train.py:21
     "KITTI": (_lib.LOSS_KITTI, 0.1, 0.1, None, None),
     "NYU": (_lib.LOSS_NYU, 0.0001, 0.001, (6, 228), (8, 304)),
 }
-_loss_ws = {}  # (device index, stream) -> the forward's partial sums, shared like _gmcb_ws
+_loss_ws = _Scratch()  # the forward's partial sums
 
 
 def _loss_args(pred, gt, lidar, correction, dataset, gt_thr, in_thr, rows, cols):
@@ -494,8 +554,8 @@ def train_loss_device(pred, gt, lidar=None, correction=None, dataset="KITTI", gt
     stats = torch.empty(len(_lib.LOSS_COLUMNS), dtype=torch.float64, device=pred.device)
     with torch.cuda.device(pred.device):
         nbytes = L.dtfill_train_loss_workspace_bytes(*args[4:7])
-        ws = _gmcb_workspace(pred.device, nbytes, _loss_ws)
-        _lib.check(L.dtfill_train_loss(*args, stats.data_ptr(), ws, nbytes, torch.cuda.current_stream(pred.device).cuda_stream))
+        with _loss_ws.hold(pred.device, nbytes) as ws:
+            _lib.check(L.dtfill_train_loss(*args, stats.data_ptr(), ws, nbytes, torch.cuda.current_stream(pred.device).cuda_stream))
     return stats
 
 
@@ -525,7 +585,7 @@ def train_loss_backward_device(pred, gt, stats, g_main=None, g_aux=None, lidar=N
     return grad_pred, grad_corr
 
 
-_fillb_ws = {}  # (device index, stream) -> the fill backward's accumulators, shared like _gmcb_ws
+_fillb_ws = _Scratch()  # the fill backward's accumulators
 
 
 def fill_backward_device(x, index, grad_depth, val_thr=0.1):
@@ -550,14 +610,14 @@ def fill_backward_device(x, index, grad_depth, val_thr=0.1):
     grad_x = torch.empty_like(x)
     status = torch.empty((B,), dtype=torch.int32, device=x.device)
     with torch.cuda.device(x.device):
-        ws = _gmcb_workspace(x.device, nbytes, _fillb_ws)
-        _lib.check(L.dtfill_fill_backward(x.data_ptr(), index.data_ptr(), grad_depth.data_ptr(), B, H, W, float(val_thr),
-                                          grad_x.data_ptr(), status.data_ptr(), ws, nbytes,
-                                          torch.cuda.current_stream(x.device).cuda_stream))
+        with _fillb_ws.hold(x.device, nbytes) as ws:
+            _lib.check(L.dtfill_fill_backward(x.data_ptr(), index.data_ptr(), grad_depth.data_ptr(), B, H, W, float(val_thr),
+                                              grad_x.data_ptr(), status.data_ptr(), ws, nbytes,
+                                              torch.cuda.current_stream(x.device).cuda_stream))
     return grad_x, status
 
 
-_near_ws = {}  # (device index, stream) -> the nearest gather's workspace (forward and backward), shared like _gmcb_ws
+_near_ws = _Scratch()  # the nearest gather's workspace (forward and backward)
 
 
 def _check_near(x, index, payload, what):
@@ -602,10 +662,10 @@ def nearest_gather_device(x, index, values=None, src_thr=0.1, want_pixel=True):
     status = torch.empty((B,), dtype=torch.int32, device=x.device)
     ptr = lambda t: None if t is None else t.data_ptr()
     with torch.cuda.device(x.device):
-        ws = _gmcb_workspace(x.device, nbytes, _near_ws)
-        _lib.check(L.dtfill_nearest_gather(x.data_ptr(), index.data_ptr(), ptr(values), C, B, H, W, float(src_thr), ptr(filled),
-                                           ptr(pixel), status.data_ptr(), ws, nbytes,
-                                           torch.cuda.current_stream(x.device).cuda_stream))
+        with _near_ws.hold(x.device, nbytes) as ws:
+            _lib.check(L.dtfill_nearest_gather(x.data_ptr(), index.data_ptr(), ptr(values), C, B, H, W, float(src_thr), ptr(filled),
+                                               ptr(pixel), status.data_ptr(), ws, nbytes,
+                                               torch.cuda.current_stream(x.device).cuda_stream))
     return filled, pixel, status
 
 
@@ -626,10 +686,10 @@ def nearest_gather_backward_device(x, index, grad_out, src_thr=0.1):
     grad_values = torch.empty_like(grad_out)
     status = torch.empty((B,), dtype=torch.int32, device=x.device)
     with torch.cuda.device(x.device):
-        ws = _gmcb_workspace(x.device, nbytes, _near_ws)
-        _lib.check(L.dtfill_nearest_gather_backward(x.data_ptr(), index.data_ptr(), grad_out.data_ptr(), C, B, H, W, float(src_thr),
-                                                    grad_values.data_ptr(), status.data_ptr(), ws, nbytes,
-                                                    torch.cuda.current_stream(x.device).cuda_stream))
+        with _near_ws.hold(x.device, nbytes) as ws:
+            _lib.check(L.dtfill_nearest_gather_backward(x.data_ptr(), index.data_ptr(), grad_out.data_ptr(), C, B, H, W,
+                                                        float(src_thr), grad_values.data_ptr(), status.data_ptr(), ws, nbytes,
+                                                        torch.cuda.current_stream(x.device).cuda_stream))
     return grad_values, status
 
 
@@ -732,15 +792,23 @@ def depth_read_device(raw, dims=None, size=(1216, 352)):
 
 
 _default_ops = {}
+_default_ops_lock = threading.Lock()
 
 
 def default_op(metric="l1_cv"):
-    """Process-wide operator on the current CUDA device (what the reference-named functions use)."""
+    """The process-wide operator of the current CUDA device and the current stream (what the reference-named functions and the
+    autograd operators use).  One per stream: passes on different streams run beside each other in workspaces of their own, and
+    an operator's buffers are always used on the stream they were allocated under.  Host threads on one stream share the
+    operator and serialise on its lock (DtFill).  Like the workspaces of the other entry points, an operator stays for the life
+    of the process: a caller that goes through many short-lived streams constructs a DtFill of its own instead."""
     _require_gpu()
-    key = (torch.cuda.current_device(), metric)
-    if key not in _default_ops:
-        _default_ops[key] = DtFill(metric=metric)
-    return _default_ops[key]
+    dev = torch.cuda.current_device()
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream, metric)
+    with _default_ops_lock:
+        op = _default_ops.get(key)
+        if op is None:
+            op = _default_ops[key] = DtFill(metric=metric)
+    return op
 
 
 def fill(x, src_thr=0.1, val_thr=0.1, metric="l1_cv", want=WANT_ALL):

@@ -84,9 +84,13 @@ def nearest_source(x, values=None, src_thr=0.1, metric="l1_cv"):
         v = v.reshape(B, -1, H, W)
     op = _device.default_op(metric)
     xd = torch.from_numpy(np.ascontiguousarray(a)).to(op.device)
-    res = op.run(xd, src_thr=src_thr, val_thr=0.1, want=("dt", "index"))
     vd = None if v is None else torch.from_numpy(np.ascontiguousarray(v)).to(op.device)
-    filled, pixel, _ = _device.nearest_gather_device(xd, res["index"], vd, src_thr)
+    # dt and index in tensors of this call's own (the operator's buffers are the next caller's, on any thread), and the
+    # operator's lock over both launches
+    res = dict(dt=torch.empty_like(xd), index=torch.empty_like(xd, dtype=torch.int32))
+    with op._lock:
+        op.run(xd, src_thr=src_thr, val_thr=0.1, want=("dt", "index"), out=res)
+        filled, pixel, _ = _device.nearest_gather_device(xd, res["index"], vd, src_thr)
     dt, pixel = res["dt"].cpu().numpy(), pixel.cpu().numpy()
     if not batch:
         dt, pixel = dt[0], pixel[0]

@@ -58,18 +58,18 @@ def true_exponent(g):
 
 def cell_sum(terms):
     """S(C) of include/dtfill.h for a sequence of float32 terms, as a float32."""
-    terms = [F(g) for g in terms]
-    nan = any(np.isnan(g) for g in terms)
-    pinf = any(np.isposinf(g) for g in terms)
-    ninf = any(np.isneginf(g) for g in terms)
+    terms = np.asarray(terms, F).reshape(-1)  # (the classification on the whole array: a frame has a term per pixel)
+    nan = bool(np.isnan(terms).any())
+    pinf = bool(np.isposinf(terms).any())
+    ninf = bool(np.isneginf(terms).any())
     if nan or (pinf and ninf):
         return np.array([QNAN], np.uint32).view(F)[0]
     if pinf or ninf:
         return F(np.inf) if pinf else F(-np.inf)
-    finite = [g for g in terms if g != 0]
-    if not finite:
+    finite = terms[terms != 0]
+    if not finite.size:
         return F(0.0)
-    q = max(true_exponent(g) for g in finite) - 37
+    q = true_exponent(np.abs(finite).max()) - 37  # the largest magnitude has the largest exponent
     T = sum(round(Fraction(float(g)) / Fraction(2) ** q) for g in finite)  # round(Fraction): half to even
     m, e = f32_of_int(T)
     return ldexp_f32(m, e + q)
