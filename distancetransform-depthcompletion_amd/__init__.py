@@ -12,14 +12,14 @@ from . import _lib
 from ._lib import METRICS, DtfillError, build, load
 from .sharding import shard_range, gather_frames, fill_sharded, release_host_slab
 from .tools import DT_complete_batch, Distance_Transform, generate_multi_channel, nearest_point, outlier_removal, subsample_lidar
-from .tools import depth_read, depth_read_batch, nearest_source
+from .tools import depth_read, depth_read_batch, nearest_source, rgb_read, rgb_read_batch
 from . import demo  # demo.py's own generate_multi_channel / _with_image / create_weight_matrix, reached as <package>.demo.*
 from .postfill import Result, Result_NYU, depth_floor, depth_to_png16, kitti_rows, nyu_eval_crop
 
 
 def __getattr__(name):
     # device.py imports torch; keep `import package` cheap for tooling that only needs the ABI
-    if name in ("DtFill", "fill", "default_op", "device"):
+    if name in ("DtFill", "fill", "default_op", "rgb_read_device", "device"):
         import importlib
 
         mod = importlib.import_module(__name__ + ".device")
@@ -33,7 +33,7 @@ def __getattr__(name):
 
 __all__ = [
     "nearest_point", "DT_complete_batch", "Distance_Transform", "outlier_removal", "generate_multi_channel", "subsample_lidar",
-    "depth_read", "depth_read_batch", "nearest_source", "demo", "fill", "DtFill",
+    "depth_read", "depth_read_batch", "rgb_read", "rgb_read_batch", "rgb_read_device", "nearest_source", "demo", "fill", "DtFill",
     "shard_range", "gather_frames", "fill_sharded", "release_host_slab", "build", "load", "METRICS", "DtfillError",
     "Result", "Result_NYU", "depth_floor", "depth_to_png16", "kitti_rows", "nyu_eval_crop",
 ]

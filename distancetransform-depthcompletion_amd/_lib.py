@@ -28,6 +28,8 @@ LINES_BAD_INTERVAL = 2  # bit: the pitch interval is 0 or not finite
 LINES_SINGULAR = 4  # bit: K or E is singular
 READ_NOT_16BIT = 1  # bit: every source value of the frame is <= 255 (DTFILL_READ_*)
 READ_BAD_DIMS = 2  # bit: the frame's dims lie outside [1, hmax] x [1, wmax]; its output is all zeros
+RGB_NHWC = 0  # out_f32 [B, H - first_row, W, C] (DTFILL_RGB_*)
+RGB_NCHW = 1  # out_f32 [B, C, H - first_row, W]
 PATHS = {"auto": 0, "general": FLAG_GENERAL_ONLY, "fused": FLAG_FUSED_ONLY}
 
 # every symbol include/dtfill.h declares (tests/test_abi.py checks the .so exports exactly these)
@@ -54,6 +56,8 @@ SYMBOLS = (
     "dtfill_line_subsample",
     "dtfill_depth_read_workspace_bytes",
     "dtfill_depth_read",
+    "dtfill_rgb_read_workspace_bytes",
+    "dtfill_rgb_read",
     "dtfill_metrics_workspace_bytes",
     "dtfill_metrics",
     "dtfill_train_loss_workspace_bytes",
@@ -151,6 +155,10 @@ def load():
     L.dtfill_depth_read_workspace_bytes.restype = sz
     L.dtfill_depth_read.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, sz, vp]
     L.dtfill_depth_read.restype = ci
+    L.dtfill_rgb_read_workspace_bytes.argtypes = [ci, ci, ci]
+    L.dtfill_rgb_read_workspace_bytes.restype = sz
+    L.dtfill_rgb_read.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]
+    L.dtfill_rgb_read.restype = ci
     L.dtfill_metrics_workspace_bytes.argtypes = [ci]
     L.dtfill_metrics_workspace_bytes.restype = sz
     L.dtfill_metrics.argtypes = [vp, vp, ci, ctypes.c_longlong, ci, vp, vp, sz, vp]

@@ -88,6 +88,7 @@ namespace {
 #include "dtfill_loss.hpp"
 #include "dtfill_lines.hpp"
 #include "dtfill_read.hpp"
+#include "dtfill_rgb.hpp"
 #include "dtfill_fillb.hpp"
 #include "dtfill_near.hpp"
 
@@ -869,6 +870,44 @@ int dtfill_depth_read(const uint16_t *raw, const int32_t *dims, int B, int hmax,
         k_read_gather<true><<<grid, DR_THREADS, 0, st>>>(raw, dims, hmax, wmax, H, W, rpb, ry, rx, fw, out, frame_status);
     else
         k_read_gather<false><<<grid, DR_THREADS, 0, st>>>(raw, dims, hmax, wmax, H, W, rpb, ry, rx, fw, out, frame_status);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+size_t dtfill_rgb_read_workspace_bytes(int B, int H, int W) { return dtfill_depth_read_workspace_bytes(B, H, W); }
+
+int dtfill_rgb_read(const uint8_t *raw, const int32_t *dims, int B, int hmax, int wmax, int C, int H, int W, int first_row,
+                    int normalize, int layout, uint8_t *out_u8, float *out_f32, int32_t *frame_status, void *workspace,
+                    size_t ws_bytes, void *stream) {
+    if (!raw || !workspace || (!out_u8 && !out_f32)) return DTFILL_ERR_NULL;
+    const size_t need = dtfill_rgb_read_workspace_bytes(B, H, W);
+    if (need == 0 || hmax < 1 || wmax < 1 || C < 1 || C > 4 || first_row < 0 || first_row >= H ||
+        (layout != DTFILL_RGB_NHWC && layout != DTFILL_RGB_NCHW))
+        return DTFILL_ERR_SHAPE;
+    const long long OH = H - first_row;
+    if ((long long)hmax * wmax >= (1ll << 31) || (long long)B * hmax * wmax * C >= (1ll << 31) || B * OH * W * C >= (1ll << 31))
+        return DTFILL_ERR_SHAPE;
+    if (ws_bytes < need || ((uintptr_t)workspace & 255)) return DTFILL_ERR_WORKSPACE;
+    char *base = static_cast<char *>(workspace);
+    int *ry = reinterpret_cast<int *>(base);
+    int *rx = reinterpret_cast<int *>(base + align256((size_t)B * H * sizeof(int)));
+    u32 *fw = reinterpret_cast<u32 *>(base + align256((size_t)B * H * sizeof(int)) + align256((size_t)B * W * sizeof(int)));
+    const int rpb = max(RG_ROWS, (int)((OH + 65534) / 65535));
+    const dim3 grid(B, (unsigned)((OH + rpb - 1) / rpb));
+    const RgArgs a{raw, dims, hmax, wmax, H, W, first_row, rpb, normalize, layout, ry, rx, out_u8, out_f32, frame_status};
+    // the LDS image holds a whole source row: rows that fit it, unless most of their bytes would go unsampled
+#ifdef RGB_NO_STAGE  // the A/B build of scripts/bench_rgb_read.py: every pick from global memory
+    const bool stage = false;
+#else
+    const bool stage = (long long)wmax * C <= RG_SPAN && wmax <= 2ll * W;
+#endif
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    k_read_maps<<<B, 128, 0, st>>>(dims, hmax, wmax, H, W, ry, rx, fw);
+    switch (C) {
+        case 1: rgb_launch<1>(grid, st, stage, a); break;
+        case 2: rgb_launch<2>(grid, st, stage, a); break;
+        case 3: rgb_launch<3>(grid, st, stage, a); break;
+        default: rgb_launch<4>(grid, st, stage, a); break;
+    }
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 

@@ -791,6 +791,59 @@ def depth_read_device(raw, dims=None, size=(1216, 352)):
     return out, status
 
 
+RGB_WANT = ("float", "uint8", "both")
+RGB_LAYOUTS = {"nhwc": _lib.RGB_NHWC, "nchw": _lib.RGB_NCHW}
+
+
+def rgb_read_device(raw, dims=None, size=(1216, 352), first_row=0, want="float", layout="nhwc", normalize=True):
+    """data_read.py:66-73 after the PNG decode, and the drivers' rgb = img_batch[:, first_row:] / 255.0 as float32
+    (train.py:213-214 and its kin), on the device (include/dtfill.h, dtfill_rgb_read): Pillow's NEAREST resize of uint8
+    images to size = (width, height), PIL's order.  raw: contiguous uint8 CUDA tensor [B, hmax, wmax, C], C in 1..4; dims:
+    (h_b, w_b) per frame as int [B, 2] (numpy, list or tensor; None: every frame hmax x wmax), the padding beyond them is
+    never read.  want: "float", "uint8" or "both"; layout of the float output: "nhwc" [B, H - first_row, W, C] (what
+    demo_multi_channel_device takes as rgb) or "nchw" [B, C, H - first_row, W] (nearest_gather_device's values);
+    normalize=False keeps (float)v.  Returns (uint8 [B, H - first_row, W, C] or None, float32 or None, status int32 [B]:
+    _lib.READ_BAD_DIMS, with an all-zero frame, for dims outside [1, hmax] x [1, wmax]).  New tensors, asynchronous on the
+    current stream."""
+    _require_gpu()
+    if raw.dtype != torch.uint8 or not raw.is_cuda or raw.dim() != 4 or not raw.is_contiguous():
+        raise ValueError("raw must be a contiguous uint8 CUDA tensor [B,hmax,wmax,C]")
+    if want not in RGB_WANT:
+        raise ValueError("want must be one of %s, got %r" % (RGB_WANT, want))
+    if layout not in RGB_LAYOUTS:
+        raise ValueError("layout must be one of %s, got %r" % (sorted(RGB_LAYOUTS), layout))
+    H, W = _read_size(size)
+    B, hmax, wmax, C = raw.shape
+    if first_row != int(first_row) or not 0 <= first_row < H:
+        raise ValueError("first_row must be an integer in [0, %d), got %r" % (H, first_row))
+    first_row = int(first_row)
+    d = None
+    if dims is not None:
+        d = dims if isinstance(dims, torch.Tensor) else torch.from_numpy(np.asarray(dims, dtype=np.int32))
+        d = d.to(device=raw.device, dtype=torch.int32).contiguous()
+        if tuple(d.shape) != (B, 2):
+            raise ValueError("dims must be [B, 2] = [%d, 2], got shape %s" % (B, tuple(d.shape)))
+    L = _lib.load()
+    nbytes = L.dtfill_rgb_read_workspace_bytes(B, H, W)
+    if nbytes == 0:
+        _lib.check(-2)
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=raw.device)
+    off = (-ws.data_ptr()) % 256
+    OH = H - first_row
+    u8 = f32 = None
+    if want != "float":
+        u8 = torch.empty((B, OH, W, C), dtype=torch.uint8, device=raw.device)
+    if want != "uint8":
+        f32 = torch.empty((B, OH, W, C) if layout == "nhwc" else (B, C, OH, W), dtype=torch.float32, device=raw.device)
+    status = torch.empty((B,), dtype=torch.int32, device=raw.device)
+    with torch.cuda.device(raw.device):
+        _lib.check(L.dtfill_rgb_read(raw.data_ptr(), None if d is None else d.data_ptr(), B, hmax, wmax, C, H, W, first_row,
+                                     1 if normalize else 0, RGB_LAYOUTS[layout], None if u8 is None else u8.data_ptr(),
+                                     None if f32 is None else f32.data_ptr(), status.data_ptr(), ws.data_ptr() + off, nbytes,
+                                     torch.cuda.current_stream(raw.device).cuda_stream))
+    return u8, f32, status
+
+
 _default_ops = {}
 _default_ops_lock = threading.Lock()
 

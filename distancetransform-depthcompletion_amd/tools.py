@@ -4,6 +4,7 @@ Same names, argument meaning and error behaviour as
   solution_DeepNet/tools.py:7-35      nearest_point, DT_complete_batch
   solution_DeepNet/eval_NYU.py:114-133 nearest_point (threshold 0.001), Distance_Transform
   data_read.py:81-99                   depth_read (and depth_read_batch for Data_load.read_batch's stack of them)
+  data_read.py:66-73                   rgb_read (and rgb_read_batch for read_batch's img_batch and the drivers' / 255.0)
 but the work is done by libdtfill.so on the current HIP device.  Differences from the reference,
 all widening: DT_complete_batch accepts any HxW (the reference hard-codes 352x1216 in its
 reshapes, tools.py:25,27), and the thresholds the reference writes as literals are keyword
@@ -269,3 +270,88 @@ def depth_read_batch(frames, size=KITTI_SIZE, check=True):
             b = int(bad[0])
             raise AssertionError("np.max(depth_png)={}, frame {}".format(np.max(frames[b]), b))
     return out
+
+
+def _rgb_values(a, what):
+    """A decoded image as the kernel reads it: [h, w] or [h, w, C <= 4] of integer values that fit uint8 (TypeError otherwise:
+    the reference's np.array(img, dtype='uint8') would wrap them silently)."""
+    a = np.asarray(a)
+    if a.ndim not in (2, 3) or 0 in a.shape or (a.ndim == 3 and a.shape[2] > 4):
+        raise ValueError("%s: expected a non-empty decoded image [h, w] or [h, w, C <= 4], got shape %s" % (what, a.shape))
+    if a.dtype == np.uint8:
+        return a
+    if a.dtype.kind not in "iub":
+        raise TypeError("%s: expected integer pixel values, got dtype %s" % (what, a.dtype))
+    if a.min() < 0 or a.max() > 255:
+        raise TypeError("%s: values in [%d, %d] do not fit uint8" % (what, a.min(), a.max()))
+    return a
+
+
+def rgb_read_batch(frames, size=KITTI_SIZE, first_row=0, dtype=np.uint8):
+    """rgb_read for a batch: frames is a list of decoded images (np.array(Image.open(path))) of any mixed sizes and one channel
+    count, [h, w, C] or all [h, w]; size = (width, height) as PIL writes it.  dtype=np.uint8 returns np.asarray of the
+    img_batch Data_load.read_batch stacks (data_read.py:163, 175), uint8 [B, H, W, C] ([B, H, W] for 2-D frames);
+    dtype=np.float32 the drivers' next two lines, img_batch[:, first_row:] / 255.0 as float32 (train.py:213-214).  first_row
+    crops either form.  size=None keeps the source size, the read_one_val path (data_read.py:206-210); every frame must then
+    have the same shape.  One padded page-locked staging buffer that carries the dims behind the bytes, one H2D copy, one
+    dtfill_rgb_read, one D2H copy of the result, which is an array of its own."""
+    import torch
+
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.uint8), np.dtype(np.float32)):
+        raise ValueError("dtype must be np.uint8 or np.float32, got %s" % dtype)
+    frames = [_rgb_values(f, "frame %d" % b) for b, f in enumerate(frames)]
+    B = len(frames)
+    if B == 0:
+        raise ValueError("rgb_read_batch needs at least one frame")
+    if any(f.shape[2:] != frames[0].shape[2:] for f in frames):
+        raise ValueError("every frame must have the same channel count; got shapes %s" % sorted({f.shape for f in frames}))
+    C = frames[0].shape[2] if frames[0].ndim == 3 else 1
+    hmax = max(f.shape[0] for f in frames)
+    wmax = max(f.shape[1] for f in frames)
+    if size is None:
+        if any(f.shape != frames[0].shape for f in frames):
+            raise ValueError("size=None keeps the source size, so every frame must have the same shape; got %s"
+                             % sorted({f.shape for f in frames}))
+        H, W = hmax, wmax
+    else:
+        H, W = _device._read_size(size)
+    if first_row != int(first_row) or not 0 <= first_row < H:
+        raise ValueError("first_row must be an integer in [0, %d), got %r" % (H, first_row))
+    first_row = int(first_row)
+    n = B * hmax * wmax * C
+    n4 = (n + 3) & ~3  # the dims start 4-byte aligned
+    stage = _device._host_pool.take((n4 + 8 * B,), np.uint8)
+    raw = stage.array[:n].reshape(B, hmax, wmax, C)  # the padding is never read: left as it is
+    for b, f in enumerate(frames):
+        raw[b, :f.shape[0], :f.shape[1]] = f.reshape(f.shape[0], f.shape[1], C)
+    stage.array[n4:].view(np.int32).reshape(B, 2)[:] = [f.shape[:2] for f in frames]
+    dev = _device.default_op().device
+    want = "uint8" if dtype == np.uint8 else "float"
+    with torch.cuda.device(dev):
+        d = torch.empty((n4 + 8 * B,), dtype=torch.uint8, device=dev)
+        d.copy_(stage.tensor, non_blocking=True)
+        u8, f32, status = _device.rgb_read_device(d[:n].view(B, hmax, wmax, C), d[n4:].view(torch.int32).view(B, 2), (W, H),
+                                                  first_row=first_row, want=want)
+        out = u8 if f32 is None else f32
+        host = _device._host_pool.take(tuple(out.shape), dtype)
+        host.tensor.copy_(out, non_blocking=True)
+        st = status.cpu().numpy()  # synchronises: the staging buffer and the result are done with
+    assert not st.any(), "dtfill_rgb_read: frame status %s" % st  # the dims are the frames' own
+    return host.array if frames[0].ndim == 3 else host.array[..., 0]
+
+
+def rgb_read(filename):
+    """data_read.py:66-73 (KITTI_demo_loader.rgb_read, :395-402, is the same): an image file -> uint8 [352, 1216, 3]
+    ([352, 1216] for a greyscale one, four channels for RGBA), NEAREST-resized as Pillow does.  The file is decoded on the
+    host, the resize runs on the device.  Raises the reference's AssertionError for a missing file; pixel values that do not
+    fit uint8 (a 16-bit PNG) raise TypeError where the reference's dtype='uint8' wraps them."""
+    import os
+
+    assert os.path.exists(filename), "file not found: {}".format(filename)
+    from PIL import Image
+
+    img_file = Image.open(filename)
+    rgb_png = _rgb_values(np.array(img_file), filename)
+    img_file.close()
+    return rgb_read_batch([rgb_png], KITTI_SIZE)[0]

@@ -345,6 +345,37 @@ int dtfill_depth_read(const uint16_t *raw, const int32_t *dims, int B, int hmax,
                       int32_t *frame_status, void *workspace, size_t ws_bytes, void *stream);
 
 /*
+ * rgb_read() of the reference's loader, data_read.py:66-73 (KITTI_demo_loader.rgb_read, :395-402, is the same), and the two
+ * lines every driver puts behind it (rgb = img_batch[:, 96:, :, :] / 255.0 as float32: train.py:213-214, eval.py:158-159,
+ * eval_NYU.py:159-160, test.py:118-119, demo.py:296-297), on the decoded uint8 images of B frames with C interleaved
+ * channels; the host keeps the PNG decode.  Frame b holds (h_b, w_b) pixels, every output frame (H - first_row) x W.
+ *   ry[0..H), rx[0..W): dtfill_depth_read's maps (Pillow's NEAREST resize, the running double sum, clamped to h_b - 1 / w_b - 1)
+ *   for i in [first_row, H), j in [0, W), c in [0, C):   v = raw[b, ry[i], rx[j], c]
+ *     out_u8[b, i - first_row, j, c] = v
+ *     out_f32[...]                   = normalize ? (float)v / 255.0f : (float)v     in the layout asked for
+ *   The division is the correctly rounded float32 division, whose bits equal the reference's float32(float64(v) / 255.0)
+ *   for all 256 values (v * (1 / 255.0f) differs for 126 of them).
+ * raw: uint8 [B, hmax, wmax, C], row pitch wmax * C bytes, any alignment.  Only the first w_b * C bytes of the source rows
+ * that ry samples are read: no byte of the padding of a ragged batch, no row that no output row samples (there is no
+ * whole-frame check as in dtfill_depth_read), nothing beyond raw.  dims: int32 [B, 2] holding (h_b, w_b), or NULL for
+ * hmax x wmax everywhere.  out_u8: uint8 [B, H - first_row, W, C]; out_f32: float32 in `layout`; either may be NULL, both are
+ * only element-aligned, neither may alias raw.  frame_status: int32 [B] (nullable): 0, or DTFILL_READ_BAD_DIMS for dims
+ * outside [1, hmax] x [1, wmax], and then the frame's outputs are all 0 / +0.0f.  workspace: ws_bytes >=
+ * dtfill_rgb_read_workspace_bytes(B, H, W), 256-B aligned, no initialisation needed, nothing kept between calls.
+ * Asynchronous on `stream`; no allocation, no host synchronisation, re-entrant across streams.
+ * Returns DTFILL_ERR_NULL for a NULL raw or workspace or both outputs NULL; DTFILL_ERR_SHAPE for B, hmax, wmax, H, W < 1,
+ * B > 65535, C outside 1..4, first_row outside [0, H), a layout that is neither of the two, B*hmax*wmax*C >= 2^31,
+ * B*(H-first_row)*W*C >= 2^31 or B*H*W >= 2^31 (the maps); DTFILL_ERR_WORKSPACE for a workspace too small or not
+ * aligned; all checked before any HIP call.
+ */
+#define DTFILL_RGB_NHWC 0 /* out_f32: [B, H - first_row, W, C]  (the drivers' array; dtfill_demo_multi_channel's rgb) */
+#define DTFILL_RGB_NCHW 1 /* out_f32: [B, C, H - first_row, W]  (dtfill_nearest_gather's values; a PyTorch conv) */
+size_t dtfill_rgb_read_workspace_bytes(int B, int H, int W); /* 0 on a bad shape */
+int dtfill_rgb_read(const uint8_t *raw, const int32_t *dims, int B, int hmax, int wmax, int C, int H, int W, int first_row,
+                    int normalize, int layout, uint8_t *out_u8, float *out_f32, int32_t *frame_status, void *workspace,
+                    size_t ws_bytes, void *stream);
+
+/*
  * Error metrics of evaluation.py, one row per frame:
  *   DTFILL_METRICS_KITTI  Result.evaluate, evaluation.py:82-123 (metres -> mm for mse/rmse/mae, -> 1/km for
  *                         irmse/imae; the deltas stay 0 as in the reference);
