@@ -32,44 +32,49 @@ RGB_NHWC = 0  # out_f32 [B, H - first_row, W, C] (DTFILL_RGB_*)
 RGB_NCHW = 1  # out_f32 [B, C, H - first_row, W]
 PATHS = {"auto": 0, "general": FLAG_GENERAL_ONLY, "fused": FLAG_FUSED_ONLY}
 
-# every symbol include/dtfill.h declares (tests/test_abi.py checks the .so exports exactly these)
-SYMBOLS = (
-    "dtfill_abi_version",
-    "dtfill_strerror",
-    "dtfill_workspace_bytes",
-    "dtfill_batch",
-    "dtfill_batch_flags",
-    "dtfill_batch_epilogue",
-    "dtfill_num_kernels",
-    "dtfill_kernel_name",
-    "dtfill_batch_timed",
-    "dtfill_pass_stats",
-    "dtfill_outlier_removal",
-    "dtfill_generate_multi_channel",
-    "dtfill_generate_multi_channel_backward_workspace_bytes",
-    "dtfill_generate_multi_channel_backward",
-    "dtfill_demo_multi_channel_workspace_bytes",
-    "dtfill_demo_multi_channel",
-    "dtfill_crop_floor",
-    "dtfill_png16",
-    "dtfill_line_subsample_workspace_bytes",
-    "dtfill_line_subsample",
-    "dtfill_depth_read_workspace_bytes",
-    "dtfill_depth_read",
-    "dtfill_rgb_read_workspace_bytes",
-    "dtfill_rgb_read",
-    "dtfill_metrics_workspace_bytes",
-    "dtfill_metrics",
-    "dtfill_train_loss_workspace_bytes",
-    "dtfill_train_loss",
-    "dtfill_train_loss_backward",
-    "dtfill_fill_backward_workspace_bytes",
-    "dtfill_fill_backward",
-    "dtfill_nearest_gather_workspace_bytes",
-    "dtfill_nearest_gather",
-    "dtfill_nearest_gather_backward_workspace_bytes",
-    "dtfill_nearest_gather_backward",
-)
+# the C ABI of include/dtfill.h: symbol -> (restype, argtypes), in the header's order.  tests/test_binding.py holds every entry to
+# the header's prototype; tests/test_abi.py checks the .so exports exactly these
+vp, ci, cf, sz, cu, ll, cs = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint, ctypes.c_longlong,
+                              ctypes.c_char_p)
+_ABI = {
+    "dtfill_abi_version": (ci, []),
+    "dtfill_strerror": (cs, [ci]),
+    "dtfill_workspace_bytes": (sz, [ci, ci, ci, ci]),
+    "dtfill_batch": (ci, [vp, ci, ci, ci, cf, cf, ci, vp, vp, vp, vp, vp, sz, vp]),
+    "dtfill_batch_flags": (ci, [vp, ci, ci, ci, cf, cf, ci, vp, vp, vp, vp, vp, sz, vp, cu]),
+    "dtfill_batch_epilogue": (ci, [vp, ci, ci, ci, cf, cf, ci, vp, vp, vp, vp, vp, sz, vp, cu, ci, ci, cf]),
+    "dtfill_num_kernels": (ci, [ci]),
+    "dtfill_kernel_name": (cs, [ci, ci]),
+    "dtfill_batch_timed": (ci, [vp, ci, ci, ci, cf, cf, ci, vp, vp, vp, vp, vp, sz, vp, cu, vp]),
+    "dtfill_pass_stats": (ci, [vp, sz, ci, ci, ci, ci, vp, vp]),
+    "dtfill_outlier_removal": (ci, [vp, ci, ci, ci, vp, vp]),
+    "dtfill_generate_multi_channel": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
+    "dtfill_generate_multi_channel_backward_workspace_bytes": (sz, [ci, ci, ci, ci]),
+    "dtfill_generate_multi_channel_backward": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "dtfill_demo_multi_channel_workspace_bytes": (sz, [ci, ci, ci, ci]),
+    "dtfill_demo_multi_channel": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, sz, vp]),
+    "dtfill_crop_floor": (ci, [vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp, vp]),
+    "dtfill_png16": (ci, [vp, ci, ci, ci, ci, ci, cf, cf, cf, cf, vp, vp]),
+    "dtfill_line_subsample_workspace_bytes": (sz, [ci, ci, ci]),
+    "dtfill_line_subsample": (ci, [vp, ci, ci, ci, vp, vp, ci, ci, vp, vp, vp, sz, vp]),
+    "dtfill_depth_read_workspace_bytes": (sz, [ci, ci, ci]),
+    "dtfill_depth_read": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, sz, vp]),
+    "dtfill_rgb_read_workspace_bytes": (sz, [ci, ci, ci]),
+    "dtfill_rgb_read": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
+    "dtfill_metrics_workspace_bytes": (sz, [ci]),
+    "dtfill_metrics": (ci, [vp, vp, ci, ll, ci, vp, vp, sz, vp]),
+    "dtfill_train_loss_workspace_bytes": (sz, [ci, ci, ci]),
+    "dtfill_train_loss": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, ci, ci, ci, ci, vp, vp, sz, vp]),
+    "dtfill_train_loss_backward": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),
+    "dtfill_fill_backward_workspace_bytes": (sz, [ci, ci, ci]),
+    "dtfill_fill_backward": (ci, [vp, vp, vp, ci, ci, ci, cf, vp, vp, vp, sz, vp]),
+    "dtfill_nearest_gather_workspace_bytes": (sz, [ci, ci, ci]),
+    "dtfill_nearest_gather": (ci, [vp, vp, vp, ci, ci, ci, ci, cf, vp, vp, vp, vp, sz, vp]),
+    "dtfill_nearest_gather_backward_workspace_bytes": (sz, [ci, ci, ci, ci]),
+    "dtfill_nearest_gather_backward": (ci, [vp, vp, vp, ci, ci, ci, ci, cf, vp, vp, vp, sz, vp]),
+}
+SYMBOLS = tuple(_ABI)
+del vp, ci, cf, sz, cu, ll, cs  # (the table's shorthands, not names of this module)
 STATS = ("all", "window", "anydist", "sky", "points", "colt")  # DTFILL_STATS_*
 METRICS_KITTI = 0
 METRICS_NYU = 1
@@ -110,77 +115,9 @@ def load():
             "`make -C %s`; this package has no CPU fallback" % (SO_PATH, CSRC)
         )
     L = ctypes.CDLL(SO_PATH)
-    vp, ci, cf, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
-    L.dtfill_abi_version.argtypes = []
-    L.dtfill_abi_version.restype = ci
-    L.dtfill_strerror.argtypes = [ci]
-    L.dtfill_strerror.restype = ctypes.c_char_p
-    L.dtfill_workspace_bytes.argtypes = [ci, ci, ci, ci]
-    L.dtfill_workspace_bytes.restype = sz
-    L.dtfill_batch.argtypes = [vp, ci, ci, ci, cf, cf, ci, vp, vp, vp, vp, vp, sz, vp]
-    L.dtfill_batch.restype = ci
-    L.dtfill_batch_flags.argtypes = [vp, ci, ci, ci, cf, cf, ci, vp, vp, vp, vp, vp, sz, vp, ctypes.c_uint]
-    L.dtfill_batch_flags.restype = ci
-    L.dtfill_batch_epilogue.argtypes = [vp, ci, ci, ci, cf, cf, ci, vp, vp, vp, vp, vp, sz, vp, ctypes.c_uint, ci, ci, cf]
-    L.dtfill_batch_epilogue.restype = ci
-    L.dtfill_num_kernels.argtypes = [ci]
-    L.dtfill_num_kernels.restype = ci
-    L.dtfill_kernel_name.argtypes = [ci, ci]
-    L.dtfill_kernel_name.restype = ctypes.c_char_p
-    L.dtfill_batch_timed.argtypes = [vp, ci, ci, ci, cf, cf, ci, vp, vp, vp, vp, vp, sz, vp, ctypes.c_uint, vp]
-    L.dtfill_batch_timed.restype = ci
-    L.dtfill_pass_stats.argtypes = [vp, sz, ci, ci, ci, ci, vp, vp]
-    L.dtfill_pass_stats.restype = ci
-    L.dtfill_outlier_removal.argtypes = [vp, ci, ci, ci, vp, vp]
-    L.dtfill_outlier_removal.restype = ci
-    L.dtfill_generate_multi_channel.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp]
-    L.dtfill_generate_multi_channel.restype = ci
-    L.dtfill_generate_multi_channel_backward_workspace_bytes.argtypes = [ci, ci, ci, ci]
-    L.dtfill_generate_multi_channel_backward_workspace_bytes.restype = sz
-    L.dtfill_generate_multi_channel_backward.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.dtfill_generate_multi_channel_backward.restype = ci
-    L.dtfill_demo_multi_channel_workspace_bytes.argtypes = [ci, ci, ci, ci]
-    L.dtfill_demo_multi_channel_workspace_bytes.restype = sz
-    L.dtfill_demo_multi_channel.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, sz, vp]
-    L.dtfill_demo_multi_channel.restype = ci
-    L.dtfill_crop_floor.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp, vp]
-    L.dtfill_crop_floor.restype = ci
-    L.dtfill_png16.argtypes = [vp, ci, ci, ci, ci, ci, cf, cf, cf, cf, vp, vp]
-    L.dtfill_png16.restype = ci
-    L.dtfill_line_subsample_workspace_bytes.argtypes = [ci, ci, ci]
-    L.dtfill_line_subsample_workspace_bytes.restype = sz
-    L.dtfill_line_subsample.argtypes = [vp, ci, ci, ci, vp, vp, ci, ci, vp, vp, vp, sz, vp]
-    L.dtfill_line_subsample.restype = ci
-    L.dtfill_depth_read_workspace_bytes.argtypes = [ci, ci, ci]
-    L.dtfill_depth_read_workspace_bytes.restype = sz
-    L.dtfill_depth_read.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, sz, vp]
-    L.dtfill_depth_read.restype = ci
-    L.dtfill_rgb_read_workspace_bytes.argtypes = [ci, ci, ci]
-    L.dtfill_rgb_read_workspace_bytes.restype = sz
-    L.dtfill_rgb_read.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]
-    L.dtfill_rgb_read.restype = ci
-    L.dtfill_metrics_workspace_bytes.argtypes = [ci]
-    L.dtfill_metrics_workspace_bytes.restype = sz
-    L.dtfill_metrics.argtypes = [vp, vp, ci, ctypes.c_longlong, ci, vp, vp, sz, vp]
-    L.dtfill_metrics.restype = ci
-    L.dtfill_train_loss_workspace_bytes.argtypes = [ci, ci, ci]
-    L.dtfill_train_loss_workspace_bytes.restype = sz
-    L.dtfill_train_loss.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, ci, ci, ci, ci, vp, vp, sz, vp]
-    L.dtfill_train_loss.restype = ci
-    L.dtfill_train_loss_backward.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
-    L.dtfill_train_loss_backward.restype = ci
-    L.dtfill_fill_backward_workspace_bytes.argtypes = [ci, ci, ci]
-    L.dtfill_fill_backward_workspace_bytes.restype = sz
-    L.dtfill_fill_backward.argtypes = [vp, vp, vp, ci, ci, ci, cf, vp, vp, vp, sz, vp]
-    L.dtfill_fill_backward.restype = ci
-    L.dtfill_nearest_gather_workspace_bytes.argtypes = [ci, ci, ci]
-    L.dtfill_nearest_gather_workspace_bytes.restype = sz
-    L.dtfill_nearest_gather.argtypes = [vp, vp, vp, ci, ci, ci, ci, cf, vp, vp, vp, vp, sz, vp]
-    L.dtfill_nearest_gather.restype = ci
-    L.dtfill_nearest_gather_backward_workspace_bytes.argtypes = [ci, ci, ci, ci]
-    L.dtfill_nearest_gather_backward_workspace_bytes.restype = sz
-    L.dtfill_nearest_gather_backward.argtypes = [vp, vp, vp, ci, ci, ci, ci, cf, vp, vp, vp, sz, vp]
-    L.dtfill_nearest_gather_backward.restype = ci
+    for name, (restype, argtypes) in _ABI.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
     _lib = L
     return L
 

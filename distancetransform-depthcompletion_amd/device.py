@@ -6,7 +6,9 @@ frame in a loop, demo.py:268-290 / eval_NYU.py:138-195) allocate nothing.
 """
 import contextlib
 import ctypes
+import os
 import threading
+import weakref
 
 import numpy as np
 import torch
@@ -23,6 +25,39 @@ def _require_gpu():
             "dtfill needs a HIP device (torch.cuda.is_available() is False); the operator has "
             "no CPU fallback -- the CPU restatement under oracle/ is test infrastructure only"
         )
+
+
+def _check_tensor(t, what, dtype=torch.float32, layout="[B,H,W]", like=None, like_name=None):
+    """The one rule for a tensor argument: contiguous, of `dtype`, on a GPU, of the rank `layout` spells out (one more than
+    its commas; at least that many where it ends in "...]"), and, with like=, of that tensor's shape and device."""
+    rank = layout.count(",") + 1
+    if t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or (t.dim() < rank if layout.endswith("...]") else t.dim() != rank):
+        raise ValueError("%s must be a contiguous %s CUDA tensor %s" % (what, str(dtype).replace("torch.", ""), layout))
+    if like is not None and (t.shape != like.shape or t.device != like.device):
+        raise ValueError("%s must have %s's shape and device" % (what, like_name))
+
+
+def _ptr(t):
+    """The device pointer the C side takes: NULL for an optional tensor that is not there."""
+    return None if t is None else t.data_ptr()
+
+
+def _stream(device):
+    """The current stream of `device` as the handle the C side takes."""
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def _sized(nbytes):
+    """A *_workspace_bytes() result: 0 is how the C side refuses a shape (DTFILL_ERR_SHAPE), raised here as that error."""
+    if nbytes == 0:
+        _lib.check(-2)
+    return nbytes
+
+
+def _workspace(nbytes, device):
+    """(a fresh uint8 tensor, the first 256-byte aligned address in it): nbytes of workspace as the C side wants them aligned."""
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+    return ws, ws.data_ptr() + (-ws.data_ptr()) % 256
 
 
 class DtFill:
@@ -55,6 +90,7 @@ class DtFill:
         self._out = None
         self._crop = None
         self._dev_in = None
+        self._pin_in = self._pin_status = self._pin_shape = None  # upload()'s page-locked staging
         self._home = {}  # buffer attribute -> the stream it was allocated under
         self._lock = threading.RLock()
 
@@ -66,11 +102,9 @@ class DtFill:
     def _ensure_locked(self, B, H, W):
         if self._shape == (B, H, W):
             return
-        nbytes = self.lib.dtfill_workspace_bytes(B, H, W, self.metric)
-        if nbytes == 0:
-            _lib.check(-2)
-        self._ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
-        self._ws_off = (-self._ws.data_ptr()) % 256
+        nbytes = _sized(self.lib.dtfill_workspace_bytes(B, H, W, self.metric))
+        self._ws, aligned = _workspace(nbytes, self.device)
+        self._ws_off = aligned - self._ws.data_ptr()
         self._ws_bytes = nbytes
         self._out = {
             "depth": torch.empty((B, H, W), dtype=torch.float32, device=self.device),
@@ -79,7 +113,7 @@ class DtFill:
             "status": torch.empty((B,), dtype=torch.int32, device=self.device),
         }
         self._shape = (B, H, W)
-        self._home["_ws"] = self._home["_out"] = torch.cuda.current_stream(self.device).cuda_stream
+        self._home["_ws"] = self._home["_out"] = _stream(self.device)
 
     def _on_stream(self, stream):
         """Before a pass on `stream` (holding the lock): every buffer of this object that was allocated under another stream
@@ -109,8 +143,7 @@ class DtFill:
         the window kernel's launch (_lib.FLAG_SEPARATE_FRAME: tests and A/B timing; the results are the same).  out: a dict of the
         caller's own tensors, name -> contiguous tensor of that output's shape and dtype on this device ("depth", "dt", "index",
         "status"), written in place of this object's buffers and returned: tensors no later call overwrites."""
-        if x.dtype != torch.float32 or not x.is_cuda or x.dim() != 3 or not x.is_contiguous():
-            raise ValueError("x must be a contiguous float32 CUDA tensor [B,H,W]")
+        _check_tensor(x, "x")
         B, H, W = x.shape
         with torch.cuda.device(x.device), self._lock:
             if x.device != self.device:
@@ -130,7 +163,7 @@ class DtFill:
                     raise ValueError("depth epilogue: 0 <= depth_rows_from < H, and not with timed=True")
                 if self._crop is None or self._crop.shape != (B, H - depth_rows_from, W):
                     self._crop = torch.empty((B, H - depth_rows_from, W), dtype=torch.float32, device=self.device)
-                    self._home["_crop"] = torch.cuda.current_stream(self.device).cuda_stream
+                    self._home["_crop"] = _stream(self.device)
                 if out is None or "depth" not in out:
                     o = dict(o, depth=self._crop)
             if out is not None:
@@ -173,7 +206,7 @@ class DtFill:
         with torch.cuda.device(self.device), self._lock:
             self._ensure_locked(B, H, W)
             current = torch.cuda.current_stream(self.device)
-            if getattr(self, "_pin_shape", None) != (B, H, W):
+            if self._pin_shape != (B, H, W):
                 self._pin_in = torch.empty((B, H, W), dtype=torch.float32).pin_memory()
                 self._dev_in = torch.empty((B, H, W), dtype=torch.float32, device=self.device)
                 self._pin_status = torch.empty((B,), dtype=torch.int32).pin_memory()
@@ -194,7 +227,7 @@ class DtFill:
             B, H, W = self._shape
             self._on_stream(torch.cuda.current_stream(self.device))
             _lib.check(self.lib.dtfill_pass_stats(self._ws.data_ptr() + self._ws_off, self._ws_bytes, B, H, W, self.metric, out.data_ptr(),
-                                                  torch.cuda.current_stream(self.device).cuda_stream))
+                                                  _stream(self.device)))
         return dict(zip(_lib.STATS, [int(v) for v in out.cpu().tolist()]))
 
     def run_numpy(self, x, src_thr=0.1, val_thr=0.1, want=WANT_ALL, depth_rows_from=0, depth_floor=None, outlier_removal=False):
@@ -250,16 +283,12 @@ class _HostPool:
     `cap_bytes` stay cached; beyond that a request gets a buffer that is simply released with its array."""
 
     def __init__(self, cap_bytes=2 << 30):
-        import threading
-
         self._free = {}
         self._lock = threading.Lock()
         self._cached = 0
         self._cap = cap_bytes
 
     def take(self, shape, dtype):
-        import weakref
-
         key = (tuple(shape), np.dtype(dtype).str)
         with self._lock:
             lst = self._free.get(key)
@@ -294,7 +323,6 @@ def _copy_pool():
     """Threads for host-side staging copies (numpy's copy loops release the GIL)."""
     global _pool
     if _pool is None:
-        import os
         from concurrent.futures import ThreadPoolExecutor
 
         n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
@@ -325,13 +353,11 @@ def host_link_bandwidth(nbytes=64 << 20, device=None, repeats=5):
 def outlier_removal_device(x):
     """x: contiguous float32 CUDA tensor [B,H,W] -> new tensor, data_read.py:103-128 on the device."""
     _require_gpu()
-    if x.dtype != torch.float32 or not x.is_cuda or x.dim() != 3 or not x.is_contiguous():
-        raise ValueError("x must be a contiguous float32 CUDA tensor [B,H,W]")
+    _check_tensor(x, "x")
     out = torch.empty_like(x)
     B, H, W = x.shape
     with torch.cuda.device(x.device):
-        _lib.check(_lib.load().dtfill_outlier_removal(x.data_ptr(), B, H, W, out.data_ptr(),
-                                                      torch.cuda.current_stream(x.device).cuda_stream))
+        _lib.check(_lib.load().dtfill_outlier_removal(x.data_ptr(), B, H, W, out.data_ptr(), _stream(x.device)))
     return out
 
 
@@ -339,9 +365,8 @@ def generate_multi_channel_device(data, mask, table_size=7, scale_num=4):
     """net.py:83-122 on the device.  data, mask: contiguous float32 CUDA tensors [B,H,W].
     Returns (lidar_1, lidar_2, lidar_3, lidar_4) with None beyond scale_num, like the reference."""
     _require_gpu()
-    for t in (data, mask):
-        if t.dtype != torch.float32 or not t.is_cuda or t.dim() != 3 or not t.is_contiguous():
-            raise ValueError("data and mask must be contiguous float32 CUDA tensors [B,H,W]")
+    _check_tensor(data, "data")
+    _check_tensor(mask, "mask")
     if data.shape != mask.shape:
         raise ValueError("data and mask shapes differ")
     B, H, W = data.shape
@@ -349,8 +374,7 @@ def generate_multi_channel_device(data, mask, table_size=7, scale_num=4):
     ptrs = [o.data_ptr() for o in outs] + [None] * (4 - scale_num)
     with torch.cuda.device(data.device):
         _lib.check(_lib.load().dtfill_generate_multi_channel(
-            data.data_ptr(), mask.data_ptr(), B, H, W, table_size, scale_num, ptrs[0], ptrs[1], ptrs[2],
-            torch.cuda.current_stream(data.device).cuda_stream))
+            data.data_ptr(), mask.data_ptr(), B, H, W, table_size, scale_num, ptrs[0], ptrs[1], ptrs[2], _stream(data.device)))
     return tuple([data] + outs + [None] * (4 - scale_num))
 
 
@@ -368,17 +392,16 @@ class _Scratch:
     @contextlib.contextmanager
     def hold(self, device, nbytes):
         """A 256-byte aligned pointer to at least nbytes of scratch on `device`, the current stream's, for one call's enqueue."""
-        key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+        key = (device.index, _stream(device))
         with self._lock:
             entry = self._entries.get(key)
             if entry is None:
-                entry = self._entries[key] = [threading.Lock(), None]
+                entry = self._entries[key] = [threading.Lock(), None, None]  # the lock, the tensor, its aligned address
         with entry[0]:
-            ws = entry[1]
-            if ws is None or ws.numel() < nbytes + 256:
+            if entry[1] is None or entry[1].numel() < nbytes + 256:
                 # (the tensor it replaces goes back to this stream's pool, behind the launches that still use it)
-                ws = entry[1] = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-            yield ws.data_ptr() + (-ws.data_ptr()) % 256
+                entry[1:] = _workspace(nbytes, device)
+            yield entry[2]
 
 
 _gmcb_ws = _Scratch()  # the backward's workspace
@@ -402,20 +425,16 @@ def generate_multi_channel_backward_device(mask, out2, out3, grads, table_size=7
             if required:
                 raise ValueError("%s is needed for scale_num %d" % (what, scale_num))
             continue
-        if t.dtype != torch.float32 or not t.is_cuda or t.dim() != 3 or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous float32 CUDA tensor [B,H,W]" % what)
-        if t.shape != mask.shape or t.device != mask.device:
-            raise ValueError("%s must have mask's shape and device" % what)
+        _check_tensor(t, what, like=mask, like_name="mask")
     B, H, W = mask.shape
     L = _lib.load()
-    ptr = lambda t: None if t is None else t.data_ptr()
     out = torch.empty_like(mask)
     with torch.cuda.device(mask.device):
         nbytes = L.dtfill_generate_multi_channel_backward_workspace_bytes(B, H, W, scale_num)
         with (_gmcb_ws.hold(mask.device, nbytes) if nbytes else contextlib.nullcontext()) as ws:
             _lib.check(L.dtfill_generate_multi_channel_backward(
-                mask.data_ptr(), ptr(out2), ptr(out3), B, H, W, int(table_size), int(scale_num), *[ptr(g) for g in grads],
-                out.data_ptr(), ws, nbytes, torch.cuda.current_stream(mask.device).cuda_stream))
+                mask.data_ptr(), _ptr(out2), _ptr(out3), B, H, W, int(table_size), int(scale_num), *[_ptr(g) for g in grads],
+                out.data_ptr(), ws, nbytes, _stream(mask.device)))
     return out
 
 
@@ -425,13 +444,11 @@ def demo_multi_channel_device(lidar, rgb=None, table_size=7, scale_range=90.0, s
     beyond scale_num: [B,H,W] = raw_k / scale_range without rgb, [B,H,W,C+1] = concat(rgb, raw_k / scale_range) /
     scale_range with it.  Asynchronous on the current stream."""
     _require_gpu()
-    if lidar.dtype != torch.float32 or not lidar.is_cuda or lidar.dim() != 3 or not lidar.is_contiguous():
-        raise ValueError("lidar must be a contiguous float32 CUDA tensor [B,H,W]")
+    _check_tensor(lidar, "lidar")
     B, H, W = lidar.shape
     C = 0
     if rgb is not None:
-        if rgb.dtype != torch.float32 or not rgb.is_cuda or rgb.dim() != 4 or not rgb.is_contiguous():
-            raise ValueError("rgb must be a contiguous float32 CUDA tensor [B,H,W,C]")
+        _check_tensor(rgb, "rgb", layout="[B,H,W,C]")
         if tuple(rgb.shape[:3]) != (B, H, W) or rgb.device != lidar.device:
             raise ValueError("rgb must hold lidar's frames: [%d,%d,%d,C] on %s" % (B, H, W, lidar.device))
         C = rgb.shape[3]
@@ -439,29 +456,21 @@ def demo_multi_channel_device(lidar, rgb=None, table_size=7, scale_range=90.0, s
         raise ValueError("scale_num must be 1, 2, 3 or 4, got %r" % (scale_num,))
     L = _lib.load()
     nbytes = L.dtfill_demo_multi_channel_workspace_bytes(B, H, W, scale_num)
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=lidar.device)
-    off = (-ws.data_ptr()) % 256
+    ws, ws_ptr = _workspace(nbytes, lidar.device)
     shape = (B, H, W) if rgb is None else (B, H, W, C + 1)
     outs = [torch.empty(shape, dtype=torch.float32, device=lidar.device) for _ in range(scale_num)]
     ptrs = [o.data_ptr() for o in outs] + [None] * (4 - scale_num)
     with torch.cuda.device(lidar.device):
-        _lib.check(L.dtfill_demo_multi_channel(lidar.data_ptr(), None if rgb is None else rgb.data_ptr(), C, B, H, W,
-                                               int(table_size), int(scale_num), float(scale_range), *ptrs,
-                                               ws.data_ptr() + off, nbytes,
-                                               torch.cuda.current_stream(lidar.device).cuda_stream))
+        _lib.check(L.dtfill_demo_multi_channel(lidar.data_ptr(), _ptr(rgb), C, B, H, W, int(table_size), int(scale_num),
+                                               float(scale_range), *ptrs, ws_ptr, nbytes, _stream(lidar.device)))
     return tuple(outs + [None] * (4 - scale_num))
-
-
-def _check_frames(t, what):
-    if t.dtype != torch.float32 or not t.is_cuda or t.dim() != 3 or not t.is_contiguous():
-        raise ValueError("%s must be a contiguous float32 CUDA tensor [B,H,W]" % what)
 
 
 def crop_floor_device(x, rows=None, cols=None, floor=None):
     """out = f(x[:, rows[0]:rows[1], cols[0]:cols[1]]); f = relu(d - floor) + floor when floor is given
     (demo.py:292-293, eval_NYU.py:202-205).  x: contiguous float32 CUDA tensor [B,H,W] -> new tensor."""
     _require_gpu()
-    _check_frames(x, "x")
+    _check_tensor(x, "x")
     B, H, W = x.shape
     r0, r1 = (0, H) if rows is None else rows
     c0, c1 = (0, W) if cols is None else cols
@@ -470,21 +479,19 @@ def crop_floor_device(x, rows=None, cols=None, floor=None):
     out = torch.empty((B, r1 - r0, c1 - c0), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         _lib.check(_lib.load().dtfill_crop_floor(x.data_ptr(), B, H, W, r0, r1, c0, c1, int(floor is not None),
-                                                 float(floor or 0.0), out.data_ptr(),
-                                                 torch.cuda.current_stream(x.device).cuda_stream))
+                                                 float(floor or 0.0), out.data_ptr(), _stream(x.device)))
     return out
 
 
 def png16_device(x, pad_top=96, floor=0.9, lo=0.0, hi=100.0, scale=256.0):
     """test.py:133-148 on the device: x float32 CUDA [B,H,W] -> uint16 CUDA [B, pad_top+H, W]."""
     _require_gpu()
-    _check_frames(x, "x")
+    _check_tensor(x, "x")
     B, H, W = x.shape
     out = torch.empty((B, H + pad_top, W), dtype=torch.uint16, device=x.device)
     with torch.cuda.device(x.device):
         _lib.check(_lib.load().dtfill_png16(x.data_ptr(), B, H, W, pad_top, int(floor is not None), float(floor or 0.0),
-                                            lo, hi, scale, out.data_ptr(),
-                                            torch.cuda.current_stream(x.device).cuda_stream))
+                                            lo, hi, scale, out.data_ptr(), _stream(x.device)))
     return out
 
 
@@ -495,20 +502,19 @@ def metrics_device(output, target, kind="kitti"):
     kinds = {"kitti": _lib.METRICS_KITTI, "nyu": _lib.METRICS_NYU}
     if kind not in kinds:
         raise ValueError("kind must be 'kitti' or 'nyu'")
-    for t in (output, target):
-        if t.dtype != torch.float32 or not t.is_cuda or t.dim() < 2 or not t.is_contiguous():
-            raise ValueError("output and target must be contiguous float32 CUDA tensors [B, ...]")
+    _check_tensor(output, "output", layout="[B, ...]")
+    _check_tensor(target, "target", layout="[B, ...]")
     if output.shape != target.shape:
         raise ValueError("output and target shapes differ")
     B = output.shape[0]
     n = output[0].numel()
     L = _lib.load()
     nbytes = L.dtfill_metrics_workspace_bytes(B)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=output.device)
+    ws, ws_ptr = _workspace(nbytes, output.device)
     out = torch.empty((B, len(_lib.METRICS_COLUMNS)), dtype=torch.float64, device=output.device)
     with torch.cuda.device(output.device):
-        _lib.check(L.dtfill_metrics(output.data_ptr(), target.data_ptr(), B, n, kinds[kind], out.data_ptr(),
-                                    ws.data_ptr(), nbytes, torch.cuda.current_stream(output.device).cuda_stream))
+        _lib.check(L.dtfill_metrics(output.data_ptr(), target.data_ptr(), B, n, kinds[kind], out.data_ptr(), ws_ptr, nbytes,
+                                    _stream(output.device)))
     return out
 
 
@@ -529,17 +535,14 @@ def _loss_args(pred, gt, lidar, correction, dataset, gt_thr, in_thr, rows, cols)
     for what, t in (("pred", pred), ("gt", gt), ("lidar", lidar), ("correction", correction)):
         if t is None:
             continue
-        _check_frames(t, what)
-        if t.shape != pred.shape or t.device != pred.device:
-            raise ValueError("%s must have pred's shape and device" % what)
+        _check_tensor(t, what, like=pred, like_name="pred")
     kind, gthr, ithr, prows, pcols = LOSS_PRESETS[dataset]
     B, H, W = pred.shape
     r0, r1 = (prows or (0, H)) if rows is None else rows
     c0, c1 = (pcols or (0, W)) if cols is None else cols
     if not (0 <= r0 < r1 <= H and 0 <= c0 < c1 <= W):
         raise ValueError("empty or out-of-frame window rows=%s cols=%s of a %dx%d frame" % ((r0, r1), (c0, c1), H, W))
-    ptrs = (pred.data_ptr(), None if correction is None else correction.data_ptr(), gt.data_ptr(),
-            None if lidar is None else lidar.data_ptr())
+    ptrs = (pred.data_ptr(), _ptr(correction), gt.data_ptr(), _ptr(lidar))
     return ptrs + (B, H, W, kind, float(gthr if gt_thr is None else gt_thr), float(ithr if in_thr is None else in_thr),
                    int(r0), int(r1), int(c0), int(c1))
 
@@ -555,7 +558,7 @@ def train_loss_device(pred, gt, lidar=None, correction=None, dataset="KITTI", gt
     with torch.cuda.device(pred.device):
         nbytes = L.dtfill_train_loss_workspace_bytes(*args[4:7])
         with _loss_ws.hold(pred.device, nbytes) as ws:
-            _lib.check(L.dtfill_train_loss(*args, stats.data_ptr(), ws, nbytes, torch.cuda.current_stream(pred.device).cuda_stream))
+            _lib.check(L.dtfill_train_loss(*args, stats.data_ptr(), ws, nbytes, _stream(pred.device)))
     return stats
 
 
@@ -576,12 +579,11 @@ def train_loss_backward_device(pred, gt, stats, g_main=None, g_aux=None, lidar=N
     for what, g in (("g_main", g_main), ("g_aux", g_aux)):
         if g is not None and (g.dtype != torch.float32 or g.device != pred.device or g.numel() != 1):
             raise ValueError("%s must be a float32 scalar on pred's device" % what)
-    ptr = lambda t: None if t is None else t.data_ptr()
     grad_pred = torch.empty_like(pred) if want_pred else None
     grad_corr = torch.empty_like(pred) if want_correction else None
     with torch.cuda.device(pred.device):
-        _lib.check(_lib.load().dtfill_train_loss_backward(*args, stats.data_ptr(), ptr(g_main), ptr(g_aux), ptr(grad_pred),
-                                                          ptr(grad_corr), torch.cuda.current_stream(pred.device).cuda_stream))
+        _lib.check(_lib.load().dtfill_train_loss_backward(*args, stats.data_ptr(), _ptr(g_main), _ptr(g_aux), _ptr(grad_pred),
+                                                          _ptr(grad_corr), _stream(pred.device)))
     return grad_pred, grad_corr
 
 
@@ -595,25 +597,18 @@ def fill_backward_device(x, index, grad_depth, val_thr=0.1):
     (grad_x, status): new tensors, status int32 [B] with _lib.FRAME_INDEX_ERROR for a frame whose gather would have raised (its
     gradient is all zeros).  Asynchronous on the current stream, no host synchronisation."""
     _require_gpu()
-    _check_frames(x, "x")
-    _check_frames(grad_depth, "grad_depth")
-    if index.dtype != torch.int32 or not index.is_cuda or index.dim() != 3 or not index.is_contiguous():
-        raise ValueError("index must be a contiguous int32 CUDA tensor [B,H,W]")
-    for what, t in (("index", index), ("grad_depth", grad_depth)):
-        if t.shape != x.shape or t.device != x.device:
-            raise ValueError("%s must have x's shape and device" % what)
+    _check_tensor(x, "x")
+    _check_tensor(index, "index", torch.int32, like=x, like_name="x")
+    _check_tensor(grad_depth, "grad_depth", like=x, like_name="x")
     B, H, W = x.shape
     L = _lib.load()
-    nbytes = L.dtfill_fill_backward_workspace_bytes(B, H, W)
-    if nbytes == 0:
-        _lib.check(-2)
+    nbytes = _sized(L.dtfill_fill_backward_workspace_bytes(B, H, W))
     grad_x = torch.empty_like(x)
     status = torch.empty((B,), dtype=torch.int32, device=x.device)
     with torch.cuda.device(x.device):
         with _fillb_ws.hold(x.device, nbytes) as ws:
             _lib.check(L.dtfill_fill_backward(x.data_ptr(), index.data_ptr(), grad_depth.data_ptr(), B, H, W, float(val_thr),
-                                              grad_x.data_ptr(), status.data_ptr(), ws, nbytes,
-                                              torch.cuda.current_stream(x.device).cuda_stream))
+                                              grad_x.data_ptr(), status.data_ptr(), ws, nbytes, _stream(x.device)))
     return grad_x, status
 
 
@@ -623,15 +618,11 @@ _near_ws = _Scratch()  # the nearest gather's workspace (forward and backward)
 def _check_near(x, index, payload, what):
     """The argument checks of the two nearest-gather calls (fill_backward_device's): x float32 [B,H,W], index int32 of x's
     shape, payload None or float32 [B,C,H,W] with x's frames, all contiguous CUDA tensors on x's device."""
-    _check_frames(x, "x")
-    if index.dtype != torch.int32 or not index.is_cuda or index.dim() != 3 or not index.is_contiguous():
-        raise ValueError("index must be a contiguous int32 CUDA tensor [B,H,W]")
-    if index.shape != x.shape or index.device != x.device:
-        raise ValueError("index must have x's shape and device")
+    _check_tensor(x, "x")
+    _check_tensor(index, "index", torch.int32, like=x, like_name="x")
     if payload is None:
         return 0
-    if payload.dtype != torch.float32 or not payload.is_cuda or payload.dim() != 4 or not payload.is_contiguous():
-        raise ValueError("%s must be a contiguous float32 CUDA tensor [B,C,H,W]" % what)
+    _check_tensor(payload, what, layout="[B,C,H,W]")
     if payload.shape[0] != x.shape[0] or payload.shape[2:] != x.shape[1:] or payload.device != x.device:
         raise ValueError("%s must have x's frames [B,C,H,W] and device" % what)
     C = payload.shape[1]
@@ -654,18 +645,14 @@ def nearest_gather_device(x, index, values=None, src_thr=0.1, want_pixel=True):
     _require_gpu()
     B, H, W = x.shape
     L = _lib.load()
-    nbytes = L.dtfill_nearest_gather_workspace_bytes(B, H, W)
-    if nbytes == 0:
-        _lib.check(-2)
+    nbytes = _sized(L.dtfill_nearest_gather_workspace_bytes(B, H, W))
     filled = torch.empty_like(values) if values is not None else None
     pixel = torch.empty_like(index) if want_pixel else None
     status = torch.empty((B,), dtype=torch.int32, device=x.device)
-    ptr = lambda t: None if t is None else t.data_ptr()
     with torch.cuda.device(x.device):
         with _near_ws.hold(x.device, nbytes) as ws:
-            _lib.check(L.dtfill_nearest_gather(x.data_ptr(), index.data_ptr(), ptr(values), C, B, H, W, float(src_thr), ptr(filled),
-                                               ptr(pixel), status.data_ptr(), ws, nbytes,
-                                               torch.cuda.current_stream(x.device).cuda_stream))
+            _lib.check(L.dtfill_nearest_gather(x.data_ptr(), index.data_ptr(), _ptr(values), C, B, H, W, float(src_thr),
+                                               _ptr(filled), _ptr(pixel), status.data_ptr(), ws, nbytes, _stream(x.device)))
     return filled, pixel, status
 
 
@@ -680,16 +667,14 @@ def nearest_gather_backward_device(x, index, grad_out, src_thr=0.1):
     _require_gpu()
     B, H, W = x.shape
     L = _lib.load()
-    nbytes = L.dtfill_nearest_gather_backward_workspace_bytes(B, H, W, C)
-    if nbytes == 0:
-        _lib.check(-2)
+    nbytes = _sized(L.dtfill_nearest_gather_backward_workspace_bytes(B, H, W, C))
     grad_values = torch.empty_like(grad_out)
     status = torch.empty((B,), dtype=torch.int32, device=x.device)
     with torch.cuda.device(x.device):
         with _near_ws.hold(x.device, nbytes) as ws:
             _lib.check(L.dtfill_nearest_gather_backward(x.data_ptr(), index.data_ptr(), grad_out.data_ptr(), C, B, H, W,
                                                         float(src_thr), grad_values.data_ptr(), status.data_ptr(), ws, nbytes,
-                                                        torch.cuda.current_stream(x.device).cuda_stream))
+                                                        _stream(x.device)))
     return grad_values, status
 
 
@@ -727,24 +712,19 @@ def line_subsample_device(x, K, E, keep_ratio=0.25, n_bins=64):
     if int(n_bins) != n_bins or n_bins < 1:
         raise ValueError("n_bins must be an integer >= 1, got %r" % (n_bins,))
     _require_gpu()
-    _check_frames(x, "x")
+    _check_tensor(x, "x")
     B, H, W = x.shape
     Kd = _calibration(K, 3, B, x.device, "K")
     Ed = _calibration(E, 4, B, x.device, "E")
     L = _lib.load()
-    nbytes = L.dtfill_line_subsample_workspace_bytes(B, H, W)
-    if nbytes == 0:
-        _lib.check(-2)
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=x.device)
-    off = (-ws.data_ptr()) % 256
+    nbytes = _sized(L.dtfill_line_subsample_workspace_bytes(B, H, W))
+    ws, ws_ptr = _workspace(nbytes, x.device)
     out = torch.empty_like(x)
     status = torch.empty((B,), dtype=torch.int32, device=x.device)
     with torch.cuda.device(x.device):
         _lib.check(L.dtfill_line_subsample(x.data_ptr(), B, H, W, Kd.data_ptr(), Ed.data_ptr(), int(n_bins), keep_every,
-                                           out.data_ptr(), status.data_ptr(), ws.data_ptr() + off, nbytes,
-                                           torch.cuda.current_stream(x.device).cuda_stream))
+                                           out.data_ptr(), status.data_ptr(), ws_ptr, nbytes, _stream(x.device)))
     return out, status
-
 
 
 def _read_size(size, what="size"):
@@ -758,6 +738,25 @@ def _read_size(size, what="size"):
     return H, W
 
 
+def _dims_arg(dims, B, device):
+    """The reads' `dims`: (h_b, w_b) per frame as numpy, list or tensor -> contiguous int32 tensor [B, 2] on `device`; None
+    (every frame fills its slot) stays None."""
+    if dims is None:
+        return None
+    d = dims if isinstance(dims, torch.Tensor) else torch.from_numpy(np.asarray(dims, dtype=np.int32))
+    d = d.to(device=device, dtype=torch.int32).contiguous()
+    if tuple(d.shape) != (B, 2):
+        raise ValueError("dims must be [B, 2] = [%d, 2], got shape %s" % (B, tuple(d.shape)))
+    return d
+
+
+def _first_row(first_row, H):
+    """The first row an rgb read keeps, as an int in [0, H)."""
+    if first_row != int(first_row) or not 0 <= first_row < H:
+        raise ValueError("first_row must be an integer in [0, %d), got %r" % (H, first_row))
+    return int(first_row)
+
+
 def depth_read_device(raw, dims=None, size=(1216, 352)):
     """data_read.py:81-99 after the PNG decode, on the device (include/dtfill.h, dtfill_depth_read): the values / 256 and
     Pillow's NEAREST resize to size = (width, height), PIL's order as data_read.py:96 writes it.  raw: contiguous uint16
@@ -766,28 +765,18 @@ def depth_read_device(raw, dims=None, size=(1216, 352)):
     _lib.READ_*: NOT_16BIT where every value of the frame is <= 255, the reference's assert; BAD_DIMS, with an all-zero
     frame, for dims outside [1, hmax] x [1, wmax]).  Asynchronous on the current stream; out feeds DtFill.run as it is."""
     _require_gpu()
-    if raw.dtype != torch.uint16 or not raw.is_cuda or raw.dim() != 3 or not raw.is_contiguous():
-        raise ValueError("raw must be a contiguous uint16 CUDA tensor [B,hmax,wmax]")
+    _check_tensor(raw, "raw", torch.uint16, "[B,hmax,wmax]")
     H, W = _read_size(size)
     B, hmax, wmax = raw.shape
-    d = None
-    if dims is not None:
-        d = dims if isinstance(dims, torch.Tensor) else torch.from_numpy(np.asarray(dims, dtype=np.int32))
-        d = d.to(device=raw.device, dtype=torch.int32).contiguous()
-        if tuple(d.shape) != (B, 2):
-            raise ValueError("dims must be [B, 2] = [%d, 2], got shape %s" % (B, tuple(d.shape)))
+    d = _dims_arg(dims, B, raw.device)
     L = _lib.load()
-    nbytes = L.dtfill_depth_read_workspace_bytes(B, H, W)
-    if nbytes == 0:
-        _lib.check(-2)
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=raw.device)
-    off = (-ws.data_ptr()) % 256
+    nbytes = _sized(L.dtfill_depth_read_workspace_bytes(B, H, W))
+    ws, ws_ptr = _workspace(nbytes, raw.device)
     out = torch.empty((B, H, W), dtype=torch.float32, device=raw.device)
     status = torch.empty((B,), dtype=torch.int32, device=raw.device)
     with torch.cuda.device(raw.device):
-        _lib.check(L.dtfill_depth_read(raw.data_ptr(), None if d is None else d.data_ptr(), B, hmax, wmax, H, W,
-                                       out.data_ptr(), status.data_ptr(), ws.data_ptr() + off, nbytes,
-                                       torch.cuda.current_stream(raw.device).cuda_stream))
+        _lib.check(L.dtfill_depth_read(raw.data_ptr(), _ptr(d), B, hmax, wmax, H, W, out.data_ptr(), status.data_ptr(), ws_ptr,
+                                       nbytes, _stream(raw.device)))
     return out, status
 
 
@@ -806,29 +795,18 @@ def rgb_read_device(raw, dims=None, size=(1216, 352), first_row=0, want="float",
     _lib.READ_BAD_DIMS, with an all-zero frame, for dims outside [1, hmax] x [1, wmax]).  New tensors, asynchronous on the
     current stream."""
     _require_gpu()
-    if raw.dtype != torch.uint8 or not raw.is_cuda or raw.dim() != 4 or not raw.is_contiguous():
-        raise ValueError("raw must be a contiguous uint8 CUDA tensor [B,hmax,wmax,C]")
+    _check_tensor(raw, "raw", torch.uint8, "[B,hmax,wmax,C]")
     if want not in RGB_WANT:
         raise ValueError("want must be one of %s, got %r" % (RGB_WANT, want))
     if layout not in RGB_LAYOUTS:
         raise ValueError("layout must be one of %s, got %r" % (sorted(RGB_LAYOUTS), layout))
     H, W = _read_size(size)
     B, hmax, wmax, C = raw.shape
-    if first_row != int(first_row) or not 0 <= first_row < H:
-        raise ValueError("first_row must be an integer in [0, %d), got %r" % (H, first_row))
-    first_row = int(first_row)
-    d = None
-    if dims is not None:
-        d = dims if isinstance(dims, torch.Tensor) else torch.from_numpy(np.asarray(dims, dtype=np.int32))
-        d = d.to(device=raw.device, dtype=torch.int32).contiguous()
-        if tuple(d.shape) != (B, 2):
-            raise ValueError("dims must be [B, 2] = [%d, 2], got shape %s" % (B, tuple(d.shape)))
+    first_row = _first_row(first_row, H)
+    d = _dims_arg(dims, B, raw.device)
     L = _lib.load()
-    nbytes = L.dtfill_rgb_read_workspace_bytes(B, H, W)
-    if nbytes == 0:
-        _lib.check(-2)
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=raw.device)
-    off = (-ws.data_ptr()) % 256
+    nbytes = _sized(L.dtfill_rgb_read_workspace_bytes(B, H, W))
+    ws, ws_ptr = _workspace(nbytes, raw.device)
     OH = H - first_row
     u8 = f32 = None
     if want != "float":
@@ -837,10 +815,9 @@ def rgb_read_device(raw, dims=None, size=(1216, 352), first_row=0, want="float",
         f32 = torch.empty((B, OH, W, C) if layout == "nhwc" else (B, C, OH, W), dtype=torch.float32, device=raw.device)
     status = torch.empty((B,), dtype=torch.int32, device=raw.device)
     with torch.cuda.device(raw.device):
-        _lib.check(L.dtfill_rgb_read(raw.data_ptr(), None if d is None else d.data_ptr(), B, hmax, wmax, C, H, W, first_row,
-                                     1 if normalize else 0, RGB_LAYOUTS[layout], None if u8 is None else u8.data_ptr(),
-                                     None if f32 is None else f32.data_ptr(), status.data_ptr(), ws.data_ptr() + off, nbytes,
-                                     torch.cuda.current_stream(raw.device).cuda_stream))
+        _lib.check(L.dtfill_rgb_read(raw.data_ptr(), _ptr(d), B, hmax, wmax, C, H, W, first_row, 1 if normalize else 0,
+                                     RGB_LAYOUTS[layout], _ptr(u8), _ptr(f32), status.data_ptr(), ws_ptr, nbytes,
+                                     _stream(raw.device)))
     return u8, f32, status
 
 
@@ -856,7 +833,7 @@ def default_op(metric="l1_cv"):
     of the process: a caller that goes through many short-lived streams constructs a DtFill of its own instead."""
     _require_gpu()
     dev = torch.cuda.current_device()
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream, metric)
+    key = (dev, _stream(dev), metric)
     with _default_ops_lock:
         op = _default_ops.get(key)
         if op is None:

@@ -12,16 +12,13 @@ step) is theirs.
 import numpy as np
 
 from . import device as _device
-from .tools import _as_f32_frames
+from .tools import _as_f32_frames, _upload
 
 
 def _to_device(a, ndim_frame=2):
-    import torch
-
     a = _as_f32_frames(a)
     lead = a.shape[:a.ndim - ndim_frame]
-    a3 = np.ascontiguousarray(a.reshape((-1,) + a.shape[a.ndim - ndim_frame:]))
-    return torch.from_numpy(a3).to(_device.default_op().device), lead
+    return _upload(a.reshape((-1,) + a.shape[a.ndim - ndim_frame:]), _device.default_op().device), lead
 
 
 def kitti_rows(lidar_batch, first_row=96):
@@ -94,14 +91,12 @@ class _ResultBase(object):
 
     def evaluate(self, output, target, photometric=0):
         """All elements of output / target (any equal shapes) count as ONE sample, as in the reference."""
-        import torch
-
         o, t = _as_f32_frames(output), _as_f32_frames(target)
         if o.shape != t.shape:
             raise IndexError("boolean index did not match indexed array: output %s, target %s" % (o.shape, t.shape))
         dev = _device.default_op().device
-        od = torch.from_numpy(np.ascontiguousarray(o.reshape(1, -1))).to(dev)
-        td = torch.from_numpy(np.ascontiguousarray(t.reshape(1, -1))).to(dev)
+        od = _upload(o.reshape(1, -1), dev)
+        td = _upload(t.reshape(1, -1), dev)
         row = _device.metrics_device(od, td, self._kind).cpu().numpy()[0]
         m = dict(zip(_device._lib.METRICS_COLUMNS, row.tolist()))
         self.mse, self.rmse, self.mae, self.irmse, self.imae = m["mse"], m["rmse"], m["mae"], m["irmse"], m["imae"]

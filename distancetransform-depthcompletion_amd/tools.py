@@ -10,8 +10,12 @@ all widening: DT_complete_batch accepts any HxW (the reference hard-codes 352x12
 reshapes, tools.py:25,27), and the thresholds the reference writes as literals are keyword
 arguments whose defaults are those literals.
 """
-import numpy as np
+import os
 
+import numpy as np
+import torch
+
+from . import _lib
 from . import device as _device
 
 
@@ -31,6 +35,11 @@ def _as_f32_frames(a):
             "the source/value predicates (tools.py:8,22) are evaluated in float32 on the device"
         )
     return a32
+
+
+def _upload(a, device):
+    """A host array -> a contiguous tensor of its dtype and shape on `device`."""
+    return torch.from_numpy(np.ascontiguousarray(a)).to(device)
 
 
 def nearest_point(refined_lidar, src_thr=0.1):
@@ -66,8 +75,6 @@ def nearest_source(x, values=None, src_thr=0.1, metric="l1_cv"):
     in a frame without one) -- with metric="l2" the raveled scipy.ndimage.distance_transform_edt(return_indices=True), ties to
     the smallest raster index.  values: float32, [H,W] or [C,H,W] for a frame, [B,H,W] or [B,C,H,W] for a batch; then
     (dt, pixel, filled), filled of values' shape with values' bits at the nearest source and +0.0 where there is none."""
-    import torch
-
     a = np.squeeze(_as_f32_frames(x))
     if a.ndim not in (2, 3):
         raise ValueError("nearest_source expects an array squeezable to [H,W] or [B,H,W], got shape %s" % (np.shape(x),))
@@ -84,8 +91,8 @@ def nearest_source(x, values=None, src_thr=0.1, metric="l1_cv"):
             raise ValueError("values of shape %s do not go with frames of shape %s" % (v.shape, np.shape(x)))
         v = v.reshape(B, -1, H, W)
     op = _device.default_op(metric)
-    xd = torch.from_numpy(np.ascontiguousarray(a)).to(op.device)
-    vd = None if v is None else torch.from_numpy(np.ascontiguousarray(v)).to(op.device)
+    xd = _upload(a, op.device)
+    vd = None if v is None else _upload(v, op.device)
     # dt and index in tensors of this call's own (the operator's buffers are the next caller's, on any thread), and the
     # operator's lock over both launches
     res = dict(dt=torch.empty_like(xd), index=torch.empty_like(xd, dtype=torch.int32))
@@ -121,27 +128,23 @@ def outlier_removal(lidar):
     """data_read.py:103-128 (the loader's optional filter in front of the fill, data_read.py:168-169):
     zero every pixel that exceeds the mean of the valid pixels in its 7x7 diamond by more than 1.0.
     Input squeezable to [H,W]; float32 [H,W] back, like the reference."""
-    import torch
-
     x = np.squeeze(_as_f32_frames(lidar))
     if x.ndim != 2:
         raise ValueError("outlier_removal expects an array squeezable to [H,W], got shape %s" % (np.shape(lidar),))
-    xd = torch.from_numpy(np.ascontiguousarray(x[None])).to(_device.default_op().device)
+    xd = _upload(x[None], _device.default_op().device)
     return _device.outlier_removal_device(xd)[0].cpu().numpy()
 
 
 def generate_multi_channel(lidar_data, lidar_mask, table_size=7, scale_num=4):
     """net.py:83-122 as a numpy function: lidar_data, lidar_mask [B,H,W,1] -> (lidar_1, .., lidar_4), each
     [B,H,W,1] float32, None beyond scale_num (the reference returns TF tensors of the same shapes)."""
-    import torch
-
     d = _as_f32_frames(lidar_data)
     m = _as_f32_frames(lidar_mask)
     if d.ndim != 4 or d.shape[-1] != 1 or m.shape != d.shape:
         raise ValueError("generate_multi_channel expects lidar_data and lidar_mask of shape [B,H,W,1]")
     dev = _device.default_op().device
-    dd = torch.from_numpy(np.ascontiguousarray(d[..., 0])).to(dev)
-    mm = torch.from_numpy(np.ascontiguousarray(m[..., 0])).to(dev)
+    dd = _upload(d[..., 0], dev)
+    mm = _upload(m[..., 0], dev)
     outs = _device.generate_multi_channel_device(dd, mm, table_size, scale_num)
     return tuple(None if o is None else o.cpu().numpy()[..., None] for o in outs)
 
@@ -153,10 +156,6 @@ def subsample_lidar(sparse_depth, intrinsic, extrinsic, keep_ratio=0.25, n_bins=
     of the input's shape: the kept pixels hold their input value, the others 0.  Raises np.linalg.LinAlgError for a
     singular intrinsic / extrinsic and ValueError for a frame without a valid pixel (> 0.1), as the reference does; a
     frame whose pitch interval is 0 or not finite comes back all zeros, as the reference's NaN labels keep nothing."""
-    import torch
-
-    from . import _lib
-
     _device.keep_every_of(keep_ratio)  # ValueError before any device work
     a = _as_f32_frames(sparse_depth)
     shape = a.shape
@@ -166,8 +165,7 @@ def subsample_lidar(sparse_depth, intrinsic, extrinsic, keep_ratio=0.25, n_bins=
         a = a[None]
     if a.ndim != 3:
         raise ValueError("subsample_lidar expects [H,W], [H,W,1], [B,H,W] or [B,H,W,1], got shape %s" % (shape,))
-    dev = _device.default_op().device
-    x = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    x = _upload(a, _device.default_op().device)
     out, status = _device.line_subsample_device(x, intrinsic, extrinsic, keep_ratio=keep_ratio, n_bins=n_bins)
     st = status.cpu().numpy()
     bad = np.flatnonzero(st & _lib.LINES_SINGULAR)
@@ -198,40 +196,53 @@ def _png_values(a, what):
     return a
 
 
-def _depth_read_frames(frames, size):
-    """The frames (checked by _png_values) -> (float32 [B, H, W, 1] in a page-locked array of its own, status int32 [B]):
-    one padded uint16 staging buffer that carries the dims behind the values, one H2D copy, one dtfill_depth_read, one
-    D2H copy of the result."""
-    import torch
+def _frame_size(frames, size):
+    """(H, W) of a batch read's output: size = (width, height) as PIL writes it, or, with size=None, the frames' own size."""
+    if size is not None:
+        return _device._read_size(size)
+    if any(f.shape != frames[0].shape for f in frames):
+        raise ValueError("size=None keeps the source size, so every frame must have the same shape; got %s"
+                         % sorted({f.shape for f in frames}))
+    return frames[0].shape[:2]
 
+
+def _stage_frames(frames, C, dtype):
+    """A ragged batch on the device.  frames: checked arrays [h, w] or [h, w, C] of any mixed sizes -> (raw [B, hmax, wmax, C]
+    of `dtype` (uint16 or uint8), dims int32 [B, 2], stage): the first two are views of one device tensor, filled by one H2D
+    copy from `stage`, a padded page-locked buffer that carries the dims behind the values.  The copy is asynchronous: the
+    caller keeps `stage` until it has synchronised (_read_back does), only then may the buffer go back to the pool."""
     B = len(frames)
-    if B == 0:
-        raise ValueError("depth_read_batch needs at least one frame")
     hmax = max(f.shape[0] for f in frames)
     wmax = max(f.shape[1] for f in frames)
-    if size is None:
-        if any(f.shape != frames[0].shape for f in frames):
-            raise ValueError("size=None keeps the source size, so every frame must have the same shape; got %s"
-                             % sorted({f.shape for f in frames}))
-        H, W = hmax, wmax
-    else:
-        H, W = _device._read_size(size)
-    n = B * hmax * wmax
-    n2 = n + (n & 1)  # the dims start 4-byte aligned
-    stage = _device._host_pool.take((n2 + 4 * B,), np.uint16)
-    raw = stage.array[:n].reshape(B, hmax, wmax)  # the padding is never read: left as it is
+    n = B * hmax * wmax * C
+    per = 4 // np.dtype(dtype).itemsize  # values per int32
+    n4 = -(-n // per) * per  # the dims start 4-byte aligned
+    stage = _device._host_pool.take((n4 + 2 * per * B,), dtype)
+    raw = stage.array[:n].reshape(B, hmax, wmax, C)  # the padding is never read: left as it is
     for b, f in enumerate(frames):
-        raw[b, :f.shape[0], :f.shape[1]] = f
-    stage.array[n2:].view(np.int32).reshape(B, 2)[:] = [f.shape for f in frames]
-    dev = _device.default_op().device
-    with torch.cuda.device(dev):
-        d = torch.empty((n2 + 4 * B,), dtype=torch.uint16, device=dev)
-        d.copy_(stage.tensor, non_blocking=True)
-        out, status = _device.depth_read_device(d[:n].view(B, hmax, wmax), d[n2:].view(torch.int32).view(B, 2), (W, H))
-        host = _device._host_pool.take((B, H, W, 1), np.float32)
-        host.tensor.copy_(out.view(B, H, W, 1), non_blocking=True)
-        st = status.cpu().numpy()  # synchronises: the staging buffer and the result are done with
-    return host.array, st
+        raw[b, :f.shape[0], :f.shape[1]] = f.reshape(f.shape[0], f.shape[1], C)
+    stage.array[n4:].view(np.int32).reshape(B, 2)[:] = [f.shape[:2] for f in frames]
+    d = torch.empty((n4 + 2 * per * B,), dtype=stage.tensor.dtype, device=_device.default_op().device)
+    d.copy_(stage.tensor, non_blocking=True)
+    return d[:n].view(B, hmax, wmax, C), d[n4:].view(torch.int32).view(B, 2), stage
+
+
+def _read_back(out, status, dtype):
+    """(the device tensor `out` in a page-locked array of its own, by one D2H copy; status as numpy)."""
+    host = _device._host_pool.take(tuple(out.shape), dtype)
+    host.tensor.copy_(out, non_blocking=True)
+    return host.array, status.cpu().numpy()  # synchronises: the staging buffer and the result are done with
+
+
+def _depth_read_frames(frames, size):
+    """The frames (checked by _png_values) -> (float32 [B, H, W, 1] in a page-locked array of its own, status int32 [B]):
+    one staged H2D copy, one dtfill_depth_read, one D2H copy of the result."""
+    if not frames:
+        raise ValueError("depth_read_batch needs at least one frame")
+    H, W = _frame_size(frames, size)
+    raw, dims, stage = _stage_frames(frames, 1, np.uint16)  # (stage: held to the end, past _read_back's synchronisation)
+    out, status = _device.depth_read_device(raw.squeeze(3), dims, (W, H))
+    return _read_back(out.unsqueeze(3), status, np.float32)
 
 
 def depth_read(filename):
@@ -239,10 +250,6 @@ def depth_read(filename):
     [352, 1216, 1], the values / 256 NEAREST-resized as Pillow does.  The PNG is decoded on the host, the rest runs on the
     device.  Raises the reference's AssertionErrors (file missing; every value <= 255) with its messages; values that do
     not fit uint16 raise TypeError."""
-    import os
-
-    from . import _lib
-
     assert os.path.exists(filename), "file not found: {}".format(filename)
     from PIL import Image
 
@@ -260,8 +267,6 @@ def depth_read_batch(frames, size=KITTI_SIZE, check=True):
     read_batch stacks (data_read.py:166, 172).  size=None keeps the source size, the read_one_val / read_one_test path
     (data_read.py:215, 261: / 256 without a resize); every frame must then have the same shape.  With check=True an
     AssertionError names the first frame whose values are all <= 255 (the reference's assert)."""
-    from . import _lib
-
     frames = [_png_values(f, "frame %d" % b) for b, f in enumerate(frames)]
     out, st = _depth_read_frames(frames, size)
     if check:
@@ -293,52 +298,23 @@ def rgb_read_batch(frames, size=KITTI_SIZE, first_row=0, dtype=np.uint8):
     img_batch Data_load.read_batch stacks (data_read.py:163, 175), uint8 [B, H, W, C] ([B, H, W] for 2-D frames);
     dtype=np.float32 the drivers' next two lines, img_batch[:, first_row:] / 255.0 as float32 (train.py:213-214).  first_row
     crops either form.  size=None keeps the source size, the read_one_val path (data_read.py:206-210); every frame must then
-    have the same shape.  One padded page-locked staging buffer that carries the dims behind the bytes, one H2D copy, one
-    dtfill_rgb_read, one D2H copy of the result, which is an array of its own."""
-    import torch
-
+    have the same shape.  One staged H2D copy, one dtfill_rgb_read, one D2H copy of the result, which is an array of its own."""
     dtype = np.dtype(dtype)
     if dtype not in (np.dtype(np.uint8), np.dtype(np.float32)):
         raise ValueError("dtype must be np.uint8 or np.float32, got %s" % dtype)
     frames = [_rgb_values(f, "frame %d" % b) for b, f in enumerate(frames)]
-    B = len(frames)
-    if B == 0:
+    if not frames:
         raise ValueError("rgb_read_batch needs at least one frame")
     if any(f.shape[2:] != frames[0].shape[2:] for f in frames):
         raise ValueError("every frame must have the same channel count; got shapes %s" % sorted({f.shape for f in frames}))
     C = frames[0].shape[2] if frames[0].ndim == 3 else 1
-    hmax = max(f.shape[0] for f in frames)
-    wmax = max(f.shape[1] for f in frames)
-    if size is None:
-        if any(f.shape != frames[0].shape for f in frames):
-            raise ValueError("size=None keeps the source size, so every frame must have the same shape; got %s"
-                             % sorted({f.shape for f in frames}))
-        H, W = hmax, wmax
-    else:
-        H, W = _device._read_size(size)
-    if first_row != int(first_row) or not 0 <= first_row < H:
-        raise ValueError("first_row must be an integer in [0, %d), got %r" % (H, first_row))
-    first_row = int(first_row)
-    n = B * hmax * wmax * C
-    n4 = (n + 3) & ~3  # the dims start 4-byte aligned
-    stage = _device._host_pool.take((n4 + 8 * B,), np.uint8)
-    raw = stage.array[:n].reshape(B, hmax, wmax, C)  # the padding is never read: left as it is
-    for b, f in enumerate(frames):
-        raw[b, :f.shape[0], :f.shape[1]] = f.reshape(f.shape[0], f.shape[1], C)
-    stage.array[n4:].view(np.int32).reshape(B, 2)[:] = [f.shape[:2] for f in frames]
-    dev = _device.default_op().device
-    want = "uint8" if dtype == np.uint8 else "float"
-    with torch.cuda.device(dev):
-        d = torch.empty((n4 + 8 * B,), dtype=torch.uint8, device=dev)
-        d.copy_(stage.tensor, non_blocking=True)
-        u8, f32, status = _device.rgb_read_device(d[:n].view(B, hmax, wmax, C), d[n4:].view(torch.int32).view(B, 2), (W, H),
-                                                  first_row=first_row, want=want)
-        out = u8 if f32 is None else f32
-        host = _device._host_pool.take(tuple(out.shape), dtype)
-        host.tensor.copy_(out, non_blocking=True)
-        st = status.cpu().numpy()  # synchronises: the staging buffer and the result are done with
+    H, W = _frame_size(frames, size)
+    first_row = _device._first_row(first_row, H)
+    raw, dims, stage = _stage_frames(frames, C, np.uint8)  # (stage: held to the end, past _read_back's synchronisation)
+    u8, f32, status = _device.rgb_read_device(raw, dims, (W, H), first_row=first_row, want="uint8" if dtype == np.uint8 else "float")
+    out, st = _read_back(u8 if f32 is None else f32, status, dtype)
     assert not st.any(), "dtfill_rgb_read: frame status %s" % st  # the dims are the frames' own
-    return host.array if frames[0].ndim == 3 else host.array[..., 0]
+    return out if frames[0].ndim == 3 else out[..., 0]
 
 
 def rgb_read(filename):
@@ -346,8 +322,6 @@ def rgb_read(filename):
     ([352, 1216] for a greyscale one, four channels for RGBA), NEAREST-resized as Pillow does.  The file is decoded on the
     host, the resize runs on the device.  Raises the reference's AssertionError for a missing file; pixel values that do not
     fit uint8 (a 16-bit PNG) raise TypeError where the reference's dtype='uint8' wraps them."""
-    import os
-
     assert os.path.exists(filename), "file not found: {}".format(filename)
     from PIL import Image
 
