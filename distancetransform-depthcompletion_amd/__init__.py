@@ -13,6 +13,7 @@ from ._lib import METRICS, DtfillError, build, load
 from .sharding import shard_range, gather_frames, fill_sharded, release_host_slab
 from .tools import DT_complete_batch, Distance_Transform, generate_multi_channel, nearest_point, outlier_removal, subsample_lidar
 from .tools import depth_read, depth_read_batch, nearest_source, rgb_read, rgb_read_batch
+from .tools import map_points_on_image, project_points
 from . import demo  # demo.py's own generate_multi_channel / _with_image / create_weight_matrix, reached as <package>.demo.*
 from .postfill import Result, Result_NYU, depth_floor, depth_to_png16, kitti_rows, nyu_eval_crop
 
@@ -24,6 +25,10 @@ def __getattr__(name):
 
         mod = importlib.import_module(__name__ + ".device")
         return mod if name == "device" else getattr(mod, name)
+    if name == "project_points_device":
+        import importlib
+
+        return importlib.import_module(__name__ + ".projection").project_points_device
     if name == "autograd":  # <package>.autograd.generate_multi_channel (net.py form) and .train_loss (imports torch too)
         import importlib
 
@@ -33,7 +38,8 @@ def __getattr__(name):
 
 __all__ = [
     "nearest_point", "DT_complete_batch", "Distance_Transform", "outlier_removal", "generate_multi_channel", "subsample_lidar",
-    "depth_read", "depth_read_batch", "rgb_read", "rgb_read_batch", "rgb_read_device", "nearest_source", "demo", "fill", "DtFill",
+    "depth_read", "depth_read_batch", "rgb_read", "rgb_read_batch", "rgb_read_device", "nearest_source",
+    "map_points_on_image", "project_points", "project_points_device", "demo", "fill", "DtFill",
     "shard_range", "gather_frames", "fill_sharded", "release_host_slab", "build", "load", "METRICS", "DtfillError",
     "Result", "Result_NYU", "depth_floor", "depth_to_png16", "kitti_rows", "nyu_eval_crop",
 ]

@@ -30,6 +30,12 @@ READ_NOT_16BIT = 1  # bit: every source value of the frame is <= 255 (DTFILL_REA
 READ_BAD_DIMS = 2  # bit: the frame's dims lie outside [1, hmax] x [1, wmax]; its output is all zeros
 RGB_NHWC = 0  # out_f32 [B, H - first_row, W, C] (DTFILL_RGB_*)
 RGB_NCHW = 1  # out_f32 [B, C, H - first_row, W]
+PROJ_REFERENCE = 0  # mode: map_points_on_image literally, last writer wins (DTFILL_PROJ_*)
+PROJ_ZBUFFER = 1  # mode: the nearest return per pixel
+PROJ_NO_POINTS = 1  # bit: nothing landed in the frame
+PROJ_INDEX_ERROR = 2  # bit (reference mode): the reference's assignment would raise IndexError; the frame is all zeros
+PROJ_BAD_COUNT = 4  # bit: counts[b] outside [0, N]; the frame is all zeros
+PROJ_COLUMNS = ("pixels", "inside", "behind", "outside")  # frame_counts' columns, DTFILL_PROJ_N of them
 PATHS = {"auto": 0, "general": FLAG_GENERAL_ONLY, "fused": FLAG_FUSED_ONLY}
 
 # the C ABI of include/dtfill.h: symbol -> (restype, argtypes), in the header's order.  tests/test_binding.py holds every entry to
@@ -61,6 +67,8 @@ _ABI = {
     "dtfill_depth_read": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, sz, vp]),
     "dtfill_rgb_read_workspace_bytes": (sz, [ci, ci, ci]),
     "dtfill_rgb_read": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
+    "dtfill_project_points_workspace_bytes": (sz, [ci, ci, ci, ci]),
+    "dtfill_project_points": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, cf, vp, vp, vp, vp, vp, sz, vp]),
     "dtfill_metrics_workspace_bytes": (sz, [ci]),
     "dtfill_metrics": (ci, [vp, vp, ci, ll, ci, vp, vp, sz, vp]),
     "dtfill_train_loss_workspace_bytes": (sz, [ci, ci, ci]),

@@ -89,6 +89,7 @@ namespace {
 #include "dtfill_lines.hpp"
 #include "dtfill_read.hpp"
 #include "dtfill_rgb.hpp"
+#include "dtfill_proj.hpp"
 #include "dtfill_fillb.hpp"
 #include "dtfill_near.hpp"
 
@@ -908,6 +909,34 @@ int dtfill_rgb_read(const uint8_t *raw, const int32_t *dims, int B, int hmax, in
         case 3: rgb_launch<3>(grid, st, stage, a); break;
         default: rgb_launch<4>(grid, st, stage, a); break;
     }
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+size_t dtfill_project_points_workspace_bytes(int B, int N, int H, int W) {
+    if (B < 1 || B > 65535 || N < 1 || H < 1 || W < 1 || (long long)B * N * 3 >= (1ll << 31) ||
+        (long long)B * H * W >= (1ll << 31))  // (stride 3: the call checks its own)
+        return 0;
+    return align256((size_t)B * H * W * sizeof(u64)) + align256((size_t)B * PJ_ACC * sizeof(int));
+}
+
+int dtfill_project_points(const float *points, const int32_t *counts, int B, int N, int stride, int H, int W, const double *K,
+                          const double *E, int mode, float min_z, float *out_f32, double *out_f64, int32_t *frame_status,
+                          int32_t *frame_counts, void *workspace, size_t ws_bytes, void *stream) {
+    if (!points || !K || !E || !workspace || (!out_f32 && !out_f64)) return DTFILL_ERR_NULL;
+    const size_t need = dtfill_project_points_workspace_bytes(B, N, H, W);
+    if (need == 0 || (stride != 3 && stride != 4) || (long long)B * N * stride >= (1ll << 31) ||
+        (mode != DTFILL_PROJ_REFERENCE && mode != DTFILL_PROJ_ZBUFFER))
+        return DTFILL_ERR_SHAPE;
+    if (mode == DTFILL_PROJ_ZBUFFER && !(min_z >= 0.0f && min_z < __builtin_inff())) return DTFILL_ERR_SHAPE;
+    if (ws_bytes < need || ((uintptr_t)workspace & 255)) return DTFILL_ERR_WORKSPACE;
+    int *acc = reinterpret_cast<int *>(static_cast<char *>(workspace) + align256((size_t)B * H * W * sizeof(u64)));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (mode == DTFILL_PROJ_REFERENCE)
+        proj_launch<DTFILL_PROJ_REFERENCE>(st, points, counts, B, N, stride, H, W, K, E, min_z, out_f32, out_f64, frame_status,
+                                           frame_counts, workspace, acc);
+    else
+        proj_launch<DTFILL_PROJ_ZBUFFER>(st, points, counts, B, N, stride, H, W, K, E, min_z, out_f32, out_f64, frame_status,
+                                         frame_counts, workspace, acc);
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 

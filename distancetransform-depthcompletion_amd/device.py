@@ -821,6 +821,15 @@ def rgb_read_device(raw, dims=None, size=(1216, 352), first_row=0, want="float",
     return u8, f32, status
 
 
+def __getattr__(name):
+    # the point projection's device function is defined in projection.py (which imports this module's helpers)
+    if name == "project_points_device":
+        from . import projection
+
+        return projection.project_points_device
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
 _default_ops = {}
 _default_ops_lock = threading.Lock()
 

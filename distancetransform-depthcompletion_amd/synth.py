@@ -9,6 +9,9 @@ There is no dataset in the container, so bench.py and the tests draw frames from
                   (data_read.py:360-364), n = 200 by default (eval_NYU.py:40)
   iid             generic HxW Bernoulli mask, depths U(lo,hi)
 All return float32 [B,H,W] with zeros at invalid pixels.
+  velodyne_points whole 360-degree sweeps of the same kind of scanner as point clouds in the Velodyne frame, float32
+                  [n, 4] (x, y, z, reflectance: the layout of a KITTI raw .bin), with K and E: the input of the point
+                  projection (project_points_device); most of a sweep lies behind or beside the camera.
   velodyne_scan   a simulated 64-laser spinning scanner projected into the camera, with the calibration that goes with
                   it: (x, K, E).  The input of the scan-line subsampling (line_subsample_device); not a bench.py config.
 """
@@ -131,6 +134,49 @@ def velodyne_scan(B, seed=0, hw=KITTI_HW, lasers=64, max_range=80.0):
         frame[v[order] * W + u[order]] = z[order]
         x[b] = (np.round(frame * 256.0) / 256.0).reshape(H, W).astype(np.float32)
     return x, K, E
+
+
+def velodyne_points(B, seed=0, hw=KITTI_HW, lasers=64, max_range=80.0, az_step_deg=0.16):
+    """B whole sweeps of a simulated spinning `lasers`-beam LiDAR: the full 360 degrees of azimuth in az_step_deg steps, in a
+    scene of velodyne_scan's kind (ground plane, a wall on either side, a few boxes, a few dropped returns), as the scanner
+    delivers them: ragged point clouds in the Velodyne frame, not projected.  Only about a quarter of a sweep lies in the
+    camera's field of view; the rest is behind or beside it.  Returns (clouds: a list of B float32 [n_b, 4] arrays, x, y, z,
+    reflectance, in firing order (azimuth-major), K float64 [B,3,3] intrinsics, E float64 [B,4,4] velo->cam extrinsics).
+    Deterministic for a given seed; a generator of its own, velodyne_scan's frames do not change with it."""
+    rng = np.random.default_rng(seed)
+    H, W = hw
+    clouds = []
+    K = np.zeros((B, 3, 3))
+    E = np.zeros((B, 4, 4))
+    perm = np.array([[0.0, -1.0, 0.0], [0.0, 0.0, -1.0], [1.0, 0.0, 0.0]])  # velo (x fwd, y left, z up) -> cam (x right, y down, z fwd)
+    for b in range(B):
+        f = 721.5 * (1.0 + rng.normal(0.0, 0.01))
+        K[b] = [[f, 0.0, W * 0.4906 + rng.normal(0.0, 2.0)], [0.0, f * (1.0 + rng.normal(0.0, 0.001)), H * 0.4585 + rng.normal(0.0, 2.0)],
+                [0.0, 0.0, 1.0]]
+        E[b, :3, :3] = _rot(rng, 0.5) @ perm
+        E[b, :3, 3] = np.array([-0.004, -0.076, -0.272]) + rng.normal(0.0, 0.01, 3)
+        E[b, 3, 3] = 1.0
+        elev = np.deg2rad(np.linspace(2.0, -24.9, lasers) + rng.normal(0.0, 0.02, lasers))
+        az = np.arange(-np.pi, np.pi, np.deg2rad(az_step_deg))
+        azl = az[:, None] + rng.uniform(0.0, np.deg2rad(az_step_deg), (1, lasers))  # [azimuth, laser]: firing order
+        el = np.broadcast_to(elev[None, :], azl.shape)
+        d = np.stack([np.cos(el) * np.cos(azl), np.cos(el) * np.sin(azl), np.sin(el)], -1).reshape(-1, 3)
+        t = np.full(d.shape[0], np.inf)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = np.where(d[:, 2] < 0, -1.73 / d[:, 2], t)
+            for side, off in ((1.0, rng.uniform(5.0, 9.0)), (-1.0, rng.uniform(4.0, 8.0))):
+                tw = side * off / d[:, 1]
+                hit = (tw > 0) & (tw * d[:, 2] < 2.5)
+                t = np.where(hit & (tw < t), tw, t)
+        for _ in range(int(rng.integers(2, 6))):
+            c = np.array([rng.uniform(6.0, 45.0) * rng.choice([-1.0, 1.0]), rng.uniform(-5.0, 5.0), -1.73])
+            size = np.array([rng.uniform(1.5, 4.5), rng.uniform(1.5, 2.0), rng.uniform(1.2, 2.5)])
+            t = np.minimum(t, _ray_box(d, c - [size[0] / 2, size[1] / 2, 0.0], c + [size[0] / 2, size[1] / 2, size[2]]))
+        keep = (t <= max_range) & (t > 0.9) & (rng.random(t.shape) > 0.03)  # range cap, blind zone, a few dropped returns
+        p = t[keep, None] * d[keep]
+        refl = rng.uniform(0.0, 1.0, (p.shape[0], 1))
+        clouds.append(np.hstack([p, refl]).astype(np.float32))
+    return clouds, K, E
 
 
 # BASELINE.json configs (index = position in BASELINE.json "configs")

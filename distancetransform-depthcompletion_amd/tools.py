@@ -5,6 +5,7 @@ Same names, argument meaning and error behaviour as
   solution_DeepNet/eval_NYU.py:114-133 nearest_point (threshold 0.001), Distance_Transform
   data_read.py:81-99                   depth_read (and depth_read_batch for Data_load.read_batch's stack of them)
   data_read.py:66-73                   rgb_read (and rgb_read_batch for read_batch's img_batch and the drivers' / 255.0)
+  subsample_Lidar_train.py:180-193     map_points_on_image (and project_points for a batch of ragged clouds, z-buffered)
 but the work is done by libdtfill.so on the current HIP device.  Differences from the reference,
 all widening: DT_complete_batch accepts any HxW (the reference hard-codes 352x1216 in its
 reshapes, tools.py:25,27), and the thresholds the reference writes as literals are keyword
@@ -176,6 +177,73 @@ def subsample_lidar(sparse_depth, intrinsic, extrinsic, keep_ratio=0.25, n_bins=
         raise ValueError("zero-size array to reduction operation maximum which has no identity (frame %d has no point "
                          "with depth > 0.1)" % bad[0])
     return out.cpu().numpy().reshape(shape)
+
+
+def _cloud(a, what):
+    """A point cloud as the kernel reads it: float32 [n, 3 or 4] (n may be 0), under _as_f32_frames' rule for other dtypes."""
+    a = np.asarray(a)
+    if a.ndim != 2 or a.shape[1] not in (3, 4):
+        raise ValueError("%s: expected points [n, 3] or [n, 4], got shape %s" % (what, a.shape))
+    return _as_f32_frames(a)
+
+
+def _stage_clouds(clouds, device):
+    """A ragged batch of clouds on the device: (points float32 [B, N, stride], counts int32 [B], stage): views of one device
+    tensor filled by one H2D copy from `stage`, a page-locked buffer that carries the counts (as bits) behind the records; the
+    padding records are never read and are left as they are.  The caller keeps `stage` until it has synchronised."""
+    B = len(clouds)
+    N = max(1, max(c.shape[0] for c in clouds))
+    stride = max(c.shape[1] for c in clouds)
+    n = B * N * stride
+    stage = _device._host_pool.take((n + B,), np.float32)
+    raw = stage.array[:n].reshape(B, N, stride)
+    for b, c in enumerate(clouds):
+        raw[b, :c.shape[0], :c.shape[1]] = c
+    stage.array[n:].view(np.int32)[:] = [c.shape[0] for c in clouds]
+    d = torch.empty((n + B,), dtype=torch.float32, device=device)
+    d.copy_(stage.tensor, non_blocking=True)
+    return d[:n].view(B, N, stride), d[n:].view(torch.int32), stage
+
+
+def _raise_index_error(status):
+    bad = np.flatnonzero(status & _lib.PROJ_INDEX_ERROR)
+    if bad.size:
+        raise IndexError("frame %d: a point's pixel index is out of bounds for the depth map (depth_map[v,u]=z)" % bad[0])
+
+
+def map_points_on_image(left_points, intrinsic, extrinsic, hw=(352, 1216)):
+    """subsample_Lidar_train.py:180-193 / subsample_Lidar_val.py:167-180: left_points [n, 3] in the Velodyne frame through
+    extrinsic [4,4] (velo->cam) and intrinsic [3,3], rounded to a pixel, depth_map[v, u] = z in point order (the last writer of
+    a pixel wins, negative indices wrap).  Returns the float64 [H, W] depth map, hw = (352, 1216) as the reference hard-codes
+    it.  Raises IndexError where the reference's assignment would (an index outside the wrap range, or not finite), and
+    ValueError for points that are not [n, 3].  The points are read as float32: float64 input must be exactly
+    float32-representable (TypeError otherwise), which holds for what get_all_points returns from float32 calibration."""
+    p = np.asarray(left_points)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError("map_points_on_image expects left_points of shape [n, 3], got shape %s" % (p.shape,))
+    cloud = _cloud(p, "left_points")  # (the argument errors come before any device work)
+    pts, counts, stage = _stage_clouds([cloud], _device.default_op().device)
+    _, status, _, f64 = _device.project_points_device(pts, counts, intrinsic, extrinsic, hw, mode="reference", want="float64")
+    out, st = _read_back(f64[0], status, np.float64)
+    _raise_index_error(st)
+    return out
+
+
+def project_points(clouds, K, E, hw=(352, 1216), mode="zbuffer", min_z=0.0):
+    """A batch of point clouds -> sparse depth frames (include/dtfill.h, dtfill_project_points).  clouds: a list of ragged
+    [n_i, 3 or 4] arrays in the Velodyne frame (a KITTI .bin read as float32 and reshaped to [-1, 4] goes in as it is; n_i may
+    be 0); K: intrinsics [3,3] or [B,3,3]; E: velo->cam extrinsics [4,4] or [B,4,4]; hw = (H, W).  mode "zbuffer" keeps the
+    nearest return per pixel and drops points with z <= min_z or outside the frame; "reference" is map_points_on_image's
+    assignment (IndexError where it would raise).  One page-locked staging buffer, one copy each way.  Returns (float32
+    [B, H, W] in an array of its own, counts int32 [B, 4]: pixels written, points inside, behind, outside)."""
+    clouds = [_cloud(c, "cloud %d" % b) for b, c in enumerate(clouds)]
+    if not clouds:
+        raise ValueError("project_points needs at least one cloud")
+    pts, counts, stage = _stage_clouds(clouds, _device.default_op().device)
+    frame, status, counts4 = _device.project_points_device(pts, counts, K, E, hw, mode=mode, min_z=min_z)
+    out, tail = _read_back(frame, torch.cat([status[:, None], counts4], 1), np.float32)
+    _raise_index_error(tail[:, 0])
+    return out, tail[:, 1:].copy()
 
 
 KITTI_SIZE = (1216, 352)  # data_read.py:96: PIL's (width, height)

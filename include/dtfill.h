@@ -376,6 +376,69 @@ int dtfill_rgb_read(const uint8_t *raw, const int32_t *dims, int B, int hmax, in
                     size_t ws_bytes, void *stream);
 
 /*
+ * map_points_on_image() of subsample_Lidar_train.py:180-193 / subsample_Lidar_val.py:167-180, on B point clouds at once: points
+ * in the Velodyne frame through E and K, rounded to a pixel, depth_map[v, u] = z.  The front of the pipeline for a caller who
+ * holds point clouds (KITTI raw .bin: float32 x, y, z, reflectance) and not frames; dtfill_line_subsample() skips this step
+ * because there the points came from a frame.  Two modes: the reference's assignment literally, and the z-buffered projection
+ * (nearest return per pixel) that sparse-depth maps are built with.
+ *
+ * points: float32 [B, N, stride], stride 3 or 4 (the 4th float is carried and ignored: a .bin buffer needs no repacking), only
+ * element-aligned.  counts: int32 [B], counts[b] = n_b, the number of frame b's records in use; NULL means N everywhere.  Only
+ * floats of the first n_b records of a frame are read: no padding record of a ragged batch.  K: float64 [B,3,3] intrinsics;
+ * E: float64 [B,4,4] velo->cam extrinsics (dtfill_line_subsample's conventions; row 3 of E is not read).
+ *
+ * Per point i < n_b, everything in IEEE double, no contraction, left to right as written:
+ *   X, Y, Z = the three floats widened;
+ *   c_r = E[r][0]*X + E[r][1]*Y + E[r][2]*Z + E[r][3]   for r = 0..2;
+ *   h_r = K[r][0]*c_0 + K[r][1]*c_1 + K[r][2]*c_2;
+ *   z = h_2,  u = rint(h_0 / z),  v = rint(h_1 / z), round half to even as np.round does.
+ *
+ * DTFILL_PROJ_REFERENCE: map_points_on_image literally.  A frame is valid when every point has finite u, v with u in [-W, W)
+ *   and v in [-H, H); a negative index wraps (u += W, v += H), as numpy's does.  Any point that violates this makes the frame
+ *   an index-error frame (the reference's assignment raises IndexError): its outputs are all +0.0 and its status
+ *   DTFILL_PROJ_INDEX_ERROR.  In a valid frame a pixel holds the z of the LARGEST i that landed on it (numpy assigns in order:
+ *   the last writer wins); any z is written, whatever its sign, +-inf included; pixels no point reached are +0.0.  min_z is
+ *   ignored.  INSIDE counts every one of the n_b points, BEHIND and OUTSIDE are 0.
+ * DTFILL_PROJ_ZBUFFER: a point is dropped in exactly these cases, checked in this order:
+ *   1. X, Y or Z is not finite, or z is not finite, or !(z > (double)min_z): counted as BEHIND;
+ *   2. u or v is not finite or lies outside [0, W) x [0, H) (no wrap): counted as OUTSIDE.
+ *   Among the points that land on a pixel the SMALLEST z wins, compared as doubles; among equal z the largest i (they hold
+ *   the same bits).  min_z must be finite and >= 0, else DTFILL_ERR_SHAPE.
+ * Both modes:
+ *   counts[b] outside [0, N]: DTFILL_PROJ_BAD_COUNT, outputs all +0.0, nothing of that frame is read;
+ *   DTFILL_PROJ_NO_POINTS is set when nothing landed (REFERENCE: n_b == 0); the outputs are then all +0.0 anyway;
+ *   out_f64[b][v][u] holds the winner's z bit for bit (the reference's float64 map; its callers' (map * 256).astype(np.uint16)
+ *     stays on the host); out_f32 holds (float)z, one round-to-nearest-even conversion: what dtfill_batch() takes.  Not both
+ *     NULL; both fully overwritten; neither may alias an input;
+ *   frame_status: int32 [B], nullable, DTFILL_PROJ_* bits; frame_counts: int32 [B, DTFILL_PROJ_N], nullable, columns PIXELS
+ *     (distinct pixels written), INSIDE (points that landed), BEHIND, OUTSIDE; all four are zero in a frame with a status bit
+ *     other than NO_POINTS.
+ * workspace: at least dtfill_project_points_workspace_bytes(B, N, H, W) bytes, 256-B aligned, the caller's, no initialisation
+ * needed (the kernels clear what they accumulate into), nothing kept between calls.  Asynchronous on `stream`; no allocation, no
+ * host synchronisation, re-entrant across streams.  The winner is decided by integer comparisons (a max of i + 1, a min of z's
+ * bit pattern), never by the order in which atomics arrive: the same bits on every run.
+ * Returns, all checked before any HIP call: DTFILL_ERR_NULL for a NULL points, K, E or workspace, or both outputs NULL;
+ * DTFILL_ERR_SHAPE for B, N, H, W < 1, B > 65535, stride not 3 or 4, B*N*stride >= 2^31, B*H*W >= 2^31, an unknown mode or a
+ * bad min_z; DTFILL_ERR_WORKSPACE for a workspace too small or not aligned; then DTFILL_ERR_LAUNCH if a launch failed.
+ */
+#define DTFILL_PROJ_REFERENCE 0 /* mode: the reference's in-order assignment, negative indices wrap */
+#define DTFILL_PROJ_ZBUFFER   1 /* mode: nearest return per pixel, points behind min_z or outside the frame dropped */
+#define DTFILL_PROJ_NO_POINTS   1 /* status bit: nothing landed in the frame */
+#define DTFILL_PROJ_INDEX_ERROR 2 /* status bit (REFERENCE): a point's pixel lies outside the wrap range or is not finite */
+#define DTFILL_PROJ_BAD_COUNT   4 /* status bit: counts[b] outside [0, N] */
+#define DTFILL_PROJ_PIXELS  0 /* frame_counts columns */
+#define DTFILL_PROJ_INSIDE  1
+#define DTFILL_PROJ_BEHIND  2
+#define DTFILL_PROJ_OUTSIDE 3
+#define DTFILL_PROJ_N 4
+size_t dtfill_project_points_workspace_bytes(int B, int N, int H, int W); /* 0 on a bad shape (B*N*3 >= 2^31 included) */
+int dtfill_project_points(const float *points, const int32_t *counts /* nullable */, int B, int N, int stride,
+                          int H, int W, const double *K, const double *E, int mode, float min_z,
+                          float *out_f32 /* nullable */, double *out_f64 /* nullable */,
+                          int32_t *frame_status /* nullable */, int32_t *frame_counts /* nullable */,
+                          void *workspace, size_t ws_bytes, void *stream);
+
+/*
  * Error metrics of evaluation.py, one row per frame:
  *   DTFILL_METRICS_KITTI  Result.evaluate, evaluation.py:82-123 (metres -> mm for mse/rmse/mae, -> 1/km for
  *                         irmse/imae; the deltas stay 0 as in the reference);
