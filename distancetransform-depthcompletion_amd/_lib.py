@@ -30,6 +30,8 @@ READ_NOT_16BIT = 1  # bit: every source value of the frame is <= 255 (DTFILL_REA
 READ_BAD_DIMS = 2  # bit: the frame's dims lie outside [1, hmax] x [1, wmax]; its output is all zeros
 RGB_NHWC = 0  # out_f32 [B, H - first_row, W, C] (DTFILL_RGB_*)
 RGB_NCHW = 1  # out_f32 [B, C, H - first_row, W]
+NYU_MAX_RADIUS = 8  # the largest filter radius per axis dtfill_nyu_read takes (DTFILL_NYU_*)
+NYU_INDEX_ERROR = 1  # bit: a sample of the frame lies outside it and was skipped; numpy would raise IndexError
 PROJ_REFERENCE = 0  # mode: map_points_on_image literally, last writer wins (DTFILL_PROJ_*)
 PROJ_ZBUFFER = 1  # mode: the nearest return per pixel
 PROJ_NO_POINTS = 1  # bit: nothing landed in the frame
@@ -67,6 +69,8 @@ _ABI = {
     "dtfill_depth_read": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, sz, vp]),
     "dtfill_rgb_read_workspace_bytes": (sz, [ci, ci, ci]),
     "dtfill_rgb_read": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
+    "dtfill_nyu_read_workspace_bytes": (sz, [ci, ci, ci]),
+    "dtfill_nyu_read": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, vp, ci, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp, sz, vp]),
     "dtfill_project_points_workspace_bytes": (sz, [ci, ci, ci, ci]),
     "dtfill_project_points": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, cf, vp, vp, vp, vp, vp, sz, vp]),
     "dtfill_metrics_workspace_bytes": (sz, [ci]),

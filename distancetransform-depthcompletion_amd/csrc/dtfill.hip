@@ -89,6 +89,7 @@ namespace {
 #include "dtfill_lines.hpp"
 #include "dtfill_read.hpp"
 #include "dtfill_rgb.hpp"
+#include "dtfill_nyu.hpp"
 #include "dtfill_proj.hpp"
 #include "dtfill_fillb.hpp"
 #include "dtfill_near.hpp"
@@ -908,6 +909,56 @@ int dtfill_rgb_read(const uint8_t *raw, const int32_t *dims, int B, int hmax, in
         case 2: rgb_launch<2>(grid, st, stage, a); break;
         case 3: rgb_launch<3>(grid, st, stage, a); break;
         default: rgb_launch<4>(grid, st, stage, a); break;
+    }
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+size_t dtfill_nyu_read_workspace_bytes(int B, int H, int W) {
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long long)B * H * W >= (1ll << 31)) return 0;
+    return align256((size_t)B * (((size_t)H * W + 31) / 32) * sizeof(u32));  // one bit per output pixel
+}
+
+int dtfill_nyu_read(const uint8_t *rgb, const float *depth, int B, int C, int hin, int win, int H, int W, const double *wy,
+                    int ry, const double *wx, int rx, const int32_t *samples, int n, int normalize, int layout,
+                    float *out_rgb, float *out_gt, float *out_lidar, int32_t *frame_status, void *workspace, size_t ws_bytes,
+                    void *stream) {
+    if ((!rgb && !depth) || !workspace || !rgb != !out_rgb || (!depth && (out_gt || out_lidar)) ||
+        (depth && !out_gt && !out_lidar))
+        return DTFILL_ERR_NULL;
+    const size_t need = dtfill_nyu_read_workspace_bytes(B, H, W);
+    if (need == 0 || hin < 1 || win < 1 || H > hin || W > win || ry < 0 || ry > DTFILL_NYU_MAX_RADIUS || rx < 0 ||
+        rx > DTFILL_NYU_MAX_RADIUS || !wy != (ry == 0) || !wx != (rx == 0) || n < 0 ||
+        (rgb && (C < 1 || C > 4 || (layout != DTFILL_RGB_NHWC && layout != DTFILL_RGB_NCHW))))
+        return DTFILL_ERR_SHAPE;
+    const long long lim = 1ll << 31, src = (long long)B * hin * win;  // (hin * win <= src: B * H * W < 2^31 bounds neither)
+    if ((long long)hin * win >= lim || src >= lim || (rgb && (src * C >= lim || (long long)B * H * W * C >= lim)) ||
+        (long long)B * n * 2 >= lim)
+        return DTFILL_ERR_SHAPE;
+    if (ws_bytes < need || ((uintptr_t)workspace & 255)) return DTFILL_ERR_WORKSPACE;
+    NyArgs a{};
+    a.y.f = (double)hin / H;
+    a.x.f = (double)win / W;
+    a.y.n_in = hin, a.y.n_out = H, a.y.r = ry;
+    a.x.n_in = win, a.x.n_out = W, a.x.r = rx;
+    for (int k = 0; k <= ry && wy; ++k) a.y.w[k] = wy[k];
+    for (int k = 0; k <= rx && wx; ++k) a.x.w[k] = wx[k];
+    a.normalize = normalize, a.layout = layout;
+    a.words = ((size_t)H * W + 31) / 32;
+    a.out_rgb = out_rgb, a.out_gt = out_gt, a.out_lidar = out_lidar;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    u32 *mask = samples && n > 0 ? static_cast<u32 *>(workspace) : nullptr;
+    const size_t nclear = mask ? (size_t)B * a.words : (size_t)B;
+    if (mask || frame_status)
+        k_nyu_clear<<<(unsigned)((nclear + 255) / 256), 256, 0, st>>>(mask, mask ? nclear : 0, frame_status, B);
+    if (mask)
+        k_nyu_mark<<<(unsigned)(((size_t)B * n + 255) / 256), 256, 0, st>>>(samples, B, n, H, W, a.words, mask, frame_status);
+    if (rgb) {
+        a.src = rgb, a.C = C, a.mask = nullptr;
+        nyu_launch<u8>(st, a, B);
+    }
+    if (depth) {
+        a.src = depth, a.C = 1, a.mask = mask;
+        nyu_launch<float>(st, a, B);
     }
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }

@@ -827,6 +827,10 @@ def __getattr__(name):
         from . import projection
 
         return projection.project_points_device
+    if name == "nyu_read_device":  # likewise in nyu.py
+        from . import nyu
+
+        return nyu.nyu_read_device
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 

@@ -9,6 +9,8 @@ There is no dataset in the container, so bench.py and the tests draw frames from
                   (data_read.py:360-364), n = 200 by default (eval_NYU.py:40)
   iid             generic HxW Bernoulli mask, depths U(lo,hi)
 All return float32 [B,H,W] with zeros at invalid pixels.
+  nyu_dense       a stored NYU sample before the loader: dense float32 depth [B,480,640] (planes and boxes, 0.5-10 m) and a
+                  uint8 image [B,3,480,640]: the input of nyu_read_device.  Tests and scripts only; not a bench.py config.
   velodyne_points whole 360-degree sweeps of the same kind of scanner as point clouds in the Velodyne frame, float32
                   [n, 4] (x, y, z, reflectance: the layout of a KITTI raw .bin), with K and E: the input of the point
                   projection (project_points_device); most of a sweep lies behind or beside the camera.
@@ -51,6 +53,37 @@ def nyu_pattern(B, n=200, seed=0, hw=NYU_HW, lo=1.0, hi=10.0):
         c = rng.integers(0, W - 16, size=n) + 8
         x[b, r, c] = rng.uniform(lo, hi, size=n).astype(np.float32)
     return x
+
+
+def nyu_dense(B, seed=0, hw=NYU_HW):
+    """A stored NYU sample before the loader: (depth float32 [B, h, w], rgb uint8 [B, 3, h, w], the h5 files' layouts).  The
+    depth is dense, 0.5-10 m: a tilted back plane, a floor plane below a horizon, and a few boxes in front of them (sharp
+    depth edges for the resize to smear).  The image is shaded from the depth, with a texture per channel, over the whole
+    0..255 range.  For the tests and scripts/bench_nyu_read.py: the input of nyu_read_device."""
+    rng = np.random.default_rng(seed)
+    h, w = hw
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    u, v = xx / max(w - 1, 1), yy / max(h - 1, 1)
+    depth = np.empty((B, h, w), np.float32)
+    rgb = np.empty((B, 3, h, w), np.uint8)
+    for b in range(B):
+        d = rng.uniform(5.0, 10.0) + rng.uniform(-2.0, 2.0) * (u - 0.5) + rng.uniform(-1.0, 1.0) * (v - 0.5)
+        horizon = rng.uniform(0.45, 0.7)
+        floor = rng.uniform(1.2, 1.8) / np.maximum(v - horizon + 0.05, 1e-3)  # a floor under the camera: nearer lower down
+        d = np.where(v > horizon, np.minimum(d, floor), d)
+        for _ in range(int(rng.integers(3, 7))):
+            y0, x0 = rng.uniform(0.0, 0.8), rng.uniform(0.0, 0.8)
+            y1, x1 = y0 + rng.uniform(0.1, 0.4), x0 + rng.uniform(0.05, 0.3)
+            box = (v >= y0) & (v < y1) & (u >= x0) & (u < x1)
+            d = np.where(box, np.minimum(d, rng.uniform(0.8, 6.0) + 0.3 * (u - x0)), d)
+        d = np.clip(d, 0.5, 10.0)
+        depth[b] = d.astype(np.float32)
+        for c in range(3):
+            shade = 1.0 - (d - 0.5) / 9.5  # near is bright
+            tex = 0.5 + 0.5 * np.sin(2 * np.pi * (rng.uniform(2, 9) * u + rng.uniform(2, 9) * v + rng.uniform()))
+            noise = rng.uniform(-0.05, 0.05, size=(h, w))
+            rgb[b, c] = np.clip(np.rint(255.0 * (0.6 * shade + 0.4 * tex + noise)), 0, 255).astype(np.uint8)
+    return depth, rgb
 
 
 def iid(B, H, W, p, seed=0, lo=1.0, hi=80.0):

@@ -397,3 +397,82 @@ def rgb_read(filename):
     rgb_png = _rgb_values(np.array(img_file), filename)
     img_file.close()
     return rgb_read_batch([rgb_png], KITTI_SIZE)[0]
+
+
+def nyu_taps(n_in, n_out):
+    """The Gaussian pre-filter of skimage's anti-aliased resize for one axis reduced from n_in to n_out, as
+    scipy.ndimage.gaussian_filter builds it: sigma = (f - 1) / 2 at f = n_in / n_out, radius r = int(4 sigma + 0.5),
+    w[k] = exp(-0.5 / sigma^2 * k^2) over the sum of all 2r + 1.  Returns (the half kernel w[0..r] as contiguous float64, r),
+    or (None, 0) where the axis has no filter pass (r == 0: f < 1.25).  The one statement of the taps: dtfill_nyu_read takes
+    them from its caller, so that numpy's exp and sum, not a C library's, decide their bits."""
+    n_in, n_out = int(n_in), int(n_out)
+    if not 1 <= n_out <= n_in:
+        raise ValueError("nyu_taps: need 1 <= n_out <= n_in, got %d -> %d" % (n_in, n_out))
+    sigma = (n_in / n_out - 1) / 2
+    r = int(4.0 * sigma + 0.5)
+    if r == 0:
+        return None, 0
+    x = np.arange(-r, r + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    phi = phi / phi.sum()
+    return np.ascontiguousarray(phi[r:]), r
+
+
+def nyu_read_batch(rgb, depth, sample_rate=64, size=(240, 320), rng=None, samples=None):
+    """read_one_val_NYU (data_read.py:337-371; Data_load_NYU.read_batch, :295-335, does the same per frame) on arrays, since
+    the h5 read stays on the host: rgb uint8 [B, 3, h, w] (or one [3, h, w]) and depth float32 [B, h, w] (or [h, w]) as the
+    files store them -> (img float32 [B, H, W, 3] = resize(rgb) * 255, lidar float32 [B, H, W] = gt * Mask, gt float32
+    [B, H, W] = resize(depth)), size = (rows, cols) as the reference passes it to skimage.  Per frame sample_rate rows are
+    drawn with randint(H - 12) and then sample_rate columns with randint(W - 16), + 6 / + 8, in the reference's order: from
+    numpy's legacy global state when rng is None (np.random.seed(s) before the call gives the reference's mask), else from
+    rng (a RandomState's randint or a Generator's integers).  samples: int [B, n, 2] of (row, col) to mark instead of any
+    draw (nothing is added to them); IndexError, as numpy's Mask[...] = 1 raises it, for one outside the frame.  One staged
+    H2D copy, one dtfill_nyu_read, one D2H copy per result."""
+    rgb, depth = np.asarray(rgb), np.asarray(depth)
+    if rgb.ndim == 3 and depth.ndim == 2:
+        rgb, depth = rgb[None], depth[None]
+    if rgb.ndim != 4 or depth.ndim != 3 or rgb.shape[0] != depth.shape[0] or rgb.shape[2:] != depth.shape[1:] or 0 in rgb.shape:
+        raise ValueError("expected rgb [B, C, h, w] and depth [B, h, w], got shapes %s and %s" % (rgb.shape, depth.shape))
+    if rgb.dtype != np.uint8:
+        raise TypeError("rgb must be uint8 as the files store it, got dtype %s" % rgb.dtype)
+    depth = _as_f32_frames(depth)
+    B, C, h, w = rgb.shape
+    from . import nyu as _nyu  # (nyu.py imports this module)
+
+    H, W = _nyu._nyu_size(size, h, w)
+    if samples is not None:
+        samples = np.asarray(samples)
+        if samples.ndim != 3 or samples.shape[0] != B or samples.shape[2] != 2 or samples.dtype.kind not in "iu":
+            raise ValueError("samples must be integers [B, n, 2] = [%d, n, 2], got %s %s" % (B, samples.dtype, samples.shape))
+        if samples.size and (samples.min() < -2 ** 31 or samples.max() >= 2 ** 31):
+            raise IndexError("a sample index does not fit int32")
+        samples = samples.astype(np.int32)
+        n = samples.shape[1]
+    else:
+        n = int(sample_rate)
+        if n != sample_rate or n < 0 or H <= 12 or W <= 16:
+            raise ValueError("sample_rate must be an integer >= 0 and size larger than (12, 16), got %r and %r"
+                             % (sample_rate, size))
+        draw = np.random.randint if rng is None else getattr(rng, "integers", None) or rng.randint
+        samples = np.empty((B, n, 2), np.int32)
+        for b in range(B):
+            samples[b, :, 0] = draw(H - 12, size=n) + 6  # first_index, then second_index: the reference's order
+            samples[b, :, 1] = draw(W - 16, size=n) + 8
+    nd, ns = depth.size * 4, samples.size * 4
+    stage = _device._host_pool.take((nd + ns + rgb.size,), np.uint8)  # depth | samples | rgb, the 4-byte values first
+    stage.array[:nd].view(np.float32)[:] = depth.reshape(-1)
+    stage.array[nd:nd + ns].view(np.int32)[:] = samples.reshape(-1)
+    stage.array[nd + ns:] = rgb.reshape(-1)
+    d = torch.empty((nd + ns + rgb.size,), dtype=torch.uint8, device=_device.default_op().device)
+    d.copy_(stage.tensor, non_blocking=True)
+    img, gt, lidar, status = _nyu.nyu_read_device(
+        d[nd + ns:].view(B, C, h, w), d[:nd].view(torch.float32).view(B, h, w),
+        d[nd:nd + ns].view(torch.int32).view(B, n, 2) if n else None, (H, W))
+    hosts = [_device._host_pool.take(tuple(t.shape), np.float32) for t in (img, lidar, gt)]
+    for host, t in zip(hosts, (img, lidar, gt)):
+        host.tensor.copy_(t, non_blocking=True)
+    st = status.cpu().numpy()  # synchronises: the staging buffer and the results are done with
+    bad = np.flatnonzero(st & _lib.NYU_INDEX_ERROR)
+    if bad.size:  # (never after the draws: they lie inside the frame)
+        raise IndexError("frame %d: a sample index is out of bounds for the %d x %d mask" % (bad[0], H, W))
+    return tuple(host.array for host in hosts)

@@ -376,6 +376,62 @@ int dtfill_rgb_read(const uint8_t *raw, const int32_t *dims, int B, int hmax, in
                     size_t ws_bytes, void *stream);
 
 /*
+ * The per-sample work of the reference's NYU loaders (Data_load_NYU.read_batch, data_read.py:295-335; read_one_val_NYU,
+ * :337-371; the two copies at :443-473 and :485-580) on B stored samples at once: the transpose of the image, the anti-aliased
+ * skimage.transform.resize of image and dense depth from hin x win to H x W, the sparse sampling depth = gt * Mask, the
+ * loader's rgb * 255 and, on request, the drivers' rgb / 255.0 (eval_NYU.py:164-165).  The host keeps the h5 read and the
+ * random draws.  For a reduction that resize is scipy.ndimage.gaussian_filter(mode='mirror') followed by
+ * scipy.ndimage.zoom(order=1, mode='mirror', grid_mode=True), and this is the arithmetic of those two, bit for bit:
+ *
+ * Geometry, per axis (n_in -> n_out, n_out <= n_in):  f = (double)n_in / n_out;  sigma = (f - 1) / 2;
+ *   radius r = int(4 sigma + 0.5), the filter's half width.  r == 0 (sigma < 0.125; f == 1 among them): the axis has no pass.
+ * Taps: the CALLER computes the half kernel w[0..r] (w[k] = exp(-0.5 / sigma^2 * k^2) over the sum of all 2r + 1, as scipy's
+ *   _gaussian_kernel1d does in numpy: tools.nyu_taps) and passes it with r, so that no exp of a C library enters the bits.
+ *   wy / wx are HOST pointers, read before the call returns; NULL exactly when the axis' r is 0; r <= DTFILL_NYU_MAX_RADIUS
+ *   (factors below 5.25).  The call does not check the taps against the geometry: any symmetric kernel is filtered with.
+ * m(i): scipy's 'mirror' into [0, n): period 2 (n - 1), the edge sample not repeated, n == 1 -> 0; it holds for r > n - 1,
+ *   where an index reflects several times.
+ * Filter pass along an axis (axis 0 = rows first, then axis 1), accumulated in double, no contraction:
+ *   acc = x[i] * w[0];  for k = r .. 1 (the outermost pair first, scipy's order):  acc += (x[m(i - k)] + x[m(i + k)]) * w[k]
+ * Resample, in double, no contraction, per axis c = (j + 0.5) * f - 0.5, i0 = floor(c), t = c - i0, neighbours m(i0), m(i0 + 1):
+ *   v = 0.0 + (x00 * (1 - tr)) * (1 - tc);  v += (x01 * (1 - tr)) * tc;  v += (x10 * tr) * (1 - tc);  v += (x11 * tr) * tc
+ *   (scipy's: each sample times its row weight, then its column weight, summed in this order from 0.0 on).  A neighbour of
+ *   weight 0 is still read and multiplied (f == 1, where i0 + 1 may mirror): a NaN there propagates, as in scipy.
+ * Depth (float32 [B, hin, win], as the files store it): each filter pass is rounded to float32 (scipy on a float32 array;
+ *   skimage >= 0.19 keeps float32), the resample runs on those values in double and is rounded once: out_gt float32 [B, H, W].
+ *   out_lidar[p] = marked(p) ? gt[p] : gt[p] * 0.0f, the product as it stands: -0.0 under a negative gt, NaN under a
+ *   non-finite one, as gt * Mask gives them.  samples: int32 [B, n, 2] holding (row, col), the loaders' + 6 / + 8 already
+ *   added, duplicates allowed; a sample outside [0, H) x [0, W) is skipped and sets DTFILL_NYU_INDEX_ERROR in its frame's
+ *   status (numpy would raise IndexError).  samples == NULL or n == 0: out_lidar is gt * 0.0f everywhere.
+ * Image (uint8 [B, C, hin, win], the stored layout; the loaders' transpose is folded in; C in 1..4): per channel
+ *   x = (double)u8 * (1.0 / 255.0) (img_as_float's multiply by the reciprocal), both passes and the resample in double -> r;
+ *   out_rgb = (float)(r * 255.0), data_read.py:329,335; with normalize, (float)((double)(float)(r * 255.0) / 255.0).
+ *   Layout DTFILL_RGB_NHWC [B, H, W, C] (the reference's) or DTFILL_RGB_NCHW [B, C, H, W].
+ * The limit of the claim: what the tests pin, bit for bit, is scipy (gaussian_filter and zoom as above, float32 and float64).
+ *   That skimage's resize is those two calls, that img_as_float multiplies by 1.0 / 255, and that skimage's 'reflect' is
+ *   scipy's 'mirror' are restated from skimage >= 0.19's source, not tested: skimage is not a dependency.  skimage < 0.19
+ *   resampled with its own warp(), which associates the four products differently and returned float64 for float32 input.
+ * rgb and depth are each nullable, not both; an output whose input is NULL must be NULL, and an input needs an output (out_rgb;
+ * out_gt or out_lidar).  Inputs and outputs are only element-aligned; no output may alias an input.  Nothing outside the
+ * rows and columns the taps reach is read.  frame_status: int32 [B], nullable, 0 or DTFILL_NYU_INDEX_ERROR, final when the
+ * stream reaches the end of the call.  workspace: ws_bytes >= dtfill_nyu_read_workspace_bytes(B, H, W), 256-B aligned, no
+ * initialisation needed, nothing kept between calls.  Asynchronous on `stream`; no allocation, no host synchronisation,
+ * re-entrant across streams.
+ * Returns, all checked before any HIP call: DTFILL_ERR_NULL for rgb and depth both NULL, an output without its input, an input
+ * without an output, or a NULL workspace; DTFILL_ERR_SHAPE for B, hin, win, H, W < 1, B > 65535, H > hin, W > win, a radius
+ * outside [0, DTFILL_NYU_MAX_RADIUS], taps that are NULL with r > 0 or not NULL with r == 0, C outside 1..4 (with rgb), an
+ * unknown layout, n < 0, or B*C*hin*win, B*hin*win, B*H*W*C, B*H*W or B*n*2 >= 2^31; DTFILL_ERR_WORKSPACE for a workspace too
+ * small or not aligned; then DTFILL_ERR_LAUNCH if a launch failed.
+ */
+#define DTFILL_NYU_MAX_RADIUS 8  /* the largest filter radius per axis: sigma < 2.125, factors below 5.25 */
+#define DTFILL_NYU_INDEX_ERROR 1 /* status bit: a sample of the frame lies outside [0, H) x [0, W) and was skipped */
+size_t dtfill_nyu_read_workspace_bytes(int B, int H, int W); /* 0 on a bad shape */
+int dtfill_nyu_read(const uint8_t *rgb, const float *depth, int B, int C, int hin, int win, int H, int W, const double *wy,
+                    int ry, const double *wx, int rx, const int32_t *samples, int n, int normalize, int layout,
+                    float *out_rgb, float *out_gt, float *out_lidar, int32_t *frame_status, void *workspace, size_t ws_bytes,
+                    void *stream);
+
+/*
  * map_points_on_image() of subsample_Lidar_train.py:180-193 / subsample_Lidar_val.py:167-180, on B point clouds at once: points
  * in the Velodyne frame through E and K, rounded to a pixel, depth_map[v, u] = z.  The front of the pipeline for a caller who
  * holds point clouds (KITTI raw .bin: float32 x, y, z, reflectance) and not frames; dtfill_line_subsample() skips this step
