@@ -56,6 +56,11 @@
 //              dense frame (the sky): a window in the column distances (l2sky_row); frames with a handful of sources: tiles
 //              over the source list (l2pts_tile)
 //
+// Where the routing rule and the tilings are written down: dtfill_route.hpp -- which kernel family takes a frame and each of its
+// rows (route_decide, sky_possible, far_row, the mode bits a pass hands to frame_facts), the window kernel's tiling and its tile
+// rows under a sky (window_tiling, tile_row_height, tile_row_culled), k_pts's and k_l2win's tiles.  frame_facts, fused_body and
+// the host below call it; tests/test_route.py compiles it for the host and holds tests/exhaustive_cases.py to it.
+//
 // No MFMA anywhere: this path is compare/min/index work (DESIGN.md "Roofline").
 
 #include <hip/hip_runtime.h>
@@ -249,20 +254,7 @@ int run_l1(Pass p, unsigned flags, hipStream_t st, hipEvent_t *ev, unsigned *idl
     m.at(S1_MASK);
     launch_mask(p, flags, st);
     // geometry of the window kernel's two tilings (k_frame pre-marks whole tile rows)
-    auto tiling = [&](int R) {
-            const int THM = F_WHM - 2 * R, TWM = F_WWM - 2 * R;
-            const int nty = (H + THM - 1) / THM, ntx = (W + TWM - 1) / TWM;
-            FusedTiles t;
-            t.TH = (H + nty - 1) / nty;  // even split
-            t.TW = (W + ntx - 1) / ntx;
-            // columns in whole 128-byte lines when the window allows it: the runs of a tile row a wave stores are then whole lines
-            if (((t.TW + 31) & ~31) <= TWM) t.TW = (t.TW + 31) & ~31;
-            t.tiles_x = ntx;
-            t.nty = nty;
-            t.ntiles = ntx * nty;
-            return t;
-        };
-    const FusedTiles t16 = tiling(16), t32 = tiling(32);
+    const FusedTiles t16 = window_tiling(H, W, 16), t32 = window_tiling(H, W, 32);
     const bool epi = p.ep.row0 != 0 || p.ep.use_floor;
     // row flags (k_frame): the sky above the first source row goes to k_sky, rows too far from every source row to the
     // any-distance kernels, the rest of the frame to the window kernel.  Not with a depth epilogue (a handed-on row costs the
@@ -271,7 +263,7 @@ int run_l1(Pass p, unsigned flags, hipStream_t st, hipEvent_t *ev, unsigned *idl
     // k_sky takes the distances of its two base rows from the distance map: without one from the caller, the scratch frame
     float *const out_dt_caller = p.out_dt;
     if (rowflags && !p.out_dt) p.out_dt = p.dscratch;
-    const int mode = (general_only ? 1 : 0) | (rowflags ? 4 | 8 : 0);
+    const int mode = (general_only ? FM_GENERAL : 0) | (rowflags ? FM_PREMARK | FM_PTS : 0);
     if (!ride) {
         m.at(S1_FRAME);  // (else the slot reads 0 ms)
         k_frame<<<B, 256, 0, st>>>(p, mode, t16.nty, t32.nty);
@@ -327,11 +319,10 @@ int run_l1(Pass p, unsigned flags, hipStream_t st, hipEvent_t *ev, unsigned *idl
         PtsArgs pa;
         pa.ptslist = p.ptslist;
         pa.out_dt = p.out_dt;
-        // 32 x 256 tiles or 64 x 128: whichever wastes fewer waves on this shape (640 columns are 2.5 tiles of 256 but 5 of 128)
-        const int nwide = ((W + 255) / 256) * ((H + 31) / 32), ntall = ((W + 127) / 128) * ((H + 63) / 64);
-        pa.tall = ntall < nwide;
-        pa.tiles_x = pa.tall ? (W + 127) / 128 : (W + 255) / 256;
-        pa.ntiles = rowflags ? (pa.tall ? ntall : nwide) : 0;
+        const PtsTiles pt = pts_tiling(H, W);  // 32 x 256 tiles or 64 x 128
+        pa.tall = pt.tall;
+        pa.tiles_x = pt.tiles_x;
+        pa.ntiles = rowflags ? pt.ntiles : 0;
         const int ttx = (W + Q_TW - 1) / Q_TW;
         pa.fin_ntiles = fin ? ttx * ((H + Q_TH - 1) / Q_TH) : 0;
         if (fin || pa.ntiles) {
@@ -354,7 +345,7 @@ int run_l2(const Pass &p, unsigned flags, hipStream_t st, hipEvent_t *ev, unsign
     m.at(S2_MASK);
     launch_mask(p, flags, st);
     m.at(S2_FRAME);
-    k_frame<<<B, 256, 0, st>>>(p, ((flags & DTFILL_FLAG_GENERAL_ONLY) ? 1 : 0) | 2, 0, 0);
+    k_frame<<<B, 256, 0, st>>>(p, ((flags & DTFILL_FLAG_GENERAL_ONLY) ? FM_GENERAL : 0) | FM_L2, 0, 0);
     m.at(S2_WIN16);
     // dense frames (k_frame's route 16 / 32): windows of 21 x 21 / 31 x 31 around every pixel, the few pixels with no source
     // that near one by one

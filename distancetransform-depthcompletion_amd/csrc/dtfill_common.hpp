@@ -1,5 +1,5 @@
-// dtfill_common.hpp -- constants, the tap table (dtfill_taps.hpp), the depth index rule (dtfill_index.hpp) and small device
-// helpers shared by every kernel
+// dtfill_common.hpp -- constants, the routing rule and the tilings (dtfill_route.hpp), the tap table (dtfill_taps.hpp), the depth
+// index rule (dtfill_index.hpp) and small device helpers shared by every kernel
 // Part of libdtfill.so; included by dtfill.hip inside its anonymous namespace (one translation unit).
 #pragma once
 
@@ -20,22 +20,15 @@ constexpr int FI_TR0 = 7;     // l1_cv, a window kernel's frame: the first row o
                               // the rest evenly, so that no tile row is spent on rows that are not the window's)
 constexpr int FI_STRIDE = 8;
 constexpr int ROUTE_UNKNOWN = -0x7FFFFFFF - 1;  // route[b] from k_mask until the frame's facts are published (reads as "no window")
-constexpr int ROUTE_POINTS = -1;  // route[b]: l2, at most L2_PTS_MAX sources in the frame (k_l2pts)
-constexpr int L2_PTS_MAX = 512;
-constexpr int W2_R16 = 10, W2_R32 = 15;  // l2: window radius of k_l2win for the frames k_frame routes 16 / 32
 constexpr u32 L2_ROW_GONE = 0x40000000u;  // l2 row flag: handed to the row search up front (above any far-pixel count's threshold)
-struct PtsSrc {  // one source of such a frame's list (k_frame writes it in raster order: index = label - 1; k_pts reads it)
+
+// the routing rule (route_decide, the mode bits FM_*, ROUTE_POINTS, ROUTE_PREMARK and the thresholds it rests on) and the tilings of
+// the window kernel, k_l2win and k_pts: stated once, there
+#include "dtfill_route.hpp"
+struct PtsSrc {  // one source of a ROUTE_POINTS frame's list (k_frame writes it in raster order: index = label - 1; k_pts reads it)
     u32 rc;      // row << 16 | column
     float v;     // its depth
 };
-constexpr int PTS_BAND_MAX = 96;  // l1_cv: ... and at most this many in any band of 32 rows
-// route[b] | ROUTE_PREMARK (l1_cv): k_frame marked rows of the frame for the any-distance kernels up front (rows farther than
-// PM16 / PM32 from every row that holds a source: the window kernel with halo 16 / 32 could not decide them, or only by running
-// its level loop to the end for a handful of their pixels)
-constexpr int ROUTE_PREMARK = 0x100;
-constexpr int PM16 = 8, PM32 = 16;
-constexpr int SKY_MAX = 320;  // ... and up to this many (k_sky's blocks stage r0 + 260 columns in LDS, in k_colT's launch)
-constexpr int SKY_MIN = 9;  // rows above the first source row are k_sky's from this many on (fewer: within every window's reach)
 
 // the l1_cv parent rule's tap table (offsets, weights, parent codes, step encoding, tap_decode): stated once, there
 #include "dtfill_taps.hpp"

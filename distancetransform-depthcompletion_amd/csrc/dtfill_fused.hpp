@@ -23,8 +23,7 @@
 // hop is two LDS reads and one add; d is |drow| + |dcol| to the root.
 // LDS: 28.9 KB ring/s_par + 8 KB rank records.
 // ------------------------------------------------------------------------------------------------
-constexpr int F_WHM = 128;  // window rows
-constexpr int F_WWM = 192;  // window columns = 6 words
+// (the window itself, F_WHM rows x F_WWM columns, is dtfill_route.hpp's: the tilings rest on it)
 constexpr int F_NT = 256;   // lane = (row, half): waves 0-1 own words 0..2 of rows 0..127, waves 2-3 words 3..5
 constexpr int F_P = 196;               // s_par row pitch: 49 dwords (odd) -> lane-per-row dword stores are conflict-free
 constexpr int F_NWD = 6;               // 32-bit words per window row
@@ -360,12 +359,7 @@ __device__ __forceinline__ bool fused_walk_epilogue(
     return any;
 }
 
-// FR = halo = largest distance the window can decide.
-// Geometry of one halo's tiling (host side computes it; the window is always F_WHM x F_WWM)
-struct FusedTiles {
-    int TH, TW, tiles_x, ntiles, nty;  // TH: the tile rows' height when they split the whole frame (the largest it gets)
-};
-
+// FR = halo = largest distance the window can decide.  The geometry of a halo's tiling: FusedTiles, window_tiling (dtfill_route.hpp)
 template <int FR, bool EPI, bool STREAM>
 __device__ __forceinline__ void fused_body(int tile, bool premarked, int tbase, int nval, int misaligned, int sky0, const u32 *__restrict__ s_bs,
     const u32 *__restrict__ s_far,
@@ -379,10 +373,11 @@ __device__ __forceinline__ void fused_body(int tile, bool premarked, int tbase, 
     // (frames along x, tiles along y: the tiles beyond a frame's own tiling, which exit, are dispatched after every working block)
     const int b = blockIdx.x;
     const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    // the tile rows split the rows from tbase = FI_TR0 on evenly (frame_facts: 0, or the first source row under a sky)
+    // the tile rows split the rows from tbase = FI_TR0 on evenly (frame_facts: 0, or the first source row under a sky): the
+    // height frame_facts culled whole tile rows by
     // s_bs, s_far (LDS, inside the ring's memory; null when a k_frame launch went before): the frame's rank bases per row and
     // its pre-marked rows as bits, as this block's own frame_facts left them -- else rowbase_s and rowfar say the same
-    const int TH = (H - tbase + nty - 1) / nty;
+    const int TH = tile_row_height(H, tbase, nty);
     int r0 = tbase + ty * TH;
     const int c0 = tx * TW;
     int th = min(TH, H - r0);

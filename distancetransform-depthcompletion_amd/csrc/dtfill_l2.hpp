@@ -53,10 +53,8 @@ __device__ __forceinline__ L2Frame l2_frame(const float *__restrict__ x, const f
 // R = 10 for the frames k_frame routes 16 (at 5 % density one pixel in 10^7 has no source that near), R = 15 for route 32;
 // frames with route 0 are left to k_colT + k_l2env, and so are the rows of a window-kernel frame with many far pixels.
 // ------------------------------------------------------------------------------------------------
-constexpr int W2_TH = 32, W2_TW = 256;
-// a row with this many far pixels (an eighth of it: the empty sky of a LiDAR frame, not the scattered voids of a uniform one)
-// is redone whole by k_l2env instead of pixel by pixel (k_l2far)
-__device__ __forceinline__ u32 w2_row_t(int W) { return (u32)max(32, W >> 3); }
+// The tile is W2_TH x W2_TW; a row with w2_row_t(W) far pixels is redone whole by k_l2env instead of pixel by pixel (k_l2far):
+// both in dtfill_route.hpp
 
 // ------------------------------------------------------------------------------------------------
 // A pixel with no source inside its window ("far"), one HALF WAVE per pixel: lane l takes the rows i - (base + l) and
@@ -694,7 +692,7 @@ __global__ __launch_bounds__(256) void k_l2far(const Pass p) {
 // delta over the frame's source list, compacts the sources inside that radius into LDS (a dozen of 200 in an NYU frame), and
 // every pixel takes the minimum of (d2, source row, source column) over them -- exact, canonical ties, no column pass at all.
 // ------------------------------------------------------------------------------------------------
-constexpr int PT_T = 32;
+// (the tile's side PT_T: dtfill_route.hpp)
 __device__ __forceinline__ void l2pts_tile(const float *__restrict__ x, const u32 *__restrict__ srclist,
                                            const int *__restrict__ finfo, const float *__restrict__ vlist, int b, int H, int W,
                                            int ty, int tx, float *__restrict__ out_depth, float *__restrict__ out_dt,

@@ -223,10 +223,7 @@ struct FrameFacts {
 template <class Sink>
 __device__ __forceinline__ FrameFacts frame_facts(const u32 *__restrict__ cs_, const u32 *__restrict__ cv_, int H, int W, int mode,
                                                   int nty16, int nty32, FrameScratch &sc, bool list, Sink sink) {
-    const bool force_general = mode & 1;  // every frame takes the any-distance kernels (tests)
-    const bool l2 = mode & 2;             // l2: the window kernel's cost does not grow with the distances it meets
-    const bool premark = mode & 4;        // l1_cv without a depth epilogue: rows too far from every source row are handed on up front
-    const bool pts_ok = mode & 8;         // l1_cv: a frame with a handful of sources may go to k_pts
+    const bool l2 = mode & FM_L2, premark = mode & FM_PREMARK;  // (the mode bits: dtfill_route.hpp)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int Hp = (H + 63) & ~63;
     // the counts of the first 256 rows are on their way before anything else; every later batch while the one before is scanned
@@ -304,14 +301,8 @@ __device__ __forceinline__ FrameFacts frame_facts(const u32 *__restrict__ cs_, c
         run_v += tv;
     }
     if (mis) atomicOr(&sc.mis, 1);
-    // Row structure of the frame (l1_cv uses all of it, l2 only FI_DLB):
-    //   r0     the first row that holds a source.  The rows above it -- the empty sky of a LiDAR frame -- need no search at all:
-    //          every source is below them, so cv2's backward sweep alone decides them, row by row from the two rows beneath
-    //          (k_sky).  Flag 2.
-    //   vd(i)  vertical distance of row i to the nearest row with a source: every pixel of row i is at least that far from
-    //          every source.  max vd = lower bound of the largest distance in the frame (FI_DLB).  A row at or below r0 with
-    //          vd above a window kernel's reach (PM16 / PM32) cannot be decided by it: it is handed to the any-distance kernels
-    //          up front (flag 1), and the window kernel takes the rest of the frame instead of nothing.
+    // Row structure of the frame (r0, vd(i), the far rows: dtfill_route.hpp says what they decide): the rows above r0 get
+    // flag 2 when they are k_sky's, a far row flag 1; max vd = lower bound of the largest distance in the frame (FI_DLB).
     // "Row has no source" as bits in LDS (H <= 8191 -> 256 words); the rows past H count as empty.
     // (a frame in which every row holds a source -- the common dense one -- has vd = 0 everywhere: nothing to search)
     bool someempty = false;
@@ -342,8 +333,7 @@ __device__ __forceinline__ FrameFacts frame_facts(const u32 *__restrict__ cs_, c
                 vd = min(up, dn);
                 dlb = max(dlb, vd);
             }
-            // l2: the rows farther from every row with a source than the window kernel's radius (no pixel of them has a source in its window)
-            const u64 f16 = __ballot(i < H && (l2 ? vd > W2_R16 : (i >= r0 && vd > PM16))), f32 = __ballot(i < H && (l2 ? vd > W2_R32 : (i >= r0 && vd > PM32)));
+            const u64 f16 = __ballot(i < H && far_row(l2, 16, i, r0, vd)), f32 = __ballot(i < H && far_row(l2, 32, i, r0, vd));
             if (lane == 0 && i < Hp) {
                 sc.far[0][i >> 5] = (u32)f16;
                 sc.far[0][(i >> 5) + 1] = (u32)(f16 >> 32);
@@ -364,37 +354,10 @@ __device__ __forceinline__ FrameFacts frame_facts(const u32 *__restrict__ cs_, c
     ff.nsrc = (int)run_s;
     ff.nval = (int)run_v;
     const int r0 = ff.r0 = sc.r0;
-    const bool sky_ok = ff.sky_ok = premark && r0 >= SKY_MIN && r0 <= SKY_MAX && r0 < H;  // rows [0, r0) can be k_sky's
-    int r;
-    {  // (every thread for itself, from what the barrier above made visible: no thread waits for another's decision)
-        // Which kernel family takes the frame -- a speed heuristic, never a correctness condition (the window kernels hand on
-        // every row in which they meet a pixel they cannot decide).  With source density p the chance that a pixel has no
-        // source within L1 distance R is about (1-p)^(2 R^2 + 2 R + 1); if the frame is expected to hold such pixels all
-        // over (N (1-p)^ball > ~1, i.e. p * ball < ln N ~ 14), a window kernel with halo R would do its work for nothing.
-        // Runs of source-free rows do not say no (l1_cv): the density is judged on the rows that are left to the window.
-        // Without the row flags (a depth epilogue: a handed-on row costs the whole frame there, k_fused's kept depths being
-        // cropped / floored already; the forced paths of the tests) the old rule stays: a run of source-free rows that forces a
-        // distance above R sends the frame to the any-distance kernels.  The l2 window kernel counts its far pixels itself.
-        // route: halo 16 if it fits, else halo 32 (three times the work per pixel, still cheaper than the any-distance
-        // kernels at a few percent density), else the any-distance kernels.
-        auto fits = [&](int R, int nfar) {
-            const long long ball = 2 * R * R + 2 * R + 1;
-            if (l2) return (long long)run_s * ball >= 14ll * H * W;
-            if (!premark) return (long long)run_s * ball >= 14ll * H * W && sc.dlb <= R;
-            const int rest = H - (sky_ok ? r0 : 0) - nfar;
-            return rest > 0 && (long long)run_s * ball >= 14ll * rest * W;
-        };
-        // l2, a handful of sources (the NYU sampling patterns): ROUTE_POINTS -- every 32 x 32 tile looks at the sources that can
-        // own one of its pixels, found by distance from the tile's centre (l2pts_tile); the blocks of k_l2win's launch
-        // write the list of sources
-        const bool points = l2 && !force_general && run_s > 0 && run_s <= (u32)L2_PTS_MAX;
-        // l1_cv, a handful of sources and too thin for a window: k_pts (per tile, the sources whose cells reach it).  Not when they
-        // crowd into one band of rows: its tiles would look at all of them for every pixel.
-        const bool points1 = !l2 && pts_ok && run_s > 0 && run_s <= (u32)L2_PTS_MAX && sc.bandmax <= PTS_BAND_MAX;
-        const int window = fits(16, sc.nfar[0]) ? 16 : fits(32, sc.nfar[1]) ? 32 : 0;
-        r = force_general ? 0 : points ? ROUTE_POINTS : window ? window : points1 ? ROUTE_POINTS : 0;
-    }
-    ff.r = r;
+    const bool sky_ok = ff.sky_ok = sky_possible(premark, r0, H);
+    // which kernel family takes the frame (every thread for itself, from what the barrier above made visible: no thread waits
+    // for another's decision)
+    const int r = ff.r = route_decide(RouteIn{H, W, mode, ff.nsrc, ff.dlb, sc.bandmax, sc.nfar[0], sc.nfar[1], r0, sky_ok});
     const bool flags = ff.flags = !l2 && premark && r >= 0;  // this frame's rows carry flags
     // k_sky starts from rows r0 and r0 + 1 as the window kernel leaves them (it runs beside the first any-distance kernel): a
     // frame that is not a window kernel's, or whose row r0 / r0 + 1 is handed on up front, keeps its sky with the other rows
@@ -408,9 +371,9 @@ __device__ __forceinline__ FrameFacts frame_facts(const u32 *__restrict__ cs_, c
         // a tile row of the window kernel that is left with only a few rows is not worth its windows: all of it goes to the
         // any-distance kernels.  One thread per tile row, whole words at a time.
         // the window kernel's tile rows: nty of them over the rows from the first source row on when the rows above are the
-        // sky's, else over the whole frame (fused_body computes the same)
+        // sky's, else over the whole frame (fused_body takes the same tile_row_height)
         const int nty = r == 16 ? nty16 : nty32, tbase = sky_ok ? r0 : 0;
-        const int TH = (H - tbase + nty - 1) / nty;
+        const int TH = tile_row_height(H, tbase, nty);
         auto bits = [&](int a, int e, int w) {  // the rows [a, e) as bits of word w
             const int lo = max(a - 32 * w, 0), hi = min(e - 32 * w, 32);
             return hi <= lo ? 0u : (hi >= 32 ? 0xFFFFFFFFu : ((1u << hi) - 1u)) & ~((1u << lo) - 1u);
@@ -419,7 +382,7 @@ __device__ __forceinline__ FrameFacts frame_facts(const u32 *__restrict__ cs_, c
             const int a = tbase + t * TH, e = min(H, tbase + (t + 1) * TH);  // its rows (all below the sky)
             int keep = 0;
             for (int w = a >> 5; w <= (e - 1) >> 5 && a < e; ++w) keep += __popc(~far[w] & bits(a, e, w));
-            if (keep && 4 * keep <= e - a)
+            if (tile_row_culled(keep, e - a))
                 for (int w = a >> 5; w <= (e - 1) >> 5; ++w) atomicOr(&far[w], bits(a, e, w));
         }
     }
@@ -472,7 +435,7 @@ __device__ __forceinline__ void frame_publish(const FrameFacts &ff, const FrameS
                                               int *__restrict__ negflag, u32 *__restrict__ rowfar, bool raise) {
     // raise: the window blocks of this very launch raise rowfar, fflag2, the status and FI_SKY's SKY_OFF bit too (all clear since k_mask):
     // only what is non-zero is stored, flags by atomicOr.  Else (k_frame) every word is stored.
-    const bool l2 = mode & 2;
+    const bool l2 = mode & FM_L2;
     const int tid = threadIdx.x, r = ff.r;
     // the route first: k_fused's late blocks look at it (they exit at once in a frame that is not their tiling's)
     if (tid == 0) __hip_atomic_store(&route[b], ff.route, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -35,7 +35,7 @@ constexpr int P_RC = 12;                  // rows per register chunk
 static_assert(P_WB % P_RC == 0, "whole chunks");
 
 // A block's tile is TH x TW pixels = (TH / 32) x (TW / 64) waves of 32 rows x 64 columns: 32 x 256 (k_fin's tile) or 64 x 128 --
-// the host picks the one that wastes fewer waves on the frame's shape (a 640-wide frame is 2.5 tiles of 256 but 5 of 128).
+// the host picks the one that wastes fewer waves on the frame's shape (pts_tiling, dtfill_route.hpp).
 template <int TH, int TW>
 struct PtsGeom {
     static_assert(TH % 32 == 0 && TW % 64 == 0 && (TH / 32) * (TW / 64) == Q_NT / 64 && TH * (TW / 32) == Q_NT, "four waves, a thread per word");
@@ -542,9 +542,9 @@ __global__ __launch_bounds__(Q_NT, 4) void k_fin(
     if (fflag[blockIdx.y] == 3) {  // (block-uniform)
         if ((int)blockIdx.x < pa.ntiles) {
             if (pa.tall)
-                pts_body<64, 128>(s_raw, x, pa.ptslist, H, W, Wp, pa.tiles_x, vlist, out_depth, pa.out_dt, out_index, frame_status, finfo, xlist, xptr, unres);
+                pts_body<PTS_TALL_TH, PTS_TALL_TW>(s_raw, x, pa.ptslist, H, W, Wp, pa.tiles_x, vlist, out_depth, pa.out_dt, out_index, frame_status, finfo, xlist, xptr, unres);
             else
-                pts_body<32, 256>(s_raw, x, pa.ptslist, H, W, Wp, pa.tiles_x, vlist, out_depth, pa.out_dt, out_index, frame_status, finfo, xlist, xptr, unres);
+                pts_body<PTS_WIDE_TH, PTS_WIDE_TW>(s_raw, x, pa.ptslist, H, W, Wp, pa.tiles_x, vlist, out_depth, pa.out_dt, out_index, frame_status, finfo, xlist, xptr, unres);
         }
         return;
     }

@@ -9,10 +9,11 @@ a whole frame of at most 16 pixels.
 Every source's value is 1 + (row * W + col) / 256: exact in float32, >= 0.95 (a source and a value alike), and distinct, so
 that the filled depth names the label's source.
 
-The kernels' constants are restated below, each with the place it is defined at (paths under
-distancetransform-depthcompletion_amd/csrc/); route() restates frame_facts' routing rule, window_tiles() the window kernel's
-tile origins, so that a sweep can say on the CPU which kernel family its frames go to (tests/test_exhaustive_cases.py holds
-every sweep to that; tests/test_gpu_exhaustive.py holds the device's pass_stats() to it).
+The kernels' constants are restated below, each under the name it has in distancetransform-depthcompletion_amd/csrc/dtfill_route.hpp
+(or with the header that defines it); decide() restates that header's route_decide, route() what frame_facts makes of it,
+window_tiles() the window kernel's tile origins, so that a sweep can say on the CPU which kernel family its frames go to.
+tests/test_route.py compiles the header for the host and holds every constant and rule here to it; tests/test_exhaustive_cases.py
+holds every sweep to route(); tests/test_gpu_exhaustive.py holds the device's pass_stats() to it.
 """
 import functools
 import zlib
@@ -22,21 +23,24 @@ import numpy as np
 import parallel_model as PM
 
 # ---- the kernels' constants ---------------------------------------------------------------------------------------------
-F_WHM, F_WWM = 128, 192      # dtfill_fused.hpp:26-27   the window kernel's window: rows, columns
-L2_PTS_MAX = 512             # dtfill_common.hpp:24     a frame with at most this many sources can be a points frame
-W2_R = {16: 10, 32: 15}      # dtfill_common.hpp:25     l2: k_l2win's radius on route 16 / 32 (W2_R16, W2_R32)
-PTS_BAND_MAX = 96            # dtfill_common.hpp:31     l1_cv points frame: at most this many sources in a band of 32 rows
-PREMARK = {16: 8, 32: 16}         # dtfill_common.hpp:36     l1_cv: rows farther than this from every source row are pre-marked (PM16, PM32)
-SKY_MAX, SKY_MIN = 320, 9    # dtfill_common.hpp:37-38  the rows above the first source row are k_sky's from SKY_MIN rows on
-BAND = 32                    # dtfill_prepass.hpp:281-284 (bandmax), dtfill_common.hpp:140 (ct): the any-distance kernels' row bands
-WORDS = (32, 64)             # dtfill_common.hpp:45 (32-pixel words of the bit rows), :134 (64-pixel words of srcbits / valbits)
-PTS_TILES = {False: (32, 256), True: (64, 128)}  # dtfill_pts.hpp:37-38, dtfill.hip:328-331  k_pts's tile: wide / tall
-PTS_WAVE = (32, 64)          # dtfill_pts.hpp:37        ... of waves of 32 rows x 64 columns
-PT_T = 32                    # dtfill_l2.hpp:697        l2 points route: 32 x 32 tiles
-W2_TH, W2_TW = 32, 256       # dtfill_l2.hpp:56         k_l2win's tile
+F_WHM, F_WWM = 128, 192      # F_WHM, F_WWM             the window kernel's window: rows, columns
+L2_PTS_MAX = 512             # L2_PTS_MAX               a frame with at most this many sources can be a points frame
+W2_R = {16: 10, 32: 15}      # W2_R16, W2_R32           l2: k_l2win's radius on route 16 / 32
+PTS_BAND_MAX = 96            # PTS_BAND_MAX             l1_cv points frame: at most this many sources in a band of 32 rows
+PREMARK = {16: 8, 32: 16}    # PM16, PM32               l1_cv: rows farther than this from every source row are pre-marked
+SKY_MAX, SKY_MIN = 320, 9    # SKY_MAX, SKY_MIN         the rows above the first source row are k_sky's from SKY_MIN rows on
+DENSITY_LN_N = 14            # DENSITY_LN_N             window_fits: sources x ball against this many times the pixels
+ROUTE_POINTS = -1            # ROUTE_POINTS             the route of a points frame
+FM_GENERAL, FM_L2, FM_PREMARK, FM_PTS = 1, 2, 4, 8  # FM_*  the mode bits of a pass
+BAND = 32                    # frame_facts' bandmax (dtfill_prepass.hpp), ct (dtfill_common.hpp): the any-distance kernels' row bands
+WORDS = (32, 64)             # dtfill_common.hpp: 32-pixel words of the bit rows, 64-pixel words of srcbits / valbits
+PTS_TILES = {False: (32, 256), True: (64, 128)}  # PTS_WIDE_TH x PTS_WIDE_TW, PTS_TALL_TH x PTS_TALL_TW  k_pts's tile: wide / tall
+PTS_WAVE = (32, 64)          # dtfill_pts.hpp (PtsGeom) ... of waves of 32 rows x 64 columns
+PT_T = 32                    # PT_T                     l2 points route: 32 x 32 tiles
+W2_TH, W2_TW = 32, 256       # W2_TH, W2_TW             k_l2win's tile
 
 
-def w2_row_t(W):             # dtfill_l2.hpp:59         l2: a row with this many far pixels is handed to the row search
+def w2_row_t(W):             # w2_row_t                 l2: a row with this many far pixels is handed to the row search
     return max(32, W >> 3)
 
 
@@ -86,22 +90,32 @@ def misaligned(x):
 
 # ---- where the seams are ------------------------------------------------------------------------------------------------
 def window_tiles(H, W, R, tbase=0):
-    """The window kernel's tiling for halo R: (row origins, column origins).  dtfill.hip:250-262 (the host: nty, ntx from
-    the whole frame, TW in whole 32-pixel words when the window allows it), dtfill_fused.hpp:385-387 (the tile rows split
-    the rows from tbase = FI_TR0 on evenly; dtfill_prepass.hpp:438: tbase is the first source row under a sky, else 0)."""
+    """The window kernel's tiling for halo R: (row origins, column origins).  window_tiling (nty, ntx from the whole frame,
+    TW in whole 32-pixel words when the window allows it) and tile_row_height (the tile rows split the rows from
+    tbase = FI_TR0 on evenly; frame_facts: tbase is the first source row under a sky, else 0)."""
     THM, TWM = F_WHM - 2 * R, F_WWM - 2 * R
     nty, ntx = -(-H // THM), -(-W // TWM)
     TW = -(-W // ntx)
     if ((TW + 31) & ~31) <= TWM:
         TW = (TW + 31) & ~31
-    TH = -(-(H - tbase) // nty)
+    TH = tile_row_height(H, tbase, nty)
     rows = [tbase + t * TH for t in range(nty) if tbase + t * TH < H]
     cols = [t * TW for t in range(ntx) if t * TW < W]
     return np.array(rows), np.array(cols)
 
 
+def tile_row_height(H, tbase, nty):
+    """tile_row_height: nty tile rows split the rows from tbase on evenly."""
+    return -(-(H - tbase) // nty)
+
+
+def tile_row_culled(keep, rows):
+    """tile_row_culled: a tile row of `rows` rows left with only `keep` of them goes to the any-distance kernels whole."""
+    return bool(keep and 4 * keep <= rows)
+
+
 def pts_tall(H, W):
-    """dtfill.hip:329-330: k_pts takes 64 x 128 tiles where they waste fewer waves than 32 x 256."""
+    """pts_tall: k_pts takes 64 x 128 tiles where they waste fewer waves than 32 x 256."""
     nwide = -(-W // 256) * -(-H // 32)
     ntall = -(-W // 128) * -(-H // 64)
     return ntall < nwide
@@ -109,7 +123,7 @@ def pts_tall(H, W):
 
 # win16, win32: the window kernel with halo 16 / 32 (l2: k_l2win with radius 10 / 15); anydist: the smallest frame with a 32-row band
 # boundary, a handful of sources (k_pts's 32 x 256 tiles and the l2 points route on the default path, the any-distance kernels on the
-# forced one); pts: the smallest frame on which k_pts takes its 64 x 128 tiles and has a seam in both directions (dtfill.hip:329-330:
+# forced one); pts: the smallest frame on which k_pts takes its 64 x 128 tiles and has a seam in both directions (pts_tall:
 # W in 257..384, H in 97..128); thin: more than L2_PTS_MAX sources, too thin for halo 32 -- the any-distance kernels and the l2 row
 # search on the default path, distances of 40 and more; sky: a window frame under SKY_MIN or more empty rows
 FAMILIES = ("win16", "win32", "anydist", "pts", "thin", "sky")
@@ -172,57 +186,84 @@ def anchors(family, H, W):
 
 
 # ---- which kernel family takes a frame ----------------------------------------------------------------------------------
+def pass_mode(metric="l1_cv", path="auto"):
+    """The FM_* bits run_l1 / run_l2 hand to frame_facts for a pass without a depth epilogue."""
+    general = FM_GENERAL if path == "general" else 0
+    return FM_L2 | general if metric == "l2" else general or (FM_PREMARK | FM_PTS)
+
+
+def sky_possible(premark, r0, H):
+    """sky_possible: the rows [0, r0) can be k_sky's."""
+    return bool(premark and SKY_MIN <= r0 <= SKY_MAX and r0 < H)
+
+
+def far_row(l2, R, i, r0, vd):
+    """far_row: row i (vd from the nearest row with a source) is out of reach of the window kernel of route R."""
+    return vd > W2_R[R] if l2 else (i >= r0) & (vd > PREMARK[R])
+
+
+def summarise(src, mode):
+    """What frame_facts' scans make of a source mask: the record route_decide takes (H, W, mode, nsrc, dlb, bandmax, nfar16,
+    nfar32, r0, sky_ok), and beside it the far rows themselves (far: {16, 32} -> bool per row)."""
+    src = np.asarray(src, bool)
+    H, W = src.shape
+    l2 = bool(mode & FM_L2)
+    ii = np.arange(H)
+    srows = np.flatnonzero(src.any(axis=1))
+    r0 = int(srows[0]) if srows.size else H
+    vd = np.abs(ii[:, None] - srows[None, :]).min(axis=1) if srows.size else np.full(H, 1 << 20)
+    far = {R: far_row(l2, R, ii, r0, vd) for R in (16, 32)}
+    return dict(H=H, W=W, mode=mode, nsrc=int(src.sum()), dlb=int(vd.max()) if srows.size else 0,
+                bandmax=max(int(src[a:a + BAND].sum()) for a in range(0, H, BAND)), nfar16=int(far[16].sum()), nfar32=int(far[32].sum()),
+                r0=r0, sky_ok=sky_possible(not l2 and mode & FM_PREMARK, r0, H), far=far)
+
+
+def decide(H, W, mode, nsrc, dlb, bandmax, nfar16, nfar32, r0, sky_ok, **_):
+    """route_decide, from the summary alone: 16 / 32 (a window), ROUTE_POINTS or 0 (any distance)."""
+    l2, general = bool(mode & FM_L2), bool(mode & FM_GENERAL)
+    premark = not l2 and bool(mode & FM_PREMARK)
+
+    def fits(R, nfar):                                                                               # window_fits
+        ball = 2 * R * R + 2 * R + 1
+        if l2:
+            return nsrc * ball >= DENSITY_LN_N * H * W
+        if not premark:
+            return nsrc * ball >= DENSITY_LN_N * H * W and dlb <= R
+        rest = H - (r0 if sky_ok else 0) - nfar
+        return rest > 0 and nsrc * ball >= DENSITY_LN_N * rest * W
+
+    points = l2 and not general and 0 < nsrc <= L2_PTS_MAX
+    points1 = not l2 and bool(mode & FM_PTS) and 0 < nsrc <= L2_PTS_MAX and bandmax <= PTS_BAND_MAX
+    window = 16 if fits(16, nfar16) else 32 if fits(32, nfar32) else 0
+    return 0 if general else ROUTE_POINTS if points else window if window else ROUTE_POINTS if points1 else 0
+
+
 def route(src, metric="l1_cv", path="auto"):
-    """frame_facts' routing (dtfill_prepass.hpp:366-441) for a pass without a depth epilogue, restated: a dict with
+    """frame_facts' routing (summarise(), then route_decide, then the cull of tile rows and the sky) for a pass without a depth
+    epilogue, restated: a dict with
       r       16 / 32 (the window kernel with that halo; l2: k_l2win with radius W2_R[r]), -1 (the points route), 0 (any distance)
       sky     rows [0, sky) are k_sky's (l1_cv)
       far     rows handed to the any-distance kernels up front (l1_cv: pre-marked rows, culled tile rows, a sky that is not k_sky's;
               l2: rows farther than the radius from every source row)
     as the publishing block decides them: rows the window kernels hand on later (a pixel beyond the halo) are not in it."""
-    src = np.asarray(src, bool)
-    H, W = src.shape
-    nsrc = int(src.sum())
-    l2, general = metric == "l2", path == "general"
-    has = src.any(axis=1)
-    ii = np.arange(H)
-    srows = np.flatnonzero(has)
-    r0 = int(srows[0]) if srows.size else H
-    vd = np.abs(ii[:, None] - srows[None, :]).min(axis=1) if srows.size else np.full(H, 1 << 20)
-    premark = not l2 and not general  # (mode bits 4 | 8, dtfill.hip:268-272)
-    sky_ok = premark and SKY_MIN <= r0 <= SKY_MAX and r0 < H                                        # :367
-    far = {R: (vd > W2_R[R]) if l2 else ((ii >= r0) & (vd > PREMARK[R])) for R in (16, 32)}               # :346
-    dlb = int(vd.max()) if srows.size else 0
-
-    def fits(R):                                                                                     # :380-386
-        ball = 2 * R * R + 2 * R + 1
-        if l2:
-            return nsrc * ball >= 14 * H * W
-        if not premark:
-            return nsrc * ball >= 14 * H * W and dlb <= R
-        rest = H - (r0 if sky_ok else 0) - int(far[R].sum())
-        return rest > 0 and nsrc * ball >= 14 * rest * W
-
-    bandmax = max(int(src[a:a + BAND].sum()) for a in range(0, H, BAND))
-    points = l2 and not general and 0 < nsrc <= L2_PTS_MAX                                           # :390
-    points1 = premark and 0 < nsrc <= L2_PTS_MAX and bandmax <= PTS_BAND_MAX                         # :393
-    window = 16 if fits(16) else 32 if fits(32) else 0
-    r = 0 if general else -1 if points else window if window else -1 if points1 else 0               # :395
-    out = dict(r=r, sky=0, far=0, nsrc=nsrc, r0=r0)
+    s = summarise(src, pass_mode(metric, path))
+    H, W, r0, sky_ok = s["H"], s["W"], s["r0"], s["sky_ok"]
+    r = decide(**s)
+    out = dict(r=r, sky=0, far=0, nsrc=s["nsrc"], r0=r0)
     if r <= 0:
         return out
-    f = far[r].copy()
-    if l2:
+    f = s["far"][r].copy()
+    if s["mode"] & FM_L2:
         out["far"] = int(f.sum())
         return out
-    if not premark:
+    if not s["mode"] & FM_PREMARK:
         return out
     tbase = r0 if sky_ok else 0
     rows = window_tiles(H, W, r, tbase)[0]
-    for a, e in zip(rows, list(rows[1:]) + [H]):                                                     # :412-424
-        keep = int((~f[a:e]).sum())
-        if keep and 4 * keep <= e - a:
+    for a, e in zip(rows, list(rows[1:]) + [H]):                                                     # frame_facts' cull
+        if tile_row_culled(int((~f[a:e]).sum()), e - a):
             f[a:e] = True
-    sky = sky_ok and not f[r0] and not (r0 + 1 < H and f[r0 + 1])                                    # :427
+    sky = sky_ok and not f[r0] and not (r0 + 1 < H and f[r0 + 1])                                    # ... and its sky-off
     out["sky"] = r0 if sky else 0
     out["far"] = int(f.sum()) + (r0 if sky_ok and not sky else 0)
     return out
@@ -230,7 +271,7 @@ def route(src, metric="l1_cv", path="auto"):
 
 def expected_stats(x, metric="l1_cv", path="auto"):
     """What DtFill.pass_stats() reports for batch x when no window block hands a row on: dict all, window, anydist, sky, points
-    in pixels (dtfill_post.hpp:154-188)."""
+    in pixels (stats_body, dtfill_post.hpp)."""
     B, H, W = x.shape
     s = dict(all=B * H * W, window=0, anydist=0, sky=0, points=0)
     for f in x:
