@@ -14,6 +14,7 @@ from .sharding import shard_range, gather_frames, fill_sharded, release_host_sla
 from .tools import DT_complete_batch, Distance_Transform, generate_multi_channel, nearest_point, outlier_removal, subsample_lidar
 from .tools import depth_read, depth_read_batch, nearest_source, rgb_read, rgb_read_batch
 from .tools import map_points_on_image, project_points
+from .tools import get_all_points, unproject_frames
 from .tools import nyu_read_batch, nyu_taps
 from . import demo  # demo.py's own generate_multi_channel / _with_image / create_weight_matrix, reached as <package>.demo.*
 from .postfill import Result, Result_NYU, depth_floor, depth_to_png16, kitti_rows, nyu_eval_crop
@@ -26,10 +27,10 @@ def __getattr__(name):
 
         mod = importlib.import_module(__name__ + ".device")
         return mod if name == "device" else getattr(mod, name)
-    if name == "project_points_device":
+    if name in ("project_points_device", "unproject_device", "unproject_backward_device"):
         import importlib
 
-        return importlib.import_module(__name__ + ".projection").project_points_device
+        return getattr(importlib.import_module(__name__ + ".projection"), name)
     if name == "nyu_read_device":
         import importlib
 
@@ -44,7 +45,8 @@ def __getattr__(name):
 __all__ = [
     "nearest_point", "DT_complete_batch", "Distance_Transform", "outlier_removal", "generate_multi_channel", "subsample_lidar",
     "depth_read", "depth_read_batch", "rgb_read", "rgb_read_batch", "rgb_read_device", "nearest_source",
-    "map_points_on_image", "project_points", "project_points_device", "nyu_read_batch", "nyu_read_device", "nyu_taps",
+    "map_points_on_image", "project_points", "project_points_device", "get_all_points", "unproject_frames",
+    "unproject_device", "unproject_backward_device", "nyu_read_batch", "nyu_read_device", "nyu_taps",
     "demo", "fill", "DtFill",
     "shard_range", "gather_frames", "fill_sharded", "release_host_slab", "build", "load", "METRICS", "DtfillError",
     "Result", "Result_NYU", "depth_floor", "depth_to_png16", "kitti_rows", "nyu_eval_crop",

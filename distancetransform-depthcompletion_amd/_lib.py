@@ -38,6 +38,14 @@ PROJ_NO_POINTS = 1  # bit: nothing landed in the frame
 PROJ_INDEX_ERROR = 2  # bit (reference mode): the reference's assignment would raise IndexError; the frame is all zeros
 PROJ_BAD_COUNT = 4  # bit: counts[b] outside [0, N]; the frame is all zeros
 PROJ_COLUMNS = ("pixels", "inside", "behind", "outside")  # frame_counts' columns, DTFILL_PROJ_N of them
+UNPROJ_NO_POINTS = 1  # bit: no valid pixel in the frame (DTFILL_UNPROJ_*)
+UNPROJ_BAD_INTERVAL = 2  # bit (keep mode): the pitch interval is 0 or not finite; nothing is written
+UNPROJ_SINGULAR = 4  # bit: K or E is singular; nothing is written
+UNPROJ_OVERFLOW = 8  # bit: more points than capacity; the first N in raster order are written
+UNPROJ_BAD_PIXEL = 16  # bit (backward): the pixel list is not strictly increasing inside the frame; zero gradients
+UNPROJ_BAD_COUNT = 32  # bit (backward): counts[b, written] outside [0, N]; zero gradients
+UNPROJ_WRITTEN = 0  # counts' columns
+UNPROJ_TOTAL = 1
 PATHS = {"auto": 0, "general": FLAG_GENERAL_ONLY, "fused": FLAG_FUSED_ONLY}
 
 # the C ABI of include/dtfill.h: symbol -> (restype, argtypes), in the header's order.  tests/test_binding.py holds every entry to
@@ -73,6 +81,10 @@ _ABI = {
     "dtfill_nyu_read": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, vp, ci, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp, sz, vp]),
     "dtfill_project_points_workspace_bytes": (sz, [ci, ci, ci, ci]),
     "dtfill_project_points": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, cf, vp, vp, vp, vp, vp, sz, vp]),
+    "dtfill_unproject_workspace_bytes": (sz, [ci, ci, ci]),
+    "dtfill_unproject": (ci, [vp, vp, ci, ci, ci, cf, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "dtfill_unproject_backward_workspace_bytes": (sz, [ci, ci, ci]),
+    "dtfill_unproject_backward": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
     "dtfill_metrics_workspace_bytes": (sz, [ci]),
     "dtfill_metrics": (ci, [vp, vp, ci, ll, ci, vp, vp, sz, vp]),
     "dtfill_train_loss_workspace_bytes": (sz, [ci, ci, ci]),

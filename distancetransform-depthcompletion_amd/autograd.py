@@ -183,3 +183,44 @@ def fill_values(x, values, src_thr=0.1, metric="l1_cv"):
     squeeze = values.dim() == 3
     out = _FillValues.apply(x.detach(), values.unsqueeze(1) if squeeze else values, float(src_thr), metric)
     return (out[0].squeeze(1) if squeeze else out[0],) + tuple(out[1:])
+
+
+class _Unproject(torch.autograd.Function):
+    """(points, counts, pixel, status) of device.unproject_device; points alone carries a gradient, to x and to payload."""
+
+    @staticmethod
+    def forward(ctx, x, payload, K, E, val_thr, capacity):
+        points, counts, status, _, pixel = device.unproject_device(x, K, E, val_thr, payload, capacity)
+        ctx.set_materialize_grads(False)  # unused points arrive as None: nothing is launched for them
+        ctx.hw = tuple(x.shape[1:])
+        ctx.save_for_backward(pixel, counts, K, E)
+        ctx.mark_non_differentiable(counts, pixel, status)
+        return points, counts, pixel, status
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_points, g_counts=None, g_pixel=None, g_status=None):
+        want_x, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if g_points is None or not (want_x or want_p):
+            return None, None, None, None, None, None
+        pixel, counts, K, E = ctx.saved_tensors
+        grad_x, grad_payload, _ = device.unproject_backward_device(g_points.to(torch.float32).contiguous(), pixel, counts, K, E,
+                                                                   ctx.hw, want_payload=want_p)
+        return (grad_x if want_x else None), grad_payload, None, None, None, None
+
+
+def unproject(x, K, E, val_thr=0.1, payload=None, capacity=None):
+    """Depth frames to ordered point clouds as a differentiable operator (include/dtfill.h, dtfill_unproject): the step from a
+    completed depth map to the pseudo-LiDAR cloud a 3D consumer trains on.  x: contiguous float32 CUDA tensor [B,H,W]; K
+    [3,3] or [B,3,3], E [4,4] or [B,4,4] (numpy or tensors, constants); payload: like x, carried as each record's fourth
+    float; capacity: records per frame (default H*W).  Returns (points [B,N,3 or 4], counts int32 [B,2], pixel int32 [B,N],
+    status int32 [B]) as device.unproject_device gives them, in tensors of the call's own.  Differentiable in x and payload
+    through points, once: the validity mask is a constant of the differentiation and the map is affine in the depth, so the
+    backward (dtfill_unproject_backward) is a scatter of one value per record, bitwise reproducible; the records beyond
+    counts[b, 0] are not written and take no gradient.  counts, pixel and status are marked non-differentiable.  No host
+    synchronisation in either direction; every buffer is the call's own, allocated under the stream it runs on."""
+    device._check_tensor(x, "x")
+    B = x.shape[0]
+    Kd = device._calibration(K, 3, B, x.device, "K")
+    Ed = device._calibration(E, 4, B, x.device, "E")
+    return _Unproject.apply(x, payload, Kd, Ed, float(val_thr), capacity)

@@ -96,6 +96,7 @@ namespace {
 #include "dtfill_rgb.hpp"
 #include "dtfill_nyu.hpp"
 #include "dtfill_proj.hpp"
+#include "dtfill_unproj.hpp"
 #include "dtfill_fillb.hpp"
 #include "dtfill_near.hpp"
 
@@ -831,10 +832,10 @@ int dtfill_line_subsample(const float *x, int B, int H, int W, const double *K, 
     hipStream_t st = static_cast<hipStream_t>(stream);
     k_lines_calib<<<B, 64, 0, st>>>(K, E, rec);
     if (vec) {
-        k_lines_range<true><<<grid, 256, 0, st>>>(x, W, HW, g.tpb, rec, part);
+        k_lines_range<true><<<grid, 256, 0, st>>>(x, 0.1f, W, HW, g.tpb, rec, part);
         k_lines_keep<true><<<grid, 256, 0, st>>>(x, W, HW, n_bins, keep_every, g.tpb, rec, part, out, frame_status);
     } else {
-        k_lines_range<false><<<grid, 256, 0, st>>>(x, W, HW, g.tpb, rec, part);
+        k_lines_range<false><<<grid, 256, 0, st>>>(x, 0.1f, W, HW, g.tpb, rec, part);
         k_lines_keep<false><<<grid, 256, 0, st>>>(x, W, HW, n_bins, keep_every, g.tpb, rec, part, out, frame_status);
     }
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
@@ -979,6 +980,68 @@ int dtfill_project_points(const float *points, const int32_t *counts, int B, int
     else
         proj_launch<DTFILL_PROJ_ZBUFFER>(st, points, counts, B, N, stride, H, W, K, E, min_z, out_f32, out_f64, frame_status,
                                          frame_counts, workspace, acc);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+size_t dtfill_unproject_workspace_bytes(int B, int H, int W) {
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long long)B * H * W >= (1ll << 31)) return 0;
+    return align256((size_t)B * LS_REC * sizeof(double)) + align256((size_t)B * lines_grid(H, W).nb * sizeof(double2)) +
+           align256((size_t)B * up_tiles(H, W) * sizeof(int));
+}
+
+int dtfill_unproject(const float *x, const float *payload, int B, int H, int W, float val_thr, const double *K, const double *E,
+                     int n_bins, int keep_every, int N, int stride, float *points, double *pitch, int32_t *pixel,
+                     int32_t *counts, int32_t *frame_status, void *workspace, size_t ws_bytes, void *stream) {
+    if (!x || !K || !E || !points || !counts || !workspace) return DTFILL_ERR_NULL;
+    const size_t need = dtfill_unproject_workspace_bytes(B, H, W);
+    if (need == 0 || N < 1 || (stride != 3 && stride != 4) || (long long)B * N * stride >= (1ll << 31) || keep_every < 0 ||
+        (keep_every >= 1 && n_bins < 1) || val_thr != val_thr)
+        return DTFILL_ERR_SHAPE;
+    if (ws_bytes < need || ((uintptr_t)workspace & 255)) return DTFILL_ERR_WORKSPACE;
+    const LinesGrid g = lines_grid(H, W);
+    char *base = static_cast<char *>(workspace);
+    UpWs ws;
+    ws.rec = reinterpret_cast<double *>(base);
+    ws.part = reinterpret_cast<double2 *>(base + align256((size_t)B * LS_REC * sizeof(double)));
+    ws.tcnt = reinterpret_cast<int *>(base + align256((size_t)B * LS_REC * sizeof(double)) +
+                                      align256((size_t)B * g.nb * sizeof(double2)));
+    const bool vec = ((H * W) & 3) == 0 && ((uintptr_t)x & 15) == 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+#define DTFILL_UNPROJ_GO(VEC, KEEP)                                                                                              \
+    unproj_launch<VEC, KEEP>(st, x, payload, B, H, W, val_thr, K, E, n_bins, keep_every, N, stride, points, pitch, pixel, counts, \
+                             frame_status, ws, g.tpb, g.nb)
+    if (keep_every >= 1) {
+        if (vec) DTFILL_UNPROJ_GO(true, true); else DTFILL_UNPROJ_GO(false, true);
+    } else {
+        if (vec) DTFILL_UNPROJ_GO(true, false); else DTFILL_UNPROJ_GO(false, false);
+    }
+#undef DTFILL_UNPROJ_GO
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+size_t dtfill_unproject_backward_workspace_bytes(int B, int H, int W) {
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long long)B * H * W >= (1ll << 31)) return 0;
+    return align256((size_t)B * LS_REC * sizeof(double)) + align256((size_t)B * sizeof(int));
+}
+
+int dtfill_unproject_backward(const float *grad_points, const int32_t *pixel, const int32_t *counts, int B, int N, int stride,
+                              int H, int W, const double *K, const double *E, float *grad_x, float *grad_payload,
+                              int32_t *frame_status, void *workspace, size_t ws_bytes, void *stream) {
+    if (!grad_points || !pixel || !counts || !K || !E || !grad_x || !workspace) return DTFILL_ERR_NULL;
+    const size_t need = dtfill_unproject_backward_workspace_bytes(B, H, W);
+    if (need == 0 || N < 1 || (stride != 3 && stride != 4) || (long long)B * N * stride >= (1ll << 31)) return DTFILL_ERR_SHAPE;
+    if (ws_bytes < need || ((uintptr_t)workspace & 255)) return DTFILL_ERR_WORKSPACE;
+    double *rec = static_cast<double *>(workspace);
+    int *flags = reinterpret_cast<int *>(static_cast<char *>(workspace) + align256((size_t)B * LS_REC * sizeof(double)));
+    const int HW = H * W;
+    const size_t n = (size_t)B * HW;
+    const dim3 recs((N + UB_BLOCK - 1) / UB_BLOCK, B);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    k_lines_calib<<<B, 64, 0, st>>>(K, E, rec);
+    k_unprojb_clear<<<(unsigned)min((n + 255) / 256, (size_t)1 << 16), 256, 0, st>>>(grad_x, grad_payload, n, flags, B);
+    k_unprojb_check<<<recs, 256, 0, st>>>(pixel, counts, N, HW, flags);
+    k_unprojb_scatter<<<recs, 256, 0, st>>>(grad_points, pixel, counts, N, stride, W, HW, rec, flags, grad_x, grad_payload,
+                                            frame_status);
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 

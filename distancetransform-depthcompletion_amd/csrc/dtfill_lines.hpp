@@ -88,19 +88,30 @@ __global__ __launch_bounds__(64) void k_lines_calib(const double *__restrict__ K
     if (t == 2) r[LS_SING] = s_ok[0] && s_ok[1] ? 0.0 : 1.0;
 }
 
-// The pitch of pixel (row v, column u) at depth d: p_cam = K^-1 [u v 1]^T d, p = (E^-1 [p_cam; 1])[0:3],
+// The point of pixel (row v, column u) at depth d: p_cam = K^-1 [u v 1]^T d, p = (E^-1 [p_cam; 1])[0:3], and its pitch
 // asin(p.z / |p|).  c: the frame record.  Every operation rounded on its own (no contraction), in the order the contract
-// writes them, so that both launches compute the same bits for the same pixel.
-__device__ __forceinline__ double ls_pitch(const double *c, int u, int v, double d) {
+// writes them, so that every launch (the range, the labels, dtfill_unproject's records) computes the same bits for the same
+// pixel.
+__device__ __forceinline__ void ls_point(const double *c, int u, int v, double d, double &px, double &py, double &pz) {
 #pragma clang fp contract(off)
     const double du = (double)u, dv = (double)v;
     const double cx = (c[0] * du + c[1] * dv + c[2]) * d;
     const double cy = (c[3] * du + c[4] * dv + c[5]) * d;
     const double cz = (c[6] * du + c[7] * dv + c[8]) * d;
-    const double px = c[9] * cx + c[10] * cy + c[11] * cz + c[12];
-    const double py = c[13] * cx + c[14] * cy + c[15] * cz + c[16];
-    const double pz = c[17] * cx + c[18] * cy + c[19] * cz + c[20];
+    px = c[9] * cx + c[10] * cy + c[11] * cz + c[12];
+    py = c[13] * cx + c[14] * cy + c[15] * cz + c[16];
+    pz = c[17] * cx + c[18] * cy + c[19] * cz + c[20];
+}
+
+__device__ __forceinline__ double ls_point_pitch(double px, double py, double pz) {
+#pragma clang fp contract(off)
     return asin(pz / sqrt(px * px + py * py + pz * pz));
+}
+
+__device__ __forceinline__ double ls_pitch(const double *c, int u, int v, double d) {
+    double px, py, pz;
+    ls_point(c, u, v, d, px, py, pz);
+    return ls_point_pitch(px, py, pz);
 }
 
 // Lane t's LS_PER pixels of a tile: VEC (16-byte aligned frames) two float4 at 4 (t + 256 j), else one float at t + 256 j.
@@ -112,11 +123,12 @@ __device__ __forceinline__ int ls_loc(int t, int j) {
 template <bool VEC>
 __device__ __forceinline__ void ls_load(const float *__restrict__ xf, int base, int HW, float (&v)[LS_PER]) {
     const int t = threadIdx.x;
+    const float pad = __builtin_nanf("");  // beyond the frame: valid under no threshold
     if (VEC) {
 #pragma unroll
         for (int q = 0; q < LS_PER / 4; ++q) {
             const int i = base + 4 * (t + 256 * q);
-            const float4 f = i < HW ? *reinterpret_cast<const float4 *>(xf + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 f = i < HW ? *reinterpret_cast<const float4 *>(xf + i) : make_float4(pad, pad, pad, pad);
             v[4 * q] = f.x;
             v[4 * q + 1] = f.y;
             v[4 * q + 2] = f.z;
@@ -126,19 +138,19 @@ __device__ __forceinline__ void ls_load(const float *__restrict__ xf, int base, 
 #pragma unroll
         for (int j = 0; j < LS_PER; ++j) {
             const int i = base + t + 256 * j;
-            v[j] = i < HW ? xf[i] : 0.0f;
+            v[j] = i < HW ? xf[i] : pad;
         }
     }
 }
 
-// Appends the lane's valid pixels (x > 0.1f, float32 as numpy compares; a padding zero is never valid) to the tile's
+// Appends the lane's valid pixels (x > thr, float32 as numpy compares; the padding's NaN is never valid) to the tile's
 // list: a wave-wide prefix sum of the lanes' counts, one LDS atomic per wave.  Returns the lane's valid mask.
 template <bool VEC>
-__device__ __forceinline__ unsigned ls_compact(const float (&v)[LS_PER], int *s_n, u16 *s_idx, float *s_val) {
+__device__ __forceinline__ unsigned ls_compact(const float (&v)[LS_PER], float thr, int *s_n, u16 *s_idx, float *s_val) {
     const int t = threadIdx.x, lane = t & 63;
     unsigned m = 0;
 #pragma unroll
-    for (int j = 0; j < LS_PER; ++j) m |= (v[j] > 0.1f ? 1u : 0u) << j;
+    for (int j = 0; j < LS_PER; ++j) m |= (v[j] > thr ? 1u : 0u) << j;
     const int c = __popc(m);
     int incl = c;
 #pragma unroll
@@ -161,7 +173,7 @@ __device__ __forceinline__ unsigned ls_compact(const float (&v)[LS_PER], int *s_
 
 // tiles [blockIdx.x * tpb, min(T, (blockIdx.x + 1) * tpb)) of frame blockIdx.y, T = ceil(HW / LS_TILE)
 template <bool VEC>
-__global__ __launch_bounds__(256) void k_lines_range(const float *__restrict__ x, int W, int HW, int tpb,
+__global__ __launch_bounds__(256) void k_lines_range(const float *__restrict__ x, float thr, int W, int HW, int tpb,
                                                      const double *__restrict__ rec, double2 *__restrict__ part) {
     __shared__ u16 s_idx[LS_TILE];
     __shared__ float s_val[LS_TILE];
@@ -183,7 +195,7 @@ __global__ __launch_bounds__(256) void k_lines_range(const float *__restrict__ x
         const int par = (tile - tile0) & 1;
         float v[LS_PER];
         ls_load<VEC>(xf, tile * LS_TILE, HW, v);
-        ls_compact<VEC>(v, &s_n[par], s_idx, s_val);
+        ls_compact<VEC>(v, thr, &s_n[par], s_idx, s_val);
         __syncthreads();
         const int n = s_n[par];
         if (t == 0) s_n[par ^ 1] = 0;  // the next tile's counter: its last reader passed the previous tile's barrier
@@ -211,6 +223,31 @@ __global__ __launch_bounds__(256) void k_lines_range(const float *__restrict__ x
     }
 }
 
+// The frame's pitch range from k_lines_range's nb partials, its bin interval and its DTFILL_LINES_* status; called by the 64
+// lanes of one wave, the same result in each.
+__device__ __forceinline__ int ls_frame_range(const double2 *__restrict__ part, int nb, int b, int n_bins,
+                                              const double *__restrict__ rec, double &lo, double &iv) {
+    const int t = threadIdx.x & 63;
+    lo = __builtin_inf();
+    double hi = -__builtin_inf();
+    for (int k = t; k < nb; k += 64) {
+        const double2 r = part[(size_t)b * nb + k];
+        lo = ls_min(lo, r.x);
+        hi = ls_max(hi, r.y);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        lo = ls_min(lo, __shfl_xor(lo, o, 64));
+        hi = ls_max(hi, __shfl_xor(hi, o, 64));
+    }
+    iv = (hi - lo) / (double)n_bins;
+    const bool sing = rec[(size_t)b * LS_REC + LS_SING] != 0.0;
+    const bool empty = lo == __builtin_inf();  // a valid pixel's pitch is finite or NaN
+    int st = (empty ? DTFILL_LINES_NO_POINTS : 0) | (sing ? DTFILL_LINES_SINGULAR : 0);
+    if (!empty && !sing && !(iv > 0.0 && iv < __builtin_inf())) st |= DTFILL_LINES_BAD_INTERVAL;
+    return st;
+}
+
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_lines_keep(const float *__restrict__ x, int W, int HW, int n_bins, int keep_every,
                                                     int tpb, const double *__restrict__ rec, const double2 *__restrict__ part,
@@ -225,24 +262,10 @@ __global__ __launch_bounds__(256) void k_lines_keep(const float *__restrict__ x,
     float *of = out + (size_t)b * HW;
     const int T = (HW + LS_TILE - 1) / LS_TILE;
     const int tile0 = blockIdx.x * tpb, tile1 = min(T, tile0 + tpb);
-    if (t < 64) {  // the frame's range from the first launch's partials
-        double lo = __builtin_inf(), hi = -__builtin_inf();
-        for (int k = t; k < (int)gridDim.x; k += 64) {
-            const double2 r = part[(size_t)b * gridDim.x + k];
-            lo = ls_min(lo, r.x);
-            hi = ls_max(hi, r.y);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            lo = ls_min(lo, __shfl_xor(lo, o, 64));
-            hi = ls_max(hi, __shfl_xor(hi, o, 64));
-        }
+    if (t < 64) {
+        double lo, iv;
+        const int st = ls_frame_range(part, (int)gridDim.x, b, n_bins, rec, lo, iv);
         if (t == 0) {
-            const double iv = (hi - lo) / (double)n_bins;
-            const bool sing = rec[(size_t)b * LS_REC + LS_SING] != 0.0;
-            const bool empty = lo == __builtin_inf();  // a valid pixel's pitch is finite or NaN
-            int st = (empty ? DTFILL_LINES_NO_POINTS : 0) | (sing ? DTFILL_LINES_SINGULAR : 0);
-            if (!empty && !sing && !(iv > 0.0 && iv < __builtin_inf())) st |= DTFILL_LINES_BAD_INTERVAL;
             s_lo = lo;
             s_iv = iv;
             s_status = st;
@@ -269,7 +292,7 @@ __global__ __launch_bounds__(256) void k_lines_keep(const float *__restrict__ x,
         const int par = (tile - tile0) & 1, base = tile * LS_TILE;
         float v[LS_PER];
         ls_load<VEC>(xf, base, HW, v);
-        const unsigned m = ls_compact<VEC>(v, &s_n[par], s_idx, s_val);
+        const unsigned m = ls_compact<VEC>(v, 0.1f, &s_n[par], s_idx, s_val);
         __syncthreads();
         const int n = s_n[par];
         if (t == 0) s_n[par ^ 1] = 0;

@@ -823,10 +823,10 @@ def rgb_read_device(raw, dims=None, size=(1216, 352), first_row=0, want="float",
 
 def __getattr__(name):
     # the point projection's device function is defined in projection.py (which imports this module's helpers)
-    if name == "project_points_device":
+    if name in ("project_points_device", "unproject_device", "unproject_backward_device"):
         from . import projection
 
-        return projection.project_points_device
+        return getattr(projection, name)
     if name == "nyu_read_device":  # likewise in nyu.py
         from . import nyu
 

@@ -6,6 +6,7 @@ Same names, argument meaning and error behaviour as
   data_read.py:81-99                   depth_read (and depth_read_batch for Data_load.read_batch's stack of them)
   data_read.py:66-73                   rgb_read (and rgb_read_batch for read_batch's img_batch and the drivers' / 255.0)
   subsample_Lidar_train.py:180-193     map_points_on_image (and project_points for a batch of ragged clouds, z-buffered)
+  subsample_Lidar_train.py:125-153     get_all_points (and unproject_frames for a batch, a payload, the pitches, keep_ratio)
 but the work is done by libdtfill.so on the current HIP device.  Differences from the reference,
 all widening: DT_complete_batch accepts any HxW (the reference hard-codes 352x1216 in its
 reshapes, tools.py:25,27), and the thresholds the reference writes as literals are keyword
@@ -244,6 +245,83 @@ def project_points(clouds, K, E, hw=(352, 1216), mode="zbuffer", min_z=0.0):
     out, tail = _read_back(frame, torch.cat([status[:, None], counts4], 1), np.float32)
     _raise_index_error(tail[:, 0])
     return out, tail[:, 1:].copy()
+
+
+def unproject_frames(x, K, E, val_thr=0.1, payload=None, keep_ratio=None, n_bins=64, with_pitch=False):
+    """Depth frames -> their point clouds in the Velodyne frame (include/dtfill.h, dtfill_unproject).  x: [H,W] or [B,H,W];
+    a pixel is a point iff x > val_thr in float32; K: intrinsics [3,3] or [B,3,3]; E: velo->cam extrinsics [4,4] or [B,4,4];
+    payload: float32 of x's shape, carried as each point's fourth float.  keep_ratio = None gives every valid pixel
+    (get_all_points), keep_ratio = 1/k the reference's left_points, sample(calculate_angle(get_all_points(...))), with
+    subsample_lidar's errors: np.linalg.LinAlgError for a singular calibration, ValueError for a frame without a valid pixel
+    (only with keep_ratio: get_all_points of an empty frame is an empty cloud); a frame whose pitch interval is 0 or not finite
+    keeps nothing.  Returns a list of B ragged float32 arrays [n_b, 3 or 4] in raster order, and with with_pitch a second
+    list of float64 [n_b] pitches.  One page-locked staging buffer, one copy each way."""
+    if keep_ratio is not None:
+        _device.keep_every_of(keep_ratio)  # ValueError before any device work
+    a = _as_f32_frames(x)
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3 or 0 in a.shape:
+        raise ValueError("unproject_frames expects [H,W] or [B,H,W], got shape %s" % (np.shape(x),))
+    B, H, W = a.shape
+    p = None
+    if payload is not None:
+        p = np.asarray(payload)
+        if p.dtype != np.float32:
+            raise TypeError("payload must be float32 (it is copied as bits), got dtype %s" % p.dtype)
+        if p.size != a.size or p.shape[-2:] != (H, W):
+            raise ValueError("payload of shape %s does not go with frames of shape %s" % (p.shape, np.shape(x)))
+        p = p.reshape(a.shape)
+    n = a.size
+    stage = _device._host_pool.take((n * (1 if p is None else 2),), np.float32)
+    stage.array[:n] = a.reshape(-1)
+    if p is not None:
+        stage.array[n:] = p.reshape(-1)
+    dev = _device.default_op().device
+    d = torch.empty(stage.array.shape, dtype=torch.float32, device=dev)
+    d.copy_(stage.tensor, non_blocking=True)
+    want = ("pitch",) if with_pitch else ()
+    points, counts, status, pitch, _ = _device.unproject_device(
+        d[:n].view(B, H, W), K, E, val_thr, None if p is None else d[n:].view(B, H, W), keep_ratio=keep_ratio, n_bins=n_bins,
+        want=want)
+    # the clouds' capacity is H*W a frame: copy back what the counts say is in use, packed on the device first
+    cnt = torch.cat([counts[:, 0], status]).cpu().numpy()  # synchronises: the staging buffer is done with
+    nb, st = cnt[:B], cnt[B:]
+    bad = np.flatnonzero(st & _lib.UNPROJ_SINGULAR)
+    if bad.size:
+        raise np.linalg.LinAlgError("Singular matrix (intrinsic or extrinsic of frame %d)" % bad[0])
+    bad = np.flatnonzero(st & _lib.UNPROJ_NO_POINTS)
+    if bad.size and keep_ratio is not None:
+        raise ValueError("zero-size array to reduction operation maximum which has no identity (frame %d has no point "
+                         "with depth > %r)" % (bad[0], val_thr))
+    total = int(nb.sum())
+    stride = points.shape[2]
+    if total:
+        out, _ = _read_back(torch.cat([points[b, :nb[b]] for b in range(B)]), status[:0], np.float32)
+    else:
+        out = np.zeros((0, stride), np.float32)
+    ends = np.cumsum(nb)
+    clouds = [out[e - k:e] for e, k in zip(ends, nb)]
+    if not with_pitch:
+        return clouds
+    if total:
+        ph, _ = _read_back(torch.cat([pitch[b, :nb[b]] for b in range(B)]), status[:0], np.float64)
+    else:
+        ph = np.zeros((0,), np.float64)
+    return clouds, [ph[e - k:e] for e, k in zip(ends, nb)]
+
+
+def get_all_points(lidar, intrinsic, extrinsic, image_coor_tensor=None):
+    """subsample_Lidar_train.py:125-153 / subsample_Lidar_val.py:112-140: the points of every pixel of `lidar` (squeezable to
+    [H,W]; any size, where the reference hard-codes 352 x 1216) with depth > 0.1, back-projected through the inverses of
+    intrinsic [3,3] and extrinsic [4,4] (velo->cam), as float32 [n, 3] in raster order.  image_coor_tensor, the reference's
+    precomputed pixel grid, is accepted and ignored.  Raises np.linalg.LinAlgError for a singular calibration, as the
+    reference's np.linalg.inv does.  The arithmetic is the contract's float64 with one rounding to float32 at the end
+    (include/dtfill.h, dtfill_unproject), where the reference computes in float32 throughout."""
+    x = np.squeeze(_as_f32_frames(lidar))
+    if x.ndim != 2:
+        raise ValueError("get_all_points expects an array squeezable to [H,W], got shape %s" % (np.shape(lidar),))
+    return unproject_frames(x, np.reshape(intrinsic, [3, 3]), np.reshape(extrinsic, [4, 4]))[0]
 
 
 KITTI_SIZE = (1216, 352)  # data_read.py:96: PIL's (width, height)

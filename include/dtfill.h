@@ -495,6 +495,79 @@ int dtfill_project_points(const float *points, const int32_t *counts /* nullable
                           void *workspace, size_t ws_bytes, void *stream);
 
 /*
+ * Back-projection, the inverse of dtfill_project_points: depth frames to ordered point clouds in the Velodyne frame.  With
+ * keep_every == 0 it is get_all_points() of subsample_Lidar_train.py:125-141 / subsample_Lidar_val.py:112-128, with
+ * keep_every >= 1 the scripts' get_all_points -> calculate_angle -> sample (their `left_points`); a dense frame (a fill's
+ * depth output) gives the pseudo-LiDAR cloud.
+ *
+ * x: float32 [B,H,W]; payload: float32 [B,H,W], nullable (any per-pixel scalar to carry: an intensity, a confidence);
+ * K: float64 [B,3,3]; E: float64 [B,4,4] (dtfill_line_subsample's conventions).
+ * VALID: pixel (row v, column u) of frame b is valid iff x > val_thr, a float32 compare: NaN is never valid, +inf is.  val_thr
+ *   must not be NaN; the reference's literal is 0.1f.
+ * THE POINT of a valid pixel, in IEEE double, no contraction, in exactly dtfill_line_subsample's order, d = (double)x:
+ *     p_cam = K^-1 [u, v, 1]^T d,  p = (E^-1 [p_cam; 1])[0:3],  pitch = asin(p.z / |p|)
+ *   with K^-1, E^-1 from the same on-device Gauss-Jordan (partial pivoting).  Each coordinate is stored as (float)p_r, one
+ *   round-to-nearest-even conversion; pitch[b, i] holds the double bit for bit: the bits dtfill_line_subsample labels with.
+ * SELECTION.  keep_every == 0: every valid pixel; n_bins is ignored.  keep_every >= 1 (n_bins >= 1): the valid pixels that
+ *   dtfill_line_subsample keeps: pmin, pmax over the frame's valid pixels, interval = (pmax - pmin) / n_bins, kept iff
+ *   ceil((pitch - pmin) / interval) mod keep_every == 0, the label not clamped.  With val_thr == 0.1f these are exactly the
+ *   non-zero pixels of dtfill_line_subsample's output.
+ * ORDER AND LAYOUT.  A frame's selected pixels go out in raster order (row-major), as numpy's boolean-mask indexing yields
+ *   them.  Record i of frame b is points[(b*N + i)*stride .. +stride), stride 3 or 4: what dtfill_project_points reads, so
+ *   the two calls chain with no repacking.  With stride == 4 the fourth float is payload[b, v, u] bit for bit, +0.0f when
+ *   payload is NULL.  pixel[b, i] = v*W + u.  pitch: float64 [B,N], nullable; pixel: int32 [B,N], nullable.
+ *   counts: int32 [B, 2]: column DTFILL_UNPROJ_WRITTEN holds n_b = min(total_b, N), column DTFILL_UNPROJ_TOTAL the number of
+ *   selected pixels total_b.  When total_b > N the first N points in raster order are written and DTFILL_UNPROJ_OVERFLOW is
+ *   set.  Records, pitches and pixels at i >= n_b are NOT written: the caller's bytes stay.  The placement is decided by
+ *   counts and prefix sums, never by the order in which atomics arrive: the same bytes on every run.
+ * STATUS.  frame_status: int32 [B], nullable, DTFILL_UNPROJ_* bits.  NO_POINTS, BAD_INTERVAL (keep_every >= 1 only) and
+ *   SINGULAR have the meanings and values of DTFILL_LINES_*.  A frame with SINGULAR or BAD_INTERVAL writes nothing and has
+ *   both counts 0.
+ * No output may alias an input.  workspace: at least dtfill_unproject_workspace_bytes(B, H, W) bytes, 256-B aligned, the
+ * caller's, no initialisation needed, nothing kept between calls.  Asynchronous on `stream`; no allocation, no host
+ * synchronisation, re-entrant across streams.  Every byte offset is a size_t: B*N*stride floats may pass 4 GiB.
+ * Returns, all checked before any HIP call: DTFILL_ERR_NULL for a NULL x, K, E, points, counts or workspace; DTFILL_ERR_SHAPE
+ * for B, H, W or N < 1, B > 65535, B*H*W >= 2^31, stride not 3 or 4, B*N*stride >= 2^31 (dtfill_project_points' rule: a legal
+ * output is a legal input there), keep_every < 0, keep_every >= 1 with n_bins < 1, or a NaN val_thr; DTFILL_ERR_WORKSPACE for
+ * a workspace too small or not aligned; then DTFILL_ERR_LAUNCH if a launch failed.
+ *
+ * dtfill_unproject_backward: the gradients of a loss with respect to x and payload, given its gradient with respect to the
+ * records.  The map is affine in the depth, so x is not needed.  grad_points: float32 [B, N, stride]; pixel and counts as the
+ * forward wrote them; grad_x: float32 [B,H,W]; grad_payload: float32 [B,H,W], nullable.
+ *   For i < counts[b].WRITTEN and (v, u) decoded from pixel[b, i], in double, left to right:
+ *     k = K^-1 [u, v, 1]^T;  j_r = Einv[r][0]*k_0 + Einv[r][1]*k_1 + Einv[r][2]*k_2;
+ *     grad_x[b, v, u] = (float)(gX*j_0 + gY*j_1 + gZ*j_2),  gX, gY, gZ the record's three floats widened.
+ *   Every other pixel of grad_x is +0.0f.  With stride == 4 and grad_payload non-NULL, grad_payload[b, v, u] is the fourth
+ *   float bit for bit, +0.0f elsewhere (and everywhere with stride == 3).
+ *   A frame's pixel list must be strictly increasing and inside [0, H*W), as the forward writes it; one that is not sets
+ *   DTFILL_UNPROJ_BAD_PIXEL and that frame's gradients are all +0.0f.  A DTFILL_UNPROJ_SINGULAR frame gets all-zero
+ *   gradients.  counts[b].WRITTEN outside [0, N] sets DTFILL_UNPROJ_BAD_COUNT: all-zero gradients, nothing of that frame is
+ *   read.  A scatter to distinct pixels: no atomics on the gradients, no float accumulation, the same bits on every run.
+ * Workspace, stream and aliasing rules as the forward's.  Returns DTFILL_ERR_NULL for a NULL grad_points, pixel, counts, K, E,
+ * grad_x or workspace; DTFILL_ERR_SHAPE for B, N, H, W < 1, B > 65535, B*H*W >= 2^31, stride not 3 or 4 or
+ * B*N*stride >= 2^31; DTFILL_ERR_WORKSPACE; all before any HIP call; then DTFILL_ERR_LAUNCH.
+ */
+#define DTFILL_UNPROJ_NO_POINTS    1 /* status bit: no valid pixel in the frame */
+#define DTFILL_UNPROJ_BAD_INTERVAL 2 /* status bit (keep_every >= 1): the pitch interval is 0 or not finite */
+#define DTFILL_UNPROJ_SINGULAR     4 /* status bit: K or E singular */
+#define DTFILL_UNPROJ_OVERFLOW     8 /* status bit: total_b > N, only the first N points were written */
+#define DTFILL_UNPROJ_BAD_PIXEL   16 /* status bit (backward): the pixel list is not strictly increasing inside [0, H*W) */
+#define DTFILL_UNPROJ_BAD_COUNT   32 /* status bit (backward): counts[b].WRITTEN outside [0, N] */
+#define DTFILL_UNPROJ_WRITTEN 0 /* counts columns */
+#define DTFILL_UNPROJ_TOTAL   1
+size_t dtfill_unproject_workspace_bytes(int B, int H, int W); /* 0 on a bad shape */
+int dtfill_unproject(const float *x, const float *payload /* nullable */, int B, int H, int W, float val_thr,
+                     const double *K, const double *E, int n_bins, int keep_every /* 0: every valid pixel */,
+                     int N, int stride, float *points, double *pitch /* nullable */, int32_t *pixel /* nullable */,
+                     int32_t *counts, int32_t *frame_status /* nullable */,
+                     void *workspace, size_t ws_bytes, void *stream);
+size_t dtfill_unproject_backward_workspace_bytes(int B, int H, int W); /* 0 on a bad shape */
+int dtfill_unproject_backward(const float *grad_points, const int32_t *pixel, const int32_t *counts,
+                              int B, int N, int stride, int H, int W, const double *K, const double *E,
+                              float *grad_x, float *grad_payload /* nullable */, int32_t *frame_status /* nullable */,
+                              void *workspace, size_t ws_bytes, void *stream);
+
+/*
  * Error metrics of evaluation.py, one row per frame:
  *   DTFILL_METRICS_KITTI  Result.evaluate, evaluation.py:82-123 (metres -> mm for mse/rmse/mae, -> 1/km for
  *                         irmse/imae; the deltas stay 0 as in the reference);
