@@ -46,6 +46,9 @@ UNPROJ_BAD_PIXEL = 16  # bit (backward): the pixel list is not strictly increasi
 UNPROJ_BAD_COUNT = 32  # bit (backward): counts[b, written] outside [0, N]; zero gradients
 UNPROJ_WRITTEN = 0  # counts' columns
 UNPROJ_TOTAL = 1
+CONV_LINEAR = 0  # act of dtfill_conv2d (DTFILL_CONV_*)
+CONV_LEAKY = 1  # y > 0 ? y : y * alpha
+CONV_ACTS = {"linear": CONV_LINEAR, "leaky": CONV_LEAKY}
 PATHS = {"auto": 0, "general": FLAG_GENERAL_ONLY, "fused": FLAG_FUSED_ONLY}
 
 # the C ABI of include/dtfill.h: symbol -> (restype, argtypes), in the header's order.  tests/test_binding.py holds every entry to
@@ -96,6 +99,7 @@ _ABI = {
     "dtfill_nearest_gather": (ci, [vp, vp, vp, ci, ci, ci, ci, cf, vp, vp, vp, vp, sz, vp]),
     "dtfill_nearest_gather_backward_workspace_bytes": (sz, [ci, ci, ci, ci]),
     "dtfill_nearest_gather_backward": (ci, [vp, vp, vp, ci, ci, ci, ci, cf, vp, vp, vp, sz, vp]),
+    "dtfill_conv2d": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, cf, vp, ci, ci, vp]),
 }
 SYMBOLS = tuple(_ABI)
 del vp, ci, cf, sz, cu, ll, cs  # (the table's shorthands, not names of this module)

@@ -61,7 +61,8 @@
 // rows under a sky (window_tiling, tile_row_height, tile_row_culled), k_pts's and k_l2win's tiles.  frame_facts, fused_body and
 // the host below call it; tests/test_route.py compiles it for the host and holds tests/exhaustive_cases.py to it.
 //
-// No MFMA anywhere: this path is compare/min/index work (DESIGN.md "Roofline").
+// No MFMA in any of the above: this path is compare/min/index work (DESIGN.md "Roofline").  The one matmul-shaped entry point,
+// dtfill_conv2d (SparsityCNN's layers), is dtfill_conv.hpp's.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -99,6 +100,7 @@ namespace {
 #include "dtfill_unproj.hpp"
 #include "dtfill_fillb.hpp"
 #include "dtfill_near.hpp"
+#include "dtfill_conv.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -1176,6 +1178,21 @@ int dtfill_nearest_gather_backward(const float *x, const int32_t *index, const f
     int c0 = 0;
     for (; c0 + 2 <= C; c0 += 2) ngb_round<2>(st, index, grad_out, grad_values, C, c0, B, H, W, ws, status);
     if (c0 < C) ngb_round<1>(st, index, grad_out, grad_values, C, c0, B, H, W, ws, status);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+int dtfill_conv2d(const float *x, int B, int H, int W, int Cin, const float *w, const float *bias, int ksize, int Cout, int act,
+                  float alpha, float *out, int out_channels, int out_offset, void *stream) {
+    if (!x || !w || !out) return DTFILL_ERR_NULL;
+    if (ksize != 1 && ksize != 3 && ksize != 5 && ksize != 7) return DTFILL_ERR_SHAPE;
+    if (Cin != 1 && (Cin < CV_G || Cin > 4 * CV_G || Cin % CV_G)) return DTFILL_ERR_SHAPE;
+    if (Cout != 1 && Cout != 16) return DTFILL_ERR_SHAPE;
+    if (out_offset < 0 || out_channels < 1 || (long long)out_offset + Cout > out_channels) return DTFILL_ERR_SHAPE;
+    if (B < 1 || H < 1 || W < 1 || (long long)B * H * W >= (1ll << 31)) return DTFILL_ERR_SHAPE;
+    if ((long long)B * H * W * max(Cin, out_channels) >= (1ll << 31)) return DTFILL_ERR_SHAPE;
+    if ((act != DTFILL_CONV_LINEAR && act != DTFILL_CONV_LEAKY) || !isfinite(alpha)) return DTFILL_ERR_SHAPE;
+    const ConvArgs a{x, w, bias, out, B, H, W, Cin, out_channels, out_offset, act, alpha};
+    conv_launch(static_cast<hipStream_t>(stream), a, ksize, Cout);
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 

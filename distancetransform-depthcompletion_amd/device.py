@@ -361,16 +361,24 @@ def outlier_removal_device(x):
     return out
 
 
-def generate_multi_channel_device(data, mask, table_size=7, scale_num=4):
+def generate_multi_channel_device(data, mask, table_size=7, scale_num=4, outs=None):
     """net.py:83-122 on the device.  data, mask: contiguous float32 CUDA tensors [B,H,W].
-    Returns (lidar_1, lidar_2, lidar_3, lidar_4) with None beyond scale_num, like the reference."""
+    Returns (lidar_1, lidar_2, lidar_3, lidar_4) with None beyond scale_num, like the reference.  outs: scale_num - 1 tensors
+    like data to hold lidar_2.. (a caller that keeps its buffers); new ones by default."""
     _require_gpu()
     _check_tensor(data, "data")
     _check_tensor(mask, "mask")
     if data.shape != mask.shape:
         raise ValueError("data and mask shapes differ")
     B, H, W = data.shape
-    outs = [torch.empty_like(data) for _ in range(scale_num - 1)]
+    if outs is None:
+        outs = [torch.empty_like(data) for _ in range(scale_num - 1)]
+    else:
+        outs = list(outs)
+        if len(outs) != scale_num - 1:
+            raise ValueError("outs must hold scale_num - 1 = %d tensors, got %d" % (scale_num - 1, len(outs)))
+        for k, o in enumerate(outs):
+            _check_tensor(o, "outs[%d]" % k, like=data, like_name="data")
     ptrs = [o.data_ptr() for o in outs] + [None] * (4 - scale_num)
     with torch.cuda.device(data.device):
         _lib.check(_lib.load().dtfill_generate_multi_channel(
@@ -831,6 +839,10 @@ def __getattr__(name):
         from . import nyu
 
         return nyu.nyu_read_device
+    if name == "conv2d_device":  # likewise in net.py
+        from . import net
+
+        return net.conv2d_device
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 

@@ -151,6 +151,20 @@ def generate_multi_channel(lidar_data, lidar_mask, table_size=7, scale_num=4):
     return tuple(None if o is None else o.cpu().numpy()[..., None] for o in outs)
 
 
+def conv2d(x, kernel, bias=None, act="linear", alpha=0.2):
+    """A stride-1 'same' float32 convolution as a numpy function, in the fixed summation order of include/dtfill.h
+    (dtfill_conv2d): what a tf.keras.layers.Conv2D(Cout, ksize, padding="same") of net.py's SparsityCNN computes, followed by
+    tf.nn.leaky_relu for act="leaky".  x [B,H,W,Cin]; kernel [ksize,ksize,Cin,Cout] and bias [Cout] as Keras stores them.
+    Returns float32 [B,H,W,Cout]."""
+    a = _as_f32_frames(x)
+    k = _as_f32_frames(kernel)
+    if a.ndim != 4 or k.ndim != 4:
+        raise ValueError("conv2d expects x [B,H,W,Cin] and kernel [ksize,ksize,Cin,Cout]")
+    dev = _device.default_op().device
+    b = None if bias is None else _upload(_as_f32_frames(bias), dev)
+    return _device.conv2d_device(_upload(a, dev), _upload(k, dev), b, act, alpha).cpu().numpy()
+
+
 def subsample_lidar(sparse_depth, intrinsic, extrinsic, keep_ratio=0.25, n_bins=64):
     """subsample_Lidar_train.py / subsample_Lidar_val.py: get_all_points -> calculate_angle -> sample(keep_ratio) ->
     map_points_on_image, in one call (the caller's `* 256 -> uint16` PNG write stays as it is).  sparse_depth [H,W],

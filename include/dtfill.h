@@ -740,6 +740,47 @@ int dtfill_nearest_gather_backward(const float *x, const int32_t *index, const f
                                    int B, int H, int W, float src_thr, float *grad_values,
                                    int32_t *frame_status /* nullable */, void *workspace, size_t ws_bytes, void *stream);
 
+/*
+ * dtfill_conv2d: a stride-1 'same' convolution in float32 whose every output bit is fixed by this statement: the layers of
+ * SparsityCNN (solution_DeepNet/net.py:11-242), so that the network between the fills and the losses runs here too.
+ *
+ * x: float32 [B,H,W,Cin], channel-last as the reference's tensors are; with Cin == 1 that is the [B,H,W] planes the fill and
+ * dtfill_generate_multi_channel() emit.  w: float32 [ksize,ksize,Cin,Cout], a Keras Conv2D.kernel as stored; the operation
+ * is cross-correlation, as TensorFlow's is, not a flipped convolution.  bias: float32 [Cout], nullable.  out: float32
+ * [B,H,W,out_channels], of which only the channels out_offset .. out_offset + Cout - 1 are written and the others left
+ * untouched (tf.concat of several layers' outputs is several calls into one tensor); out may not alias x.
+ *
+ * THE CONTRACT.  Per output (b, h, v, o), in float32, with r = (ksize - 1) / 2:
+ *   acc = +0
+ *   for g in 0 .. ceil(Cin / 16) - 1:                          groups of 16 input channels, outermost
+ *     for i in 0 .. ksize - 1:  for j in 0 .. ksize - 1:       the taps in raster order
+ *       for c in 16 g .. min(16 g + 15, Cin - 1):
+ *         a = x[b, h + i - r, v + j - r, c] inside the frame, +0.0f outside it      (padding taps are links of the chain)
+ *         acc = fmaf(a, w[i, j, c, o], acc)
+ *   y = acc + bias[o]                                          one rounded add; skipped when bias is NULL
+ *   y = act == DTFILL_CONV_LEAKY ? (y > 0 ? y : y * alpha) : y
+ * +0 and -0 count as equal: the zero operands that fill the last matrix-core step of a Cin == 1 chain can turn a -0
+ * accumulator into +0.  Non-finite values follow fmaf, so a padding tap under an infinite weight makes NaN; nothing faults.
+ * The bits are a function of the inputs and the shape alone, never of the tiling, the grid or the position in the batch.
+ * TensorFlow documents no summation order, so this order is the library's own, as the tap order of
+ * dtfill_generate_multi_channel() is: a float32 evaluation in any other order lies within
+ * gamma_(K+2) (sum |x| |w| + |bias|) of it, K = ksize^2 Cin, gamma_n = n 2^-24 / (1 - n 2^-24).
+ * Why the groups are outermost: a block keeps the haloed input tile of 16 channels in LDS (34 KB for 7x7), not of all 64.
+ *
+ * Pointers need float alignment only; x is read by 16-byte loads where its address allows.  Asynchronous on `stream`; no
+ * workspace, no allocation, no atomics, no host synchronisation.
+ * Returns, all checked before any HIP call: DTFILL_ERR_NULL for a NULL x, w or out; DTFILL_ERR_SHAPE unless ksize is 1, 3, 5
+ * or 7, Cin is 1, 16, 32, 48 or 64, Cout is 1 or 16, 0 <= out_offset and out_offset + Cout <= out_channels, B, H, W >= 1,
+ * B H W max(Cin, out_channels) < 2^31, act is one of the two values below and alpha is finite; then DTFILL_ERR_LAUNCH if a
+ * launch failed.
+ */
+#define DTFILL_CONV_LINEAR 0
+#define DTFILL_CONV_LEAKY  1 /* y > 0 ? y : y * alpha; tf.nn.leaky_relu's alpha is 0.2f */
+int dtfill_conv2d(const float *x, int B, int H, int W, int Cin,
+                  const float *w, const float *bias /* nullable */, int ksize, int Cout,
+                  int act, float alpha,
+                  float *out, int out_channels, int out_offset, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
