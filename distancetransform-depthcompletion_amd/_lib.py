@@ -99,6 +99,8 @@ _ABI = {
     "dtfill_nearest_gather": (ci, [vp, vp, vp, ci, ci, ci, ci, cf, vp, vp, vp, vp, sz, vp]),
     "dtfill_nearest_gather_backward_workspace_bytes": (sz, [ci, ci, ci, ci]),
     "dtfill_nearest_gather_backward": (ci, [vp, vp, vp, ci, ci, ci, ci, cf, vp, vp, vp, sz, vp]),
+    "dtfill_conv2d_strided": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, vp, ci, cf, vp, ci, ci, vp]),
+    "dtfill_conv2d_transpose": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, cf, vp, ci, ci, vp]),
     "dtfill_conv2d": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, cf, vp, ci, ci, vp]),
 }
 SYMBOLS = tuple(_ABI)

@@ -61,8 +61,9 @@
 // rows under a sky (window_tiling, tile_row_height, tile_row_culled), k_pts's and k_l2win's tiles.  frame_facts, fused_body and
 // the host below call it; tests/test_route.py compiles it for the host and holds tests/exhaustive_cases.py to it.
 //
-// No MFMA in any of the above: this path is compare/min/index work (DESIGN.md "Roofline").  The one matmul-shaped entry point,
-// dtfill_conv2d (SparsityCNN's layers), is dtfill_conv.hpp's.
+// No MFMA in any of the above: this path is compare/min/index work (DESIGN.md "Roofline").  The matmul-shaped entry points are
+// dtfill_conv2d (SparsityCNN's layers), dtfill_conv.hpp's, and dtfill_conv2d_strided and dtfill_conv2d_transpose (ResNet18's wide
+// layers), dtfill_conv2.hpp's.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -101,6 +102,7 @@ namespace {
 #include "dtfill_fillb.hpp"
 #include "dtfill_near.hpp"
 #include "dtfill_conv.hpp"
+#include "dtfill_conv2.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -1178,6 +1180,51 @@ int dtfill_nearest_gather_backward(const float *x, const int32_t *index, const f
     int c0 = 0;
     for (; c0 + 2 <= C; c0 += 2) ngb_round<2>(st, index, grad_out, grad_values, C, c0, B, H, W, ws, status);
     if (c0 < C) ngb_round<1>(st, index, grad_out, grad_values, C, c0, B, H, W, ws, status);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+// TensorFlow's 'same' rule for one axis: the output extent and the padding in front
+static void conv2_same(int n, int ksize, int stride, int *out, int *front) {
+    *out = (int)(((long long)n + stride - 1) / stride);
+    const long long pad = (long long)(*out - 1) * stride + ksize - n;
+    *front = pad > 0 ? (int)(pad / 2) : 0;
+}
+
+// what the two wide entry points check alike; Ho, Wo: the output frame
+static int conv2_check(const float *x, int B, int H, int W, int Cin, const float *w, int Cout, int act, float alpha, const float *out,
+                       int out_channels, int out_offset, long long Ho, long long Wo) {
+    if (!x || !w || !out) return DTFILL_ERR_NULL;
+    if (Cin < CV_G || Cin % CV_G || Cout < 16 || Cout % 16) return DTFILL_ERR_SHAPE;
+    if (out_offset < 0 || out_channels < 1 || (long long)out_offset + Cout > out_channels) return DTFILL_ERR_SHAPE;
+    if (B < 1 || H < 1 || W < 1 || (long long)B * H * W >= (1ll << 31) || B * Ho * Wo >= (1ll << 31)) return DTFILL_ERR_SHAPE;
+    if ((long long)B * H * W * Cin >= (1ll << 31) || B * Ho * Wo * max(Cout, out_channels) >= (1ll << 31)) return DTFILL_ERR_SHAPE;
+    if ((act != DTFILL_CONV_LINEAR && act != DTFILL_CONV_LEAKY) || !isfinite(alpha)) return DTFILL_ERR_SHAPE;
+    return DTFILL_OK;
+}
+
+int dtfill_conv2d_strided(const float *x, int B, int H, int W, int Cin, const float *w, const float *bias, int ksize, int Cout,
+                          int stride, const float *residual, int act, float alpha, float *out, int out_channels, int out_offset,
+                          void *stream) {
+    if (!x || !w || !out) return DTFILL_ERR_NULL;
+    if (stride != 1 && stride != 2) return DTFILL_ERR_SHAPE;
+    if (ksize != 1 && ksize != 3 && (stride == 2 || (ksize != 5 && ksize != 7))) return DTFILL_ERR_SHAPE;
+    if (H < 1 || W < 1) return DTFILL_ERR_SHAPE;
+    int Ho, Wo, pt, pl;
+    conv2_same(H, ksize, stride, &Ho, &pt);
+    conv2_same(W, ksize, stride, &Wo, &pl);
+    const int rc = conv2_check(x, B, H, W, Cin, w, Cout, act, alpha, out, out_channels, out_offset, Ho, Wo);
+    if (rc != DTFILL_OK) return rc;
+    const Conv2Args a{x, w, bias, residual, out, B, H, W, Cin, Cout, Ho, Wo, pt, pl, out_channels, out_offset, act, alpha};
+    conv2_launch(static_cast<hipStream_t>(stream), a, ksize, stride);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+int dtfill_conv2d_transpose(const float *x, int B, int H, int W, int Cin, const float *w, const float *bias, int Cout, int act,
+                            float alpha, float *out, int out_channels, int out_offset, void *stream) {
+    const int rc = conv2_check(x, B, H, W, Cin, w, Cout, act, alpha, out, out_channels, out_offset, 2ll * H, 2ll * W);
+    if (rc != DTFILL_OK) return rc;
+    const Conv2Args a{x, w, bias, nullptr, out, B, H, W, Cin, Cout, 2 * H, 2 * W, 0, 0, out_channels, out_offset, act, alpha};
+    conv2_transpose_launch(static_cast<hipStream_t>(stream), a);
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 

@@ -839,10 +839,10 @@ def __getattr__(name):
         from . import nyu
 
         return nyu.nyu_read_device
-    if name == "conv2d_device":  # likewise in net.py
+    if name in ("conv2d_device", "conv2d_strided_device", "conv2d_transpose_device"):  # likewise in net.py
         from . import net
 
-        return net.conv2d_device
+        return getattr(net, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 

@@ -1,11 +1,14 @@
-"""SparsityCNN (solution_DeepNet/net.py:11-242), the reference's light network, as an inference class on the device: every
-convolution is dtfill_conv2d's fixed-order float32 chain (include/dtfill.h), the multi-channel fill in its middle is
-dtfill_generate_multi_channel, and the three elementwise steps are single IEEE operations in torch.  So the output bits are a
+"""The reference's networks as inference classes on the device: SparsityCNN (solution_DeepNet/net.py:11-242), its light
+network, and ResNet18 (ResNet18_NO_BN_l2, net.py:245-745), the paper's.  Every convolution is a fixed-order float32 chain of
+include/dtfill.h (dtfill_conv2d, dtfill_conv2d_strided, dtfill_conv2d_transpose), the multi-channel fill in the middle is
+dtfill_generate_multi_channel, and the elementwise steps are single IEEE operations in torch.  So the output bits are a
 function of the weights and the input alone, from run to run and from shape to shape.
 
-The other eleven models of the reference's net.py need stride 2 and Conv2DTranspose and are not here.  conv2d_device, the
-device function of one convolution, is reached as device.conv2d_device as well; it lives here, beside device.py's helpers, with
-its argument checks in tests/test_conv2d.py and tests/test_gpu_conv2d.py.
+The other ten models of the reference's net.py are not here; what they need beyond these two (widths in multiples of 16, stride
+2, Conv2DTranspose, the residual add) is.  conv2d_device, conv2d_strided_device and conv2d_transpose_device, the device
+functions of one convolution, are reached as device.<name> as well; they live here, beside device.py's helpers, with their
+argument checks in tests/test_conv2d.py, tests/test_gpu_conv2d.py, tests/test_conv2d_strided.py and
+tests/test_gpu_conv2d_strided.py.
 """
 import numpy as np
 import torch
@@ -59,6 +62,116 @@ def conv2d_device(x, w, bias=None, act="linear", alpha=0.2, out=None, out_offset
     return out
 
 
+
+def _check_conv_args(x, w, bias, act, what):
+    """The checks the two wide convolutions share; returns (B, H, W, Cin, Cout)."""
+    if act not in _lib.CONV_ACTS:
+        raise ValueError("act must be one of %s, got %r" % (sorted(_lib.CONV_ACTS), act))
+    _require_gpu()
+    _check_tensor(x, "x", layout="[B,H,W,Cin]")
+    B, H, W, Cin = x.shape
+    _check_tensor(w, "w", layout=what)
+    if w.shape[0] != w.shape[1] or w.shape[2] != Cin or w.device != x.device:
+        raise ValueError("w must be %s with Cin = %d on %s, got %s" % (what, Cin, x.device, tuple(w.shape)))
+    Cout = w.shape[3]
+    if bias is not None:
+        _check_tensor(bias, "bias", layout="[Cout]")
+        if bias.shape[0] != Cout or bias.device != x.device:
+            raise ValueError("bias must be [%d] on %s, got %s" % (Cout, x.device, tuple(bias.shape)))
+    return B, H, W, Cin, Cout
+
+
+def _check_conv_out(x, out, out_offset, frame, Cout):
+    """out of a wide convolution, [B,Ho,Wo,C] with frame = (B, Ho, Wo): a new [.., Cout] tensor when None."""
+    if out is None:
+        if out_offset != 0:
+            raise ValueError("out_offset needs an out tensor to point into")
+        return torch.empty(frame + (Cout,), dtype=torch.float32, device=x.device)
+    _check_tensor(out, "out", layout="[B,Ho,Wo,C]")
+    if tuple(out.shape[:3]) != frame or out.device != x.device:
+        raise ValueError("out must be [%d,%d,%d,C] on %s, got %s" % (frame + (x.device, tuple(out.shape))))
+    if out.data_ptr() == x.data_ptr():
+        raise ValueError("out may not alias x")
+    return out
+
+
+def conv2d_strided_device(x, w, bias=None, stride=1, residual=None, act="linear", alpha=0.2, out=None, out_offset=0):
+    """A 'same' float32 convolution of stride 1 or 2 with many output channels and an optional residual add, in the fixed
+    summation order of include/dtfill.h, dtfill_conv2d_strided (a layer of net.py's ResNet18_NO_BN_l2).  x: contiguous float32
+    CUDA tensor [B,H,W,Cin]; w: [ksize,ksize,Cin,Cout], a Keras Conv2D.kernel as stored; Cin and Cout multiples of 16; bias:
+    [Cout] or None; residual: contiguous [B,Ho,Wo,Cout] or None, added after the bias and before the activation (it may be x,
+    not out); Ho = ceil(H / stride), Wo likewise, TensorFlow's 'same' rule.  out: a contiguous float32 tensor [B,Ho,Wo,C] of
+    which the channels out_offset .. out_offset + Cout - 1 are written; a new [B,Ho,Wo,Cout] tensor by default.  Returns out.
+    Asynchronous on the current stream; the shapes the library takes are the header's (DtfillError otherwise)."""
+    if stride not in (1, 2):
+        raise ValueError("stride must be 1 or 2, got %r" % (stride,))
+    B, H, W, Cin, Cout = _check_conv_args(x, w, bias, act, "[ksize,ksize,Cin,Cout]")
+    frame = (B, -(-H // stride), -(-W // stride))
+    if residual is not None:
+        _check_tensor(residual, "residual", layout="[B,Ho,Wo,Cout]")
+        if tuple(residual.shape) != frame + (Cout,) or residual.device != x.device:
+            raise ValueError("residual must be %s on %s, got %s" % (frame + (Cout,), x.device, tuple(residual.shape)))
+    out = _check_conv_out(x, out, out_offset, frame, Cout)
+    if residual is not None and out.data_ptr() == residual.data_ptr():
+        raise ValueError("out may not alias residual")
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dtfill_conv2d_strided(x.data_ptr(), B, H, W, Cin, w.data_ptr(), _ptr(bias), w.shape[0], Cout,
+                                                     stride, _ptr(residual), _lib.CONV_ACTS[act], float(alpha), out.data_ptr(),
+                                                     out.shape[3], int(out_offset), _stream(x.device)))
+    return out
+
+
+def conv2d_transpose_device(x, w_packed, bias=None, act="linear", alpha=0.2, out=None, out_offset=0):
+    """tf.keras.layers.Conv2DTranspose(Cout, 3, strides=2, padding='same') in the fixed summation order of include/dtfill.h,
+    dtfill_conv2d_transpose.  x: contiguous float32 CUDA tensor [B,H,W,Cin]; w_packed: [3,3,Cin,Cout], pack_transpose_kernel()
+    of the layer's kernel; bias: [Cout] or None.  out: [B,2H,2W,C], written at out_offset .. out_offset + Cout - 1; a new
+    [B,2H,2W,Cout] tensor by default.  Returns out.  Asynchronous on the current stream."""
+    B, H, W, Cin, Cout = _check_conv_args(x, w_packed, bias, act, "[3,3,Cin,Cout]")
+    if w_packed.shape[0] != 3:
+        raise ValueError("w_packed must be [3,3,Cin,Cout], got %s" % (tuple(w_packed.shape),))
+    out = _check_conv_out(x, out, out_offset, (B, 2 * H, 2 * W), Cout)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dtfill_conv2d_transpose(x.data_ptr(), B, H, W, Cin, w_packed.data_ptr(), _ptr(bias), Cout,
+                                                       _lib.CONV_ACTS[act], float(alpha), out.data_ptr(), out.shape[3],
+                                                       int(out_offset), _stream(x.device)))
+    return out
+
+
+def pack_transpose_kernel(kernel):
+    """A Keras Conv2DTranspose.kernel [3,3,Cout,Cin] -> the ABI's [3,3,Cin,Cout], contiguous float32: the last two axes
+    exchanged, once, when the weights are loaded."""
+    k = np.asarray(kernel, dtype=np.float32)
+    if k.ndim != 4 or k.shape[:2] != (3, 3):
+        raise ValueError("a Conv2DTranspose kernel is [3,3,Cout,Cin], got %s" % (k.shape,))
+    return np.ascontiguousarray(k.transpose(0, 1, 3, 2))
+
+
+def _uploaded(x, kernel, *others):
+    """Host arrays of a numpy form, checked as tools.conv2d checks its own, as tensors on the default operator's device (None
+    stays None)."""
+    from .tools import _as_f32_frames, _upload
+
+    arrays = [None if a is None else _as_f32_frames(a) for a in (x, kernel) + others]
+    if arrays[0].ndim != 4 or arrays[1].ndim != 4:
+        raise ValueError("expected x [B,H,W,Cin] and a kernel of four axes")
+    dev = _device.default_op().device
+    return [None if a is None else _upload(a, dev) for a in arrays]
+
+
+def conv2d_strided(x, kernel, bias=None, stride=1, residual=None, act="linear", alpha=0.2):
+    """conv2d_strided_device as a numpy function: x [B,H,W,Cin], kernel [ksize,ksize,Cin,Cout] and bias [Cout] as Keras stores
+    them, residual [B,Ho,Wo,Cout] or None.  Returns float32 [B,Ho,Wo,Cout]."""
+    a, k, b, r = _uploaded(x, kernel, bias, residual)
+    return conv2d_strided_device(a, k, b, stride, r, act, alpha).cpu().numpy()
+
+
+def conv2d_transpose(x, kernel, bias=None, act="linear", alpha=0.2):
+    """conv2d_transpose_device as a numpy function: x [B,H,W,Cin], kernel [3,3,Cout,Cin] as Keras stores a Conv2DTranspose's
+    (packed here), bias [Cout].  Returns float32 [B,2H,2W,Cout]."""
+    a, k, b = _uploaded(x, kernel, bias)
+    return conv2d_transpose_device(a, k.permute(0, 1, 3, 2).contiguous(), b, act, alpha).cpu().numpy()
+
+
 def stem_layers(scale_num):
     """The layer that reads lidar_1 .. lidar_<scale_num>, in that order.  net.py:206 calls lidar_conv_extra_1 again on
     lidar_4: lidar_conv_extra_3 is built (net.py:46) and never used, and that is reproduced here."""
@@ -98,11 +211,60 @@ def glorot_weights(seed, scale_num=4, if_correct=True, bias=0.0):
     return weights
 
 
+
+
+RESNET_WIDTHS = (64, 128, 256, 512)  # channels of levels 1 .. 4; level k lives at 1 / 2^(k-1) of the frame each way
+RESNET_STRIDE2 = ("conv2a", "conv2a_extra", "conv3a", "conv3a_extra", "conv4a", "conv4a_extra")
+RESNET_TRANSPOSED = ("upsample_4", "upsample_3", "upsample_2")  # Conv2DTranspose: Keras stores [3,3,Cout,Cin]
+
+
+def layer_shapes_resnet18(scale_num=4, if_correct=True):
+    """{layer name: (ksize, Cin, Cout)} of the layers ResNet18_NO_BN_l2's forward uses (net.py:262-400), under the reference's
+    attribute names.  The layers of RESNET_STRIDE2 have stride 2; those of RESNET_TRANSPOSED are Conv2DTranspose(Cout, 3,
+    strides=2), whose Keras kernel is [3,3,Cout,Cin]; upsample_1 is an ordinary convolution, as in the reference."""
+    shapes = {}
+    if if_correct:
+        shapes.update(correct_1=(7, 1, 16), correct_2=(5, 16, 16), correct_3=(3, 16, 16), correct_4=(3, 16, 1))
+    for name in stem_layers(scale_num):
+        shapes[name] = (3, 1, STEM_WIDTH)
+    below = STEM_WIDTH * scale_num
+    for level, width in enumerate(RESNET_WIDTHS, 1):
+        shapes["conv%da" % level] = (3, below, width)
+        shapes["conv%db" % level] = (3, width, width)
+        shapes["conv%da_extra" % level] = (1, below, width)
+        shapes["conv%dc" % level] = (3, width, width)
+        shapes["conv%dd" % level] = (3, width, width)
+        below = width
+    shapes.update(upsample_4=(3, 512, 256), upsample_4_post=(3, 512, 256), upsample_3=(3, 256, 128), upsample_3_post=(3, 256, 128),
+                  upsample_2=(3, 128, 64), upsample_2_post=(3, 128, 64), upsample_1=(3, 64, 64),
+                  upsample_1_post=(3, 64 + STEM_WIDTH * scale_num, 64), conv_output=(1, 64, 1))
+    return shapes
+
+
+def _keras_shape(name, k, cin, cout):
+    return (k, k, cout, cin) if name in RESNET_TRANSPOSED else (k, k, cin, cout)
+
+
+def glorot_weights_resnet18(seed, scale_num=4, if_correct=True, bias=0.0):
+    """glorot_weights() for ResNet18: float32 numpy arrays of Keras' shapes, [3,3,Cout,Cin] for the transposed layers."""
+    rng = np.random.default_rng(seed)
+    shapes = layer_shapes_resnet18(scale_num, if_correct)
+    if scale_num > 3:
+        shapes["lidar_conv_extra_3"] = (3, 1, STEM_WIDTH)
+    weights = {}
+    for name, (k, cin, cout) in shapes.items():
+        limit = np.sqrt(6.0 / (k * k * (cin + cout)))
+        weights[name] = (rng.uniform(-limit, limit, _keras_shape(name, k, cin, cout)).astype(np.float32),
+                         rng.uniform(-bias, bias, (cout,)).astype(np.float32))
+    return weights
+
+
 class _Buffers:
     """What one (device, B, H, W) needs: the weights' device copies are the instance's, these are the activations."""
 
     def __init__(self, device, B, H, W, scale_num):
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
+        self.new = new
         self.mask, self.scaled, self.correct = new(B, H, W), new(B, H, W), new(B, H, W)
         self.a16, self.b16, self.one = new(B, H, W, 16), new(B, H, W, 16), new(B, H, W, 1)
         self.fills = [new(B, H, W) for _ in range(scale_num - 1)]
@@ -110,7 +272,68 @@ class _Buffers:
         self.output, self.correct_out = new(B, H, W), new(B, H, W)
 
 
-class SparsityCNN:
+class _LidarNet:
+    """What the reference's networks share: the settings, the weights dict and its checks, the device copies, and the head
+    (net.py:125-212 and 464-547, the same lines twice): mask, division, correction, multi-channel fill, stems."""
+
+    NAME = None  # the reference's class, for messages
+    KNOWN = ()  # every attribute name of the reference's class
+    layer_shapes = None  # (scale_num, if_correct) -> {name: (ksize, Cin, Cout)}
+
+    def __init__(self, weights, table_size=7, if_correct=True, scale_range=90.0, scale_num=4):
+        self.table_size, self.if_correct, self.scale_range, self.scale_num = int(table_size), bool(if_correct), float(scale_range), scale_num
+        if (self.table_size + 1) % 2 != 0:
+            raise ValueError("table_size must be odd, got %r" % (table_size,))
+        if not np.isfinite(self.scale_range) or self.scale_range == 0.0:
+            raise ValueError("scale_range must be finite and not 0, got %r" % (scale_range,))
+        self.shapes = type(self).layer_shapes(scale_num, self.if_correct)
+        unknown = sorted(set(weights) - set(self.KNOWN))
+        if unknown:
+            raise ValueError("not a layer of %s: %s" % (self.NAME, ", ".join(unknown)))
+        self._host = {}
+        for name, (k, cin, cout) in self.shapes.items():
+            if name not in weights:
+                raise ValueError("weights lack layer %r" % name)
+            kernel, bias = (np.ascontiguousarray(a, dtype=np.float32) for a in weights[name])
+            if kernel.shape != _keras_shape(name, k, cin, cout) or bias.shape != (cout,):
+                raise ValueError("layer %r needs a kernel %s and a bias %s, got %s and %s"
+                                 % (name, _keras_shape(name, k, cin, cout), (cout,), kernel.shape, bias.shape))
+            self._host[name] = (pack_transpose_kernel(kernel) if name in RESNET_TRANSPOSED else kernel, bias)
+        self._on = {}  # device -> ({name: (kernel, bias)}, threshold, scale_range), as tensors there
+        self._buffers = {}  # (device, B, H, W) -> the activations
+
+    def _conv(self, on, x, name, act, out, out_offset=0):
+        kernel, bias = on[name]
+        return conv2d_device(x, kernel, bias, act, LEAKY_ALPHA, out, out_offset)
+
+    def _state(self, dev):
+        """({name: (kernel, bias)}, threshold, scale_range) as tensors on dev, uploaded on the first call there."""
+        if dev not in self._on:
+            up = lambda a: torch.from_numpy(a).to(dev)
+            self._on[dev] = ({n: (up(k), up(b)) for n, (k, b) in self._host.items()},
+                             torch.tensor(0.1, dtype=torch.float32, device=dev),
+                             torch.tensor(self.scale_range, dtype=torch.float32, device=dev))
+        return self._on[dev]
+
+    def _head(self, on, threshold, scale, x, t):
+        """x [B,H,W] -> t.correct, and the stems' [B,H,W,16 scale_num] in t.stems."""
+        B, H, W = x.shape
+        torch.gt(x, threshold, out=t.mask)  # valued_mask, as float32
+        torch.div(x, scale, out=t.scaled)  # (a tensor divisor: an IEEE division, not a product with 1 / scale_range)
+        if self.if_correct:
+            self._conv(on, t.scaled, "correct_1", "leaky", t.a16)
+            self._conv(on, t.a16, "correct_2", "leaky", t.b16)
+            self._conv(on, t.b16, "correct_3", "leaky", t.a16)
+            self._conv(on, t.a16, "correct_4", "linear", t.one)
+            torch.mul(t.one.view(B, H, W), t.mask, out=t.correct)
+        else:
+            torch.mul(t.scaled, t.mask, out=t.correct)
+        lidars = _device.generate_multi_channel_device(t.correct, t.mask, self.table_size, self.scale_num, outs=t.fills)
+        for k, name in enumerate(stem_layers(self.scale_num)):  # tf.concat: each stem writes its 16 channels
+            self._conv(on, lidars[k], name, "leaky", t.stems, STEM_WIDTH * k)
+
+
+class SparsityCNN(_LidarNet):
     """net.py's SparsityCNN for inference.  weights: {layer name: (kernel, bias)} under the reference's attribute names
     (correct_1..4 with if_correct, lidar_conv, lidar_conv_extra_1..2 as scale_num asks, conv1a..d, conv_output), kernel
     [ksize,ksize,Cin,Cout] and bias [Cout] as Keras stores them (layer.get_weights()), float32.  lidar_conv_extra_3 and layers
@@ -121,31 +344,9 @@ class SparsityCNN:
     that shape and the next call at that shape overwrites them, so clone what has to outlive it.  One instance serves one stream
     at a time."""
 
-    def __init__(self, weights, table_size=7, if_correct=True, scale_range=90.0, scale_num=4):
-        self.table_size, self.if_correct, self.scale_range, self.scale_num = int(table_size), bool(if_correct), float(scale_range), scale_num
-        if (self.table_size + 1) % 2 != 0:
-            raise ValueError("table_size must be odd, got %r" % (table_size,))
-        if not np.isfinite(self.scale_range) or self.scale_range == 0.0:
-            raise ValueError("scale_range must be finite and not 0, got %r" % (scale_range,))
-        self.shapes = layer_shapes(scale_num, self.if_correct)
-        unknown = sorted(set(weights) - set(_KNOWN))
-        if unknown:
-            raise ValueError("not a layer of SparsityCNN: %s" % ", ".join(unknown))
-        self._host = {}
-        for name, (k, cin, cout) in self.shapes.items():
-            if name not in weights:
-                raise ValueError("weights lack layer %r" % name)
-            kernel, bias = (np.ascontiguousarray(a, dtype=np.float32) for a in weights[name])
-            if kernel.shape != (k, k, cin, cout) or bias.shape != (cout,):
-                raise ValueError("layer %r needs a kernel %s and a bias %s, got %s and %s"
-                                 % (name, (k, k, cin, cout), (cout,), kernel.shape, bias.shape))
-            self._host[name] = (kernel, bias)
-        self._on = {}  # device -> ({name: (kernel, bias)}, threshold, scale_range), as tensors there
-        self._buffers = {}  # (device, B, H, W) -> _Buffers
-
-    def _conv(self, on, x, name, act, out, out_offset=0):
-        kernel, bias = on[name]
-        return conv2d_device(x, kernel, bias, act, LEAKY_ALPHA, out, out_offset)
+    NAME = "SparsityCNN"
+    KNOWN = _KNOWN
+    layer_shapes = staticmethod(layer_shapes)
 
     def __call__(self, input_lidar):
         """input_lidar: contiguous float32 CUDA tensor [B,H,W] in metres.  Returns (output * scale_range, lidar_correct *
@@ -155,34 +356,103 @@ class SparsityCNN:
         B, H, W = x.shape
         dev = x.device
         with torch.cuda.device(dev):
-            if dev not in self._on:
-                up = lambda a: torch.from_numpy(a).to(dev)
-                self._on[dev] = ({n: (up(k), up(b)) for n, (k, b) in self._host.items()},
-                                 torch.tensor(0.1, dtype=torch.float32, device=dev),
-                                 torch.tensor(self.scale_range, dtype=torch.float32, device=dev))
-            on, threshold, scale = self._on[dev]
+            on, threshold, scale = self._state(dev)
             key = (dev, B, H, W)
             if key not in self._buffers:
                 self._buffers[key] = _Buffers(dev, B, H, W, self.scale_num)
             t = self._buffers[key]
-            torch.gt(x, threshold, out=t.mask)  # valued_mask, as float32
-            torch.div(x, scale, out=t.scaled)  # (a tensor divisor: an IEEE division, not a product with 1 / scale_range)
-            if self.if_correct:
-                self._conv(on, t.scaled, "correct_1", "leaky", t.a16)
-                self._conv(on, t.a16, "correct_2", "leaky", t.b16)
-                self._conv(on, t.b16, "correct_3", "leaky", t.a16)
-                self._conv(on, t.a16, "correct_4", "linear", t.one)
-                torch.mul(t.one.view(B, H, W), t.mask, out=t.correct)
-            else:
-                torch.mul(t.scaled, t.mask, out=t.correct)
-            lidars = _device.generate_multi_channel_device(t.correct, t.mask, self.table_size, self.scale_num, outs=t.fills)
-            for k, name in enumerate(stem_layers(self.scale_num)):  # tf.concat: each stem writes its 16 channels
-                self._conv(on, lidars[k], name, "leaky", t.stems, STEM_WIDTH * k)
+            self._head(on, threshold, scale, x, t)
             self._conv(on, t.stems, "conv1a", "leaky", t.a16)
             self._conv(on, t.a16, "conv1b", "leaky", t.b16)
             self._conv(on, t.b16, "conv1c", "leaky", t.a16)
             self._conv(on, t.a16, "conv1d", "leaky", t.b16)
             self._conv(on, t.b16, "conv_output", "linear", t.one)
+            torch.mul(t.one.view(B, H, W), scale, out=t.output)
+            torch.mul(t.correct, scale, out=t.correct_out)
+        return t.output, t.correct_out
+
+
+class _ResNetBuffers(_Buffers):
+    """_Buffers and, per level k (1 / 2^(k-1) of the frame each way, RESNET_WIDTHS[k-1] channels), three tensors that take turns
+    and the wide tensor a tf.concat([up, skip]) of that level is."""
+
+    def __init__(self, device, B, H, W, scale_num):
+        super().__init__(device, B, H, W, scale_num)
+        self.level, self.wide = [], []
+        for k, width in enumerate(RESNET_WIDTHS):
+            frame = (B, H >> k, W >> k)
+            self.level.append([self.new(*frame, width) for _ in range(3)])
+            if k < 3:  # [up | skip]: level 1's is upsample_1's 64 channels and the stems, the others twice the level's width
+                self.wide.append(self.new(*frame, 64 + STEM_WIDTH * scale_num if k == 0 else 2 * width))
+        self.wide1 = self.new(B, H, W, 128)  # upsample_2's 64 channels and tensor_1_total
+
+
+class ResNet18(_LidarNet):
+    """net.py's ResNet18_NO_BN_l2 (net.py:245-745, the paper's network) for inference.  weights: {layer name: (kernel, bias)}
+    under the reference's attribute names (layer_shapes_resnet18: correct_1..4, the stems, conv1a .. conv4d,
+    conv1a_extra .. conv4a_extra, upsample_4 .. upsample_1, upsample_1_post .. upsample_4_post, conv_output), as Keras stores
+    them (layer.get_weights()): [ksize,ksize,Cin,Cout], and [3,3,Cout,Cin] for the three Conv2DTranspose layers, which are
+    repacked once here (pack_transpose_kernel).  lidar_conv_extra_3 is accepted and ignored, as the reference builds it and
+    calls lidar_conv_extra_1 on lidar_4 instead (net.py:541); a name the reference's class does not have raises.
+
+    The head is SparsityCNN's.  A residual block's tensor + tensor_add and the leaky_relu after it are the convolution's own
+    finish (dtfill_conv2d_strided's residual).  Each tf.concat([up, skip]) is the transposed convolution (at level 1, the
+    convolution upsample_1) writing the channels from 0 of a wide tensor, and one strided torch copy of the skip tensor into
+    the channels above: one memory pass beside a layer of hundreds of MFLOP per kilopixel.
+
+    H and W must be multiples of 8: with any other size the reference's own concat fails.  Detached, no host synchronisation,
+    no activation buffer allocated after the first call at a shape, the returned tensors are the instance's own, one stream
+    at a time: as SparsityCNN."""
+
+    NAME = "ResNet18_NO_BN_l2"
+    KNOWN = tuple(layer_shapes_resnet18(4, True)) + ("lidar_conv_extra_3",)
+    layer_shapes = staticmethod(layer_shapes_resnet18)
+
+    def _wide(self, on, x, name, out, stride=1, residual=None, act="leaky"):
+        kernel, bias = on[name]
+        return conv2d_strided_device(x, kernel, bias, stride, residual, act, LEAKY_ALPHA, out)
+
+    def _up(self, on, x, name, out):
+        kernel, bias = on[name]
+        return conv2d_transpose_device(x, kernel, bias, "leaky", LEAKY_ALPHA, out)
+
+    def __call__(self, input_lidar):
+        """input_lidar: contiguous float32 CUDA tensor [B,H,W] in metres, H and W multiples of 8.  Returns (output *
+        scale_range, lidar_correct * scale_range), net.py:745, each [B,H,W]."""
+        x = input_lidar.detach()
+        if x.dim() == 3 and (x.shape[1] % 8 or x.shape[2] % 8):
+            raise ValueError("H and W must be multiples of 8, got %d x %d" % tuple(x.shape[1:]))
+        _check_tensor(x, "input_lidar")
+        B, H, W = x.shape
+        dev = x.device
+        with torch.cuda.device(dev):
+            on, threshold, scale = self._state(dev)
+            key = (dev, B, H, W)
+            if key not in self._buffers:
+                self._buffers[key] = _ResNetBuffers(dev, B, H, W, self.scale_num)
+            t = self._buffers[key]
+            self._head(on, threshold, scale, x, t)
+            below = t.stems
+            for k in range(4):  # net.py:551-674; `below` ends as tensor_<k+1>_total (level 4: tensor_4)
+                p, q, r = t.level[k]
+                name, stride = "conv%d" % (k + 1), 1 if k == 0 else 2
+                self._wide(on, below, name + "a", p, stride)
+                self._wide(on, below, name + "a_extra", q, stride, act="linear")
+                self._wide(on, p, name + "b", r, residual=q)
+                self._wide(on, r, name + "c", p)
+                self._wide(on, p, name + "d", q, residual=r if k < 3 else None)
+                below = q
+            for k in (2, 1, 0):  # net.py:680-724: upsample_<k+2>, the concat with tensor_<k+1>_total, upsample_<k+2>_post
+                wide = t.wide1 if k == 0 else t.wide[k]
+                width = RESNET_WIDTHS[k]
+                self._up(on, below, "upsample_%d" % (k + 2), wide)
+                wide[..., width:].copy_(t.level[k][1])
+                below = self._wide(on, wide, "upsample_%d_post" % (k + 2), t.level[k][0])
+            wide = t.wide[0]  # net.py:728-742
+            self._wide(on, below, "upsample_1", wide)
+            wide[..., 64:].copy_(t.stems)
+            self._wide(on, wide, "upsample_1_post", t.level[0][2])
+            self._conv(on, t.level[0][2], "conv_output", "linear", t.one)
             torch.mul(t.one.view(B, H, W), scale, out=t.output)
             torch.mul(t.correct, scale, out=t.correct_out)
         return t.output, t.correct_out

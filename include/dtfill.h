@@ -741,6 +741,69 @@ int dtfill_nearest_gather_backward(const float *x, const int32_t *index, const f
                                    int32_t *frame_status /* nullable */, void *workspace, size_t ws_bytes, void *stream);
 
 /*
+ * dtfill_conv2d_strided and dtfill_conv2d_transpose: the wide layers of ResNet18_NO_BN_l2 (solution_DeepNet/net.py:245-745),
+ * in the same sense as dtfill_conv2d below, whose statement they extend: every output bit is fixed here.  Convolutions with
+ * Cin == 1 or Cout == 1 (the correction branch, the stems, conv_output) stay with dtfill_conv2d.
+ *
+ * dtfill_conv2d_strided.  x: float32 [B,H,W,Cin]; w: float32 [ksize,ksize,Cin,Cout], a Keras Conv2D.kernel as stored
+ * (cross-correlation); bias: [Cout], nullable; stride: 1 or 2; residual: float32 [B,Ho,Wo,Cout], dense, nullable; act, alpha,
+ * out_channels and out_offset as in dtfill_conv2d; out: float32 [B,Ho,Wo,out_channels].  The output size and the padding are
+ * TensorFlow's 'same' rule, per axis:
+ *   Ho = ceil(H / stride),  pad = max((Ho - 1) stride + ksize - H, 0),  pt = pad / 2   (integer division: the smaller half
+ *   in front), and Wo and pl likewise from W.  Stride 1: pt = (ksize - 1) / 2.  Stride 2, ksize 3: pt = 0 for an even H and
+ *   1 for an odd one.  Stride 2, ksize 1: pt = 0.
+ * THE CONTRACT.  Per output (b, h, v, o), in float32:
+ *   acc = +0
+ *   for g in 0 .. Cin / 16 - 1:                                groups of 16 input channels, outermost
+ *     for i in 0 .. ksize - 1:  for j in 0 .. ksize - 1:       the taps in raster order
+ *       for c in 16 g .. 16 g + 15:
+ *         a = x[b, stride h + i - pt, stride v + j - pl, c] inside the frame, +0.0f outside it
+ *         acc = fmaf(a, w[i, j, c, o], acc)
+ *   y = acc + bias[o]                                          one rounded add; skipped when bias is NULL
+ *   y = y + residual[b, h, v, o]                               one more rounded add; skipped when residual is NULL
+ *   y = act == DTFILL_CONV_LEAKY ? (y > 0 ? y : y * alpha) : y
+ * which is the order of the reference's graph: the bias inside the layer, then tensor + tensor_add, then leaky_relu.  At
+ * stride 1 without a residual this is dtfill_conv2d's statement, and for Cout == 16 the two entry points give the same bits.
+ * residual may alias x; neither may alias out.  +0 and -0 count as equal; non-finite values follow fmaf; the bits are a
+ * function of the inputs and the shape alone.
+ * Returns, all checked before any HIP call: DTFILL_ERR_NULL for a NULL x, w or out; DTFILL_ERR_SHAPE unless stride is 1 or 2,
+ * ksize is 1, 3, 5 or 7 at stride 1 and 1 or 3 at stride 2, Cin and Cout are multiples of 16 and at least 16,
+ * 0 <= out_offset and out_offset + Cout <= out_channels, B, H, W >= 1, B H W Cin < 2^31 and B Ho Wo max(Cout, out_channels)
+ * < 2^31, act is one of the two values and alpha is finite; then DTFILL_ERR_LAUNCH if a launch failed.
+ *
+ * dtfill_conv2d_transpose: tf.keras.layers.Conv2DTranspose(Cout, 3, strides=2, padding='same'), which TensorFlow defines as
+ * the gradient, with respect to its input, of the stride-2 'same' 3x3 convolution of a [2H,2W] frame (pt = pl = 0 there).
+ * x: float32 [B,H,W,Cin]; out: float32 [B,2H,2W,out_channels], written at out_offset .. out_offset + Cout - 1.
+ * w: float32 [3,3,Cin,Cout]: Keras's Conv2DTranspose.kernel is [3,3,Cout,Cin], and w is that array with its last two axes
+ * exchanged, a one-time repack on the host when the weights are loaded.  It makes the weights of four consecutive input
+ * channels and sixteen output channels, a matrix-core k-step, 64 consecutive floats per k index, as dtfill_conv2d's are.
+ * THE CONTRACT.  Per output (b, y, u, o), in float32:
+ *   acc = +0
+ *   for g in 0 .. Cin / 16 - 1:
+ *     for ky in 0 .. 2:  for kx in 0 .. 2:                     raster order; only the taps with y - ky and u - kx both even
+ *       for c in 16 g .. 16 g + 15:
+ *         a = x[b, (y - ky) / 2, (u - kx) / 2, c] inside the frame, +0.0f outside it
+ *             (only the index -1 occurs, at y = 0 or u = 0 under tap 2; it is a link of the chain like any padding tap)
+ *         acc = fmaf(a, w[ky, kx, c, o], acc)
+ *   y = acc + bias[o]                                          skipped when bias is NULL
+ *   y = act == DTFILL_CONV_LEAKY ? (y > 0 ? y : y * alpha) : y
+ * so an output has 1, 2, 2 or 4 taps by the parity of (y, u): (odd, odd) reads x[(y-1)/2, (u-1)/2] under w[1,1] alone,
+ * (even, even) reads four pixels under w[0,0], w[0,2], w[2,0], w[2,2].  No residual.
+ * Returns as dtfill_conv2d_strided's, with B 2H 2W max(Cout, out_channels) < 2^31 for the output.
+ *
+ * Both: pointers need float alignment only, x is read by 16-byte loads where its address allows; asynchronous on `stream`;
+ * no workspace, no allocation, no atomics, no host synchronisation.
+ */
+int dtfill_conv2d_strided(const float *x, int B, int H, int W, int Cin,
+                          const float *w, const float *bias /* nullable */, int ksize, int Cout, int stride,
+                          const float *residual /* nullable */, int act, float alpha,
+                          float *out, int out_channels, int out_offset, void *stream);
+int dtfill_conv2d_transpose(const float *x, int B, int H, int W, int Cin,
+                            const float *w, const float *bias /* nullable */, int Cout,
+                            int act, float alpha,
+                            float *out, int out_channels, int out_offset, void *stream);
+
+/*
  * dtfill_conv2d: a stride-1 'same' convolution in float32 whose every output bit is fixed by this statement: the layers of
  * SparsityCNN (solution_DeepNet/net.py:11-242), so that the network between the fills and the losses runs here too.
  *
