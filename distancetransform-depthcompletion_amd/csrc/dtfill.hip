@@ -62,8 +62,8 @@
 // the host below call it; tests/test_route.py compiles it for the host and holds tests/exhaustive_cases.py to it.
 //
 // No MFMA in any of the above: this path is compare/min/index work (DESIGN.md "Roofline").  The matmul-shaped entry points are
-// dtfill_conv2d (SparsityCNN's layers), dtfill_conv.hpp's, and dtfill_conv2d_strided and dtfill_conv2d_transpose (ResNet18's wide
-// layers), dtfill_conv2.hpp's.
+// dtfill_conv2d (SparsityCNN's layers), dtfill_conv2d_strided and dtfill_conv2d_transpose (ResNet18's wide layers), all three
+// dtfill_conv.hpp's.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -102,7 +102,6 @@ namespace {
 #include "dtfill_fillb.hpp"
 #include "dtfill_near.hpp"
 #include "dtfill_conv.hpp"
-#include "dtfill_conv2.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -1190,11 +1189,10 @@ static void conv2_same(int n, int ksize, int stride, int *out, int *front) {
     *front = pad > 0 ? (int)(pad / 2) : 0;
 }
 
-// what the two wide entry points check alike; Ho, Wo: the output frame
-static int conv2_check(const float *x, int B, int H, int W, int Cin, const float *w, int Cout, int act, float alpha, const float *out,
-                       int out_channels, int out_offset, long long Ho, long long Wo) {
+// what the three convolutions check alike; Ho, Wo: the output frame.  The channel counts an entry point takes are its own rule.
+static int conv_check(const float *x, int B, int H, int W, int Cin, const float *w, int Cout, int act, float alpha, const float *out,
+                      int out_channels, int out_offset, long long Ho, long long Wo) {
     if (!x || !w || !out) return DTFILL_ERR_NULL;
-    if (Cin < CV_G || Cin % CV_G || Cout < 16 || Cout % 16) return DTFILL_ERR_SHAPE;
     if (out_offset < 0 || out_channels < 1 || (long long)out_offset + Cout > out_channels) return DTFILL_ERR_SHAPE;
     if (B < 1 || H < 1 || W < 1 || (long long)B * H * W >= (1ll << 31) || B * Ho * Wo >= (1ll << 31)) return DTFILL_ERR_SHAPE;
     if ((long long)B * H * W * Cin >= (1ll << 31) || B * Ho * Wo * max(Cout, out_channels) >= (1ll << 31)) return DTFILL_ERR_SHAPE;
@@ -1202,44 +1200,46 @@ static int conv2_check(const float *x, int B, int H, int W, int Cin, const float
     return DTFILL_OK;
 }
 
+// the channel counts of the wide kernels: whole groups in, whole N-tiles out
+static bool conv_wide_channels(int Cin, int Cout) { return Cin >= CV_G && Cin % CV_G == 0 && Cout >= 16 && Cout % 16 == 0; }
+
 int dtfill_conv2d_strided(const float *x, int B, int H, int W, int Cin, const float *w, const float *bias, int ksize, int Cout,
                           int stride, const float *residual, int act, float alpha, float *out, int out_channels, int out_offset,
                           void *stream) {
     if (!x || !w || !out) return DTFILL_ERR_NULL;
     if (stride != 1 && stride != 2) return DTFILL_ERR_SHAPE;
     if (ksize != 1 && ksize != 3 && (stride == 2 || (ksize != 5 && ksize != 7))) return DTFILL_ERR_SHAPE;
-    if (H < 1 || W < 1) return DTFILL_ERR_SHAPE;
+    if (H < 1 || W < 1 || !conv_wide_channels(Cin, Cout)) return DTFILL_ERR_SHAPE;
     int Ho, Wo, pt, pl;
     conv2_same(H, ksize, stride, &Ho, &pt);
     conv2_same(W, ksize, stride, &Wo, &pl);
-    const int rc = conv2_check(x, B, H, W, Cin, w, Cout, act, alpha, out, out_channels, out_offset, Ho, Wo);
+    const int rc = conv_check(x, B, H, W, Cin, w, Cout, act, alpha, out, out_channels, out_offset, Ho, Wo);
     if (rc != DTFILL_OK) return rc;
-    const Conv2Args a{x, w, bias, residual, out, B, H, W, Cin, Cout, Ho, Wo, pt, pl, out_channels, out_offset, act, alpha};
-    conv2_launch(static_cast<hipStream_t>(stream), a, ksize, stride);
+    const ConvArgs a{x, w, bias, residual, out, B, H, W, Cin, Cout, Ho, Wo, pt, pl, out_channels, out_offset, act, alpha};
+    conv_strided_launch(static_cast<hipStream_t>(stream), a, ksize, stride);
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 
 int dtfill_conv2d_transpose(const float *x, int B, int H, int W, int Cin, const float *w, const float *bias, int Cout, int act,
                             float alpha, float *out, int out_channels, int out_offset, void *stream) {
-    const int rc = conv2_check(x, B, H, W, Cin, w, Cout, act, alpha, out, out_channels, out_offset, 2ll * H, 2ll * W);
+    const int rc = conv_check(x, B, H, W, Cin, w, Cout, act, alpha, out, out_channels, out_offset, 2ll * H, 2ll * W);
     if (rc != DTFILL_OK) return rc;
-    const Conv2Args a{x, w, bias, nullptr, out, B, H, W, Cin, Cout, 2 * H, 2 * W, 0, 0, out_channels, out_offset, act, alpha};
-    conv2_transpose_launch(static_cast<hipStream_t>(stream), a);
+    if (!conv_wide_channels(Cin, Cout)) return DTFILL_ERR_SHAPE;
+    const ConvArgs a{x, w, bias, nullptr, out, B, H, W, Cin, Cout, 2 * H, 2 * W, 0, 0, out_channels, out_offset, act, alpha};
+    conv_transpose_launch(static_cast<hipStream_t>(stream), a);
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 
 int dtfill_conv2d(const float *x, int B, int H, int W, int Cin, const float *w, const float *bias, int ksize, int Cout, int act,
                   float alpha, float *out, int out_channels, int out_offset, void *stream) {
-    if (!x || !w || !out) return DTFILL_ERR_NULL;
+    const int rc = conv_check(x, B, H, W, Cin, w, Cout, act, alpha, out, out_channels, out_offset, H, W);
+    if (rc != DTFILL_OK) return rc;
     if (ksize != 1 && ksize != 3 && ksize != 5 && ksize != 7) return DTFILL_ERR_SHAPE;
     if (Cin != 1 && (Cin < CV_G || Cin > 4 * CV_G || Cin % CV_G)) return DTFILL_ERR_SHAPE;
     if (Cout != 1 && Cout != 16) return DTFILL_ERR_SHAPE;
-    if (out_offset < 0 || out_channels < 1 || (long long)out_offset + Cout > out_channels) return DTFILL_ERR_SHAPE;
-    if (B < 1 || H < 1 || W < 1 || (long long)B * H * W >= (1ll << 31)) return DTFILL_ERR_SHAPE;
-    if ((long long)B * H * W * max(Cin, out_channels) >= (1ll << 31)) return DTFILL_ERR_SHAPE;
-    if ((act != DTFILL_CONV_LINEAR && act != DTFILL_CONV_LEAKY) || !isfinite(alpha)) return DTFILL_ERR_SHAPE;
-    const ConvArgs a{x, w, bias, out, B, H, W, Cin, out_channels, out_offset, act, alpha};
-    conv_launch(static_cast<hipStream_t>(stream), a, ksize, Cout);
+    const int r = (ksize - 1) / 2;
+    const ConvArgs a{x, w, bias, nullptr, out, B, H, W, Cin, Cout, H, W, r, r, out_channels, out_offset, act, alpha};
+    conv_launch(static_cast<hipStream_t>(stream), a, ksize);
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 

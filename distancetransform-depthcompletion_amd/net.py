@@ -21,55 +21,17 @@ LEAKY_ALPHA = 0.2  # tf.nn.leaky_relu's default
 STEM_WIDTH = 16  # channels every stem writes of the [B,H,W,16 * scale_num] tensor conv1a reads
 
 
-def conv2d_device(x, w, bias=None, act="linear", alpha=0.2, out=None, out_offset=0):
-    """A stride-1 'same' float32 convolution in the fixed summation order of include/dtfill.h, dtfill_conv2d (a layer of
-    net.py's SparsityCNN).  x: contiguous float32 CUDA tensor [B,H,W,Cin], or [B,H,W] for Cin = 1; w: [ksize,ksize,Cin,Cout], a
-    Keras Conv2D.kernel as stored (cross-correlation); bias: [Cout] or None; act: "linear" or "leaky" (y > 0 ? y : y * alpha).
-    out: a contiguous float32 tensor [B,H,W,C] on x's device of which the channels out_offset .. out_offset + Cout - 1 are
-    written and the others left as they are (not x itself); a new [B,H,W,Cout] tensor by default.  Returns out.  Asynchronous on
-    the current stream; the shapes the library takes are the header's (DtfillError otherwise)."""
+def _check_conv_args(x, w, bias, act, what, plane_ok=False):
+    """The checks the convolutions share; returns (B, H, W, Cin, Cout).  plane_ok: x may be [B,H,W], which is Cin = 1."""
     if act not in _lib.CONV_ACTS:
         raise ValueError("act must be one of %s, got %r" % (sorted(_lib.CONV_ACTS), act))
     _require_gpu()
-    if x.dim() == 3:
+    if plane_ok and x.dim() == 3:
         _check_tensor(x, "x")
     else:
         _check_tensor(x, "x", layout="[B,H,W,Cin]")
     B, H, W = x.shape[:3]
     Cin = x.shape[3] if x.dim() == 4 else 1
-    _check_tensor(w, "w", layout="[ksize,ksize,Cin,Cout]")
-    ksize, Cout = w.shape[0], w.shape[3]
-    if w.shape[1] != ksize or w.shape[2] != Cin or w.device != x.device:
-        raise ValueError("w must be [ksize,ksize,%d,Cout] on %s, got %s" % (Cin, x.device, tuple(w.shape)))
-    if bias is not None:
-        _check_tensor(bias, "bias", layout="[Cout]")
-        if bias.shape[0] != Cout or bias.device != x.device:
-            raise ValueError("bias must be [%d] on %s, got %s" % (Cout, x.device, tuple(bias.shape)))
-    if out is None:
-        if out_offset != 0:
-            raise ValueError("out_offset needs an out tensor to point into")
-        out = torch.empty((B, H, W, Cout), dtype=torch.float32, device=x.device)
-    else:
-        _check_tensor(out, "out", layout="[B,H,W,C]")
-        if tuple(out.shape[:3]) != (B, H, W) or out.device != x.device:
-            raise ValueError("out must be [%d,%d,%d,C] on %s, got %s" % (B, H, W, x.device, tuple(out.shape)))
-        if out.data_ptr() == x.data_ptr():
-            raise ValueError("out may not alias x")
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().dtfill_conv2d(x.data_ptr(), B, H, W, Cin, w.data_ptr(), _ptr(bias), ksize, Cout,
-                                             _lib.CONV_ACTS[act], float(alpha), out.data_ptr(), out.shape[3], int(out_offset),
-                                             _stream(x.device)))
-    return out
-
-
-
-def _check_conv_args(x, w, bias, act, what):
-    """The checks the two wide convolutions share; returns (B, H, W, Cin, Cout)."""
-    if act not in _lib.CONV_ACTS:
-        raise ValueError("act must be one of %s, got %r" % (sorted(_lib.CONV_ACTS), act))
-    _require_gpu()
-    _check_tensor(x, "x", layout="[B,H,W,Cin]")
-    B, H, W, Cin = x.shape
     _check_tensor(w, "w", layout=what)
     if w.shape[0] != w.shape[1] or w.shape[2] != Cin or w.device != x.device:
         raise ValueError("w must be %s with Cin = %d on %s, got %s" % (what, Cin, x.device, tuple(w.shape)))
@@ -82,7 +44,7 @@ def _check_conv_args(x, w, bias, act, what):
 
 
 def _check_conv_out(x, out, out_offset, frame, Cout):
-    """out of a wide convolution, [B,Ho,Wo,C] with frame = (B, Ho, Wo): a new [.., Cout] tensor when None."""
+    """out of a convolution, [B,Ho,Wo,C] with frame = (B, Ho, Wo): a new [.., Cout] tensor when None."""
     if out is None:
         if out_offset != 0:
             raise ValueError("out_offset needs an out tensor to point into")
@@ -92,6 +54,22 @@ def _check_conv_out(x, out, out_offset, frame, Cout):
         raise ValueError("out must be [%d,%d,%d,C] on %s, got %s" % (frame + (x.device, tuple(out.shape))))
     if out.data_ptr() == x.data_ptr():
         raise ValueError("out may not alias x")
+    return out
+
+
+def conv2d_device(x, w, bias=None, act="linear", alpha=0.2, out=None, out_offset=0):
+    """A stride-1 'same' float32 convolution in the fixed summation order of include/dtfill.h, dtfill_conv2d (a layer of
+    net.py's SparsityCNN).  x: contiguous float32 CUDA tensor [B,H,W,Cin], or [B,H,W] for Cin = 1; w: [ksize,ksize,Cin,Cout], a
+    Keras Conv2D.kernel as stored (cross-correlation); bias: [Cout] or None; act: "linear" or "leaky" (y > 0 ? y : y * alpha).
+    out: a contiguous float32 tensor [B,H,W,C] on x's device of which the channels out_offset .. out_offset + Cout - 1 are
+    written and the others left as they are (not x itself); a new [B,H,W,Cout] tensor by default.  Returns out.  Asynchronous on
+    the current stream; the shapes the library takes are the header's (DtfillError otherwise)."""
+    B, H, W, Cin, Cout = _check_conv_args(x, w, bias, act, "[ksize,ksize,Cin,Cout]", plane_ok=True)
+    out = _check_conv_out(x, out, out_offset, (B, H, W), Cout)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dtfill_conv2d(x.data_ptr(), B, H, W, Cin, w.data_ptr(), _ptr(bias), w.shape[0], Cout,
+                                             _lib.CONV_ACTS[act], float(alpha), out.data_ptr(), out.shape[3], int(out_offset),
+                                             _stream(x.device)))
     return out
 
 
@@ -180,13 +158,19 @@ def stem_layers(scale_num):
     return ("lidar_conv", "lidar_conv_extra_1", "lidar_conv_extra_2", "lidar_conv_extra_1")[:scale_num]
 
 
-def layer_shapes(scale_num=4, if_correct=True):
-    """{layer name: (ksize, Cin, Cout)} of the layers the forward uses, under the reference's attribute names."""
+def _head_shapes(scale_num, if_correct):
+    """The layers of the head the two networks share: the correction branch and the stems."""
     shapes = {}
     if if_correct:
         shapes.update(correct_1=(7, 1, 16), correct_2=(5, 16, 16), correct_3=(3, 16, 16), correct_4=(3, 16, 1))
     for name in stem_layers(scale_num):
         shapes[name] = (3, 1, STEM_WIDTH)
+    return shapes
+
+
+def layer_shapes(scale_num=4, if_correct=True):
+    """{layer name: (ksize, Cin, Cout)} of the layers the forward uses, under the reference's attribute names."""
+    shapes = _head_shapes(scale_num, if_correct)
     shapes.update(conv1a=(7, STEM_WIDTH * scale_num, 16), conv1b=(5, 16, 16), conv1c=(3, 16, 16), conv1d=(3, 16, 16),
                   conv_output=(1, 16, 1))
     return shapes
@@ -195,22 +179,24 @@ def layer_shapes(scale_num=4, if_correct=True):
 _KNOWN = tuple(layer_shapes(4, True)) + ("lidar_conv_extra_3",)  # every attribute name of the reference's class
 
 
-def glorot_weights(seed, scale_num=4, if_correct=True, bias=0.0):
-    """A weights dict for tests and benchmarks: Keras' default glorot_uniform kernels, uniform(+-sqrt(6 / (fan_in + fan_out))),
-    and biases uniform in +-bias (Keras starts them at zero), as float32 numpy arrays of Keras' shapes.  Holds
-    lidar_conv_extra_3 when the reference would build it (scale_num 4)."""
+def _glorot(shapes_of, seed, scale_num, if_correct, bias):
     rng = np.random.default_rng(seed)
-    shapes = layer_shapes(scale_num, if_correct)
+    shapes = shapes_of(scale_num, if_correct)
     if scale_num > 3:
         shapes["lidar_conv_extra_3"] = (3, 1, STEM_WIDTH)
     weights = {}
     for name, (k, cin, cout) in shapes.items():
         limit = np.sqrt(6.0 / (k * k * (cin + cout)))
-        weights[name] = (rng.uniform(-limit, limit, (k, k, cin, cout)).astype(np.float32),
+        weights[name] = (rng.uniform(-limit, limit, _keras_shape(name, k, cin, cout)).astype(np.float32),
                          rng.uniform(-bias, bias, (cout,)).astype(np.float32))
     return weights
 
 
+def glorot_weights(seed, scale_num=4, if_correct=True, bias=0.0):
+    """A weights dict for tests and benchmarks: Keras' default glorot_uniform kernels, uniform(+-sqrt(6 / (fan_in + fan_out))),
+    and biases uniform in +-bias (Keras starts them at zero), as float32 numpy arrays of Keras' shapes.  Holds
+    lidar_conv_extra_3 when the reference would build it (scale_num 4)."""
+    return _glorot(layer_shapes, seed, scale_num, if_correct, bias)
 
 
 RESNET_WIDTHS = (64, 128, 256, 512)  # channels of levels 1 .. 4; level k lives at 1 / 2^(k-1) of the frame each way
@@ -222,11 +208,7 @@ def layer_shapes_resnet18(scale_num=4, if_correct=True):
     """{layer name: (ksize, Cin, Cout)} of the layers ResNet18_NO_BN_l2's forward uses (net.py:262-400), under the reference's
     attribute names.  The layers of RESNET_STRIDE2 have stride 2; those of RESNET_TRANSPOSED are Conv2DTranspose(Cout, 3,
     strides=2), whose Keras kernel is [3,3,Cout,Cin]; upsample_1 is an ordinary convolution, as in the reference."""
-    shapes = {}
-    if if_correct:
-        shapes.update(correct_1=(7, 1, 16), correct_2=(5, 16, 16), correct_3=(3, 16, 16), correct_4=(3, 16, 1))
-    for name in stem_layers(scale_num):
-        shapes[name] = (3, 1, STEM_WIDTH)
+    shapes = _head_shapes(scale_num, if_correct)
     below = STEM_WIDTH * scale_num
     for level, width in enumerate(RESNET_WIDTHS, 1):
         shapes["conv%da" % level] = (3, below, width)
@@ -247,16 +229,7 @@ def _keras_shape(name, k, cin, cout):
 
 def glorot_weights_resnet18(seed, scale_num=4, if_correct=True, bias=0.0):
     """glorot_weights() for ResNet18: float32 numpy arrays of Keras' shapes, [3,3,Cout,Cin] for the transposed layers."""
-    rng = np.random.default_rng(seed)
-    shapes = layer_shapes_resnet18(scale_num, if_correct)
-    if scale_num > 3:
-        shapes["lidar_conv_extra_3"] = (3, 1, STEM_WIDTH)
-    weights = {}
-    for name, (k, cin, cout) in shapes.items():
-        limit = np.sqrt(6.0 / (k * k * (cin + cout)))
-        weights[name] = (rng.uniform(-limit, limit, _keras_shape(name, k, cin, cout)).astype(np.float32),
-                         rng.uniform(-bias, bias, (cout,)).astype(np.float32))
-    return weights
+    return _glorot(layer_shapes_resnet18, seed, scale_num, if_correct, bias)
 
 
 class _Buffers:

@@ -12,7 +12,7 @@ from test_gpu_conv2d import run as run_conv2d
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-TILE_H, TILE_W = 8, 32  # the block tile of csrc/dtfill_conv2.hpp: output pixels at stride 1, input pixels of the transpose
+TILE_H, TILE_W = 8, 32  # the block tile of csrc/dtfill_conv.hpp: output pixels at stride 1, input pixels of the transpose
 TILE_H2 = 4  # rows of output pixels at stride 2
 WIDTHS = ((16, 16), (32, 48), (16, 80))  # one, three and five N-tiles: a full pass of four and partial last ones
 # (B, H, W) in input pixels.  Stride 1 and the transpose: one pixel, 3 x 5, one below, at and one above the tile, two frames
