@@ -40,7 +40,7 @@ def __getattr__(name):
         import importlib
 
         return getattr(importlib.import_module(__name__ + ".net"), name)
-    if name == "net":  # <package>.net.SparsityCNN and .ResNet18: the reference's networks, inference only (imports torch)
+    if name == "net":  # <package>.net.SparsityCNN and .ResNet18 (inference), .SparsityCNNTrainable (a torch.nn.Module); imports torch
         import importlib
 
         return importlib.import_module(__name__ + ".net")

@@ -49,6 +49,7 @@ UNPROJ_TOTAL = 1
 CONV_LINEAR = 0  # act of dtfill_conv2d (DTFILL_CONV_*)
 CONV_LEAKY = 1  # y > 0 ? y : y * alpha
 CONV_ACTS = {"linear": CONV_LINEAR, "leaky": CONV_LEAKY}
+CONV_BW_ROWS, CONV_BW_COLS = 32, 64  # DTFILL_CONV_BW_ROWS, _COLS: a segment of dtfill_conv2d_backward_weights' sum
 PATHS = {"auto": 0, "general": FLAG_GENERAL_ONLY, "fused": FLAG_FUSED_ONLY}
 
 # the C ABI of include/dtfill.h: symbol -> (restype, argtypes), in the header's order.  tests/test_binding.py holds every entry to
@@ -99,6 +100,9 @@ _ABI = {
     "dtfill_nearest_gather": (ci, [vp, vp, vp, ci, ci, ci, ci, cf, vp, vp, vp, vp, sz, vp]),
     "dtfill_nearest_gather_backward_workspace_bytes": (sz, [ci, ci, ci, ci]),
     "dtfill_nearest_gather_backward": (ci, [vp, vp, vp, ci, ci, ci, ci, cf, vp, vp, vp, sz, vp]),
+    "dtfill_conv2d_backward_workspace_bytes": (sz, [ci, ci, ci, ci, ci, ci]),
+    "dtfill_conv2d_backward_data": (ci, [vp, ci, ci, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp, ci, ci, vp, sz, vp]),
+    "dtfill_conv2d_backward_weights": (ci, [vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp, vp, vp, sz, vp]),
     "dtfill_conv2d_strided": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, vp, ci, cf, vp, ci, ci, vp]),
     "dtfill_conv2d_transpose": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, cf, vp, ci, ci, vp]),
     "dtfill_conv2d": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, cf, vp, ci, ci, vp]),

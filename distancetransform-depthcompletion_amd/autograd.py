@@ -9,6 +9,10 @@ dtfill_generate_multi_channel, backward by dtfill_generate_multi_channel_backwar
 Differentiable in `data` only, once: tf.equal / tf.cast / tf.greater give the mask no gradient, and there is no double
 backward.  joint_train = False is the caller's .detach() on the input.
 
+conv2d() is a layer of the network itself under the tape (dtfill_conv2d forward; dtfill_conv2d_backward_data and
+dtfill_conv2d_backward_weights backward, both in fixed summation orders), and net.SparsityCNNTrainable is net.py's SparsityCNN
+composed of it, of generate_multi_channel() and of single torch operations: with train_loss() that is train.py:232-254's step.
+
 Threads and streams: every operator here may be called from several host threads on one stream and on several streams at once.
 The cached pieces (device.default_op's operator, the backward workspaces) are per stream, and one call's launches are enqueued
 under that piece's lock, so they stay contiguous on their stream; the outputs are the call's own tensors.  No lock is held
@@ -224,3 +228,45 @@ def unproject(x, K, E, val_thr=0.1, payload=None, capacity=None):
     Kd = device._calibration(K, 3, B, x.device, "K")
     Ed = device._calibration(E, 4, B, x.device, "E")
     return _Unproject.apply(x, payload, Kd, Ed, float(val_thr), capacity)
+
+
+class _Conv2d(torch.autograd.Function):
+    """y of device.conv2d_device; the backward asks the library only for the gradients that are needed."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, act, alpha):
+        y = device.conv2d_device(x, w, bias, act, alpha)
+        ctx.set_materialize_grads(False)  # an unused y arrives as None: nothing is launched for it
+        ctx.act, ctx.alpha = act, alpha
+        ctx.save_for_backward(x, w, None if act == "linear" else y)  # (a linear layer's derivative does not read y)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_y):
+        want_x, want_w, want_b = ctx.needs_input_grad[:3]
+        if g_y is None or not (want_x or want_w or want_b):
+            return None, None, None, None, None
+        x, w, y = ctx.saved_tensors
+        dy = g_y.to(torch.float32).contiguous()
+        dx = dw = db = None
+        if want_x:
+            dx = device.conv2d_backward_data_device(dy, w, y, ctx.act, ctx.alpha)
+            dx = dx.view(x.shape)  # ([B,H,W,1] of a plane x)
+        if want_w or want_b:
+            dw, db = device.conv2d_backward_weights_device(x, dy, w.shape[0], y, ctx.act, ctx.alpha, want_bias=want_b)
+        return dx, (dw if want_w else None), db, None, None
+
+
+def conv2d(x, w, bias=None, act="linear", alpha=0.2):
+    """A stride-1 'same' float32 convolution with its activation as a differentiable operator: a layer of net.py's SparsityCNN
+    under train.py:232-254's tape.  x: contiguous float32 CUDA tensor [B,H,W,Cin], or [B,H,W] for Cin = 1; w: [ksize,ksize,Cin,
+    Cout], a Keras Conv2D.kernel as stored; bias: [Cout] or None; act: "linear" or "leaky" (y > 0 ? y : y * alpha, alpha >= 0).
+    Returns y [B,H,W,Cout] by device.conv2d_device (include/dtfill.h, dtfill_conv2d).  Differentiable in x, w and bias, once:
+    the backward calls dtfill_conv2d_backward_data for x and dtfill_conv2d_backward_weights for w and bias, each only where
+    that gradient is needed, in their fixed summation orders, so every gradient bit is a function of the inputs and the shape
+    alone.  The shapes are dtfill_conv2d's domain (DtfillError otherwise).  No host synchronisation in either direction; the
+    workspace is the stream's cached one."""
+    if not alpha >= 0:
+        raise ValueError("alpha must be >= 0 (the derivative is taken by the sign of the output), got %r" % (alpha,))
+    return _Conv2d.apply(x, w, bias, act, float(alpha))

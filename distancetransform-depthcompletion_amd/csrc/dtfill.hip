@@ -63,7 +63,7 @@
 //
 // No MFMA in any of the above: this path is compare/min/index work (DESIGN.md "Roofline").  The matmul-shaped entry points are
 // dtfill_conv2d (SparsityCNN's layers), dtfill_conv2d_strided and dtfill_conv2d_transpose (ResNet18's wide layers), all three
-// dtfill_conv.hpp's.
+// dtfill_conv.hpp's, and their gradients dtfill_conv2d_backward_data and dtfill_conv2d_backward_weights, dtfill_convb.hpp's.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -102,6 +102,7 @@ namespace {
 #include "dtfill_fillb.hpp"
 #include "dtfill_near.hpp"
 #include "dtfill_conv.hpp"
+#include "dtfill_convb.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -1240,6 +1241,82 @@ int dtfill_conv2d(const float *x, int B, int H, int W, int Cin, const float *w, 
     const int r = (ksize - 1) / 2;
     const ConvArgs a{x, w, bias, nullptr, out, B, H, W, Cin, Cout, H, W, r, r, out_channels, out_offset, act, alpha};
     conv_launch(static_cast<hipStream_t>(stream), a, ksize);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+// the domain of the backward calls: dtfill_conv2d's, with B H W Cin < 2^31
+static bool convb_domain(int B, int H, int W, int Cin, int ksize, int Cout) {
+    if (ksize != 1 && ksize != 3 && ksize != 5 && ksize != 7) return false;
+    if (Cin != 1 && (Cin < CV_G || Cin > 4 * CV_G || Cin % CV_G)) return false;
+    if (Cout != 1 && Cout != 16) return false;
+    return B >= 1 && H >= 1 && W >= 1 && (long long)B * H * W * Cin < (1ll << 31);
+}
+
+// a slice of `channels` channels at `offset` of a [B,H,W,width] tensor
+static bool convb_slice(int B, int H, int W, int channels, int width, int offset) {
+    return offset >= 0 && width >= 1 && (long long)offset + channels <= width && (long long)B * H * W * width < (1ll << 31);
+}
+
+static size_t convb_align(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// the bytes of g (the data gradient's first part of the workspace; wT follows) and of the segments' partials
+static size_t convb_g_bytes(int B, int H, int W, int Cout) { return convb_align((size_t)B * H * W * Cout * sizeof(float)); }
+static size_t convb_segments(int B, int H, int W) {
+    return (size_t)B * ((H + DTFILL_CONV_BW_ROWS - 1) / DTFILL_CONV_BW_ROWS) * ((W + DTFILL_CONV_BW_COLS - 1) / DTFILL_CONV_BW_COLS);
+}
+
+size_t dtfill_conv2d_backward_workspace_bytes(int B, int H, int W, int Cin, int ksize, int Cout) {
+    if (!convb_domain(B, H, W, Cin, ksize, Cout)) return 0;
+    const size_t taps = (size_t)ksize * ksize;
+    const size_t data = convb_g_bytes(B, H, W, Cout) + convb_align(taps * Cin * Cout * sizeof(float));
+    const size_t weights = convb_align(convb_segments(B, H, W) * (taps * Cin + 1) * Cout * sizeof(float));
+    return data > weights ? data : weights;
+}
+
+// what the two backward calls check alike, and the kernels' view of dy and y
+static int convb_check(const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels, int y_offset, int B, int H,
+                       int W, int Cin, int ksize, int Cout, int act, float alpha, const void *workspace, size_t ws_bytes,
+                       ConvBwArgs *a) {
+    if (!dy || !workspace || (act == DTFILL_CONV_LEAKY && !y)) return DTFILL_ERR_NULL;
+    if ((act != DTFILL_CONV_LINEAR && act != DTFILL_CONV_LEAKY) || !isfinite(alpha) || alpha < 0.0f) return DTFILL_ERR_SHAPE;
+    if (act == DTFILL_CONV_LINEAR) y = nullptr;  // not read
+    if (!convb_domain(B, H, W, Cin, ksize, Cout) || !convb_slice(B, H, W, Cout, dy_channels, dy_offset)) return DTFILL_ERR_SHAPE;
+    if (y && !convb_slice(B, H, W, Cout, y_channels, y_offset)) return DTFILL_ERR_SHAPE;
+    if (ws_bytes < dtfill_conv2d_backward_workspace_bytes(B, H, W, Cin, ksize, Cout) || ((uintptr_t)workspace & 255))
+        return DTFILL_ERR_WORKSPACE;
+    const float *dys = dy + dy_offset, *ys = y ? y + y_offset : nullptr;
+    const bool gvec = (((uintptr_t)dys | (uintptr_t)ys) & 15) == 0 && dy_channels % 4 == 0 && (!y || y_channels % 4 == 0);
+    *a = ConvBwArgs{nullptr, dys, ys, dy_channels, y ? y_channels : 0, B, H, W, Cin, Cout, act, alpha,
+                    (H + CB_R - 1) / CB_R, (W + CB_C - 1) / CB_C, false, gvec};
+    return DTFILL_OK;
+}
+
+int dtfill_conv2d_backward_data(const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels, int y_offset,
+                                const float *w, int B, int H, int W, int Cin, int ksize, int Cout, int act, float alpha, float *dx,
+                                int dx_channels, int dx_offset, void *workspace, size_t ws_bytes, void *stream) {
+    if (!w || !dx) return DTFILL_ERR_NULL;
+    ConvBwArgs a;
+    const int rc = convb_check(dy, dy_channels, dy_offset, y, y_channels, y_offset, B, H, W, Cin, ksize, Cout, act, alpha, workspace,
+                               ws_bytes, &a);
+    if (rc != DTFILL_OK) return rc;
+    if (!convb_slice(B, H, W, Cin, dx_channels, dx_offset)) return DTFILL_ERR_SHAPE;
+    float *g = static_cast<float *>(workspace);
+    float *wt = reinterpret_cast<float *>(static_cast<char *>(workspace) + convb_g_bytes(B, H, W, Cout));
+    convb_data_launch(static_cast<hipStream_t>(stream), a, w, ksize, dx, dx_channels, dx_offset, g, wt);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+int dtfill_conv2d_backward_weights(const float *x, const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels,
+                                   int y_offset, int B, int H, int W, int Cin, int ksize, int Cout, int act, float alpha, float *dw,
+                                   float *db, void *workspace, size_t ws_bytes, void *stream) {
+    if (!x || !dw) return DTFILL_ERR_NULL;
+    ConvBwArgs a;
+    const int rc = convb_check(dy, dy_channels, dy_offset, y, y_channels, y_offset, B, H, W, Cin, ksize, Cout, act, alpha, workspace,
+                               ws_bytes, &a);
+    if (rc != DTFILL_OK) return rc;
+    a.x = x;
+    a.xvec = ((uintptr_t)x & 15) == 0;  // (Cin is a multiple of 16 wherever 16-byte loads of x are used)
+    convb_weights_launch(static_cast<hipStream_t>(stream), a, ksize, dw, db, static_cast<float *>(workspace));
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 

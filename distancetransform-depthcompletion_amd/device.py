@@ -839,7 +839,8 @@ def __getattr__(name):
         from . import nyu
 
         return nyu.nyu_read_device
-    if name in ("conv2d_device", "conv2d_strided_device", "conv2d_transpose_device"):  # likewise in net.py
+    if name in ("conv2d_device", "conv2d_strided_device", "conv2d_transpose_device", "conv2d_backward_data_device",
+                "conv2d_backward_weights_device", "conv2d_backward_workspace_bytes"):  # likewise in net.py
         from . import net
 
         return getattr(net, name)

@@ -2,7 +2,9 @@
 network, and ResNet18 (ResNet18_NO_BN_l2, net.py:245-745), the paper's.  Every convolution is a fixed-order float32 chain of
 include/dtfill.h (dtfill_conv2d, dtfill_conv2d_strided, dtfill_conv2d_transpose), the multi-channel fill in the middle is
 dtfill_generate_multi_channel, and the elementwise steps are single IEEE operations in torch.  So the output bits are a
-function of the weights and the input alone, from run to run and from shape to shape.
+function of the weights and the input alone, from run to run and from shape to shape.  SparsityCNNTrainable is SparsityCNN
+under a tape, a torch.nn.Module over autograd.conv2d, for train.py:232-254's step; conv2d_backward_data_device and
+conv2d_backward_weights_device are the device functions of one layer's backward (dtfill_conv2d_backward_data, _weights).
 
 The other ten models of the reference's net.py are not here; what they need beyond these two (widths in multiples of 16, stride
 2, Conv2DTranspose, the residual add) is.  conv2d_device, conv2d_strided_device and conv2d_transpose_device, the device
@@ -71,6 +73,103 @@ def conv2d_device(x, w, bias=None, act="linear", alpha=0.2, out=None, out_offset
                                              _lib.CONV_ACTS[act], float(alpha), out.data_ptr(), out.shape[3], int(out_offset),
                                              _stream(x.device)))
     return out
+
+
+_convb_ws = _device._Scratch()  # the workspace of the two backward calls
+
+
+def conv2d_backward_workspace_bytes(B, H, W, Cin, ksize, Cout):
+    """The bytes of workspace either backward call of a layer needs (dtfill_conv2d_backward_workspace_bytes): host arithmetic,
+    no device.  DtfillError for a shape outside dtfill_conv2d's domain."""
+    return _device._sized(_lib.load().dtfill_conv2d_backward_workspace_bytes(int(B), int(H), int(W), int(Cin), int(ksize), int(Cout)))
+
+
+def _check_conv_slice(t, what, like, offset, channels):
+    """A gradient or an output of a layer as the backward reads it: [B,H,W,C] (or [B,H,W] as C = 1) with like's frames and
+    device, of which the channels offset .. offset + channels - 1 are the layer's.  Returns C."""
+    if t.dim() == 3:
+        _check_tensor(t, what)
+    else:
+        _check_tensor(t, what, layout="[B,H,W,C]")
+    C = t.shape[3] if t.dim() == 4 else 1
+    if t.shape[:3] != like.shape[:3] or t.device != like.device:
+        raise ValueError("%s must have the frames %s on %s, got %s" % (what, tuple(like.shape[:3]), like.device, tuple(t.shape)))
+    if offset < 0 or offset + channels > C:
+        raise ValueError("%s has %d channels: no room for %d at offset %d" % (what, C, channels, offset))
+    return C
+
+
+def _check_conv_act(act, alpha):
+    if act not in _lib.CONV_ACTS:
+        raise ValueError("act must be one of %s, got %r" % (sorted(_lib.CONV_ACTS), act))
+    if not alpha >= 0:
+        raise ValueError("alpha must be >= 0 (the derivative is taken by the sign of the output), got %r" % (alpha,))
+    _require_gpu()
+
+
+def _check_conv_backward(dy, y, act, dy_offset, y_offset, Cout):
+    """dy and y as a layer's backward reads them; returns (dy's width, y or None for a linear layer, y's width)."""
+    Cdy = _check_conv_slice(dy, "dy", dy, dy_offset, Cout)
+    if act == "linear":
+        return Cdy, None, 0
+    if y is None:
+        raise ValueError("the derivative of act = %r needs y, the forward's output" % act)
+    return Cdy, y, _check_conv_slice(y, "y", dy, y_offset, Cout)
+
+
+def conv2d_backward_data_device(dy, w, y=None, act="linear", alpha=0.2, dy_offset=0, y_offset=0, dx=None, dx_offset=0):
+    """The gradient of conv2d_device with respect to x, in the fixed order of include/dtfill.h, dtfill_conv2d_backward_data.
+    dy: contiguous float32 CUDA tensor [B,H,W,C] (or [B,H,W], C = 1), the gradient of the layer's output in the channels
+    dy_offset .. dy_offset + Cout - 1; w: the layer's [ksize,ksize,Cin,Cout]; y: the forward's output, read at y_offset likewise,
+    needed unless act is "linear".  dx: a contiguous float32 tensor [B,H,W,C'] of which the channels dx_offset .. dx_offset +
+    Cin - 1 are written; a new [B,H,W,Cin] tensor by default.  Returns dx.  Asynchronous on the current stream."""
+    _check_conv_act(act, alpha)
+    _check_tensor(w, "w", layout="[ksize,ksize,Cin,Cout]")
+    ksize, Cin, Cout = w.shape[0], w.shape[2], w.shape[3]
+    Cdy, y, Cy = _check_conv_backward(dy, y, act, dy_offset, y_offset, Cout)
+    if w.shape[1] != ksize or w.device != dy.device:
+        raise ValueError("w must be [ksize,ksize,Cin,Cout] on %s, got %s" % (dy.device, tuple(w.shape)))
+    B, H, W = dy.shape[:3]
+    dx = _check_conv_out(dy, dx, dx_offset, (B, H, W), Cin)
+    if y is not None and dx.data_ptr() == y.data_ptr():
+        raise ValueError("dx may not alias y")
+    L = _lib.load()
+    nbytes = conv2d_backward_workspace_bytes(B, H, W, Cin, ksize, Cout)
+    with torch.cuda.device(dy.device):
+        with _convb_ws.hold(dy.device, nbytes) as ws:
+            _lib.check(L.dtfill_conv2d_backward_data(dy.data_ptr(), Cdy, int(dy_offset), _ptr(y), Cy, int(y_offset), w.data_ptr(), B, H,
+                                                     W, Cin, ksize, Cout, _lib.CONV_ACTS[act], float(alpha), dx.data_ptr(),
+                                                     dx.shape[3], int(dx_offset), ws, nbytes, _stream(dy.device)))
+    return dx
+
+
+def conv2d_backward_weights_device(x, dy, ksize, y=None, act="linear", alpha=0.2, dy_offset=0, y_offset=0, cout=None, want_bias=True):
+    """The gradients of conv2d_device with respect to w and bias, in the fixed two-level order of include/dtfill.h,
+    dtfill_conv2d_backward_weights.  x: the forward's input, [B,H,W,Cin] or [B,H,W]; dy, y, act, alpha and the offsets as in
+    conv2d_backward_data_device; cout: the layer's output channels (default: all of dy's).  Returns (dw [ksize,ksize,Cin,Cout],
+    db [Cout] or None without want_bias): new tensors.  Asynchronous on the current stream."""
+    _check_conv_act(act, alpha)
+    if x.dim() == 3:
+        _check_tensor(x, "x")
+    else:
+        _check_tensor(x, "x", layout="[B,H,W,Cin]")
+    Cin = x.shape[3] if x.dim() == 4 else 1
+    Cout = int(cout) if cout is not None else (dy.shape[3] if dy.dim() == 4 else 1)
+    Cdy, y, Cy = _check_conv_backward(dy, y, act, dy_offset, y_offset, Cout)
+    if x.shape[:3] != dy.shape[:3] or x.device != dy.device:
+        raise ValueError("x must have dy's frames %s on %s, got %s" % (tuple(dy.shape[:3]), dy.device, tuple(x.shape)))
+    B, H, W = x.shape[:3]
+    ksize = int(ksize)
+    L = _lib.load()
+    nbytes = conv2d_backward_workspace_bytes(B, H, W, Cin, ksize, Cout)
+    dw = torch.empty((ksize, ksize, Cin, Cout), dtype=torch.float32, device=x.device)
+    db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_bias else None
+    with torch.cuda.device(x.device):
+        with _convb_ws.hold(x.device, nbytes) as ws:
+            _lib.check(L.dtfill_conv2d_backward_weights(x.data_ptr(), dy.data_ptr(), Cdy, int(dy_offset), _ptr(y), Cy, int(y_offset), B,
+                                                        H, W, Cin, ksize, Cout, _lib.CONV_ACTS[act], float(alpha), dw.data_ptr(),
+                                                        _ptr(db), ws, nbytes, _stream(x.device)))
+    return dw, db
 
 
 def conv2d_strided_device(x, w, bias=None, stride=1, residual=None, act="linear", alpha=0.2, out=None, out_offset=0):
@@ -343,6 +442,77 @@ class SparsityCNN(_LidarNet):
             torch.mul(t.one.view(B, H, W), scale, out=t.output)
             torch.mul(t.correct, scale, out=t.correct_out)
         return t.output, t.correct_out
+
+
+class _ConvVariables(torch.nn.Module):
+    """The two variables of a Keras Conv2D under its attribute names: kernel [ksize,ksize,Cin,Cout] and bias [Cout]."""
+
+    def __init__(self, kernel, bias):
+        super().__init__()
+        self.kernel = torch.nn.Parameter(torch.from_numpy(kernel.copy()))
+        self.bias = torch.nn.Parameter(torch.from_numpy(bias.copy()))
+
+
+class SparsityCNNTrainable(torch.nn.Module):
+    """net.py's SparsityCNN under a tape: the network of SparsityCNN above as a torch.nn.Module, for train.py:232-254's step
+    (a forward, autograd.train_loss, backward(), an optimizer's step).  weights: as SparsityCNN takes them; they become the
+    module's parameters <layer>.kernel and <layer>.bias under the reference's attribute names (correct_1.kernel, ..), in Keras'
+    layouts, so a state_dict maps to layer.get_weights() name by name.  lidar_conv_extra_3 and layers the settings do not use
+    are accepted and ignored, as there.  The module is built on the host: move it with .to(device).
+
+    forward(input_lidar) returns (output * scale_range, lidar_correct * scale_range) with the bits SparsityCNN returns for the
+    same weights: every convolution is autograd.conv2d (dtfill_conv2d forward, dtfill_conv2d_backward_data and _weights
+    backward), the multi-channel fill is autograd.generate_multi_channel, and the mask and scale steps are single torch
+    operations.  joint_train = False cuts the gradient behind the fill (net.py:157-162), so the correction branch learns from
+    the auxiliary loss alone; with joint_train the fill's backward carries the main loss into it.  lidar_conv_extra_1 reads
+    lidar_2 and lidar_4 (net.py:176, 206): its gradient is the sum of both uses.  Every gradient bit is a function of the
+    weights, the input and the shape alone.  No host synchronisation in either direction; activations are new tensors of each
+    call, as a tape needs them."""
+
+    def __init__(self, weights, table_size=7, if_correct=True, scale_range=90.0, scale_num=4, joint_train=False):
+        super().__init__()
+        checked = SparsityCNN(weights, table_size, if_correct, scale_range, scale_num)  # the settings' and the weights' checks
+        self.table_size, self.if_correct, self.scale_num = checked.table_size, checked.if_correct, checked.scale_num
+        self.scale_range, self.joint_train = checked.scale_range, bool(joint_train)
+        for name, (kernel, bias) in checked._host.items():
+            setattr(self, name, _ConvVariables(kernel, bias))
+        self.register_buffer("_threshold", torch.tensor(0.1, dtype=torch.float32), persistent=False)
+        self.register_buffer("_scale", torch.tensor(self.scale_range, dtype=torch.float32), persistent=False)
+
+    def _conv(self, x, name, act):
+        from . import autograd
+
+        layer = getattr(self, name)
+        return autograd.conv2d(x, layer.kernel, layer.bias, act, LEAKY_ALPHA)
+
+    def forward(self, input_lidar):
+        """input_lidar: contiguous float32 CUDA tensor [B,H,W] in metres, a constant.  Returns two [B,H,W] tensors."""
+        from . import autograd
+
+        x = input_lidar.detach()
+        _check_tensor(x, "input_lidar")
+        B, H, W = x.shape
+        with torch.cuda.device(x.device):
+            mask = torch.gt(x, self._threshold).to(torch.float32)  # valued_mask
+            scaled = torch.div(x, self._scale)  # (a tensor divisor: an IEEE division, as in SparsityCNN)
+            if self.if_correct:
+                t = self._conv(scaled, "correct_1", "leaky")
+                t = self._conv(t, "correct_2", "leaky")
+                t = self._conv(t, "correct_3", "leaky")
+                correct = self._conv(t, "correct_4", "linear").view(B, H, W) * mask
+            else:
+                correct = scaled * mask
+            # The fill's input is ONE consumer of lidar_correct (the second output is the other), and has two itself (the
+            # window steps, and the first stem as lidar_1): every gradient sum on the tape has two terms, so no float32 sum
+            # depends on the order in which the autograd engine happens to run the nodes.
+            fill_in = correct.view_as(correct) if self.joint_train else correct.detach()
+            lidars = autograd.generate_multi_channel(fill_in, mask, self.table_size, self.scale_num)
+            stems = [self._conv(lidars[k], name, "leaky") for k, name in enumerate(stem_layers(self.scale_num))]
+            t = torch.cat(stems, dim=3) if len(stems) > 1 else stems[0]  # tf.concat
+            for name in ("conv1a", "conv1b", "conv1c", "conv1d"):
+                t = self._conv(t, name, "leaky")
+            output = self._conv(t, "conv_output", "linear").view(B, H, W)
+            return output * self._scale, correct * self._scale
 
 
 class _ResNetBuffers(_Buffers):

@@ -741,6 +741,85 @@ int dtfill_nearest_gather_backward(const float *x, const int32_t *index, const f
                                    int32_t *frame_status /* nullable */, void *workspace, size_t ws_bytes, void *stream);
 
 /*
+ * dtfill_conv2d_backward_data and dtfill_conv2d_backward_weights: the gradients of dtfill_conv2d with respect to x, and to w
+ * and bias, in float32 with every output bit fixed by this statement, so that the layers of SparsityCNN can be trained
+ * (train.py:232-254: a forward under a tape, the masked loss, the gradients of every variable).  The domain is
+ * dtfill_conv2d's: ksize 1, 3, 5 or 7, Cin 1, 16, 32, 48 or 64, Cout 1 or 16, stride 1, 'same', NHWC.
+ *
+ * dy: float32 [B,H,W,dy_channels], the gradient of the loss with respect to the layer's output, read at the channels
+ * dy_offset .. dy_offset + Cout - 1 (the counterpart of out_channels and out_offset: each stem reads its 16 channels of
+ * conv1a's 64-wide input gradient).  y: float32 [B,H,W,y_channels], the forward's output, read at y_offset likewise; NULL is
+ * allowed when act is DTFILL_CONV_LINEAR, and y is not read then.  x, w: the forward's.  Nothing else of dy's or y's tensor
+ * is read or written.
+ *
+ * THE CONTRACTS.
+ * The activation's derivative, per (b, h, v, o):
+ *   g = act == DTFILL_CONV_LEAKY ? (y > 0 ? dy : dy * alpha) : dy
+ * a float32 compare on the forward OUTPUT and one rounded multiply: tf.nn.leaky_relu's gradient.  With alpha >= 0 the sign of
+ * y is the sign of the pre-activation, so it is the derivative at the pre-activation too; alpha < 0 is refused.  y == +-0
+ * and a NaN y take the alpha branch.
+ *
+ * dtfill_conv2d_backward_data.  dx: float32 [B,H,W,dx_channels], written at dx_offset .. dx_offset + Cin - 1, the rest left
+ * untouched.  dx is dtfill_conv2d's own chain applied to g under the kernel flipped and its channel axes exchanged,
+ *   wT[i, j, o, c] = w[ksize - 1 - i, ksize - 1 - j, c, o],
+ * without bias or activation.  Per (b, h, v, c), r = (ksize - 1) / 2:
+ *   acc = +0
+ *   for G in 0 .. ceil(Cout / 16) - 1:                         groups of 16 of the Cout channels, outermost
+ *     for i in 0 .. ksize - 1:  for j in 0 .. ksize - 1:       the taps in raster order
+ *       for o in 16 G .. min(16 G + 15, Cout - 1):
+ *         a = g[b, h + i - r, v + j - r, o] inside the frame, +0.0f outside it
+ *         acc = fmaf(a, wT[i, j, o, c], acc)
+ *   dx[b, h, v, c] = acc
+ * So dx equals dtfill_conv2d(g, wT) (Cin of 32, 48 or 64: dtfill_conv2d_strided(g, wT) at stride 1) bit for bit.
+ *
+ * dtfill_conv2d_backward_weights.  dw: float32 [ksize,ksize,Cin,Cout]; db: float32 [Cout], nullable; both fully overwritten.
+ * A sum over all B H W pixels, in two levels.  A segment (b, t, s) is frame b, rows [R t, R t + R), columns [C s, C s + C),
+ * cut at the frame's edges, R = DTFILL_CONV_BW_ROWS and C = DTFILL_CONV_BW_COLS; there are ceil(H / R) ceil(W / C) a frame.
+ *   level 1, per segment and per (i, j, c, o):
+ *     p = +0
+ *     for (h, v) in the segment's pixels, in raster order:
+ *       a = x[b, h + i - r, v + j - r, c] inside the frame, +0.0f outside it
+ *       p = fmaf(a, g[b, h, v, o], p)
+ *   level 2:
+ *     acc = +0
+ *     for b: for t: for s:  acc = acc + p(b, t, s)            one rounded add each
+ *     dw[i, j, c, o] = acc
+ * db[o] is the same with a = 1.0f everywhere.  The segment size is part of the contract: it fixes the bits.  It is not a
+ * tuning parameter of a device, and the bits do not depend on the grid, the CU count, the stream or the run.
+ * +0 and -0 count as equal (zero operands pad a matrix-core step at a row's end; level 2 starts from +0).  Non-finite values
+ * follow fmaf.  A float32 evaluation in any other order lies within gamma_(R C + S) sum |x| |g| of dw, S the number of
+ * segments, gamma_n as in dtfill_conv2d.
+ *
+ * workspace: dtfill_conv2d_backward_workspace_bytes(B, H, W, Cin, ksize, Cout) bytes, 256-byte aligned; one size serves both
+ * calls (g and wT for the data gradient: 4 (B H W Cout + ksize^2 Cin Cout) bytes and alignment; the segments' partials for
+ * the weights': 4 S (ksize^2 Cin + 1) Cout bytes).  Pure host arithmetic; 0 for a shape outside the domain.
+ * Pointers need float alignment only.  Both calls are asynchronous on `stream`: no allocation, no float atomics, no host
+ * synchronisation.  dx may not alias dy or y.
+ * Returns, all checked before any HIP call: DTFILL_ERR_NULL for a NULL dy, w, dx (x, dy, dw for the weights), workspace, or a
+ * NULL y under DTFILL_CONV_LEAKY; DTFILL_ERR_SHAPE unless the shape is in dtfill_conv2d's domain, every offset lies in its
+ * tensor (0 <= offset, offset + channels <= width), B H W max(Cin, every width) < 2^31, act is one of the two values and
+ * alpha is finite and >= 0; DTFILL_ERR_WORKSPACE for a workspace too small or not aligned; then DTFILL_ERR_LAUNCH.
+ */
+enum {
+    DTFILL_CONV_BW_ROWS = 32, /* R: rows of a segment of the weight gradient's sum */
+    DTFILL_CONV_BW_COLS = 64  /* C: columns of it */
+};
+size_t dtfill_conv2d_backward_workspace_bytes(int B, int H, int W, int Cin, int ksize, int Cout);
+int dtfill_conv2d_backward_data(const float *dy, int dy_channels, int dy_offset,
+                                const float *y /* nullable if linear */, int y_channels, int y_offset,
+                                const float *w, int B, int H, int W, int Cin, int ksize, int Cout,
+                                int act, float alpha,
+                                float *dx, int dx_channels, int dx_offset,
+                                void *workspace, size_t ws_bytes, void *stream);
+int dtfill_conv2d_backward_weights(const float *x,
+                                   const float *dy, int dy_channels, int dy_offset,
+                                   const float *y /* nullable if linear */, int y_channels, int y_offset,
+                                   int B, int H, int W, int Cin, int ksize, int Cout,
+                                   int act, float alpha,
+                                   float *dw, float *db /* nullable */,
+                                   void *workspace, size_t ws_bytes, void *stream);
+
+/*
  * dtfill_conv2d_strided and dtfill_conv2d_transpose: the wide layers of ResNet18_NO_BN_l2 (solution_DeepNet/net.py:245-745),
  * in the same sense as dtfill_conv2d below, whose statement they extend: every output bit is fixed here.  Convolutions with
  * Cin == 1 or Cout == 1 (the correction branch, the stems, conv_output) stay with dtfill_conv2d.
