@@ -12,6 +12,9 @@ backward.  joint_train = False is the caller's .detach() on the input.
 conv2d() is a layer of the network itself under the tape (dtfill_conv2d forward; dtfill_conv2d_backward_data and
 dtfill_conv2d_backward_weights backward, both in fixed summation orders), and net.SparsityCNNTrainable is net.py's SparsityCNN
 composed of it, of generate_multi_channel() and of single torch operations: with train_loss() that is train.py:232-254's step.
+conv2d_strided() and conv2d_transpose() are the wide layers of ResNet18_NO_BN_l2 under the tape (dtfill_conv2d_strided and
+dtfill_conv2d_transpose forward; their _backward_data and _backward_weights entry points backward), and net.ResNet18Trainable is
+the paper's network composed of them.
 
 Threads and streams: every operator here may be called from several host threads on one stream and on several streams at once.
 The cached pieces (device.default_op's operator, the backward workspaces) are per stream, and one call's launches are enqueued
@@ -270,3 +273,107 @@ def conv2d(x, w, bias=None, act="linear", alpha=0.2):
     if not alpha >= 0:
         raise ValueError("alpha must be >= 0 (the derivative is taken by the sign of the output), got %r" % (alpha,))
     return _Conv2d.apply(x, w, bias, act, float(alpha))
+
+
+def _channel_slice(g):
+    """g [B,H,W,C] as (tensor, offset): g itself at 0 if it is contiguous; the wider contiguous tensor it is a channel slice of
+    (what torch.cat's backward hands out) and its first channel there, read in place; else a contiguous copy at 0."""
+    g = g.to(torch.float32)
+    if g.is_contiguous() or g.dim() != 4:
+        return g.contiguous(), 0
+    B, H, W, C = g.shape
+    wide = g.stride(2)
+    if g.stride(3) == 1 and wide > C and g.stride(1) == W * wide and g.stride(0) == H * W * wide:
+        offset = g.storage_offset() % wide
+        start = g.storage_offset() - offset
+        if offset + C <= wide and start + B * H * W * wide <= g.untyped_storage().nbytes() // 4:
+            return g.as_strided((B, H, W, wide), (H * W * wide, W * wide, wide, 1), start), offset
+    return g.contiguous(), 0
+
+
+class _Conv2dStrided(torch.autograd.Function):
+    """y of device.conv2d_strided_device; the backward asks the library only for the gradients that are needed."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, residual, stride, act, alpha):
+        y = device.conv2d_strided_device(x, w, bias, stride, residual, act, alpha)
+        ctx.set_materialize_grads(False)
+        ctx.stride, ctx.act, ctx.alpha = stride, act, alpha
+        ctx.save_for_backward(x, w, None if act == "linear" else y)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_y):
+        want_x, want_w, want_b, want_r = ctx.needs_input_grad[:4]
+        if g_y is None or not (want_x or want_w or want_b or want_r):
+            return None, None, None, None, None, None, None
+        x, w, y = ctx.saved_tensors
+        dy, at = _channel_slice(g_y)
+        dx = dr = dw = db = None
+        if want_x:
+            dx = device.conv2d_strided_backward_data_device(dy, w, ctx.stride, y, ctx.act, ctx.alpha, dy_offset=at, want_residual=want_r)
+            if want_r:
+                dx, dr = dx
+        elif want_r:  # g alone: the compare and the one rounded product of the contract, as single torch operations
+            g = dy[..., at:at + w.shape[3]]
+            dr = (g if y is None else torch.where(y > 0, g, g * ctx.alpha)).contiguous()
+        if want_w or want_b:
+            dw, db = device.conv2d_strided_backward_weights_device(x, dy, w.shape[0], ctx.stride, y, ctx.act, ctx.alpha, dy_offset=at,
+                                                                   cout=w.shape[3], want_bias=want_b)
+        return dx, (dw if want_w else None), db, dr, None, None, None
+
+
+def conv2d_strided(x, w, bias=None, stride=1, residual=None, act="linear", alpha=0.2):
+    """A wide 'same' float32 convolution of stride 1 or 2 with its residual add and its activation as a differentiable operator:
+    a layer of net.py's ResNet18_NO_BN_l2 under train.py:232-254's tape.  x: contiguous float32 CUDA tensor [B,H,W,Cin]; w:
+    [ksize,ksize,Cin,Cout], a Keras Conv2D.kernel as stored; bias: [Cout] or None; residual: [B,Ho,Wo,Cout] or None, added in
+    front of the activation.  Returns y by device.conv2d_strided_device (include/dtfill.h, dtfill_conv2d_strided).
+    Differentiable in x, w, bias and residual, once: dtfill_conv2d_strided_backward_data gives the gradients of x and of the
+    residual (g itself), dtfill_conv2d_strided_backward_weights those of w and bias, each only where it is needed, in their
+    fixed summation orders.  A gradient of y that is a channel slice of a wider contiguous tensor (torch.cat's backward) is
+    read in place.  The reference's kernel_regularizer takes no part: train.py:253 differentiates total_loss alone.  At
+    stride 2 H and W must be even.  No host synchronisation in either direction."""
+    if not alpha >= 0:
+        raise ValueError("alpha must be >= 0 (the derivative is taken by the sign of the output), got %r" % (alpha,))
+    return _Conv2dStrided.apply(x, w, bias, residual, int(stride), act, float(alpha))
+
+
+class _Conv2dTranspose(torch.autograd.Function):
+    """y of device.conv2d_transpose_device under the packed kernel [3,3,Cin,Cout]."""
+
+    @staticmethod
+    def forward(ctx, x, w_packed, bias, act, alpha):
+        y = device.conv2d_transpose_device(x, w_packed, bias, act, alpha)
+        ctx.set_materialize_grads(False)
+        ctx.act, ctx.alpha = act, alpha
+        ctx.save_for_backward(x, w_packed, None if act == "linear" else y)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_y):
+        want_x, want_w, want_b = ctx.needs_input_grad[:3]
+        if g_y is None or not (want_x or want_w or want_b):
+            return None, None, None, None, None
+        x, w, y = ctx.saved_tensors
+        dy, at = _channel_slice(g_y)
+        dx = dw = db = None
+        if want_x:
+            dx = device.conv2d_transpose_backward_data_device(dy, w, y, ctx.act, ctx.alpha, dy_offset=at)
+        if want_w or want_b:
+            dw, db = device.conv2d_transpose_backward_weights_device(x, dy, y, ctx.act, ctx.alpha, dy_offset=at, cout=w.shape[3],
+                                                                     want_bias=want_b)
+        return dx, (dw if want_w else None), db, None, None
+
+
+def conv2d_transpose(x, kernel, bias=None, act="linear", alpha=0.2):
+    """tf.keras.layers.Conv2DTranspose(Cout, 3, strides=2, padding='same') with its activation as a differentiable operator.
+    x: contiguous float32 CUDA tensor [B,H,W,Cin]; kernel: [3,3,Cout,Cin], the layer's kernel as Keras stores it; bias: [Cout]
+    or None.  Returns y [B,2H,2W,Cout] by device.conv2d_transpose_device (include/dtfill.h, dtfill_conv2d_transpose).  The
+    pack to the ABI's [3,3,Cin,Cout] is a permute inside the graph, so the kernel's gradient arrives in Keras' layout through
+    autograd's own permute.  Differentiable in x, kernel and bias, once, by dtfill_conv2d_transpose_backward_data and _weights
+    in their fixed summation orders.  No weight-decay term, as in conv2d_strided.  No host synchronisation."""
+    if not alpha >= 0:
+        raise ValueError("alpha must be >= 0 (the derivative is taken by the sign of the output), got %r" % (alpha,))
+    return _Conv2dTranspose.apply(x, kernel.permute(0, 1, 3, 2).contiguous(), bias, act, float(alpha))

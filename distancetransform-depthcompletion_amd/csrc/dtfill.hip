@@ -63,7 +63,8 @@
 //
 // No MFMA in any of the above: this path is compare/min/index work (DESIGN.md "Roofline").  The matmul-shaped entry points are
 // dtfill_conv2d (SparsityCNN's layers), dtfill_conv2d_strided and dtfill_conv2d_transpose (ResNet18's wide layers), all three
-// dtfill_conv.hpp's, and their gradients dtfill_conv2d_backward_data and dtfill_conv2d_backward_weights, dtfill_convb.hpp's.
+// dtfill_conv.hpp's, and their gradients dtfill_conv2d_backward_data and dtfill_conv2d_backward_weights (dtfill_conv2d's) and
+// dtfill_conv2d_strided_backward_data / _weights and dtfill_conv2d_transpose_backward_data / _weights, all dtfill_convb.hpp's.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -1318,6 +1319,123 @@ int dtfill_conv2d_backward_weights(const float *x, const float *dy, int dy_chann
     a.xvec = ((uintptr_t)x & 15) == 0;  // (Cin is a multiple of 16 wherever 16-byte loads of x are used)
     convb_weights_launch(static_cast<hipStream_t>(stream), a, ksize, dw, db, static_cast<float *>(workspace));
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+// the domain of the wide backward calls and the frame of dy: [Ho,Wo] of a strided layer, [2H,2W] of the transposed one
+static bool convbw_domain(int B, int H, int W, int Cin, int ksize, int Cout, int stride, int transposed, int *Ho, int *Wo) {
+    if (B < 1 || H < 1 || W < 1 || !conv_wide_channels(Cin, Cout)) return false;
+    long long ho = H, wo = W;
+    if (transposed) {
+        if (ksize != 3 || stride != 2) return false;
+        ho = 2ll * H, wo = 2ll * W;
+    } else if (stride == 2) {
+        if ((ksize != 1 && ksize != 3) || H % 2 || W % 2) return false;
+        ho = H / 2, wo = W / 2;
+    } else if (stride != 1 || (ksize != 1 && ksize != 3 && ksize != 5 && ksize != 7)) {
+        return false;
+    }
+    if ((long long)B * H * W * Cin >= (1ll << 31) || B * ho * wo * Cout >= (1ll << 31)) return false;
+    if (((long long)ksize * ksize * Cin + 1) * Cout >= (1ll << 31)) return false;
+    *Ho = (int)ho, *Wo = (int)wo;
+    return true;
+}
+
+size_t dtfill_conv2d_wide_backward_workspace_bytes(int B, int H, int W, int Cin, int ksize, int Cout, int stride, int transposed) {
+    int Ho, Wo;
+    if (!convbw_domain(B, H, W, Cin, ksize, Cout, stride, transposed, &Ho, &Wo)) return 0;
+    const size_t taps = (size_t)ksize * ksize;
+    size_t data = convb_g_bytes(B, Ho, Wo, Cout) + convb_align(taps * Cin * Cout * sizeof(float));
+    if (!transposed && stride == 2 && ksize == 1) data += convb_g_bytes(B, Ho, Wo, Cin);  // the chain's values before the spread
+    const size_t nseg = transposed ? convb_segments(B, H, W) : convb_segments(B, Ho, Wo);
+    const size_t weights = convb_align(nseg * (taps * Cin + 1) * Cout * sizeof(float));
+    return data > weights ? data : weights;
+}
+
+// what the four wide backward calls check alike, in convb_check's order, and the kernels' view of dy and y
+static int convbw_check(const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels, int y_offset, int B, int H,
+                        int W, int Cin, int ksize, int Cout, int stride, int transposed, int act, float alpha, const void *workspace,
+                        size_t ws_bytes, ConvBwArgs *a, int *Ho, int *Wo) {
+    if (!dy || !workspace || (act == DTFILL_CONV_LEAKY && !y)) return DTFILL_ERR_NULL;
+    if ((act != DTFILL_CONV_LINEAR && act != DTFILL_CONV_LEAKY) || !isfinite(alpha) || alpha < 0.0f) return DTFILL_ERR_SHAPE;
+    if (act == DTFILL_CONV_LINEAR) y = nullptr;  // not read
+    if (!convbw_domain(B, H, W, Cin, ksize, Cout, stride, transposed, Ho, Wo)) return DTFILL_ERR_SHAPE;
+    if (!convb_slice(B, *Ho, *Wo, Cout, dy_channels, dy_offset)) return DTFILL_ERR_SHAPE;
+    if (y && !convb_slice(B, *Ho, *Wo, Cout, y_channels, y_offset)) return DTFILL_ERR_SHAPE;
+    if (ws_bytes < dtfill_conv2d_wide_backward_workspace_bytes(B, H, W, Cin, ksize, Cout, stride, transposed) ||
+        ((uintptr_t)workspace & 255))
+        return DTFILL_ERR_WORKSPACE;
+    const float *dys = dy + dy_offset, *ys = y ? y + y_offset : nullptr;
+    const bool gvec = (((uintptr_t)dys | (uintptr_t)ys) & 15) == 0 && dy_channels % 4 == 0 && (!y || y_channels % 4 == 0);
+    // H, W: the frame the segments of the weight gradient lie over
+    const int Hs = transposed ? H : *Ho, Ws = transposed ? W : *Wo;
+    *a = ConvBwArgs{nullptr, dys, ys, dy_channels, y ? y_channels : 0, B, Hs, Ws, Cin, Cout, act, alpha,
+                    (Hs + CB_R - 1) / CB_R, (Ws + CB_C - 1) / CB_C, false, gvec};
+    return DTFILL_OK;
+}
+
+static int convbw_data(const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels, int y_offset, const float *w,
+                       int B, int H, int W, int Cin, int ksize, int Cout, int stride, int transposed, int act, float alpha, float *dx,
+                       int dx_channels, int dx_offset, float *dresidual, void *workspace, size_t ws_bytes, void *stream) {
+    if (!w || !dx) return DTFILL_ERR_NULL;
+    ConvBwArgs a;
+    int Ho, Wo;
+    const int rc = convbw_check(dy, dy_channels, dy_offset, y, y_channels, y_offset, B, H, W, Cin, ksize, Cout, stride, transposed, act,
+                                alpha, workspace, ws_bytes, &a, &Ho, &Wo);
+    if (rc != DTFILL_OK) return rc;
+    if (!convb_slice(B, H, W, Cin, dx_channels, dx_offset)) return DTFILL_ERR_SHAPE;
+    char *ws = static_cast<char *>(workspace);
+    float *g = reinterpret_cast<float *>(ws);
+    float *wt = reinterpret_cast<float *>(ws + convb_g_bytes(B, Ho, Wo, Cout));
+    float *tmp = reinterpret_cast<float *>(ws + convb_g_bytes(B, Ho, Wo, Cout) + convb_align((size_t)ksize * ksize * Cin * Cout * sizeof(float)));
+    convb_wide_data_launch(static_cast<hipStream_t>(stream), a, w, ksize, stride, transposed != 0, Ho, Wo, H, W, dx, dx_channels,
+                           dx_offset, dresidual, g, wt, tmp);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+static int convbw_weights(const float *x, const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels, int y_offset,
+                          int B, int H, int W, int Cin, int ksize, int Cout, int stride, int transposed, int act, float alpha, float *dw,
+                          float *db, void *workspace, size_t ws_bytes, void *stream) {
+    if (!x || !dw) return DTFILL_ERR_NULL;
+    ConvBwWide a;
+    int Ho, Wo;
+    const int rc = convbw_check(dy, dy_channels, dy_offset, y, y_channels, y_offset, B, H, W, Cin, ksize, Cout, stride, transposed, act,
+                                alpha, workspace, ws_bytes, &a.b, &Ho, &Wo);
+    if (rc != DTFILL_OK) return rc;
+    a.b.x = x;
+    a.b.xvec = ((uintptr_t)x & 15) == 0;  // (Cin is a multiple of 16)
+    a.HL = transposed ? Ho : H;
+    a.WL = transposed ? Wo : W;
+    convb_wide_weights_launch(static_cast<hipStream_t>(stream), a, ksize, stride, transposed != 0, dw, db, static_cast<float *>(workspace));
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+int dtfill_conv2d_strided_backward_data(const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels, int y_offset,
+                                        const float *w, int B, int H, int W, int Cin, int ksize, int Cout, int stride, int act,
+                                        float alpha, float *dx, int dx_channels, int dx_offset, float *dresidual, void *workspace,
+                                        size_t ws_bytes, void *stream) {
+    return convbw_data(dy, dy_channels, dy_offset, y, y_channels, y_offset, w, B, H, W, Cin, ksize, Cout, stride, 0, act, alpha, dx,
+                       dx_channels, dx_offset, dresidual, workspace, ws_bytes, stream);
+}
+
+int dtfill_conv2d_strided_backward_weights(const float *x, const float *dy, int dy_channels, int dy_offset, const float *y,
+                                           int y_channels, int y_offset, int B, int H, int W, int Cin, int ksize, int Cout, int stride,
+                                           int act, float alpha, float *dw, float *db, void *workspace, size_t ws_bytes, void *stream) {
+    return convbw_weights(x, dy, dy_channels, dy_offset, y, y_channels, y_offset, B, H, W, Cin, ksize, Cout, stride, 0, act, alpha, dw, db,
+                          workspace, ws_bytes, stream);
+}
+
+int dtfill_conv2d_transpose_backward_data(const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels, int y_offset,
+                                          const float *w, int B, int H, int W, int Cin, int Cout, int act, float alpha, float *dx,
+                                          int dx_channels, int dx_offset, void *workspace, size_t ws_bytes, void *stream) {
+    return convbw_data(dy, dy_channels, dy_offset, y, y_channels, y_offset, w, B, H, W, Cin, 3, Cout, 2, 1, act, alpha, dx, dx_channels,
+                       dx_offset, nullptr, workspace, ws_bytes, stream);
+}
+
+int dtfill_conv2d_transpose_backward_weights(const float *x, const float *dy, int dy_channels, int dy_offset, const float *y,
+                                             int y_channels, int y_offset, int B, int H, int W, int Cin, int Cout, int act, float alpha,
+                                             float *dw, float *db, void *workspace, size_t ws_bytes, void *stream) {
+    return convbw_weights(x, dy, dy_channels, dy_offset, y, y_channels, y_offset, B, H, W, Cin, 3, Cout, 2, 1, act, alpha, dw, db,
+                          workspace, ws_bytes, stream);
 }
 
 }  // extern "C"

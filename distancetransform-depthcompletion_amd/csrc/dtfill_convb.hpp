@@ -1,7 +1,8 @@
 // dtfill_convb.hpp -- the backward pass of dtfill_conv2d in a fixed summation order: dx, dw and db of the layers of
 // SparsityCNN (solution_DeepNet/net.py:11-242), what train.py:232-254's tape needs of a convolution.  include/dtfill.h,
 // dtfill_conv2d_backward_data() and dtfill_conv2d_backward_weights(), has the contracts.  Part of libdtfill.so; included by
-// dtfill.hip inside its anonymous namespace, after dtfill_conv.hpp, whose kernels the input gradient runs on.
+// dtfill.hip inside its anonymous namespace, after dtfill_conv.hpp, whose kernels the input gradient runs on.  The backward of
+// the wide layers of ResNet18_NO_BN_l2 (dtfill_conv2d_strided, dtfill_conv2d_transpose) is the second half of this file.
 #pragma once
 
 // ------------------------------------------------------------------------------------------------
@@ -61,23 +62,26 @@ __device__ __forceinline__ float convb_g(float dy, float y, int act, float alpha
     return act == DTFILL_CONV_LEAKY ? (y > 0.0f ? dy : dy * alpha) : dy;
 }
 
-// g[n, o] of all n = B H W pixels, dense
-__global__ __launch_bounds__(256) void k_convb_g(ConvBwArgs a, float *__restrict__ g, long long total) {
+// g[n, o] of all n pixels of dy's frames, dense; g2 (the wide layers' dresidual, which is g itself) is a second copy, or NULL
+__global__ __launch_bounds__(256) void k_convb_g(ConvBwArgs a, float *__restrict__ g, float *__restrict__ g2, long long total) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
     const long long pixel = idx / a.Cout;
     const int o = (int)(idx - pixel * a.Cout);
     const float dy = a.dy[pixel * a.dy_channels + o];
-    g[idx] = convb_g(dy, a.y ? a.y[pixel * a.y_channels + o] : 0.0f, a.act, a.alpha);
+    const float v = convb_g(dy, a.y ? a.y[pixel * a.y_channels + o] : 0.0f, a.act, a.alpha);
+    g[idx] = v;
+    if (g2) g2[idx] = v;
 }
 
 // wT[i, j, o, c] = w[ksize - 1 - i, ksize - 1 - j, c, o]; `blocked` (Cout == 1, Cin >= 32): [c / 16][tap][c % 16]
+// without `flip` the taps stay where they are, wX[i, j, o, c] = w[i, j, c, o]: the stride-2 and the transposed wide layers
 __global__ __launch_bounds__(256) void k_convb_flip(const float *__restrict__ w, float *__restrict__ wt, int taps, int Cin, int Cout,
-                                                    bool blocked) {
+                                                    bool blocked, bool flip) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= taps * Cin * Cout) return;
     const int o = idx % Cout, c = idx / Cout % Cin, tap = idx / Cout / Cin;
-    const int ft = taps - 1 - tap;  // (ksize - 1 - i) ksize + (ksize - 1 - j)
+    const int ft = flip ? taps - 1 - tap : tap;  // (ksize - 1 - i) ksize + (ksize - 1 - j)
     wt[blocked ? ((c / 16) * taps + ft) * 16 + c % 16 : (ft * Cout + o) * Cin + c] = w[idx];
 }
 
@@ -87,8 +91,8 @@ inline void convb_data_launch(hipStream_t st, const ConvBwArgs &b, const float *
     const long long total = (long long)b.B * b.H * b.W * b.Cout;
     const int taps = ksize * ksize, r = (ksize - 1) / 2;
     const bool blocked = b.Cout == 1 && b.Cin > 16;
-    k_convb_g<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(b, g, total);
-    k_convb_flip<<<(taps * b.Cin * b.Cout + 255) / 256, 256, 0, st>>>(w, wt, taps, b.Cin, b.Cout, blocked);
+    k_convb_g<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(b, g, nullptr, total);
+    k_convb_flip<<<(taps * b.Cin * b.Cout + 255) / 256, 256, 0, st>>>(w, wt, taps, b.Cin, b.Cout, blocked, true);
     ConvArgs a{g, wt, nullptr, nullptr, dx, b.B, b.H, b.W, b.Cout, b.Cin, b.H, b.W, r, r, dx_channels, dx_offset, DTFILL_CONV_LINEAR, 0.0f};
     if (blocked) {
         a.Cout = 16;
@@ -104,6 +108,19 @@ inline void convb_data_launch(hipStream_t st, const ConvBwArgs &b, const float *
     }
 }
 
+// g of the channels c .. c + 3 of a pixel of dy's and y's frames; vec: by 16-byte loads
+__device__ __forceinline__ cv_f4 convb_g4(const ConvBwArgs &a, size_t pixel, int c, bool vec) {
+    const float *pd = a.dy + pixel * a.dy_channels + c;
+    cv_f4 f = vec ? *reinterpret_cast<const cv_f4 *>(pd) : cv_f4{pd[0], pd[1], pd[2], pd[3]};
+    if (a.act == DTFILL_CONV_LEAKY) {
+        const float *py = a.y + pixel * a.y_channels + c;
+        const cv_f4 y = vec ? *reinterpret_cast<const cv_f4 *>(py) : cv_f4{py[0], py[1], py[2], py[3]};
+        f = cv_f4{convb_g(f.x, y.x, a.act, a.alpha), convb_g(f.y, y.y, a.act, a.alpha), convb_g(f.z, y.z, a.act, a.alpha),
+                  convb_g(f.w, y.w, a.act, a.alpha)};
+    }
+    return f;
+}
+
 // what a strip of g is: rows h1 .. h1 + CB_RS - 1, columns v0 .. v0 + CB_C - 1 of frame fb, +0 outside the frame, [pixel][16]
 __device__ __forceinline__ void convb_stage_g(float *s_g, const ConvBwArgs &a, size_t fb, int h1, int v0, int t) {
     for (int e = t; e < CB_RS * CB_C * 4; e += 256) {
@@ -111,17 +128,7 @@ __device__ __forceinline__ void convb_stage_g(float *s_g, const ConvBwArgs &a, s
         const int row = p / CB_C, col = p - row * CB_C;
         const int h = h1 + row, v = v0 + col;
         cv_f4 f{0.0f, 0.0f, 0.0f, 0.0f};
-        if (h < a.H && v < a.W) {
-            const size_t pixel = fb + (size_t)h * a.W + v;
-            const float *pd = a.dy + pixel * a.dy_channels + 4 * s;
-            f = a.gvec ? *reinterpret_cast<const cv_f4 *>(pd) : cv_f4{pd[0], pd[1], pd[2], pd[3]};
-            if (a.act == DTFILL_CONV_LEAKY) {
-                const float *py = a.y + pixel * a.y_channels + 4 * s;
-                const cv_f4 y = a.gvec ? *reinterpret_cast<const cv_f4 *>(py) : cv_f4{py[0], py[1], py[2], py[3]};
-                f = cv_f4{convb_g(f.x, y.x, a.act, a.alpha), convb_g(f.y, y.y, a.act, a.alpha), convb_g(f.z, y.z, a.act, a.alpha),
-                          convb_g(f.w, y.w, a.act, a.alpha)};
-            }
-        }
+        if (h < a.H && v < a.W) f = convb_g4(a, fb + (size_t)h * a.W + v, 4 * s, a.gvec);
         *reinterpret_cast<cv_f4 *>(s_g + p * 16 + 4 * s) = f;
     }
 }
@@ -312,4 +319,258 @@ inline void convb_weights_launch(hipStream_t st, const ConvBwArgs &a, int ksize,
         }
     }
     k_convb_sum<<<(pstride + 255) / 256, 256, 0, st>>>(part, pstride, nseg, ndw, dw, db);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The wide layers: the backward of dtfill_conv2d_strided and dtfill_conv2d_transpose (include/dtfill.h has the contracts).
+//
+// dx runs on dtfill_conv.hpp's kernels as they are, behind k_convb_g (which also writes dresidual, g itself) and k_convb_flip:
+//   stride 1                 conv_strided_launch at stride 1 over g under wT, as above
+//   stride 2, 3x3            conv_transpose_launch over g [B,H/2,W/2,Cout] under wX (the channel axes exchanged, no flip)
+//   stride 2, 1x1            the same chain has the single tap (0, 0): conv_strided_launch (1x1, stride 1) over g under wX into
+//                            the workspace, and k_convb_spread writes it to the even pixels of dx and +0 to the others
+//   transposed               conv_strided_launch (3x3, stride 2) over g [B,2H,2W,Cout] under wX
+//
+// dw and db.  The sum has a SMALL frame, the one the segments lie over and whose pixels are the k index, and a LARGE frame
+// that is read under the taps at (S h + i - P, S v + j - P): the output and the input frame of a strided layer (S its stride,
+// P = (ksize - 1) / 2 at stride 1 and 0 at stride 2, where H and W are even), the input and the output frame of the
+// transposed one (S = 2, P = 0).  k_convb_dw_wide is k_convb_dw over that pair, with one more loop: a work item is (segment,
+// group of 16 channels of the large tensor, pass of CBW NB tiles of 16 channels of the small tensor), and the staged strip of
+// the large tensor's group serves the NB tiles, one accumulator per (tap of the wave, tile).  TR says which tensor carries
+// the derivative: the small one (g, a strided layer; the B operand, x under the tap is A) or the large one (g under the tap
+// is B, a transposed layer; x is A).  The product is commutative and the MFMA's k order is the pixels' either way.
+// At S = 2 the strip of the large tensor is staged split by column parity, [row][parity][column / 2][16], so that a tap is a
+// constant offset again and a wave reads 64 consecutive floats (the plain image would have lanes 32 floats apart on the same
+// bank pairs: a two-way conflict).
+// db of a strided layer is one more accumulator per tile on wave 3 of the items of group 0, its A operand 1.0f; db of the
+// transposed layer is four, the chains q[ky][kx] of the header over g under the taps (0,0), (0,1), (1,0), (1,1), on wave 3
+// of the items of pass 0, added as ((q00 + q01) + q10) + q11.
+// ------------------------------------------------------------------------------------------------
+struct ConvBwWide {
+    ConvBwArgs b;  // b.H, b.W: the SMALL frame, the one the segments lie over
+    int HL, WL;    // the large frame
+};
+
+template <int KS, int S>
+struct ConvBwGeo {
+    static constexpr int RS = S == 1 ? 2 : 1;     // rows of the small frame a strip
+    static constexpr int NB = KS <= 3 ? 4 : 1;    // tiles of the small tensor a pass (13 taps a wave at 7x7: one)
+    static constexpr int P = S == 1 ? (KS - 1) / 2 : 0;
+    static constexpr int TAPS = KS * KS, NT = (TAPS + 3) / 4;
+    static constexpr int LH = (RS - 1) * S + KS, LWS = (CB_C - 1) * S + KS, LWH = CB_C + (KS - 1 + S - 1) / S;
+    // the float offset of tap (i, j) in the image [LH][S][LWH][16] from the pixel under tap (0, 0)
+    static __device__ __forceinline__ int tap_offset(int i, int j) { return ((i * S + j % S) * LWH + j / S) * 16; }
+};
+
+// dx of a 1x1 stride-2 layer: the chain's value at the even pixels, +0 elsewhere.  t: [B,H/2,W/2,Cin] dense
+__global__ __launch_bounds__(256) void k_convb_spread(const float *__restrict__ t, float *__restrict__ dx, int H, int W, int Cin,
+                                                      int dx_channels, int dx_offset, long long total) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const long long pixel = idx / Cin;
+    const int c = (int)(idx - pixel * Cin);
+    const int v = (int)(pixel % W), h = (int)(pixel / W % H);
+    const long long b = pixel / W / H;
+    const bool even = !((h | v) & 1);
+    dx[pixel * dx_channels + dx_offset + c] = even ? t[((b * (H / 2) + h / 2) * (W / 2) + v / 2) * Cin + c] : 0.0f;
+}
+
+template <int KS, int S, bool TR, bool VEC>
+__global__ __launch_bounds__(256, 2) void k_convb_dw_wide(ConvBwWide a, float *__restrict__ part, unsigned seg0, unsigned gl0) {
+    typedef ConvBwGeo<KS, S> G;
+    constexpr int RS = G::RS, NB = G::NB, TAPS = G::TAPS, NT = G::NT, LH = G::LH, LWS = G::LWS, LWH = G::LWH;
+    constexpr int NDB = TR ? 4 : NB;
+    __shared__ __attribute__((aligned(16))) float s_l[LH * S * LWH * 16];
+    __shared__ __attribute__((aligned(16))) float s_s[NB * RS * CB_C * 16];
+    const int t = threadIdx.x, lane = t & 63;
+    const int wave = t >> 6;
+    const int m = lane & 15, kq = lane >> 4;  // A: row m, pixel kq; B: pixel kq, column m; D: column m, rows 4 kq ..+3
+    const int Hs = a.b.H, Ws = a.b.W, HL = a.HL, WL = a.WL;
+    const unsigned Cin = a.b.Cin, Cout = a.b.Cout;
+    const int tiles = (TR ? Cin : Cout) / 16;
+    int aoff[NT], boff[4];
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+        const int tap = min(wave + 4 * n, TAPS - 1);
+        aoff[n] = G::tap_offset(tap / KS, tap % KS) + kq * 16 + m;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) boff[q] = TR ? G::tap_offset(q >> 1, q & 1) + kq * 16 + m : 0;
+    // a work item is (segment, group, pass), one a block: the pass is the grid's x, the group its y from gl0 on, the segment
+    // its z from seg0 on (the launch is repeated where a grid axis is too short).  A loop over a linear index, its 64-bit
+    // divisions and signed sizes cost some twenty scalar registers more than there are.  Every pixel index is below 2^31,
+    // the entry points' rule.
+    const unsigned pass = blockIdx.x, gl = gl0 + blockIdx.y, seg = seg0 + blockIdx.z;
+    {
+        const unsigned sx = seg % (unsigned)a.b.segs_x, sy = seg / (unsigned)a.b.segs_x % (unsigned)a.b.segs_y;
+        const unsigned fr = seg / (unsigned)a.b.segs_x / (unsigned)a.b.segs_y;
+        const int h0 = sy * CB_R, v0 = sx * CB_C, n0 = pass * NB, nt = min(NB, tiles - n0);
+        const int cols = min(CB_C, Ws - v0), steps = (cols + 3) / 4, whole = cols / 4;
+        // x and g from the item's frame and its first channel on: the large tensor's group, the small tensor's pass
+        const unsigned fs = fr * Hs * Ws, fl = fr * HL * WL;
+        const float *xi = a.b.x + (size_t)(TR ? fs : fl) * Cin + (TR ? n0 : gl) * 16;
+        ConvBwArgs b = a.b;
+        b.dy += (size_t)(TR ? fl : fs) * b.dy_channels + (TR ? gl : n0) * 16;
+        if (b.act == DTFILL_CONV_LEAKY) b.y += (size_t)(TR ? fl : fs) * b.y_channels + (TR ? gl : n0) * 16;
+        auto load_x = [&](unsigned pixel, int c) {
+            const float *src = xi + (size_t)pixel * Cin + c;
+            return VEC ? *reinterpret_cast<const cv_f4 *>(src) : cv_f4{src[0], src[1], src[2], src[3]};
+        };
+        cv_f4 acc[NT][NB], accb[NDB];
+#pragma unroll
+        for (int n = 0; n < NT; ++n)
+#pragma unroll
+            for (int k = 0; k < NB; ++k) acc[n][k] = cv_f4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int k = 0; k < NDB; ++k) accb[k] = cv_f4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+        for (int h1 = h0; h1 < min(h0 + CB_R, Hs); h1 += RS) {
+            // ---- the strip of the large tensor's group under every tap, +0 outside its frame ----
+            for (int e = t; e < LH * LWS * 4; e += 256) {
+                const int p = e >> 2, s = e & 3;
+                const int r = p / LWS, lc = p - r * LWS;
+                const int h = S * h1 - G::P + r, v = S * v0 - G::P + lc;
+                cv_f4 f{0.0f, 0.0f, 0.0f, 0.0f};
+                if (h >= 0 && h < HL && v >= 0 && v < WL) {
+                    const unsigned pixel = (unsigned)h * WL + v;
+                    f = TR ? convb_g4(b, pixel, 4 * s, VEC) : load_x(pixel, 4 * s);
+                }
+                *reinterpret_cast<cv_f4 *>(s_l + ((r * S + lc % S) * LWH + lc / S) * 16 + 4 * s) = f;
+            }
+            // ---- the strip of the small tensor's nt tiles, [tile][pixel][16], +0 outside its frame ----
+            for (int e = t; e < nt * RS * CB_C * 4; e += 256) {
+                const int p = e >> 2, s = e & 3;  // p: (tile, row, column)
+                const int n = p / (RS * CB_C), row = p / CB_C % RS, col = p % CB_C;
+                const int h = h1 + row, v = v0 + col;
+                cv_f4 f{0.0f, 0.0f, 0.0f, 0.0f};
+                if (h < Hs && v < Ws) {
+                    const unsigned pixel = (unsigned)h * Ws + v;
+                    f = TR ? load_x(pixel, n * 16 + 4 * s) : convb_g4(b, pixel, n * 16 + 4 * s, VEC);
+                }
+                *reinterpret_cast<cv_f4 *>(s_s + p * 16 + 4 * s) = f;
+            }
+            __syncthreads();
+            // ---- the strip's links of every chain, in raster order (EDGE: as in k_convb_dw) ----
+            const int rows = min(RS, Hs - h1);
+            auto k_step = [&](auto edge, int row, int s) {
+                const bool real = !decltype(edge)::value || v0 + 4 * s + kq < Ws;
+                const int at = (row * S * S * LWH + 4 * s) * 16;
+                float sv[NB];
+#pragma unroll
+                for (int k = 0; k < NB; ++k) sv[k] = s_s[((k * RS + row) * CB_C + 4 * s + kq) * 16 + m];
+#pragma unroll
+                for (int n = 0; n < NT; ++n)
+                    if (wave + 4 * n < TAPS) {
+                        const float lv = real ? s_l[at + aoff[n]] : 0.0f;
+#pragma unroll
+                        for (int k = 0; k < NB; ++k)
+                            acc[n][k] = __builtin_amdgcn_mfma_f32_16x16x4f32(TR ? sv[k] : lv, TR ? lv : sv[k], acc[n][k], 0, 0, 0);
+                    }
+                if (wave == 3) {
+                    const float one = real ? 1.0f : 0.0f;
+#pragma unroll
+                    for (int k = 0; k < NDB; ++k) {
+                        if (TR)
+                            accb[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(one, real ? s_l[at + boff[k]] : 0.0f, accb[k], 0, 0, 0);
+                        else
+                            accb[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(one, sv[k], accb[k], 0, 0, 0);
+                    }
+                }
+            };
+#pragma unroll 1
+            for (int row = 0; row < rows; ++row) {
+#pragma unroll 1
+                for (int s = 0; s < whole; ++s) k_step(std::false_type{}, row, s);
+                if (whole < steps) k_step(std::true_type{}, row, whole);
+            }
+            __syncthreads();  // the strips are rewritten by the next one
+        }
+        // ---- the segment's partials: [tap][Cin][Cout], then db ----
+        float *ps = part + (size_t)seg * (((size_t)TAPS * Cin + 1) * Cout);
+#pragma unroll
+        for (int n = 0; n < NT; ++n)
+            if (wave + 4 * n < TAPS) {
+#pragma unroll
+                for (int k = 0; k < NB; ++k)
+                    if (k < nt) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const int c = (TR ? n0 + k : gl) * 16 + 4 * kq + e, o = (TR ? gl : n0 + k) * 16 + m;
+                            ps[((size_t)(wave + 4 * n) * Cin + c) * Cout + o] = acc[n][k][e];
+                        }
+                    }
+            }
+        if (wave == 3 && (TR ? pass == 0 : gl == 0) && kq == 0) {
+#pragma clang fp contract(off)
+            if (TR) {
+                ps[(size_t)TAPS * Cin * Cout + gl * 16 + m] = ((accb[0][0] + accb[1][0]) + accb[2][0]) + accb[3][0];
+            } else {
+#pragma unroll
+                for (int k = 0; k < NB; ++k)
+                    if (k < nt) ps[(size_t)TAPS * Cin * Cout + (n0 + k) * 16 + m] = accb[k][0];
+            }
+        }
+    }
+}
+
+template <int KS, int S, bool TR>
+void convb_dw_wide_launch(hipStream_t st, const ConvBwWide &a, float *part, long long nseg) {
+    const int groups = (TR ? a.b.Cout : a.b.Cin) / 16, tiles = (TR ? a.b.Cin : a.b.Cout) / 16;
+    const int npass = (tiles + ConvBwGeo<KS, S>::NB - 1) / ConvBwGeo<KS, S>::NB;  // (< 2^24: a multiple of 16 below 2^31)
+    const bool vec = a.b.xvec && a.b.gvec;  // x, dy and y all allow 16-byte loads
+    for (long long seg0 = 0; seg0 < nseg; seg0 += 65535)
+        for (int gl0 = 0; gl0 < groups; gl0 += 65535) {
+            const dim3 grid((unsigned)npass, (unsigned)min(groups - gl0, 65535), (unsigned)min(nseg - seg0, 65535ll));
+            (vec ? k_convb_dw_wide<KS, S, TR, true> : k_convb_dw_wide<KS, S, TR, false>)<<<grid, 256, 0, st>>>(a, part, (unsigned)seg0,
+                                                                                                              (unsigned)gl0);
+        }
+}
+
+// dtfill_conv2d_strided_backward_weights and dtfill_conv2d_transpose_backward_weights: the workspace is the partials
+inline void convb_wide_weights_launch(hipStream_t st, const ConvBwWide &a, int ksize, int stride, bool transposed, float *dw, float *db,
+                                      float *part) {
+    const int nseg = a.b.B * a.b.segs_y * a.b.segs_x;
+    const int ndw = ksize * ksize * a.b.Cin * a.b.Cout, pstride = ndw + a.b.Cout;  // (< 2^31: the entry points' domain)
+    if (transposed) {
+        convb_dw_wide_launch<3, 2, true>(st, a, part, nseg);
+    } else if (stride == 2) {
+        if (ksize == 1)
+            convb_dw_wide_launch<1, 2, false>(st, a, part, nseg);
+        else
+            convb_dw_wide_launch<3, 2, false>(st, a, part, nseg);
+    } else {
+        switch (ksize) {
+            case 1: convb_dw_wide_launch<1, 1, false>(st, a, part, nseg); break;
+            case 3: convb_dw_wide_launch<3, 1, false>(st, a, part, nseg); break;
+            case 5: convb_dw_wide_launch<5, 1, false>(st, a, part, nseg); break;
+            default: convb_dw_wide_launch<7, 1, false>(st, a, part, nseg); break;
+        }
+    }
+    k_convb_sum<<<(pstride + 255) / 256, 256, 0, st>>>(part, pstride, nseg, ndw, dw, db);
+}
+
+// the data gradients of the wide layers.  b: dy's and y's view, b.B frames of Hg x Wg pixels of b.Cout channels; H, W: the
+// frame of dx, b.Cin channels.  The workspace is g, then the repacked weights, then (1x1 at stride 2) the chain's values.
+inline void convb_wide_data_launch(hipStream_t st, const ConvBwArgs &b, const float *w, int ksize, int stride, bool transposed, int Hg,
+                                   int Wg, int H, int W, float *dx, int dx_channels, int dx_offset, float *dres, float *g, float *wt,
+                                   float *tmp) {
+    const long long total = (long long)b.B * Hg * Wg * b.Cout;
+    const int taps = ksize * ksize, r = (ksize - 1) / 2;
+    k_convb_g<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(b, g, dres, total);
+    k_convb_flip<<<(taps * b.Cin * b.Cout + 255) / 256, 256, 0, st>>>(w, wt, taps, b.Cin, b.Cout, false, !transposed && stride == 1);
+    // the forward over g: its input channels are the layer's Cout, its output channels the layer's Cin
+    ConvArgs a{g, wt, nullptr, nullptr, dx, b.B, Hg, Wg, b.Cout, b.Cin, H, W, 0, 0, dx_channels, dx_offset, DTFILL_CONV_LINEAR, 0.0f};
+    if (transposed) {
+        conv_strided_launch(st, a, 3, 2);  // [2H,2W] -> [H,W], pt = pl = 0
+    } else if (stride == 1) {
+        a.pt = a.pl = r;
+        conv_strided_launch(st, a, ksize, 1);
+    } else if (ksize == 3) {
+        conv_transpose_launch(st, a);  // [H/2,W/2] -> [H,W]
+    } else {
+        a.out = tmp, a.Ho = Hg, a.Wo = Wg, a.out_channels = b.Cin, a.out_offset = 0;
+        conv_strided_launch(st, a, 1, 1);
+        const long long n = (long long)b.B * H * W * b.Cin;
+        k_convb_spread<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(tmp, dx, H, W, b.Cin, dx_channels, dx_offset, n);
+    }
 }

@@ -5,6 +5,9 @@ dtfill_generate_multi_channel, and the elementwise steps are single IEEE operati
 function of the weights and the input alone, from run to run and from shape to shape.  SparsityCNNTrainable is SparsityCNN
 under a tape, a torch.nn.Module over autograd.conv2d, for train.py:232-254's step; conv2d_backward_data_device and
 conv2d_backward_weights_device are the device functions of one layer's backward (dtfill_conv2d_backward_data, _weights).
+ResNet18Trainable is ResNet18 under a tape, over autograd.conv2d_strided and autograd.conv2d_transpose, the network train.py:113
+trains; conv2d_strided_backward_data_device, conv2d_strided_backward_weights_device, conv2d_transpose_backward_data_device and
+conv2d_transpose_backward_weights_device are the device functions of a wide layer's backward.
 
 The other ten models of the reference's net.py are not here; what they need beyond these two (widths in multiples of 16, stride
 2, Conv2DTranspose, the residual add) is.  conv2d_device, conv2d_strided_device and conv2d_transpose_device, the device
@@ -212,6 +215,125 @@ def conv2d_transpose_device(x, w_packed, bias=None, act="linear", alpha=0.2, out
                                                        _lib.CONV_ACTS[act], float(alpha), out.data_ptr(), out.shape[3],
                                                        int(out_offset), _stream(x.device)))
     return out
+
+
+def conv2d_wide_backward_workspace_bytes(B, H, W, Cin, ksize, Cout, stride=1, transposed=False):
+    """The bytes of workspace either backward call of a wide layer needs (dtfill_conv2d_wide_backward_workspace_bytes): host
+    arithmetic, no device.  B, H, W, Cin: the forward's input shape.  DtfillError for a shape outside the domain."""
+    return _device._sized(_lib.load().dtfill_conv2d_wide_backward_workspace_bytes(int(B), int(H), int(W), int(Cin), int(ksize),
+                                                                                 int(Cout), int(stride), int(bool(transposed))))
+
+
+def _check_wide_weights(x, dy, frame):
+    """x [B,H,W,Cin] of a wide layer's weight gradient, beside a dy whose frames must be `frame`."""
+    _check_tensor(x, "x", layout="[B,H,W,Cin]")
+    if dy.dim() != 4 or tuple(dy.shape[:3]) != frame or x.device != dy.device:
+        raise ValueError("dy must have the frames %s on %s, got %s" % (frame, x.device, tuple(dy.shape)))
+
+
+def conv2d_strided_backward_data_device(dy, w, stride=1, y=None, act="linear", alpha=0.2, dy_offset=0, y_offset=0, dx=None,
+                                        dx_offset=0, want_residual=False):
+    """The gradient of conv2d_strided_device with respect to x, and with want_residual to its residual, in the fixed order of
+    include/dtfill.h, dtfill_conv2d_strided_backward_data.  dy: contiguous float32 CUDA tensor [B,Ho,Wo,C], the gradient of the
+    layer's output in the channels dy_offset .. dy_offset + Cout - 1; w: the layer's [ksize,ksize,Cin,Cout]; y: the forward's
+    output, read at y_offset likewise, needed unless act is "linear".  The forward's input frame is [stride Ho, stride Wo]: at
+    stride 2 only even frames have a backward.  dx: a contiguous float32 tensor [B,H,W,C'] written at dx_offset .. dx_offset +
+    Cin - 1; a new [B,H,W,Cin] tensor by default.  Returns dx, or (dx, dresidual [B,Ho,Wo,Cout]) with want_residual.
+    Asynchronous on the current stream."""
+    _check_conv_act(act, alpha)
+    if stride not in (1, 2):
+        raise ValueError("stride must be 1 or 2, got %r" % (stride,))
+    _check_tensor(w, "w", layout="[ksize,ksize,Cin,Cout]")
+    ksize, Cin, Cout = w.shape[0], w.shape[2], w.shape[3]
+    Cdy, y, Cy = _check_conv_backward(dy, y, act, dy_offset, y_offset, Cout)
+    if dy.dim() != 4 or w.shape[1] != ksize or w.device != dy.device:
+        raise ValueError("dy must be [B,Ho,Wo,C] and w [ksize,ksize,Cin,Cout] on %s, got %s and %s" % (dy.device, tuple(dy.shape), tuple(w.shape)))
+    B, Ho, Wo = dy.shape[:3]
+    H, W = stride * Ho, stride * Wo
+    dx = _check_conv_out(dy, dx, dx_offset, (B, H, W), Cin)
+    if y is not None and dx.data_ptr() == y.data_ptr():
+        raise ValueError("dx may not alias y")
+    dres = torch.empty((B, Ho, Wo, Cout), dtype=torch.float32, device=dy.device) if want_residual else None
+    nbytes = conv2d_wide_backward_workspace_bytes(B, H, W, Cin, ksize, Cout, stride)
+    with torch.cuda.device(dy.device):
+        with _convb_ws.hold(dy.device, nbytes) as ws:
+            _lib.check(_lib.load().dtfill_conv2d_strided_backward_data(
+                dy.data_ptr(), Cdy, int(dy_offset), _ptr(y), Cy, int(y_offset), w.data_ptr(), B, H, W, Cin, ksize, Cout, stride,
+                _lib.CONV_ACTS[act], float(alpha), dx.data_ptr(), dx.shape[3], int(dx_offset), _ptr(dres), ws, nbytes,
+                _stream(dy.device)))
+    return (dx, dres) if want_residual else dx
+
+
+def conv2d_strided_backward_weights_device(x, dy, ksize, stride=1, y=None, act="linear", alpha=0.2, dy_offset=0, y_offset=0, cout=None,
+                                           want_bias=True):
+    """The gradients of conv2d_strided_device with respect to w and bias, in the fixed two-level order of include/dtfill.h,
+    dtfill_conv2d_strided_backward_weights.  x: the forward's input [B,H,W,Cin] (H and W even at stride 2); dy [B,H / stride,
+    W / stride,C], y, act, alpha and the offsets as in conv2d_strided_backward_data_device; cout: the layer's output channels
+    (default: all of dy's).  Returns (dw [ksize,ksize,Cin,Cout], db [Cout] or None without want_bias): new tensors.
+    Asynchronous on the current stream."""
+    _check_conv_act(act, alpha)
+    if stride not in (1, 2):
+        raise ValueError("stride must be 1 or 2, got %r" % (stride,))
+    if x.dim() == 4 and (x.shape[1] % stride or x.shape[2] % stride):
+        raise ValueError("the backward of a stride-2 layer needs an even frame, got %d x %d" % tuple(x.shape[1:3]))
+    B, H, W, Cin = x.shape if x.dim() == 4 else (0, 0, 0, 0)
+    _check_wide_weights(x, dy, (B, H // stride, W // stride))
+    Cout = int(cout) if cout is not None else dy.shape[3]
+    Cdy, y, Cy = _check_conv_backward(dy, y, act, dy_offset, y_offset, Cout)
+    ksize = int(ksize)
+    nbytes = conv2d_wide_backward_workspace_bytes(B, H, W, Cin, ksize, Cout, stride)
+    dw = torch.empty((ksize, ksize, Cin, Cout), dtype=torch.float32, device=x.device)
+    db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_bias else None
+    with torch.cuda.device(x.device):
+        with _convb_ws.hold(x.device, nbytes) as ws:
+            _lib.check(_lib.load().dtfill_conv2d_strided_backward_weights(
+                x.data_ptr(), dy.data_ptr(), Cdy, int(dy_offset), _ptr(y), Cy, int(y_offset), B, H, W, Cin, ksize, Cout, stride,
+                _lib.CONV_ACTS[act], float(alpha), dw.data_ptr(), _ptr(db), ws, nbytes, _stream(x.device)))
+    return dw, db
+
+
+def conv2d_transpose_backward_data_device(dy, w_packed, y=None, act="linear", alpha=0.2, dy_offset=0, y_offset=0, dx=None, dx_offset=0):
+    """The gradient of conv2d_transpose_device with respect to x, in the fixed order of include/dtfill.h,
+    dtfill_conv2d_transpose_backward_data.  dy: [B,2H,2W,C], read at dy_offset; w_packed: the [3,3,Cin,Cout] the forward takes;
+    y: the forward's output, needed unless act is "linear".  dx: [B,H,W,C'], written at dx_offset .. dx_offset + Cin - 1; a
+    new [B,H,W,Cin] tensor by default.  Returns dx.  Asynchronous on the current stream."""
+    _check_conv_act(act, alpha)
+    _check_tensor(w_packed, "w_packed", layout="[3,3,Cin,Cout]")
+    Cin, Cout = w_packed.shape[2], w_packed.shape[3]
+    Cdy, y, Cy = _check_conv_backward(dy, y, act, dy_offset, y_offset, Cout)
+    if dy.dim() != 4 or tuple(w_packed.shape[:2]) != (3, 3) or w_packed.device != dy.device or dy.shape[1] % 2 or dy.shape[2] % 2:
+        raise ValueError("dy must be [B,2H,2W,C] and w_packed [3,3,Cin,Cout] on %s, got %s and %s"
+                         % (dy.device, tuple(dy.shape), tuple(w_packed.shape)))
+    B, H, W = dy.shape[0], dy.shape[1] // 2, dy.shape[2] // 2
+    dx = _check_conv_out(dy, dx, dx_offset, (B, H, W), Cin)
+    nbytes = conv2d_wide_backward_workspace_bytes(B, H, W, Cin, 3, Cout, 2, True)
+    with torch.cuda.device(dy.device):
+        with _convb_ws.hold(dy.device, nbytes) as ws:
+            _lib.check(_lib.load().dtfill_conv2d_transpose_backward_data(
+                dy.data_ptr(), Cdy, int(dy_offset), _ptr(y), Cy, int(y_offset), w_packed.data_ptr(), B, H, W, Cin, Cout,
+                _lib.CONV_ACTS[act], float(alpha), dx.data_ptr(), dx.shape[3], int(dx_offset), ws, nbytes, _stream(dy.device)))
+    return dx
+
+
+def conv2d_transpose_backward_weights_device(x, dy, y=None, act="linear", alpha=0.2, dy_offset=0, y_offset=0, cout=None, want_bias=True):
+    """The gradients of conv2d_transpose_device with respect to w_packed and bias, in the fixed two-level order of
+    include/dtfill.h, dtfill_conv2d_transpose_backward_weights.  x: the forward's input [B,H,W,Cin]; dy [B,2H,2W,C].  Returns
+    (dw in the packed layout [3,3,Cin,Cout], db [Cout] or None without want_bias): new tensors; the gradient of the Keras kernel
+    [3,3,Cout,Cin] is dw.permute(0, 1, 3, 2).  Asynchronous on the current stream."""
+    _check_conv_act(act, alpha)
+    B, H, W, Cin = x.shape if x.dim() == 4 else (0, 0, 0, 0)
+    _check_wide_weights(x, dy, (B, 2 * H, 2 * W))
+    Cout = int(cout) if cout is not None else dy.shape[3]
+    Cdy, y, Cy = _check_conv_backward(dy, y, act, dy_offset, y_offset, Cout)
+    nbytes = conv2d_wide_backward_workspace_bytes(B, H, W, Cin, 3, Cout, 2, True)
+    dw = torch.empty((3, 3, Cin, Cout), dtype=torch.float32, device=x.device)
+    db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_bias else None
+    with torch.cuda.device(x.device):
+        with _convb_ws.hold(x.device, nbytes) as ws:
+            _lib.check(_lib.load().dtfill_conv2d_transpose_backward_weights(
+                x.data_ptr(), dy.data_ptr(), Cdy, int(dy_offset), _ptr(y), Cy, int(y_offset), B, H, W, Cin, Cout,
+                _lib.CONV_ACTS[act], float(alpha), dw.data_ptr(), _ptr(db), ws, nbytes, _stream(x.device)))
+    return dw, db
 
 
 def pack_transpose_kernel(kernel):
@@ -453,7 +575,53 @@ class _ConvVariables(torch.nn.Module):
         self.bias = torch.nn.Parameter(torch.from_numpy(bias.copy()))
 
 
-class SparsityCNNTrainable(torch.nn.Module):
+class _TrainableNet(torch.nn.Module):
+    """What the trainable networks share: the settings and the weights' checks (the inference class's), the parameters
+    <layer>.kernel and <layer>.bias in Keras' layouts, and the head (net.py:125-212 and 464-547) under the tape."""
+
+    INFERENCE = None  # the inference class whose checks and layer table these are
+
+    def __init__(self, weights, table_size=7, if_correct=True, scale_range=90.0, scale_num=4, joint_train=False):
+        super().__init__()
+        checked = self.INFERENCE(weights, table_size, if_correct, scale_range, scale_num)  # the settings' and the weights' checks
+        self.table_size, self.if_correct, self.scale_num = checked.table_size, checked.if_correct, checked.scale_num
+        self.scale_range, self.joint_train = checked.scale_range, bool(joint_train)
+        for name, (k, cin, cout) in checked.shapes.items():
+            kernel, bias = (np.ascontiguousarray(a, dtype=np.float32) for a in weights[name])  # Keras' layouts, not the packed one
+            setattr(self, name, _ConvVariables(kernel, bias))
+        self.register_buffer("_threshold", torch.tensor(0.1, dtype=torch.float32), persistent=False)
+        self.register_buffer("_scale", torch.tensor(self.scale_range, dtype=torch.float32), persistent=False)
+
+    def _conv(self, x, name, act):
+        from . import autograd
+
+        layer = getattr(self, name)
+        return autograd.conv2d(x, layer.kernel, layer.bias, act, LEAKY_ALPHA)
+
+    def _head(self, x):
+        """x [B,H,W] -> (lidar_correct [B,H,W], the stems' tf.concat [B,H,W,16 scale_num])."""
+        from . import autograd
+
+        B, H, W = x.shape
+        mask = torch.gt(x, self._threshold).to(torch.float32)  # valued_mask
+        scaled = torch.div(x, self._scale)  # (a tensor divisor: an IEEE division, as in SparsityCNN)
+        if self.if_correct:
+            t = self._conv(scaled, "correct_1", "leaky")
+            t = self._conv(t, "correct_2", "leaky")
+            t = self._conv(t, "correct_3", "leaky")
+            correct = self._conv(t, "correct_4", "linear").view(B, H, W) * mask
+        else:
+            correct = scaled * mask
+        # The fill's input is ONE consumer of lidar_correct (the second output is the other), and has two itself (the
+        # window steps, and the first stem as lidar_1): every gradient sum on the tape has two terms, so no float32 sum
+        # depends on the order in which the autograd engine happens to run the nodes.
+        fill_in = correct.view_as(correct) if self.joint_train else correct.detach()
+        lidars = autograd.generate_multi_channel(fill_in, mask, self.table_size, self.scale_num)
+        stems = [self._conv(lidars[k], name, "leaky") for k, name in enumerate(stem_layers(self.scale_num))]
+        return correct, (torch.cat(stems, dim=3) if len(stems) > 1 else stems[0])  # tf.concat
+
+
+class SparsityCNNTrainable(_TrainableNet):
     """net.py's SparsityCNN under a tape: the network of SparsityCNN above as a torch.nn.Module, for train.py:232-254's step
     (a forward, autograd.train_loss, backward(), an optimizer's step).  weights: as SparsityCNN takes them; they become the
     module's parameters <layer>.kernel and <layer>.bias under the reference's attribute names (correct_1.kernel, ..), in Keras'
@@ -469,46 +637,15 @@ class SparsityCNNTrainable(torch.nn.Module):
     weights, the input and the shape alone.  No host synchronisation in either direction; activations are new tensors of each
     call, as a tape needs them."""
 
-    def __init__(self, weights, table_size=7, if_correct=True, scale_range=90.0, scale_num=4, joint_train=False):
-        super().__init__()
-        checked = SparsityCNN(weights, table_size, if_correct, scale_range, scale_num)  # the settings' and the weights' checks
-        self.table_size, self.if_correct, self.scale_num = checked.table_size, checked.if_correct, checked.scale_num
-        self.scale_range, self.joint_train = checked.scale_range, bool(joint_train)
-        for name, (kernel, bias) in checked._host.items():
-            setattr(self, name, _ConvVariables(kernel, bias))
-        self.register_buffer("_threshold", torch.tensor(0.1, dtype=torch.float32), persistent=False)
-        self.register_buffer("_scale", torch.tensor(self.scale_range, dtype=torch.float32), persistent=False)
-
-    def _conv(self, x, name, act):
-        from . import autograd
-
-        layer = getattr(self, name)
-        return autograd.conv2d(x, layer.kernel, layer.bias, act, LEAKY_ALPHA)
+    INFERENCE = SparsityCNN
 
     def forward(self, input_lidar):
         """input_lidar: contiguous float32 CUDA tensor [B,H,W] in metres, a constant.  Returns two [B,H,W] tensors."""
-        from . import autograd
-
         x = input_lidar.detach()
         _check_tensor(x, "input_lidar")
         B, H, W = x.shape
         with torch.cuda.device(x.device):
-            mask = torch.gt(x, self._threshold).to(torch.float32)  # valued_mask
-            scaled = torch.div(x, self._scale)  # (a tensor divisor: an IEEE division, as in SparsityCNN)
-            if self.if_correct:
-                t = self._conv(scaled, "correct_1", "leaky")
-                t = self._conv(t, "correct_2", "leaky")
-                t = self._conv(t, "correct_3", "leaky")
-                correct = self._conv(t, "correct_4", "linear").view(B, H, W) * mask
-            else:
-                correct = scaled * mask
-            # The fill's input is ONE consumer of lidar_correct (the second output is the other), and has two itself (the
-            # window steps, and the first stem as lidar_1): every gradient sum on the tape has two terms, so no float32 sum
-            # depends on the order in which the autograd engine happens to run the nodes.
-            fill_in = correct.view_as(correct) if self.joint_train else correct.detach()
-            lidars = autograd.generate_multi_channel(fill_in, mask, self.table_size, self.scale_num)
-            stems = [self._conv(lidars[k], name, "leaky") for k, name in enumerate(stem_layers(self.scale_num))]
-            t = torch.cat(stems, dim=3) if len(stems) > 1 else stems[0]  # tf.concat
+            correct, t = self._head(x)
             for name in ("conv1a", "conv1b", "conv1c", "conv1d"):
                 t = self._conv(t, name, "leaky")
             output = self._conv(t, "conv_output", "linear").view(B, H, W)
@@ -599,3 +736,65 @@ class ResNet18(_LidarNet):
             torch.mul(t.one.view(B, H, W), scale, out=t.output)
             torch.mul(t.correct, scale, out=t.correct_out)
         return t.output, t.correct_out
+
+
+class ResNet18Trainable(_TrainableNet):
+    """net.py's ResNet18_NO_BN_l2 under a tape: the network of ResNet18 above as a torch.nn.Module, the network train.py:113
+    trains, for train.py:232-254's step.  weights: as ResNet18 takes them; they become the parameters <layer>.kernel and
+    <layer>.bias under the reference's attribute names in Keras' layouts ([3,3,Cout,Cin] for the three Conv2DTranspose layers:
+    the pack is a permute inside the graph, autograd.conv2d_transpose), so a state_dict maps to layer.get_weights() name by
+    name.  Built on the host: move it with .to(device).
+
+    forward(input_lidar) returns (output * scale_range, lidar_correct * scale_range) with the bits ResNet18 returns for the
+    same weights.  The head is SparsityCNNTrainable's; the wide layers are autograd.conv2d_strided and
+    autograd.conv2d_transpose, every tf.concat a torch.cat.  joint_train as in SparsityCNNTrainable.  H and W must be
+    multiples of 8.  The reference declares kernel_regularizer=l2(0.05) on its layers, but train.py:253 differentiates
+    total_loss alone and never adds depth_network.losses: the gradient reproduced here has no weight-decay term.
+
+    Every float32 gradient sum the tape makes has exactly two terms, so the order in which the autograd engine runs the nodes
+    cannot change a bit.  Four tensors have three consumers, the stems (conv1a, conv1a_extra, the concat in front of
+    upsample_1_post) and tensor_k_total for k = 1..3 (conv(k+1)a, conv(k+1)a_extra, the concat of level k): the two
+    convolutions read one identity view, so the tensor's gradient is (d conv_a + d conv_a_extra) + d concat.
+    No host synchronisation in either direction; activations are new tensors of each call."""
+
+    INFERENCE = ResNet18
+
+    def _wide(self, x, name, stride=1, residual=None, act="leaky"):
+        from . import autograd
+
+        layer = getattr(self, name)
+        return autograd.conv2d_strided(x, layer.kernel, layer.bias, stride, residual, act, LEAKY_ALPHA)
+
+    def _up(self, x, name):
+        from . import autograd
+
+        layer = getattr(self, name)
+        return autograd.conv2d_transpose(x, layer.kernel, layer.bias, "leaky", LEAKY_ALPHA)
+
+    def forward(self, input_lidar):
+        """input_lidar: contiguous float32 CUDA tensor [B,H,W] in metres, H and W multiples of 8, a constant.  Returns two
+        [B,H,W] tensors."""
+        x = input_lidar.detach()
+        if x.dim() == 3 and (x.shape[1] % 8 or x.shape[2] % 8):
+            raise ValueError("H and W must be multiples of 8, got %d x %d" % tuple(x.shape[1:]))
+        _check_tensor(x, "input_lidar")
+        B, H, W = x.shape
+        with torch.cuda.device(x.device):
+            correct, stems = self._head(x)
+            below, totals = stems, []
+            for level in (1, 2, 3, 4):  # net.py:551-674
+                name, stride = "conv%d" % level, 1 if level == 1 else 2
+                both = below.view_as(below)  # ONE consumer of `below` for the two convolutions; the concat is the other
+                t = self._wide(both, name + "a", stride)
+                add = self._wide(both, name + "a_extra", stride, act="linear")
+                total = self._wide(t, name + "b", residual=add)
+                t = self._wide(total, name + "c")
+                below = self._wide(t, name + "d", residual=total if level < 4 else None)
+                totals.append(below)
+            for level in (4, 3, 2):  # net.py:680-724
+                up = torch.cat([self._up(below, "upsample_%d" % level), totals[level - 2]], dim=3)
+                below = self._wide(up, "upsample_%d_post" % level)
+            up = torch.cat([self._wide(below, "upsample_1"), stems], dim=3)  # net.py:728-742
+            t = self._wide(up, "upsample_1_post")
+            output = self._conv(t, "conv_output", "linear").view(B, H, W)
+            return output * self._scale, correct * self._scale

@@ -820,6 +820,120 @@ int dtfill_conv2d_backward_weights(const float *x,
                                    void *workspace, size_t ws_bytes, void *stream);
 
 /*
+ * dtfill_conv2d_strided_backward_data, _weights and dtfill_conv2d_transpose_backward_data, _weights: the gradients of the wide
+ * layers below, dtfill_conv2d_strided and dtfill_conv2d_transpose, in the same sense as the two calls above, whose statements
+ * they extend: every output bit is fixed here, so that ResNet18_NO_BN_l2 can be trained (train.py:113, 232-254).  The
+ * reference declares kernel_regularizer=l2(0.05) on its layers, and train.py:253 differentiates total_loss alone without
+ * depth_network.losses: the gradient to reproduce has no weight-decay term, and nothing here adds one.
+ *
+ * B, H, W, Cin: the FORWARD's input shape, as in the forward calls; x: [B,H,W,Cin].  dy and y live on the forward's output
+ * frame, [B,Ho,Wo,.] with Ho = ceil(H / stride) for the strided layer and [B,2H,2W,.] for the transposed one, and are read at
+ * a channel offset of a wider tensor, as above.  g = y > 0 ? dy : dy * alpha, as above, on that frame.
+ * The domain: Cin and Cout multiples of 16 and at least 16.  Stride 1: ksize 1, 3, 5 or 7.  Stride 2: ksize 1 or 3, and H and
+ * W EVEN for both strided backward calls: narrower than the forward's domain, which takes odd frames (pt = 1 there); the
+ * reference's networks cannot run on them, because their own concat fails.  An odd frame at stride 2 is DTFILL_ERR_SHAPE.
+ * With H and W even, pt = pl = 0 at stride 2.  The transposed layer is the forward's: 3x3, stride 2.
+ *
+ * THE CONTRACTS.
+ * dresidual (strided data call, nullable): float32 [B,Ho,Wo,Cout], dense; dresidual = g.  The forward adds the residual in
+ * front of the activation, so the residual's gradient is g itself.
+ *
+ * dx of dtfill_conv2d_strided, stride 1: the statement of dtfill_conv2d_backward_data with Cout any multiple of 16: groups of
+ * 16 of the Cout channels outermost, the taps in raster order, wT[i, j, o, c] = w[ksize - 1 - i, ksize - 1 - j, c, o].  dx
+ * equals dtfill_conv2d_strided(g, wT) at stride 1 bit for bit.  A float32 evaluation in any other order lies within
+ * gamma_K sum |g| |w|, K = ksize^2 Cout.
+ *
+ * dx of dtfill_conv2d_strided, stride 2, 3x3, H and W even: dtfill_conv2d_transpose's chain over g [B,H/2,W/2,Cout] under
+ *   wX[ky, kx, o, c] = w[ky, kx, c, o]                          the channel axes exchanged, NO flip
+ * without bias or activation.  Per (b, h, v, c):
+ *   acc = +0
+ *   for G in 0 .. Cout / 16 - 1:
+ *     for ky in 0 .. 2:  for kx in 0 .. 2:                     only the taps with h - ky and v - kx both even
+ *       for o in 16 G .. 16 G + 15:
+ *         a = g[b, (h - ky) / 2, (v - kx) / 2, o] inside the frame, +0.0f outside it (index -1, at h = 0 or v = 0 under tap 2)
+ *         acc = fmaf(a, w[ky, kx, c, o], acc)
+ *   dx[b, h, v, c] = acc
+ * (pt = pl = 0: exactly the case dtfill_conv2d_transpose's contract was written for.)  Within gamma_K sum |g| |w|, K = 4 Cout.
+ *
+ * dx of dtfill_conv2d_strided, stride 2, 1x1: the same chain with the single tap (0, 0).  For h and v both even
+ *   acc = +0;  for o in 0 .. Cout - 1:  acc = fmaf(g[b, h / 2, v / 2, o], w[0, 0, c, o], acc);  dx[b, h, v, c] = acc
+ * and every other dx is +0.0f, also where g is not finite elsewhere: no zero weight stands in for a missing tap.
+ * Within gamma_Cout sum |g| |w|.
+ *
+ * dx of dtfill_conv2d_transpose.  w is the packed [3,3,Cin,Cout] the forward takes.  dx equals dtfill_conv2d_strided(g, wX,
+ * stride 2) on the [2H,2W] frame with wX[ky, kx, o, c] = w[ky, kx, c, o] bit for bit.  Per (b, h, v, c):
+ *   acc = +0
+ *   for G in 0 .. Cout / 16 - 1:  for ky in 0 .. 2:  for kx in 0 .. 2:  for o in 16 G .. 16 G + 15:
+ *     a = g[b, 2 h + ky, 2 v + kx, o] inside [2H,2W], +0.0f outside it (row 2H, column 2W)
+ *     acc = fmaf(a, w[ky, kx, c, o], acc)
+ * Within gamma_K sum |g| |w|, K = 9 Cout.
+ *
+ * dw and db of dtfill_conv2d_strided: the two levels of dtfill_conv2d_backward_weights with the segments laid over the OUTPUT
+ * frame [Ho,Wo]; R and C are the same constants.  pt and pl are the forward's ((ksize - 1) / 2 at stride 1, 0 at stride 2).
+ *   level 1, per segment and per (i, j, c, o):
+ *     p = +0
+ *     for (h, v) in the segment's output pixels, in raster order:
+ *       a = x[b, stride h + i - pt, stride v + j - pl, c] inside the frame, +0.0f outside it
+ *       p = fmaf(a, g[b, h, v, o], p)
+ *   level 2: acc = +0;  for b: for t: for s:  acc = acc + p(b, t, s);  dw[i, j, c, o] = acc
+ * db[o] with a = 1.0f.  At stride 1 with Cout == 16 (Cin 16 .. 64) these are the bits of dtfill_conv2d_backward_weights.
+ * Within gamma_(min(R C, Ho Wo) + S) sum |x| |g|, S the number of segments.
+ *
+ * dw and db of dtfill_conv2d_transpose: the segments lie over the INPUT frame [H,W], the small one; dw is in the packed layout
+ * [3,3,Cin,Cout] (Keras's kernel gradient is dw with its last two axes exchanged).
+ *   level 1, per segment and per (ky, kx, c, o):
+ *     p = +0
+ *     for (h, v) in the segment's input pixels, in raster order:
+ *       p = fmaf(x[b, h, v, c], g[b, 2 h + ky, 2 v + kx, o] inside [2H,2W] else +0.0f, p)
+ *   db, per segment and per o: four chains q[ky][kx], ky, kx in {0, 1}, over the same pixels in the same order,
+ *       q[ky][kx] = fmaf(1.0f, g[b, 2 h + ky, 2 v + kx, o], q[ky][kx])
+ *     and the segment's partial is ((q[0][0] + q[0][1]) + q[1][0]) + q[1][1], each a rounded add: every output pixel is
+ *     counted exactly once.
+ *   level 2 as above.
+ * Within gamma_(min(R C, H W) + S) sum |x| |g| for dw and gamma_(min(R C, H W) + S + 3) sum |g| for db.
+ * +0 and -0 count as equal; non-finite values follow fmaf; the bits depend on the inputs and the shape alone.
+ *
+ * workspace: dtfill_conv2d_wide_backward_workspace_bytes(B, H, W, Cin, ksize, Cout, stride, transposed) bytes, 256-byte
+ * aligned; transposed != 0 asks for ksize 3 and stride 2.  One size serves the data and the weights call of a layer: g and the
+ * repacked weights (and, 1x1 at stride 2, the chain's B Ho Wo Cin values before they are spread) for the data gradient, the
+ * partials 4 S (ksize^2 Cin + 1) Cout bytes for the weights'.  Pure host arithmetic; 0 outside the domain.
+ * Pointers need float alignment only.  All four calls are asynchronous on `stream`: no allocation, no float atomics, no host
+ * synchronisation.  dx and dresidual may not alias dy, y or each other.
+ * Returns, all checked before any HIP call and in the order of the calls above: DTFILL_ERR_NULL for a NULL dy, w, dx (x, dy,
+ * dw for the weights), workspace, or a NULL y under DTFILL_CONV_LEAKY; DTFILL_ERR_SHAPE unless the shape is in the domain
+ * above, every offset lies in its tensor, every tensor has fewer than 2^31 elements (B H W max(Cin, dx_channels), B Ho Wo
+ * max(Cout, dy_channels, y_channels), (ksize^2 Cin + 1) Cout), act is one of the two values and alpha is finite and >= 0;
+ * DTFILL_ERR_WORKSPACE for a workspace too small or not aligned; then DTFILL_ERR_LAUNCH.
+ */
+size_t dtfill_conv2d_wide_backward_workspace_bytes(int B, int H, int W, int Cin, int ksize, int Cout, int stride, int transposed);
+int dtfill_conv2d_strided_backward_data(const float *dy, int dy_channels, int dy_offset,
+                                        const float *y /* nullable if linear */, int y_channels, int y_offset,
+                                        const float *w, int B, int H, int W, int Cin, int ksize, int Cout, int stride,
+                                        int act, float alpha,
+                                        float *dx, int dx_channels, int dx_offset, float *dresidual /* nullable */,
+                                        void *workspace, size_t ws_bytes, void *stream);
+int dtfill_conv2d_strided_backward_weights(const float *x,
+                                           const float *dy, int dy_channels, int dy_offset,
+                                           const float *y /* nullable if linear */, int y_channels, int y_offset,
+                                           int B, int H, int W, int Cin, int ksize, int Cout, int stride,
+                                           int act, float alpha,
+                                           float *dw, float *db /* nullable */,
+                                           void *workspace, size_t ws_bytes, void *stream);
+int dtfill_conv2d_transpose_backward_data(const float *dy, int dy_channels, int dy_offset,
+                                          const float *y /* nullable if linear */, int y_channels, int y_offset,
+                                          const float *w /* packed [3,3,Cin,Cout] */, int B, int H, int W, int Cin, int Cout,
+                                          int act, float alpha,
+                                          float *dx, int dx_channels, int dx_offset,
+                                          void *workspace, size_t ws_bytes, void *stream);
+int dtfill_conv2d_transpose_backward_weights(const float *x,
+                                             const float *dy, int dy_channels, int dy_offset,
+                                             const float *y /* nullable if linear */, int y_channels, int y_offset,
+                                             int B, int H, int W, int Cin, int Cout,
+                                             int act, float alpha,
+                                             float *dw /* packed layout */, float *db /* nullable */,
+                                             void *workspace, size_t ws_bytes, void *stream);
+
+/*
  * dtfill_conv2d_strided and dtfill_conv2d_transpose: the wide layers of ResNet18_NO_BN_l2 (solution_DeepNet/net.py:245-745),
  * in the same sense as dtfill_conv2d below, whose statement they extend: every output bit is fixed here.  Convolutions with
  * Cin == 1 or Cout == 1 (the correction branch, the stems, conv_output) stay with dtfill_conv2d.
