@@ -11,15 +11,15 @@
 //   E_t = dilate4(D_{t-1}) & ~D_{t-1} & in-image
 //   forward tap T = (di,dj,w) offers   shift(L_{t-w}, di, dj)   to the pixels of E_t; L_t = those offered any
 //   backward tap (negated offset)      candidates of level t-w for the pixels of E_t \ L_t
-//   the FIRST tap in cv2 order wins (taken-mask chain); the winning step is recorded in six "code planes"
-//   holding the bits of enc = (di+2)<<3 | (dj+2)  (sources: enc 18 = step (0,0)).
+//   the FIRST tap in cv2 order wins (taken-mask chain); the winner is recorded in four "code planes"
+//   holding the bits of its plane code (dtfill_taps.hpp): the parent code 0..15 itself; sources: CODE_SOURCE.
 // The level loop runs the forward taps (they define L_t) and ORs E_t into three planes of d mod 8; the backward
 // taps run ONCE after it for all levels, on those planes (bwd_tap).  A horizontal shift of a row is one
 // v_alignbit per word; rows r-2..r+2 of the previous three levels come from a 4-slot LDS ring (one barrier per
 // level).  Levels stop at FR, when a level is empty, or when every tile pixel is decided.
-// Then every lane un-slices its row, 4 pixels per step, into the byte array s_par (2 * enc; F_NONE =
+// Then every lane un-slices its row, 8 pixels per step, into the byte array s_par (2 * plane code; F_NONE =
 // undecided), which reuses the ring's memory, and the tile pixels walk to their sources in lock-step:
-// the byte is the byte offset of the step's s_par displacement in a 64-entry int16 table (s_tab), so a
+// the byte is the byte offset of the step's s_par displacement in a 16-entry int16 table (s_tab), so a
 // hop is two LDS reads and one add; d is |drow| + |dcol| to the root.
 // LDS: 28.9 KB ring/s_par + 8 KB rank records.
 // ------------------------------------------------------------------------------------------------
@@ -33,27 +33,30 @@ constexpr int F_RS = 7;                // ring row stride in words: 6 + one zero
 constexpr int F_RROWS = F_WHM + 4;     // ring rows: 2 zero rows above and below the window
 constexpr int F_RPLANE = F_RROWS * F_RS;
 constexpr int F_RING = 1 + 4 * 2 * F_RPLANE;  // one leading zero word, then [slot][plane E/L][row][7]
+constexpr int F_NPLANES = 4;           // code planes: the bits of the plane code (dtfill_taps.hpp)
 constexpr int F_EB = 8;                // tile pixels per lane walked in lock-step
-// byte code of a decided pixel: 2 * enc (a source: 2 * 18 = step (0,0))
-constexpr int F_NONE = 2 * 63;         // byte code of an undecided pixel: table entry 63, also step (0,0)
+// byte code of a decided pixel: 2 * plane code (a source: 2 * CODE_SOURCE = step (0,0))
+constexpr int F_NONE = 2 * CODE_NONE;  // byte code of an undecided pixel: also step (0,0)
+static_assert(CODE_SOURCE < (1 << F_NPLANES) && CODE_NONE < (1 << F_NPLANES) && !code_wins(CODE_SOURCE) && !code_wins(CODE_NONE), "the reserved codes fit the planes and never win");
 static_assert(F_WWM == 32 * F_NWD, "window width must be six words");
 static_assert(F_RING * 4 >= F_WHM * F_P + 256 * 8, "s_par and the un-slicing table must fit in the ring's memory");
 static_assert((F_WHM * F_P) % 8 == 0 && F_WHM * F_P >= 4 * (1 + 4 * F_RPLANE), "the table is 8-byte aligned and lies behind the planes of P1b");
 
 // One forward tap T (dtfill_taps.hpp) of the first-match chain.  src = the live pixels of the level BACK levels back, in the
 // window row ROW below the lane's, with their neighbour words (src[1..3] = the lane's three words): what the call site loaded
-// must be what the table says.  cand = shift(src, dj); the winners get the bits of the step encoding in the code planes.
+// must be what the table says.  cand = shift(src, dj); the winners get the bits of the plane code in the code planes.
 template <int T, int ROW, int BACK>
-__device__ __forceinline__ void tap_step(const u32 (&src)[5], u32 (&taken)[F_HW], u32 (&C)[6][F_HW]) {
+__device__ __forceinline__ void tap_step(const u32 (&src)[5], u32 (&taken)[F_HW], u32 (&C)[F_NPLANES][F_HW]) {
     static_assert(T >= 0 && T < 8 && ROW == code_di(T) && BACK == code_weight(T), "tap T reads row r + di of level t - weight");
+    static_assert(code_wins(T), "a reserved code is no tap");
 #pragma unroll
     for (int i = 0; i < F_HW; ++i) {
         const u32 cand = row_shift<code_dj(T)>(src + i);
         const u32 sel = cand & ~taken[i];
         taken[i] |= cand;
 #pragma unroll
-        for (int j = 0; j < 6; ++j)
-            if (code_enc(T) & (1 << j)) C[j][i] |= sel;
+        for (int j = 0; j < F_NPLANES; ++j)
+            if (plane_code(T) & (1 << j)) C[j][i] |= sel;
     }
 }
 
@@ -62,9 +65,10 @@ __device__ __forceinline__ void tap_step(const u32 (&src)[5], u32 (&taken)[F_HW]
 template <int T, int ROW>
 __device__ __forceinline__ void bwd_tap(const u32 (&a0)[5], const u32 (&a1)[5], const u32 (&a2)[5], const u32 (&dv)[5],
                                         const u32 (&b0)[F_HW], const u32 (&b1)[F_HW], const u32 (&b2)[F_HW],
-                                        u32 (&taken)[F_HW], u32 (&C)[6][F_HW]) {
+                                        u32 (&taken)[F_HW], u32 (&C)[F_NPLANES][F_HW]) {
     constexpr int CODE = T | 8, DJ = code_dj(CODE);
     static_assert(T >= 0 && T < 8 && ROW == code_di(CODE), "backward tap T reads row r - di");
+    static_assert(code_wins(CODE), "codes 13 and 14 never select (dtfill_taps.hpp): they mean source and undecided here");
 #pragma unroll
     for (int i = 0; i < F_HW; ++i) {
         const u32 m = dist_match<code_weight(CODE)>(row_shift<DJ>(a0 + i), row_shift<DJ>(a1 + i), row_shift<DJ>(a2 + i), b0[i], b1[i], b2[i]) &
@@ -72,8 +76,8 @@ __device__ __forceinline__ void bwd_tap(const u32 (&a0)[5], const u32 (&a1)[5], 
         const u32 sel = m & ~taken[i];
         taken[i] |= m;
 #pragma unroll
-        for (int j = 0; j < 6; ++j)
-            if (code_enc(CODE) & (1 << j)) C[j][i] |= sel;
+        for (int j = 0; j < F_NPLANES; ++j)
+            if (plane_code(CODE) & (1 << j)) C[j][i] |= sel;
     }
 }
 
@@ -469,18 +473,22 @@ __device__ __forceinline__ void fused_body(int tile, bool premarked, int tbase, 
     // level 0: E_0 = L_0 = sources; zero the rest of the ring (levels "-1,-2,-3", the guard rows, the pads)
     if (s_bs) __syncthreads();  // block-uniform: everybody has read the frame facts that lie in the ring's memory
     for (int k = tid; k < F_RING; k += F_NT) s_ring[k] = 0;
-    if (tid < 64) {
-        const int hi = tid >> 3, lo = tid & 7;
-        s_tab[tid] = (hi <= 4 && lo <= 4) ? (short)((hi - 2) * F_P + (lo - 2)) : (short)0;
+    if (tid < (1 << F_NPLANES)) {
+        int di, dj;
+        code_step(tid, di, dj);
+        s_tab[tid] = (short)(di * F_P + dj);
     }
     __syncthreads();
     ring_store3(s_ring, 0, 0, r + 2, wb, D);
     ring_store3(s_ring, 0, 1, r + 2, wb, D);
-    u32 C[6][F_HW];
+    u32 C[F_NPLANES][F_HW];
+    u32 Lv[F_HW];  // the live pixels so far: L_0 | .. | L_t (forward tap 0's plane code is 0, so the planes alone do not tell)
 #pragma unroll
-    for (int j = 0; j < 6; ++j)
+    for (int i = 0; i < F_HW; ++i) {
+        Lv[i] = D[i];
 #pragma unroll
-        for (int i = 0; i < F_HW; ++i) C[j][i] = ((18 >> j) & 1) ? D[i] : 0u;  // sources: enc 18
+        for (int j = 0; j < F_NPLANES; ++j) C[j][i] = ((CODE_SOURCE >> j) & 1) ? D[i] : 0u;  // sources
+    }
     u32 Dup[F_HW], Ddn[F_HW];
     u32 Dl = 0, Dr = 0;  // D's neighbour words left / right of the lane's three (other half or nothing)
 #pragma unroll
@@ -492,7 +500,9 @@ __device__ __forceinline__ void fused_body(int tile, bool premarked, int tbase, 
     u32 P0[F_HW], P1[F_HW], P2[F_HW];  // bits 0..2 of the level at which a pixel was decided (sources: 0)
 #pragma unroll
     for (int i = 0; i < F_HW; ++i) P0[i] = P1[i] = P2[i] = 0;
-    for (int t = 1; t <= FR; ++t) {
+    // (the level as a lambda that says whether to go on, the loop asking it in its condition: with the body written into the loop
+    // and a break at its end the kernel came out with 20 bytes of scratch)
+    auto level = [&](const int t) __attribute__((always_inline)) -> bool {
         FPROF(++prof.n[1]);
         const int s1 = (t - 1) & 3, s2 = (t - 2) & 3, s3 = (t - 3) & 3, sw = t & 3;
         u32 nb[5], e1[5], l1[5], taken[F_HW], Et[F_HW], Lt[F_HW];
@@ -540,6 +550,7 @@ __device__ __forceinline__ void fused_body(int tile, bool premarked, int tbase, 
 #pragma unroll
             for (int i = 0; i < F_HW; ++i) {
                 Lt[i] = taken[i] & Et[i];
+                Lv[i] |= Lt[i];
                 P0[i] |= Et[i] & m0;
                 P1[i] |= Et[i] & m1;
                 P2[i] |= Et[i] & m2;
@@ -564,9 +575,10 @@ __device__ __forceinline__ void fused_body(int tile, bool premarked, int tbase, 
             u32 any = 0;
 #pragma unroll
             for (int w = 0; w < F_NT / 64; ++w) any |= s_any[t & 1][w];
-            if (any != 3u) break;
+            return any == 3u;
         }
-    }
+    };
+    for (int t = 1; t <= FR && level(t); ++t) {}
     FPROF(prof.mark(1));
     // ---- P1b: the backward taps of ALL levels in one pass (pixels that are decided but not live).  The d mod 8
     // planes and D go through the ring's memory (slots 0 and 1; its guard rows and pad words are still zero).
@@ -583,19 +595,16 @@ __device__ __forceinline__ void fused_body(int tile, bool premarked, int tbase, 
     {
         u32 taken[F_HW], a0[5], a1[5], a2[5], dv[5];
 #pragma unroll
-        for (int i = 0; i < F_HW; ++i) {
-            // live = has a forward code or is a source (every forward enc and 18 are non-zero)
-            const u32 live = C[0][i] | C[1][i] | C[2][i] | C[3][i] | C[4][i] | C[5][i];
-            taken[i] = ~(D[i] & ~live);
-        }
+        for (int i = 0; i < F_HW; ++i) taken[i] = ~(D[i] & ~Lv[i]);  // live = a source or offered by a forward tap
         auto row4 = [&](int row) {
             ring_load5(s_ring, 0, 0, row, wb, a0);
             ring_load5(s_ring, 0, 1, row, wb, a1);
             ring_load5(s_ring, 1, 0, row, wb, a2);
             ring_load5(s_ring, 1, 1, row, wb, dv);
         };
-        // the negated cv2 taps, same order; bwd_tap<T, row>: the row that row4 loaded, checked against the table.  (Taps 5 and 6
-        // never win and stay all the same: see fin_body, dtfill_rows.hpp.)
+        // the negated cv2 taps, same order; bwd_tap<T, row>: the row that row4 loaded, checked against the table.  Taps 5 and 6
+        // are not asked: they never select, and what they match tap 4 has matched before them, so tap 7 sees the same taken
+        // mask without them (the proof stands in dtfill_taps.hpp, whose codes 13 and 14 mean source and undecided here).
         row4(r + 4);
         bwd_tap<0, 2>(a0, a1, a2, dv, P0, P1, P2, taken, C);
         bwd_tap<1, 2>(a0, a1, a2, dv, P0, P1, P2, taken, C);
@@ -603,15 +612,13 @@ __device__ __forceinline__ void fused_body(int tile, bool premarked, int tbase, 
         bwd_tap<2, 1>(a0, a1, a2, dv, P0, P1, P2, taken, C);
         bwd_tap<3, 1>(a0, a1, a2, dv, P0, P1, P2, taken, C);
         bwd_tap<4, 1>(a0, a1, a2, dv, P0, P1, P2, taken, C);
-        bwd_tap<5, 1>(a0, a1, a2, dv, P0, P1, P2, taken, C);
-        bwd_tap<6, 1>(a0, a1, a2, dv, P0, P1, P2, taken, C);
         row4(r + 2);
         bwd_tap<7, 0>(a0, a1, a2, dv, P0, P1, P2, taken, C);
     }
 
-    // ---- P2: un-slice the code planes of this half row into bytes (2 * enc), 8 pixels per step: a byte of a plane goes
+    // ---- P2: un-slice the code planes of this half row into bytes (2 * plane code), 8 pixels per step: a byte of a plane goes
     // through the table above (one 8-byte LDS read), two shift-ors put it into its bit of the eight bytes.  Undecided pixels
-    // (not in D) get every plane bit: 2 * 63 = F_NONE.
+    // (not in D; no tap ever selected them, their planes are 0) get the plane bits of CODE_NONE: F_NONE.
     FPROF(prof.mark(2));
     u8 *s_par = reinterpret_cast<u8 *>(s_ring);
     __syncthreads();  // the ring is dead for everybody before its memory becomes s_par
@@ -619,14 +626,14 @@ __device__ __forceinline__ void fused_body(int tile, bool premarked, int tbase, 
         u32 *prow = reinterpret_cast<u32 *>(s_par + r * F_P) + wb * 8;
 #pragma unroll
         for (int i = 0; i < F_HW; ++i) {
-            u32 cj[6];
+            u32 cj[F_NPLANES];
 #pragma unroll
-            for (int j = 0; j < 6; ++j) cj[j] = C[j][i] | ~D[i];
+            for (int j = 0; j < F_NPLANES; ++j) cj[j] = ((CODE_NONE >> j) & 1) ? C[j][i] | ~D[i] : C[j][i];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 u32 lo = 0, hi = 0;
 #pragma unroll
-                for (int j = 0; j < 6; ++j) {
+                for (int j = 0; j < F_NPLANES; ++j) {
                     const uint2 sp = s_lut[(cj[j] >> (8 * q)) & 0xFFu];
                     lo |= sp.x << (j + 1);
                     hi |= sp.y << (j + 1);
@@ -659,7 +666,7 @@ __device__ __forceinline__ void fused_body(int tile, bool premarked, int tbase, 
 // trip for the frame's row counts, then LDS), and the first block of every frame also publishes them for the later launches
 // (frame_publish).  No block waits for another.  Else route, finfo, rowbase_s and rowfar are read as k_frame stored them.
 // the block's LDS: one buffer, carved here
-constexpr size_t F_OFF_RW = (sizeof(u32) * F_RING + 15) & ~(size_t)15, F_OFF_TAB = F_OFF_RW + sizeof(uint2) * F_WHM * 8, F_OFF_ANY = F_OFF_TAB + sizeof(short) * 64,
+constexpr size_t F_OFF_RW = (sizeof(u32) * F_RING + 15) & ~(size_t)15, F_OFF_TAB = F_OFF_RW + sizeof(uint2) * F_WHM * 8, F_OFF_ANY = F_OFF_TAB + sizeof(short) * (1 << F_NPLANES),
                  F_LDS_OWN = F_OFF_ANY + sizeof(u32) * 2 * (F_NT / 64);
 constexpr size_t F_LDS = F_LDS_OWN;
 // frames of up to this many rows can ride: their facts (FrameScratch, then two rank bases per row) lie in the ring's memory
@@ -679,7 +686,7 @@ __global__ __launch_bounds__(F_NT, 4) void k_fused(
     // per window row, the eight image-aligned 32-pixel half words it touches: {source bits, 1 + sources before them
     // in frame raster order} -- one 8-byte LDS read and a 32-bit popcount per rank lookup
     uint2 *s_rw = reinterpret_cast<uint2 *>(s_raw + F_OFF_RW);
-    short *s_tab = reinterpret_cast<short *>(s_raw + F_OFF_TAB);  // s_par displacement of the step enc (0 for the codes that are no step)
+    short *s_tab = reinterpret_cast<short *>(s_raw + F_OFF_TAB);  // s_par displacement of a plane code's step (0 for the two reserved codes)
     u32(*s_any)[F_NT / 64] = reinterpret_cast<u32(*)[F_NT / 64]>(s_raw + F_OFF_ANY);  // per wave: did level t produce anything (double-buffered by level parity)
     const int b = blockIdx.x, tile = blockIdx.y;
     int rt, tbase, nval, misaligned, sky0;  // block-uniform
