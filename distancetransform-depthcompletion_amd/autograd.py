@@ -25,6 +25,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import device
+from . import net as _net
 
 
 class _WindowSteps(torch.autograd.Function):
@@ -233,48 +234,6 @@ def unproject(x, K, E, val_thr=0.1, payload=None, capacity=None):
     return _Unproject.apply(x, payload, Kd, Ed, float(val_thr), capacity)
 
 
-class _Conv2d(torch.autograd.Function):
-    """y of device.conv2d_device; the backward asks the library only for the gradients that are needed."""
-
-    @staticmethod
-    def forward(ctx, x, w, bias, act, alpha):
-        y = device.conv2d_device(x, w, bias, act, alpha)
-        ctx.set_materialize_grads(False)  # an unused y arrives as None: nothing is launched for it
-        ctx.act, ctx.alpha = act, alpha
-        ctx.save_for_backward(x, w, None if act == "linear" else y)  # (a linear layer's derivative does not read y)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_y):
-        want_x, want_w, want_b = ctx.needs_input_grad[:3]
-        if g_y is None or not (want_x or want_w or want_b):
-            return None, None, None, None, None
-        x, w, y = ctx.saved_tensors
-        dy = g_y.to(torch.float32).contiguous()
-        dx = dw = db = None
-        if want_x:
-            dx = device.conv2d_backward_data_device(dy, w, y, ctx.act, ctx.alpha)
-            dx = dx.view(x.shape)  # ([B,H,W,1] of a plane x)
-        if want_w or want_b:
-            dw, db = device.conv2d_backward_weights_device(x, dy, w.shape[0], y, ctx.act, ctx.alpha, want_bias=want_b)
-        return dx, (dw if want_w else None), db, None, None
-
-
-def conv2d(x, w, bias=None, act="linear", alpha=0.2):
-    """A stride-1 'same' float32 convolution with its activation as a differentiable operator: a layer of net.py's SparsityCNN
-    under train.py:232-254's tape.  x: contiguous float32 CUDA tensor [B,H,W,Cin], or [B,H,W] for Cin = 1; w: [ksize,ksize,Cin,
-    Cout], a Keras Conv2D.kernel as stored; bias: [Cout] or None; act: "linear" or "leaky" (y > 0 ? y : y * alpha, alpha >= 0).
-    Returns y [B,H,W,Cout] by device.conv2d_device (include/dtfill.h, dtfill_conv2d).  Differentiable in x, w and bias, once:
-    the backward calls dtfill_conv2d_backward_data for x and dtfill_conv2d_backward_weights for w and bias, each only where
-    that gradient is needed, in their fixed summation orders, so every gradient bit is a function of the inputs and the shape
-    alone.  The shapes are dtfill_conv2d's domain (DtfillError otherwise).  No host synchronisation in either direction; the
-    workspace is the stream's cached one."""
-    if not alpha >= 0:
-        raise ValueError("alpha must be >= 0 (the derivative is taken by the sign of the output), got %r" % (alpha,))
-    return _Conv2d.apply(x, w, bias, act, float(alpha))
-
-
 def _channel_slice(g):
     """g [B,H,W,C] as (tensor, offset): g itself at 0 if it is contiguous; the wider contiguous tensor it is a channel slice of
     (what torch.cat's backward hands out) and its first channel there, read in place; else a contiguous copy at 0."""
@@ -291,37 +250,62 @@ def _channel_slice(g):
     return g.contiguous(), 0
 
 
-class _Conv2dStrided(torch.autograd.Function):
-    """y of device.conv2d_strided_device; the backward asks the library only for the gradients that are needed."""
+class _Conv(torch.autograd.Function):
+    """y of a convolution of `kind` (net._KINDS: narrow, strided, transposed) by its device function; the backward asks the
+    library only for the gradients that are needed, through net.py's two cores."""
 
     @staticmethod
-    def forward(ctx, x, w, bias, residual, stride, act, alpha):
-        y = device.conv2d_strided_device(x, w, bias, stride, residual, act, alpha)
-        ctx.set_materialize_grads(False)
-        ctx.stride, ctx.act, ctx.alpha = stride, act, alpha
-        ctx.save_for_backward(x, w, None if act == "linear" else y)
+    def forward(ctx, kind, x, w, bias, residual, stride, act, alpha):
+        if kind == "narrow":
+            y = device.conv2d_device(x, w, bias, act, alpha)
+        elif kind == "strided":
+            y = device.conv2d_strided_device(x, w, bias, stride, residual, act, alpha)
+        else:  # w: the packed kernel [3,3,Cin,Cout]
+            y = device.conv2d_transpose_device(x, w, bias, act, alpha)
+        ctx.set_materialize_grads(False)  # an unused y arrives as None: nothing is launched for it
+        ctx.kind, ctx.stride, ctx.act, ctx.alpha = kind, stride, act, alpha
+        ctx.save_for_backward(x, w, None if act == "linear" else y)  # (a linear layer's derivative does not read y)
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_y):
-        want_x, want_w, want_b, want_r = ctx.needs_input_grad[:4]
+        want_x, want_w, want_b, want_r = ctx.needs_input_grad[1:5]
         if g_y is None or not (want_x or want_w or want_b or want_r):
-            return None, None, None, None, None, None, None
+            return (None,) * 8
         x, w, y = ctx.saved_tensors
         dy, at = _channel_slice(g_y)
         dx = dr = dw = db = None
         if want_x:
-            dx = device.conv2d_strided_backward_data_device(dy, w, ctx.stride, y, ctx.act, ctx.alpha, dy_offset=at, want_residual=want_r)
+            dx = _net._backward_data(ctx.kind, dy, w, ctx.stride, y, ctx.act, ctx.alpha, at, 0, None, 0, want_r)
             if want_r:
                 dx, dr = dx
+            dx = dx.view(x.shape)  # ([B,H,W,1] of a plane x)
         elif want_r:  # g alone: the compare and the one rounded product of the contract, as single torch operations
             g = dy[..., at:at + w.shape[3]]
             dr = (g if y is None else torch.where(y > 0, g, g * ctx.alpha)).contiguous()
         if want_w or want_b:
-            dw, db = device.conv2d_strided_backward_weights_device(x, dy, w.shape[0], ctx.stride, y, ctx.act, ctx.alpha, dy_offset=at,
-                                                                   cout=w.shape[3], want_bias=want_b)
-        return dx, (dw if want_w else None), db, dr, None, None, None
+            dw, db = _net._backward_weights(ctx.kind, x, dy, w.shape[0], ctx.stride, y, ctx.act, ctx.alpha, at, 0, w.shape[3], want_b)
+        return None, dx, (dw if want_w else None), db, dr, None, None, None
+
+
+def _conv(kind, x, w, bias, residual, stride, act, alpha):
+    if not alpha >= 0:
+        raise ValueError("alpha must be >= 0 (the derivative is taken by the sign of the output), got %r" % (alpha,))
+    return _Conv.apply(kind, x, w, bias, residual, stride, act, float(alpha))
+
+
+def conv2d(x, w, bias=None, act="linear", alpha=0.2):
+    """A stride-1 'same' float32 convolution with its activation as a differentiable operator: a layer of net.py's SparsityCNN
+    under train.py:232-254's tape.  x: contiguous float32 CUDA tensor [B,H,W,Cin], or [B,H,W] for Cin = 1; w: [ksize,ksize,Cin,
+    Cout], a Keras Conv2D.kernel as stored; bias: [Cout] or None; act: "linear" or "leaky" (y > 0 ? y : y * alpha, alpha >= 0).
+    Returns y [B,H,W,Cout] by device.conv2d_device (include/dtfill.h, dtfill_conv2d).  Differentiable in x, w and bias, once:
+    the backward calls dtfill_conv2d_backward_data for x and dtfill_conv2d_backward_weights for w and bias, each only where
+    that gradient is needed, in their fixed summation orders, so every gradient bit is a function of the inputs and the shape
+    alone.  A gradient of y that is a channel slice of a wider contiguous tensor (torch.cat's backward: a stem's 16 channels
+    of conv1a's input gradient) is read in place, at dy_offset.  The shapes are dtfill_conv2d's domain (DtfillError otherwise).
+    No host synchronisation in either direction; the workspace is the stream's cached one."""
+    return _conv("narrow", x, w, bias, None, 1, act, alpha)
 
 
 def conv2d_strided(x, w, bias=None, stride=1, residual=None, act="linear", alpha=0.2):
@@ -334,37 +318,7 @@ def conv2d_strided(x, w, bias=None, stride=1, residual=None, act="linear", alpha
     fixed summation orders.  A gradient of y that is a channel slice of a wider contiguous tensor (torch.cat's backward) is
     read in place.  The reference's kernel_regularizer takes no part: train.py:253 differentiates total_loss alone.  At
     stride 2 H and W must be even.  No host synchronisation in either direction."""
-    if not alpha >= 0:
-        raise ValueError("alpha must be >= 0 (the derivative is taken by the sign of the output), got %r" % (alpha,))
-    return _Conv2dStrided.apply(x, w, bias, residual, int(stride), act, float(alpha))
-
-
-class _Conv2dTranspose(torch.autograd.Function):
-    """y of device.conv2d_transpose_device under the packed kernel [3,3,Cin,Cout]."""
-
-    @staticmethod
-    def forward(ctx, x, w_packed, bias, act, alpha):
-        y = device.conv2d_transpose_device(x, w_packed, bias, act, alpha)
-        ctx.set_materialize_grads(False)
-        ctx.act, ctx.alpha = act, alpha
-        ctx.save_for_backward(x, w_packed, None if act == "linear" else y)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_y):
-        want_x, want_w, want_b = ctx.needs_input_grad[:3]
-        if g_y is None or not (want_x or want_w or want_b):
-            return None, None, None, None, None
-        x, w, y = ctx.saved_tensors
-        dy, at = _channel_slice(g_y)
-        dx = dw = db = None
-        if want_x:
-            dx = device.conv2d_transpose_backward_data_device(dy, w, y, ctx.act, ctx.alpha, dy_offset=at)
-        if want_w or want_b:
-            dw, db = device.conv2d_transpose_backward_weights_device(x, dy, y, ctx.act, ctx.alpha, dy_offset=at, cout=w.shape[3],
-                                                                     want_bias=want_b)
-        return dx, (dw if want_w else None), db, None, None
+    return _conv("strided", x, w, bias, residual, int(stride), act, alpha)
 
 
 def conv2d_transpose(x, kernel, bias=None, act="linear", alpha=0.2):
@@ -374,6 +328,4 @@ def conv2d_transpose(x, kernel, bias=None, act="linear", alpha=0.2):
     pack to the ABI's [3,3,Cin,Cout] is a permute inside the graph, so the kernel's gradient arrives in Keras' layout through
     autograd's own permute.  Differentiable in x, kernel and bias, once, by dtfill_conv2d_transpose_backward_data and _weights
     in their fixed summation orders.  No weight-decay term, as in conv2d_strided.  No host synchronisation."""
-    if not alpha >= 0:
-        raise ValueError("alpha must be >= 0 (the derivative is taken by the sign of the output), got %r" % (alpha,))
-    return _Conv2dTranspose.apply(x, kernel.permute(0, 1, 3, 2).contiguous(), bias, act, float(alpha))
+    return _conv("transposed", x, kernel.permute(0, 1, 3, 2).contiguous(), bias, None, 2, act, alpha)

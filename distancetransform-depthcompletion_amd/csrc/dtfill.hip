@@ -1245,197 +1245,153 @@ int dtfill_conv2d(const float *x, int B, int H, int W, int Cin, const float *w, 
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 
-// the domain of the backward calls: dtfill_conv2d's, with B H W Cin < 2^31
-static bool convb_domain(int B, int H, int W, int Cin, int ksize, int Cout) {
-    if (ksize != 1 && ksize != 3 && ksize != 5 && ksize != 7) return false;
-    if (Cin != 1 && (Cin < CV_G || Cin > 4 * CV_G || Cin % CV_G)) return false;
-    if (Cout != 1 && Cout != 16) return false;
-    return B >= 1 && H >= 1 && W >= 1 && (long long)B * H * W * Cin < (1ll << 31);
-}
-
 // a slice of `channels` channels at `offset` of a [B,H,W,width] tensor
 static bool convb_slice(int B, int H, int W, int channels, int width, int offset) {
     return offset >= 0 && width >= 1 && (long long)offset + channels <= width && (long long)B * H * W * width < (1ll << 31);
 }
 
-static size_t convb_align(size_t n) { return (n + 255) & ~(size_t)255; }
+// The domain of the six backward calls and everything they and the two size functions derive from a layer; false outside
+// the domain.  The narrow rule is dtfill_conv2d's with B H W Cin < 2^31.  The wide rule: whole groups in, whole N-tiles out,
+// the frame of dy [Ho,Wo] of a strided layer (stride 2: of an even frame) or [2H,2W] of the transposed one, and x, dy and a
+// segment's partials each below 2^31 floats.
+static bool convb_plan(const ConvBwLayer &l, ConvBwPlan *p) {
+    const int B = l.B, H = l.H, W = l.W, Cin = l.Cin, ksize = l.ksize, Cout = l.Cout;
+    const bool k1357 = ksize == 1 || ksize == 3 || ksize == 5 || ksize == 7;
+    if (B < 1 || H < 1 || W < 1) return false;
+    long long ho = H, wo = W;
+    if (l.narrow) {
+        if (!k1357 || l.stride != 1 || l.transposed) return false;
+        if (Cin != 1 && (Cin < CV_G || Cin > 4 * CV_G || Cin % CV_G)) return false;
+        if (Cout != 1 && Cout != 16) return false;
+        if ((long long)B * H * W * Cin >= (1ll << 31)) return false;
+    } else {
+        if (!conv_wide_channels(Cin, Cout)) return false;
+        if (l.transposed) {
+            if (ksize != 3 || l.stride != 2) return false;
+            ho = 2ll * H, wo = 2ll * W;
+        } else if (l.stride == 2) {
+            if ((ksize != 1 && ksize != 3) || H % 2 || W % 2) return false;
+            ho = H / 2, wo = W / 2;
+        } else if (l.stride != 1 || !k1357) {
+            return false;
+        }
+        if ((long long)B * H * W * Cin >= (1ll << 31) || B * ho * wo * Cout >= (1ll << 31)) return false;
+        if (((long long)ksize * ksize * Cin + 1) * Cout >= (1ll << 31)) return false;
+    }
+    p->Ho = (int)ho, p->Wo = (int)wo;
+    // the weight sum: the segments lie over the output frame, over the input frame of the transposed layer
+    p->Hs = l.transposed ? H : p->Ho, p->Ws = l.transposed ? W : p->Wo;
+    p->HL = l.transposed ? p->Ho : H, p->WL = l.transposed ? p->Wo : W;
+    p->segs_y = (p->Hs + CB_R - 1) / CB_R, p->segs_x = (p->Ws + CB_C - 1) / CB_C;
+    const size_t taps = (size_t)ksize * ksize, pixels = (size_t)B * p->Ho * p->Wo;
+    p->wt = align256(pixels * Cout * sizeof(float));
+    p->tmp = p->wt + align256(taps * Cin * Cout * sizeof(float));
+    const bool spread = !l.transposed && l.stride == 2 && ksize == 1;  // the chain's values before k_convb_spread
+    const size_t data = p->tmp + (spread ? align256(pixels * Cin * sizeof(float)) : 0);
+    const size_t weights = align256((size_t)B * p->segs_y * p->segs_x * (taps * Cin + 1) * Cout * sizeof(float));
+    p->bytes = data > weights ? data : weights;
+    return true;
+}
 
-// the bytes of g (the data gradient's first part of the workspace; wT follows) and of the segments' partials
-static size_t convb_g_bytes(int B, int H, int W, int Cout) { return convb_align((size_t)B * H * W * Cout * sizeof(float)); }
-static size_t convb_segments(int B, int H, int W) {
-    return (size_t)B * ((H + DTFILL_CONV_BW_ROWS - 1) / DTFILL_CONV_BW_ROWS) * ((W + DTFILL_CONV_BW_COLS - 1) / DTFILL_CONV_BW_COLS);
+static size_t convb_workspace_bytes(const ConvBwLayer &l) {
+    ConvBwPlan p;
+    return convb_plan(l, &p) ? p.bytes : 0;
 }
 
 size_t dtfill_conv2d_backward_workspace_bytes(int B, int H, int W, int Cin, int ksize, int Cout) {
-    if (!convb_domain(B, H, W, Cin, ksize, Cout)) return 0;
-    const size_t taps = (size_t)ksize * ksize;
-    const size_t data = convb_g_bytes(B, H, W, Cout) + convb_align(taps * Cin * Cout * sizeof(float));
-    const size_t weights = convb_align(convb_segments(B, H, W) * (taps * Cin + 1) * Cout * sizeof(float));
-    return data > weights ? data : weights;
+    return convb_workspace_bytes(ConvBwLayer{B, H, W, Cin, ksize, Cout, 1, false, true});
 }
 
-// what the two backward calls check alike, and the kernels' view of dy and y
-static int convb_check(const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels, int y_offset, int B, int H,
-                       int W, int Cin, int ksize, int Cout, int act, float alpha, const void *workspace, size_t ws_bytes,
-                       ConvBwArgs *a) {
+size_t dtfill_conv2d_wide_backward_workspace_bytes(int B, int H, int W, int Cin, int ksize, int Cout, int stride, int transposed) {
+    return convb_workspace_bytes(ConvBwLayer{B, H, W, Cin, ksize, Cout, stride, transposed != 0, false});
+}
+
+// what the six backward calls check alike, in the header's order; the layer's plan and the kernels' view of dy and y over the
+// plan's small frame
+static int convb_check(const ConvBwLayer &l, const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels,
+                       int y_offset, int act, float alpha, const void *workspace, size_t ws_bytes, ConvBwPlan *p, ConvBwArgs *a) {
     if (!dy || !workspace || (act == DTFILL_CONV_LEAKY && !y)) return DTFILL_ERR_NULL;
     if ((act != DTFILL_CONV_LINEAR && act != DTFILL_CONV_LEAKY) || !isfinite(alpha) || alpha < 0.0f) return DTFILL_ERR_SHAPE;
     if (act == DTFILL_CONV_LINEAR) y = nullptr;  // not read
-    if (!convb_domain(B, H, W, Cin, ksize, Cout) || !convb_slice(B, H, W, Cout, dy_channels, dy_offset)) return DTFILL_ERR_SHAPE;
-    if (y && !convb_slice(B, H, W, Cout, y_channels, y_offset)) return DTFILL_ERR_SHAPE;
-    if (ws_bytes < dtfill_conv2d_backward_workspace_bytes(B, H, W, Cin, ksize, Cout) || ((uintptr_t)workspace & 255))
-        return DTFILL_ERR_WORKSPACE;
+    if (!convb_plan(l, p) || !convb_slice(l.B, p->Ho, p->Wo, l.Cout, dy_channels, dy_offset)) return DTFILL_ERR_SHAPE;
+    if (y && !convb_slice(l.B, p->Ho, p->Wo, l.Cout, y_channels, y_offset)) return DTFILL_ERR_SHAPE;
+    if (ws_bytes < p->bytes || ((uintptr_t)workspace & 255)) return DTFILL_ERR_WORKSPACE;
     const float *dys = dy + dy_offset, *ys = y ? y + y_offset : nullptr;
     const bool gvec = (((uintptr_t)dys | (uintptr_t)ys) & 15) == 0 && dy_channels % 4 == 0 && (!y || y_channels % 4 == 0);
-    *a = ConvBwArgs{nullptr, dys, ys, dy_channels, y ? y_channels : 0, B, H, W, Cin, Cout, act, alpha,
-                    (H + CB_R - 1) / CB_R, (W + CB_C - 1) / CB_C, false, gvec};
+    *a = ConvBwArgs{nullptr, dys, ys, dy_channels, y ? y_channels : 0, l.B, p->Hs, p->Ws, l.Cin, l.Cout, act, alpha,
+                    p->segs_y, p->segs_x, false, gvec};
     return DTFILL_OK;
+}
+
+static int convb_data(const ConvBwLayer &l, const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels,
+                      int y_offset, const float *w, int act, float alpha, float *dx, int dx_channels, int dx_offset, float *dresidual,
+                      void *workspace, size_t ws_bytes, void *stream) {
+    if (!w || !dx) return DTFILL_ERR_NULL;
+    ConvBwPlan p;
+    ConvBwArgs a;
+    const int rc = convb_check(l, dy, dy_channels, dy_offset, y, y_channels, y_offset, act, alpha, workspace, ws_bytes, &p, &a);
+    if (rc != DTFILL_OK) return rc;
+    if (!convb_slice(l.B, l.H, l.W, l.Cin, dx_channels, dx_offset)) return DTFILL_ERR_SHAPE;
+    convb_data_launch(static_cast<hipStream_t>(stream), l, p, a, w, dx, dx_channels, dx_offset, dresidual, workspace);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+static int convb_weights(const ConvBwLayer &l, const float *x, const float *dy, int dy_channels, int dy_offset, const float *y,
+                         int y_channels, int y_offset, int act, float alpha, float *dw, float *db, void *workspace, size_t ws_bytes,
+                         void *stream) {
+    if (!x || !dw) return DTFILL_ERR_NULL;
+    ConvBwPlan p;
+    ConvBwWide a;
+    const int rc = convb_check(l, dy, dy_channels, dy_offset, y, y_channels, y_offset, act, alpha, workspace, ws_bytes, &p, &a.b);
+    if (rc != DTFILL_OK) return rc;
+    a.b.x = x;
+    a.b.xvec = ((uintptr_t)x & 15) == 0;  // (Cin is a multiple of 16 wherever 16-byte loads of x are used)
+    a.HL = p.HL, a.WL = p.WL;
+    convb_weights_launch(static_cast<hipStream_t>(stream), l, a, dw, db, workspace);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 
 int dtfill_conv2d_backward_data(const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels, int y_offset,
                                 const float *w, int B, int H, int W, int Cin, int ksize, int Cout, int act, float alpha, float *dx,
                                 int dx_channels, int dx_offset, void *workspace, size_t ws_bytes, void *stream) {
-    if (!w || !dx) return DTFILL_ERR_NULL;
-    ConvBwArgs a;
-    const int rc = convb_check(dy, dy_channels, dy_offset, y, y_channels, y_offset, B, H, W, Cin, ksize, Cout, act, alpha, workspace,
-                               ws_bytes, &a);
-    if (rc != DTFILL_OK) return rc;
-    if (!convb_slice(B, H, W, Cin, dx_channels, dx_offset)) return DTFILL_ERR_SHAPE;
-    float *g = static_cast<float *>(workspace);
-    float *wt = reinterpret_cast<float *>(static_cast<char *>(workspace) + convb_g_bytes(B, H, W, Cout));
-    convb_data_launch(static_cast<hipStream_t>(stream), a, w, ksize, dx, dx_channels, dx_offset, g, wt);
-    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+    return convb_data(ConvBwLayer{B, H, W, Cin, ksize, Cout, 1, false, true}, dy, dy_channels, dy_offset, y, y_channels, y_offset, w,
+                      act, alpha, dx, dx_channels, dx_offset, nullptr, workspace, ws_bytes, stream);
 }
 
 int dtfill_conv2d_backward_weights(const float *x, const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels,
                                    int y_offset, int B, int H, int W, int Cin, int ksize, int Cout, int act, float alpha, float *dw,
                                    float *db, void *workspace, size_t ws_bytes, void *stream) {
-    if (!x || !dw) return DTFILL_ERR_NULL;
-    ConvBwArgs a;
-    const int rc = convb_check(dy, dy_channels, dy_offset, y, y_channels, y_offset, B, H, W, Cin, ksize, Cout, act, alpha, workspace,
-                               ws_bytes, &a);
-    if (rc != DTFILL_OK) return rc;
-    a.x = x;
-    a.xvec = ((uintptr_t)x & 15) == 0;  // (Cin is a multiple of 16 wherever 16-byte loads of x are used)
-    convb_weights_launch(static_cast<hipStream_t>(stream), a, ksize, dw, db, static_cast<float *>(workspace));
-    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
-}
-
-// the domain of the wide backward calls and the frame of dy: [Ho,Wo] of a strided layer, [2H,2W] of the transposed one
-static bool convbw_domain(int B, int H, int W, int Cin, int ksize, int Cout, int stride, int transposed, int *Ho, int *Wo) {
-    if (B < 1 || H < 1 || W < 1 || !conv_wide_channels(Cin, Cout)) return false;
-    long long ho = H, wo = W;
-    if (transposed) {
-        if (ksize != 3 || stride != 2) return false;
-        ho = 2ll * H, wo = 2ll * W;
-    } else if (stride == 2) {
-        if ((ksize != 1 && ksize != 3) || H % 2 || W % 2) return false;
-        ho = H / 2, wo = W / 2;
-    } else if (stride != 1 || (ksize != 1 && ksize != 3 && ksize != 5 && ksize != 7)) {
-        return false;
-    }
-    if ((long long)B * H * W * Cin >= (1ll << 31) || B * ho * wo * Cout >= (1ll << 31)) return false;
-    if (((long long)ksize * ksize * Cin + 1) * Cout >= (1ll << 31)) return false;
-    *Ho = (int)ho, *Wo = (int)wo;
-    return true;
-}
-
-size_t dtfill_conv2d_wide_backward_workspace_bytes(int B, int H, int W, int Cin, int ksize, int Cout, int stride, int transposed) {
-    int Ho, Wo;
-    if (!convbw_domain(B, H, W, Cin, ksize, Cout, stride, transposed, &Ho, &Wo)) return 0;
-    const size_t taps = (size_t)ksize * ksize;
-    size_t data = convb_g_bytes(B, Ho, Wo, Cout) + convb_align(taps * Cin * Cout * sizeof(float));
-    if (!transposed && stride == 2 && ksize == 1) data += convb_g_bytes(B, Ho, Wo, Cin);  // the chain's values before the spread
-    const size_t nseg = transposed ? convb_segments(B, H, W) : convb_segments(B, Ho, Wo);
-    const size_t weights = convb_align(nseg * (taps * Cin + 1) * Cout * sizeof(float));
-    return data > weights ? data : weights;
-}
-
-// what the four wide backward calls check alike, in convb_check's order, and the kernels' view of dy and y
-static int convbw_check(const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels, int y_offset, int B, int H,
-                        int W, int Cin, int ksize, int Cout, int stride, int transposed, int act, float alpha, const void *workspace,
-                        size_t ws_bytes, ConvBwArgs *a, int *Ho, int *Wo) {
-    if (!dy || !workspace || (act == DTFILL_CONV_LEAKY && !y)) return DTFILL_ERR_NULL;
-    if ((act != DTFILL_CONV_LINEAR && act != DTFILL_CONV_LEAKY) || !isfinite(alpha) || alpha < 0.0f) return DTFILL_ERR_SHAPE;
-    if (act == DTFILL_CONV_LINEAR) y = nullptr;  // not read
-    if (!convbw_domain(B, H, W, Cin, ksize, Cout, stride, transposed, Ho, Wo)) return DTFILL_ERR_SHAPE;
-    if (!convb_slice(B, *Ho, *Wo, Cout, dy_channels, dy_offset)) return DTFILL_ERR_SHAPE;
-    if (y && !convb_slice(B, *Ho, *Wo, Cout, y_channels, y_offset)) return DTFILL_ERR_SHAPE;
-    if (ws_bytes < dtfill_conv2d_wide_backward_workspace_bytes(B, H, W, Cin, ksize, Cout, stride, transposed) ||
-        ((uintptr_t)workspace & 255))
-        return DTFILL_ERR_WORKSPACE;
-    const float *dys = dy + dy_offset, *ys = y ? y + y_offset : nullptr;
-    const bool gvec = (((uintptr_t)dys | (uintptr_t)ys) & 15) == 0 && dy_channels % 4 == 0 && (!y || y_channels % 4 == 0);
-    // H, W: the frame the segments of the weight gradient lie over
-    const int Hs = transposed ? H : *Ho, Ws = transposed ? W : *Wo;
-    *a = ConvBwArgs{nullptr, dys, ys, dy_channels, y ? y_channels : 0, B, Hs, Ws, Cin, Cout, act, alpha,
-                    (Hs + CB_R - 1) / CB_R, (Ws + CB_C - 1) / CB_C, false, gvec};
-    return DTFILL_OK;
-}
-
-static int convbw_data(const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels, int y_offset, const float *w,
-                       int B, int H, int W, int Cin, int ksize, int Cout, int stride, int transposed, int act, float alpha, float *dx,
-                       int dx_channels, int dx_offset, float *dresidual, void *workspace, size_t ws_bytes, void *stream) {
-    if (!w || !dx) return DTFILL_ERR_NULL;
-    ConvBwArgs a;
-    int Ho, Wo;
-    const int rc = convbw_check(dy, dy_channels, dy_offset, y, y_channels, y_offset, B, H, W, Cin, ksize, Cout, stride, transposed, act,
-                                alpha, workspace, ws_bytes, &a, &Ho, &Wo);
-    if (rc != DTFILL_OK) return rc;
-    if (!convb_slice(B, H, W, Cin, dx_channels, dx_offset)) return DTFILL_ERR_SHAPE;
-    char *ws = static_cast<char *>(workspace);
-    float *g = reinterpret_cast<float *>(ws);
-    float *wt = reinterpret_cast<float *>(ws + convb_g_bytes(B, Ho, Wo, Cout));
-    float *tmp = reinterpret_cast<float *>(ws + convb_g_bytes(B, Ho, Wo, Cout) + convb_align((size_t)ksize * ksize * Cin * Cout * sizeof(float)));
-    convb_wide_data_launch(static_cast<hipStream_t>(stream), a, w, ksize, stride, transposed != 0, Ho, Wo, H, W, dx, dx_channels,
-                           dx_offset, dresidual, g, wt, tmp);
-    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
-}
-
-static int convbw_weights(const float *x, const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels, int y_offset,
-                          int B, int H, int W, int Cin, int ksize, int Cout, int stride, int transposed, int act, float alpha, float *dw,
-                          float *db, void *workspace, size_t ws_bytes, void *stream) {
-    if (!x || !dw) return DTFILL_ERR_NULL;
-    ConvBwWide a;
-    int Ho, Wo;
-    const int rc = convbw_check(dy, dy_channels, dy_offset, y, y_channels, y_offset, B, H, W, Cin, ksize, Cout, stride, transposed, act,
-                                alpha, workspace, ws_bytes, &a.b, &Ho, &Wo);
-    if (rc != DTFILL_OK) return rc;
-    a.b.x = x;
-    a.b.xvec = ((uintptr_t)x & 15) == 0;  // (Cin is a multiple of 16)
-    a.HL = transposed ? Ho : H;
-    a.WL = transposed ? Wo : W;
-    convb_wide_weights_launch(static_cast<hipStream_t>(stream), a, ksize, stride, transposed != 0, dw, db, static_cast<float *>(workspace));
-    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+    return convb_weights(ConvBwLayer{B, H, W, Cin, ksize, Cout, 1, false, true}, x, dy, dy_channels, dy_offset, y, y_channels,
+                         y_offset, act, alpha, dw, db, workspace, ws_bytes, stream);
 }
 
 int dtfill_conv2d_strided_backward_data(const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels, int y_offset,
                                         const float *w, int B, int H, int W, int Cin, int ksize, int Cout, int stride, int act,
                                         float alpha, float *dx, int dx_channels, int dx_offset, float *dresidual, void *workspace,
                                         size_t ws_bytes, void *stream) {
-    return convbw_data(dy, dy_channels, dy_offset, y, y_channels, y_offset, w, B, H, W, Cin, ksize, Cout, stride, 0, act, alpha, dx,
-                       dx_channels, dx_offset, dresidual, workspace, ws_bytes, stream);
+    return convb_data(ConvBwLayer{B, H, W, Cin, ksize, Cout, stride, false, false}, dy, dy_channels, dy_offset, y, y_channels,
+                      y_offset, w, act, alpha, dx, dx_channels, dx_offset, dresidual, workspace, ws_bytes, stream);
 }
 
 int dtfill_conv2d_strided_backward_weights(const float *x, const float *dy, int dy_channels, int dy_offset, const float *y,
                                            int y_channels, int y_offset, int B, int H, int W, int Cin, int ksize, int Cout, int stride,
                                            int act, float alpha, float *dw, float *db, void *workspace, size_t ws_bytes, void *stream) {
-    return convbw_weights(x, dy, dy_channels, dy_offset, y, y_channels, y_offset, B, H, W, Cin, ksize, Cout, stride, 0, act, alpha, dw, db,
-                          workspace, ws_bytes, stream);
+    return convb_weights(ConvBwLayer{B, H, W, Cin, ksize, Cout, stride, false, false}, x, dy, dy_channels, dy_offset, y, y_channels,
+                         y_offset, act, alpha, dw, db, workspace, ws_bytes, stream);
 }
 
 int dtfill_conv2d_transpose_backward_data(const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels, int y_offset,
                                           const float *w, int B, int H, int W, int Cin, int Cout, int act, float alpha, float *dx,
                                           int dx_channels, int dx_offset, void *workspace, size_t ws_bytes, void *stream) {
-    return convbw_data(dy, dy_channels, dy_offset, y, y_channels, y_offset, w, B, H, W, Cin, 3, Cout, 2, 1, act, alpha, dx, dx_channels,
-                       dx_offset, nullptr, workspace, ws_bytes, stream);
+    return convb_data(ConvBwLayer{B, H, W, Cin, 3, Cout, 2, true, false}, dy, dy_channels, dy_offset, y, y_channels, y_offset, w, act,
+                      alpha, dx, dx_channels, dx_offset, nullptr, workspace, ws_bytes, stream);
 }
 
 int dtfill_conv2d_transpose_backward_weights(const float *x, const float *dy, int dy_channels, int dy_offset, const float *y,
                                              int y_channels, int y_offset, int B, int H, int W, int Cin, int Cout, int act, float alpha,
                                              float *dw, float *db, void *workspace, size_t ws_bytes, void *stream) {
-    return convbw_weights(x, dy, dy_channels, dy_offset, y, y_channels, y_offset, B, H, W, Cin, 3, Cout, 2, 1, act, alpha, dw, db,
-                          workspace, ws_bytes, stream);
+    return convb_weights(ConvBwLayer{B, H, W, Cin, 3, Cout, 2, true, false}, x, dy, dy_channels, dy_offset, y, y_channels, y_offset,
+                         act, alpha, dw, db, workspace, ws_bytes, stream);
 }
 
 }  // extern "C"

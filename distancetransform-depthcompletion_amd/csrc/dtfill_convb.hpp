@@ -1,8 +1,11 @@
 // dtfill_convb.hpp -- the backward pass of dtfill_conv2d in a fixed summation order: dx, dw and db of the layers of
 // SparsityCNN (solution_DeepNet/net.py:11-242), what train.py:232-254's tape needs of a convolution.  include/dtfill.h,
 // dtfill_conv2d_backward_data() and dtfill_conv2d_backward_weights(), has the contracts.  Part of libdtfill.so; included by
-// dtfill.hip inside its anonymous namespace, after dtfill_conv.hpp, whose kernels the input gradient runs on.  The backward of
-// the wide layers of ResNet18_NO_BN_l2 (dtfill_conv2d_strided, dtfill_conv2d_transpose) is the second half of this file.
+// dtfill.hip inside its anonymous namespace, after dtfill_conv.hpp, whose kernels the input gradient runs on.  The kernels of
+// the wide layers of ResNet18_NO_BN_l2 (dtfill_conv2d_strided, dtfill_conv2d_transpose) are the second part of this file; the
+// host side, the last, is one path for all six entry points: dtfill.hip's convb_plan checks a ConvBwLayer's domain and derives
+// its frames, segment counts and workspace layout (ConvBwPlan), and convb_data_launch and convb_weights_launch each hold one
+// dispatch, in which the narrow layers' kernels are branches beside the wide ones'.
 #pragma once
 
 // ------------------------------------------------------------------------------------------------
@@ -83,29 +86,6 @@ __global__ __launch_bounds__(256) void k_convb_flip(const float *__restrict__ w,
     const int o = idx % Cout, c = idx / Cout % Cin, tap = idx / Cout / Cin;
     const int ft = flip ? taps - 1 - tap : tap;  // (ksize - 1 - i) ksize + (ksize - 1 - j)
     wt[blocked ? ((c / 16) * taps + ft) * 16 + c % 16 : (ft * Cout + o) * Cin + c] = w[idx];
-}
-
-// dtfill_conv2d_backward_data: the workspace is g, then wT
-inline void convb_data_launch(hipStream_t st, const ConvBwArgs &b, const float *w, int ksize, float *dx, int dx_channels, int dx_offset,
-                              float *g, float *wt) {
-    const long long total = (long long)b.B * b.H * b.W * b.Cout;
-    const int taps = ksize * ksize, r = (ksize - 1) / 2;
-    const bool blocked = b.Cout == 1 && b.Cin > 16;
-    k_convb_g<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(b, g, nullptr, total);
-    k_convb_flip<<<(taps * b.Cin * b.Cout + 255) / 256, 256, 0, st>>>(w, wt, taps, b.Cin, b.Cout, blocked, true);
-    ConvArgs a{g, wt, nullptr, nullptr, dx, b.B, b.H, b.W, b.Cout, b.Cin, b.H, b.W, r, r, dx_channels, dx_offset, DTFILL_CONV_LINEAR, 0.0f};
-    if (blocked) {
-        a.Cout = 16;
-        for (int n = 0; n < b.Cin / 16; ++n) {
-            a.w = wt + (size_t)n * taps * 16;
-            a.out_offset = dx_offset + 16 * n;
-            conv_launch(st, a, ksize);
-        }
-    } else if (b.Cin > 16) {
-        conv_strided_launch(st, a, ksize, 1);
-    } else {
-        conv_launch(st, a, ksize);
-    }
 }
 
 // g of the channels c .. c + 3 of a pixel of dy's and y's frames; vec: by 16-byte loads
@@ -302,23 +282,6 @@ void convb_dw_launch(hipStream_t st, const ConvBwArgs &a, float *part, long long
         k_convb_dw<KS, true><<<grid, 256, 0, st>>>(a, part, n_items);
     else
         k_convb_dw<KS, false><<<grid, 256, 0, st>>>(a, part, n_items);
-}
-
-// dtfill_conv2d_backward_weights: the workspace is the partials
-inline void convb_weights_launch(hipStream_t st, const ConvBwArgs &a, int ksize, float *dw, float *db, float *part) {
-    const int nseg = a.B * a.segs_y * a.segs_x;  // (< 2^31: B H W is)
-    const int ndw = ksize * ksize * a.Cin * a.Cout, pstride = ndw + a.Cout;
-    if (a.Cout == 1) {
-        k_convb_dw_lane<<<dim3((unsigned)nseg, (unsigned)((pstride + 255) / 256)), 256, 0, st>>>(a, ksize, part);
-    } else {
-        switch (ksize) {
-            case 1: convb_dw_launch<1>(st, a, part, nseg); break;
-            case 3: convb_dw_launch<3>(st, a, part, nseg); break;
-            case 5: convb_dw_launch<5>(st, a, part, nseg); break;
-            default: convb_dw_launch<7>(st, a, part, nseg); break;
-        }
-    }
-    k_convb_sum<<<(pstride + 255) / 256, 256, 0, st>>>(part, pstride, nseg, ndw, dw, db);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -526,20 +489,77 @@ void convb_dw_wide_launch(hipStream_t st, const ConvBwWide &a, float *part, long
         }
 }
 
-// dtfill_conv2d_strided_backward_weights and dtfill_conv2d_transpose_backward_weights: the workspace is the partials
-inline void convb_wide_weights_launch(hipStream_t st, const ConvBwWide &a, int ksize, int stride, bool transposed, float *dw, float *db,
-                                      float *part) {
-    const int nseg = a.b.B * a.b.segs_y * a.b.segs_x;
-    const int ndw = ksize * ksize * a.b.Cin * a.b.Cout, pstride = ndw + a.b.Cout;  // (< 2^31: the entry points' domain)
-    if (transposed) {
-        convb_dw_wide_launch<3, 2, true>(st, a, part, nseg);
-    } else if (stride == 2) {
-        if (ksize == 1)
-            convb_dw_wide_launch<1, 2, false>(st, a, part, nseg);
-        else
-            convb_dw_wide_launch<3, 2, false>(st, a, part, nseg);
+// ---- the host side: one layer record, one plan (dtfill.hip's convb_plan), one dispatch per gradient for all six entry points ----
+struct ConvBwLayer {  // a layer as its backward sees it: the forward's input [B,H,W,Cin] and what made its output
+    int B, H, W, Cin, ksize, Cout, stride;
+    bool transposed, narrow;  // narrow: dtfill_conv2d's domain (Cin 1/16/32/48/64, Cout 1/16, stride 1) and kernels; else the wide ones
+};
+
+struct ConvBwPlan {         // what convb_plan derives from a layer in its domain
+    int Ho, Wo;             // dy's frame
+    int Hs, Ws, HL, WL;     // the weight sum's SMALL frame, the one the segments lie over, and its LARGE one
+    int segs_y, segs_x;     // segments of a small frame
+    size_t wt, tmp, bytes;  // the bytes from g, at 0, to the repacked weights and to the 1x1 stride-2 chain's values; max(data, weights)
+};
+
+// dx.  b: dy's and y's view; the forward over g has the layer's Cout as its input channels and its Cin as its output channels
+inline void convb_data_launch(hipStream_t st, const ConvBwLayer &l, const ConvBwPlan &p, const ConvBwArgs &b, const float *w, float *dx,
+                              int dx_channels, int dx_offset, float *dres, void *workspace) {
+    char *ws = static_cast<char *>(workspace);
+    float *g = reinterpret_cast<float *>(ws), *wt = reinterpret_cast<float *>(ws + p.wt), *tmp = reinterpret_cast<float *>(ws + p.tmp);
+    const long long total = (long long)l.B * p.Ho * p.Wo * l.Cout;
+    const int taps = l.ksize * l.ksize, r = (l.ksize - 1) / 2;
+    const bool blocked = l.Cout == 1 && l.Cin > 16;
+    k_convb_g<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(b, g, dres, total);
+    k_convb_flip<<<(taps * l.Cin * l.Cout + 255) / 256, 256, 0, st>>>(w, wt, taps, l.Cin, l.Cout, blocked, !l.transposed && l.stride == 1);
+    ConvArgs a{g, wt, nullptr, nullptr, dx, l.B, p.Ho, p.Wo, l.Cout, l.Cin, l.H, l.W, 0, 0, dx_channels, dx_offset, DTFILL_CONV_LINEAR,
+               0.0f};
+    if (l.transposed) {
+        conv_strided_launch(st, a, 3, 2);  // [2H,2W] -> [H,W], pt = pl = 0
+    } else if (l.stride == 2 && l.ksize == 3) {
+        conv_transpose_launch(st, a);  // [H/2,W/2] -> [H,W]
+    } else if (l.stride == 2) {
+        a.out = tmp, a.Ho = p.Ho, a.Wo = p.Wo, a.out_channels = l.Cin, a.out_offset = 0;
+        conv_strided_launch(st, a, 1, 1);
+        const long long n = (long long)l.B * l.H * l.W * l.Cin;
+        k_convb_spread<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(tmp, dx, l.H, l.W, l.Cin, dx_channels, dx_offset, n);
     } else {
-        switch (ksize) {
+        a.pt = a.pl = r;
+        if (blocked) {
+            a.Cout = 16;
+            for (int n = 0; n < l.Cin / 16; ++n) {
+                a.w = wt + (size_t)n * taps * 16;
+                a.out_offset = dx_offset + 16 * n;
+                conv_launch(st, a, l.ksize);
+            }
+        } else if (l.narrow && l.Cin <= 16) {
+            conv_launch(st, a, l.ksize);
+        } else {
+            conv_strided_launch(st, a, l.ksize, 1);
+        }
+    }
+}
+
+// dw and db: level 1 into the segments' partials (the workspace), then level 2
+inline void convb_weights_launch(hipStream_t st, const ConvBwLayer &l, const ConvBwWide &a, float *dw, float *db, void *workspace) {
+    float *part = static_cast<float *>(workspace);
+    const int nseg = l.B * a.b.segs_y * a.b.segs_x;                      // (< 2^31: the small frames' pixels are)
+    const int ndw = l.ksize * l.ksize * l.Cin * l.Cout, pstride = ndw + l.Cout;  // (< 2^31: the entry points' domain)
+    if (l.Cout == 1) {
+        k_convb_dw_lane<<<dim3((unsigned)nseg, (unsigned)((pstride + 255) / 256)), 256, 0, st>>>(a.b, l.ksize, part);
+    } else if (l.narrow) {
+        switch (l.ksize) {
+            case 1: convb_dw_launch<1>(st, a.b, part, nseg); break;
+            case 3: convb_dw_launch<3>(st, a.b, part, nseg); break;
+            case 5: convb_dw_launch<5>(st, a.b, part, nseg); break;
+            default: convb_dw_launch<7>(st, a.b, part, nseg); break;
+        }
+    } else if (l.transposed) {
+        convb_dw_wide_launch<3, 2, true>(st, a, part, nseg);
+    } else if (l.stride == 2) {
+        (l.ksize == 1 ? convb_dw_wide_launch<1, 2, false> : convb_dw_wide_launch<3, 2, false>)(st, a, part, nseg);
+    } else {
+        switch (l.ksize) {
             case 1: convb_dw_wide_launch<1, 1, false>(st, a, part, nseg); break;
             case 3: convb_dw_wide_launch<3, 1, false>(st, a, part, nseg); break;
             case 5: convb_dw_wide_launch<5, 1, false>(st, a, part, nseg); break;
@@ -547,30 +567,4 @@ inline void convb_wide_weights_launch(hipStream_t st, const ConvBwWide &a, int k
         }
     }
     k_convb_sum<<<(pstride + 255) / 256, 256, 0, st>>>(part, pstride, nseg, ndw, dw, db);
-}
-
-// the data gradients of the wide layers.  b: dy's and y's view, b.B frames of Hg x Wg pixels of b.Cout channels; H, W: the
-// frame of dx, b.Cin channels.  The workspace is g, then the repacked weights, then (1x1 at stride 2) the chain's values.
-inline void convb_wide_data_launch(hipStream_t st, const ConvBwArgs &b, const float *w, int ksize, int stride, bool transposed, int Hg,
-                                   int Wg, int H, int W, float *dx, int dx_channels, int dx_offset, float *dres, float *g, float *wt,
-                                   float *tmp) {
-    const long long total = (long long)b.B * Hg * Wg * b.Cout;
-    const int taps = ksize * ksize, r = (ksize - 1) / 2;
-    k_convb_g<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(b, g, dres, total);
-    k_convb_flip<<<(taps * b.Cin * b.Cout + 255) / 256, 256, 0, st>>>(w, wt, taps, b.Cin, b.Cout, false, !transposed && stride == 1);
-    // the forward over g: its input channels are the layer's Cout, its output channels the layer's Cin
-    ConvArgs a{g, wt, nullptr, nullptr, dx, b.B, Hg, Wg, b.Cout, b.Cin, H, W, 0, 0, dx_channels, dx_offset, DTFILL_CONV_LINEAR, 0.0f};
-    if (transposed) {
-        conv_strided_launch(st, a, 3, 2);  // [2H,2W] -> [H,W], pt = pl = 0
-    } else if (stride == 1) {
-        a.pt = a.pl = r;
-        conv_strided_launch(st, a, ksize, 1);
-    } else if (ksize == 3) {
-        conv_transpose_launch(st, a);  // [H/2,W/2] -> [H,W]
-    } else {
-        a.out = tmp, a.Ho = Hg, a.Wo = Wg, a.out_channels = b.Cin, a.out_offset = 0;
-        conv_strided_launch(st, a, 1, 1);
-        const long long n = (long long)b.B * H * W * b.Cin;
-        k_convb_spread<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(tmp, dx, H, W, b.Cin, dx_channels, dx_offset, n);
-    }
 }

@@ -7,7 +7,10 @@ under a tape, a torch.nn.Module over autograd.conv2d, for train.py:232-254's ste
 conv2d_backward_weights_device are the device functions of one layer's backward (dtfill_conv2d_backward_data, _weights).
 ResNet18Trainable is ResNet18 under a tape, over autograd.conv2d_strided and autograd.conv2d_transpose, the network train.py:113
 trains; conv2d_strided_backward_data_device, conv2d_strided_backward_weights_device, conv2d_transpose_backward_data_device and
-conv2d_transpose_backward_weights_device are the device functions of a wide layer's backward.
+conv2d_transpose_backward_weights_device are the device functions of a wide layer's backward.  The six are one path: each is
+a call of _backward_data or _backward_weights, which hold the checks, the frames, the outputs, the workspace and the ABI call
+once, under a kind (narrow, strided, transposed) whose entry in _KINDS supplies the frame arithmetic, the symbol and the
+arguments only that kind takes.
 
 The other ten models of the reference's net.py are not here; what they need beyond these two (widths in multiples of 16, stride
 2, Conv2DTranspose, the residual add) is.  conv2d_device, conv2d_strided_device and conv2d_transpose_device, the device
@@ -15,6 +18,8 @@ functions of one convolution, are reached as device.<name> as well; they live he
 argument checks in tests/test_conv2d.py, tests/test_gpu_conv2d.py, tests/test_conv2d_strided.py and
 tests/test_gpu_conv2d_strided.py.
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -26,11 +31,19 @@ LEAKY_ALPHA = 0.2  # tf.nn.leaky_relu's default
 STEM_WIDTH = 16  # channels every stem writes of the [B,H,W,16 * scale_num] tensor conv1a reads
 
 
-def _check_conv_args(x, w, bias, act, what, plane_ok=False):
-    """The checks the convolutions share; returns (B, H, W, Cin, Cout).  plane_ok: x may be [B,H,W], which is Cin = 1."""
+def _check_act(act, alpha=0.0):
+    """The activation of a convolution, and with alpha that of its backward, which takes the derivative by the sign of the
+    output; then the device, so that nothing below starts without one."""
     if act not in _lib.CONV_ACTS:
         raise ValueError("act must be one of %s, got %r" % (sorted(_lib.CONV_ACTS), act))
+    if not alpha >= 0:
+        raise ValueError("alpha must be >= 0 (the derivative is taken by the sign of the output), got %r" % (alpha,))
     _require_gpu()
+
+
+def _check_conv_args(x, w, bias, act, what, plane_ok=False):
+    """The checks the convolutions share; returns (B, H, W, Cin, Cout).  plane_ok: x may be [B,H,W], which is Cin = 1."""
+    _check_act(act)
     if plane_ok and x.dim() == 3:
         _check_tensor(x, "x")
     else:
@@ -78,7 +91,7 @@ def conv2d_device(x, w, bias=None, act="linear", alpha=0.2, out=None, out_offset
     return out
 
 
-_convb_ws = _device._Scratch()  # the workspace of the two backward calls
+_convb_ws = _device._Scratch()  # the workspace of the backward calls, of every kind of layer
 
 
 def conv2d_backward_workspace_bytes(B, H, W, Cin, ksize, Cout):
@@ -102,14 +115,6 @@ def _check_conv_slice(t, what, like, offset, channels):
     return C
 
 
-def _check_conv_act(act, alpha):
-    if act not in _lib.CONV_ACTS:
-        raise ValueError("act must be one of %s, got %r" % (sorted(_lib.CONV_ACTS), act))
-    if not alpha >= 0:
-        raise ValueError("alpha must be >= 0 (the derivative is taken by the sign of the output), got %r" % (alpha,))
-    _require_gpu()
-
-
 def _check_conv_backward(dy, y, act, dy_offset, y_offset, Cout):
     """dy and y as a layer's backward reads them; returns (dy's width, y or None for a linear layer, y's width)."""
     Cdy = _check_conv_slice(dy, "dy", dy, dy_offset, Cout)
@@ -120,30 +125,97 @@ def _check_conv_backward(dy, y, act, dy_offset, y_offset, Cout):
     return Cdy, y, _check_conv_slice(y, "y", dy, y_offset, Cout)
 
 
+# What tells the three kinds of layer apart in the backward.  data, weights: the ABI's symbols; abi_shape(ksize, Cout, stride):
+# what they take between Cin and act; has_residual: the data call takes dresidual; ws_bytes(L, B, H, W, Cin, ksize, Cout,
+# stride): the library's size function; ksize: the [3,3,..] rule, or None for any square kernel; x_frame(Ho, Wo, stride): the
+# forward's input frame under a dy of [Ho,Wo], and dy_frame(H, W, stride) the reverse, each None where the kind has no such
+# layer (the evenness rule).
+_Kind = collections.namedtuple("_Kind", "data weights abi_shape has_residual ws_bytes w_name w_layout ksize dy_layout plane_ok "
+                                        "x_frame dy_frame")
+_KINDS = {
+    "narrow": _Kind("dtfill_conv2d_backward_data", "dtfill_conv2d_backward_weights", lambda ksize, Cout, s: (ksize, Cout), False,
+                    lambda L, B, H, W, Cin, ksize, Cout, s: L.dtfill_conv2d_backward_workspace_bytes(B, H, W, Cin, ksize, Cout),
+                    "w", "[ksize,ksize,Cin,Cout]", None, "[B,H,W,C]", True, lambda Ho, Wo, s: (Ho, Wo), lambda H, W, s: (H, W)),
+    "strided": _Kind("dtfill_conv2d_strided_backward_data", "dtfill_conv2d_strided_backward_weights",
+                     lambda ksize, Cout, s: (ksize, Cout, s), True,
+                     lambda L, B, H, W, Cin, ksize, Cout, s: L.dtfill_conv2d_wide_backward_workspace_bytes(B, H, W, Cin, ksize, Cout, s, 0),
+                     "w", "[ksize,ksize,Cin,Cout]", None, "[B,Ho,Wo,C]", False, lambda Ho, Wo, s: (s * Ho, s * Wo),
+                     lambda H, W, s: None if H % s or W % s else (H // s, W // s)),
+    "transposed": _Kind("dtfill_conv2d_transpose_backward_data", "dtfill_conv2d_transpose_backward_weights",
+                        lambda ksize, Cout, s: (Cout,), False,
+                        lambda L, B, H, W, Cin, ksize, Cout, s: L.dtfill_conv2d_wide_backward_workspace_bytes(B, H, W, Cin, 3, Cout, 2, 1),
+                        "w_packed", "[3,3,Cin,Cout]", 3, "[B,2H,2W,C]", False,
+                        lambda Ho, Wo, s: None if Ho % 2 or Wo % 2 else (Ho // 2, Wo // 2), lambda H, W, s: (2 * H, 2 * W)),
+}
+
+
+def _check_backward_kind(kind, act, alpha, stride):
+    _check_act(act, alpha)
+    if stride not in (1, 2):
+        raise ValueError("stride must be 1 or 2, got %r" % (stride,))
+    return _KINDS[kind]
+
+
+def _backward_data(kind, dy, w, stride, y, act, alpha, dy_offset, y_offset, dx, dx_offset, want_residual=False):
+    """The data gradient of a layer of `kind`: the six public functions' shared sequence, once."""
+    k = _check_backward_kind(kind, act, alpha, stride)
+    _check_tensor(w, k.w_name, layout=k.w_layout)
+    ksize, Cin, Cout = w.shape[0], w.shape[2], w.shape[3]
+    Cdy, y, Cy = _check_conv_backward(dy, y, act, dy_offset, y_offset, Cout)
+    frame = k.x_frame(dy.shape[1], dy.shape[2], stride) if dy.dim() == 4 or k.plane_ok else None
+    if frame is None or w.shape[1] != ksize or ksize != (k.ksize or ksize) or w.device != dy.device:
+        raise ValueError("dy must be %s and %s %s on %s, got %s and %s"
+                         % (k.dy_layout, k.w_name, k.w_layout, dy.device, tuple(dy.shape), tuple(w.shape)))
+    B, (H, W) = dy.shape[0], frame
+    dx = _check_conv_out(dy, dx, dx_offset, (B, H, W), Cin)
+    if y is not None and dx.data_ptr() == y.data_ptr():
+        raise ValueError("dx may not alias y")
+    dres = torch.empty(tuple(dy.shape[:3]) + (Cout,), dtype=torch.float32, device=dy.device) if want_residual else None
+    L = _lib.load()
+    nbytes = _device._sized(k.ws_bytes(L, B, H, W, Cin, ksize, Cout, stride))
+    with torch.cuda.device(dy.device):
+        with _convb_ws.hold(dy.device, nbytes) as ws:
+            _lib.check(getattr(L, k.data)(
+                dy.data_ptr(), Cdy, int(dy_offset), _ptr(y), Cy, int(y_offset), w.data_ptr(), B, H, W, Cin,
+                *k.abi_shape(ksize, Cout, stride), _lib.CONV_ACTS[act], float(alpha), dx.data_ptr(), dx.shape[3], int(dx_offset),
+                *((_ptr(dres),) if k.has_residual else ()), ws, nbytes, _stream(dy.device)))
+    return (dx, dres) if want_residual else dx
+
+
+def _backward_weights(kind, x, dy, ksize, stride, y, act, alpha, dy_offset, y_offset, cout, want_bias):
+    """The weight and bias gradients of a layer of `kind`: the shared sequence, once."""
+    k = _check_backward_kind(kind, act, alpha, stride)
+    plane = k.plane_ok and x.dim() == 3
+    _check_tensor(x, "x", layout="[B,H,W]" if plane else "[B,H,W,Cin]")
+    B, H, W, Cin = (*x.shape, 1) if plane else x.shape
+    frame = k.dy_frame(H, W, stride)
+    if frame is None:
+        raise ValueError("the backward of a stride-2 layer needs an even frame, got %d x %d" % (H, W))
+    if (dy.dim() != 4 and not k.plane_ok) or dy.shape[:3] != (B, *frame) or x.device != dy.device:
+        raise ValueError("dy must have the frames %s on %s, got %s" % ((B, *frame), x.device, tuple(dy.shape)))
+    Cout = int(cout) if cout is not None else (dy.shape[3] if dy.dim() == 4 else 1)
+    Cdy, y, Cy = _check_conv_backward(dy, y, act, dy_offset, y_offset, Cout)
+    ksize = int(ksize)
+    L = _lib.load()
+    nbytes = _device._sized(k.ws_bytes(L, B, H, W, Cin, ksize, Cout, stride))
+    dw = torch.empty((ksize, ksize, Cin, Cout), dtype=torch.float32, device=x.device)
+    db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_bias else None
+    with torch.cuda.device(x.device):
+        with _convb_ws.hold(x.device, nbytes) as ws:
+            _lib.check(getattr(L, k.weights)(
+                x.data_ptr(), dy.data_ptr(), Cdy, int(dy_offset), _ptr(y), Cy, int(y_offset), B, H, W, Cin,
+                *k.abi_shape(ksize, Cout, stride), _lib.CONV_ACTS[act], float(alpha), dw.data_ptr(), _ptr(db), ws, nbytes,
+                _stream(x.device)))
+    return dw, db
+
+
 def conv2d_backward_data_device(dy, w, y=None, act="linear", alpha=0.2, dy_offset=0, y_offset=0, dx=None, dx_offset=0):
     """The gradient of conv2d_device with respect to x, in the fixed order of include/dtfill.h, dtfill_conv2d_backward_data.
     dy: contiguous float32 CUDA tensor [B,H,W,C] (or [B,H,W], C = 1), the gradient of the layer's output in the channels
     dy_offset .. dy_offset + Cout - 1; w: the layer's [ksize,ksize,Cin,Cout]; y: the forward's output, read at y_offset likewise,
     needed unless act is "linear".  dx: a contiguous float32 tensor [B,H,W,C'] of which the channels dx_offset .. dx_offset +
     Cin - 1 are written; a new [B,H,W,Cin] tensor by default.  Returns dx.  Asynchronous on the current stream."""
-    _check_conv_act(act, alpha)
-    _check_tensor(w, "w", layout="[ksize,ksize,Cin,Cout]")
-    ksize, Cin, Cout = w.shape[0], w.shape[2], w.shape[3]
-    Cdy, y, Cy = _check_conv_backward(dy, y, act, dy_offset, y_offset, Cout)
-    if w.shape[1] != ksize or w.device != dy.device:
-        raise ValueError("w must be [ksize,ksize,Cin,Cout] on %s, got %s" % (dy.device, tuple(w.shape)))
-    B, H, W = dy.shape[:3]
-    dx = _check_conv_out(dy, dx, dx_offset, (B, H, W), Cin)
-    if y is not None and dx.data_ptr() == y.data_ptr():
-        raise ValueError("dx may not alias y")
-    L = _lib.load()
-    nbytes = conv2d_backward_workspace_bytes(B, H, W, Cin, ksize, Cout)
-    with torch.cuda.device(dy.device):
-        with _convb_ws.hold(dy.device, nbytes) as ws:
-            _lib.check(L.dtfill_conv2d_backward_data(dy.data_ptr(), Cdy, int(dy_offset), _ptr(y), Cy, int(y_offset), w.data_ptr(), B, H,
-                                                     W, Cin, ksize, Cout, _lib.CONV_ACTS[act], float(alpha), dx.data_ptr(),
-                                                     dx.shape[3], int(dx_offset), ws, nbytes, _stream(dy.device)))
-    return dx
+    return _backward_data("narrow", dy, w, 1, y, act, alpha, dy_offset, y_offset, dx, dx_offset)
 
 
 def conv2d_backward_weights_device(x, dy, ksize, y=None, act="linear", alpha=0.2, dy_offset=0, y_offset=0, cout=None, want_bias=True):
@@ -151,28 +223,7 @@ def conv2d_backward_weights_device(x, dy, ksize, y=None, act="linear", alpha=0.2
     dtfill_conv2d_backward_weights.  x: the forward's input, [B,H,W,Cin] or [B,H,W]; dy, y, act, alpha and the offsets as in
     conv2d_backward_data_device; cout: the layer's output channels (default: all of dy's).  Returns (dw [ksize,ksize,Cin,Cout],
     db [Cout] or None without want_bias): new tensors.  Asynchronous on the current stream."""
-    _check_conv_act(act, alpha)
-    if x.dim() == 3:
-        _check_tensor(x, "x")
-    else:
-        _check_tensor(x, "x", layout="[B,H,W,Cin]")
-    Cin = x.shape[3] if x.dim() == 4 else 1
-    Cout = int(cout) if cout is not None else (dy.shape[3] if dy.dim() == 4 else 1)
-    Cdy, y, Cy = _check_conv_backward(dy, y, act, dy_offset, y_offset, Cout)
-    if x.shape[:3] != dy.shape[:3] or x.device != dy.device:
-        raise ValueError("x must have dy's frames %s on %s, got %s" % (tuple(dy.shape[:3]), dy.device, tuple(x.shape)))
-    B, H, W = x.shape[:3]
-    ksize = int(ksize)
-    L = _lib.load()
-    nbytes = conv2d_backward_workspace_bytes(B, H, W, Cin, ksize, Cout)
-    dw = torch.empty((ksize, ksize, Cin, Cout), dtype=torch.float32, device=x.device)
-    db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_bias else None
-    with torch.cuda.device(x.device):
-        with _convb_ws.hold(x.device, nbytes) as ws:
-            _lib.check(L.dtfill_conv2d_backward_weights(x.data_ptr(), dy.data_ptr(), Cdy, int(dy_offset), _ptr(y), Cy, int(y_offset), B,
-                                                        H, W, Cin, ksize, Cout, _lib.CONV_ACTS[act], float(alpha), dw.data_ptr(),
-                                                        _ptr(db), ws, nbytes, _stream(x.device)))
-    return dw, db
+    return _backward_weights("narrow", x, dy, ksize, 1, y, act, alpha, dy_offset, y_offset, cout, want_bias)
 
 
 def conv2d_strided_device(x, w, bias=None, stride=1, residual=None, act="linear", alpha=0.2, out=None, out_offset=0):
@@ -224,13 +275,6 @@ def conv2d_wide_backward_workspace_bytes(B, H, W, Cin, ksize, Cout, stride=1, tr
                                                                                  int(Cout), int(stride), int(bool(transposed))))
 
 
-def _check_wide_weights(x, dy, frame):
-    """x [B,H,W,Cin] of a wide layer's weight gradient, beside a dy whose frames must be `frame`."""
-    _check_tensor(x, "x", layout="[B,H,W,Cin]")
-    if dy.dim() != 4 or tuple(dy.shape[:3]) != frame or x.device != dy.device:
-        raise ValueError("dy must have the frames %s on %s, got %s" % (frame, x.device, tuple(dy.shape)))
-
-
 def conv2d_strided_backward_data_device(dy, w, stride=1, y=None, act="linear", alpha=0.2, dy_offset=0, y_offset=0, dx=None,
                                         dx_offset=0, want_residual=False):
     """The gradient of conv2d_strided_device with respect to x, and with want_residual to its residual, in the fixed order of
@@ -240,28 +284,7 @@ def conv2d_strided_backward_data_device(dy, w, stride=1, y=None, act="linear", a
     stride 2 only even frames have a backward.  dx: a contiguous float32 tensor [B,H,W,C'] written at dx_offset .. dx_offset +
     Cin - 1; a new [B,H,W,Cin] tensor by default.  Returns dx, or (dx, dresidual [B,Ho,Wo,Cout]) with want_residual.
     Asynchronous on the current stream."""
-    _check_conv_act(act, alpha)
-    if stride not in (1, 2):
-        raise ValueError("stride must be 1 or 2, got %r" % (stride,))
-    _check_tensor(w, "w", layout="[ksize,ksize,Cin,Cout]")
-    ksize, Cin, Cout = w.shape[0], w.shape[2], w.shape[3]
-    Cdy, y, Cy = _check_conv_backward(dy, y, act, dy_offset, y_offset, Cout)
-    if dy.dim() != 4 or w.shape[1] != ksize or w.device != dy.device:
-        raise ValueError("dy must be [B,Ho,Wo,C] and w [ksize,ksize,Cin,Cout] on %s, got %s and %s" % (dy.device, tuple(dy.shape), tuple(w.shape)))
-    B, Ho, Wo = dy.shape[:3]
-    H, W = stride * Ho, stride * Wo
-    dx = _check_conv_out(dy, dx, dx_offset, (B, H, W), Cin)
-    if y is not None and dx.data_ptr() == y.data_ptr():
-        raise ValueError("dx may not alias y")
-    dres = torch.empty((B, Ho, Wo, Cout), dtype=torch.float32, device=dy.device) if want_residual else None
-    nbytes = conv2d_wide_backward_workspace_bytes(B, H, W, Cin, ksize, Cout, stride)
-    with torch.cuda.device(dy.device):
-        with _convb_ws.hold(dy.device, nbytes) as ws:
-            _lib.check(_lib.load().dtfill_conv2d_strided_backward_data(
-                dy.data_ptr(), Cdy, int(dy_offset), _ptr(y), Cy, int(y_offset), w.data_ptr(), B, H, W, Cin, ksize, Cout, stride,
-                _lib.CONV_ACTS[act], float(alpha), dx.data_ptr(), dx.shape[3], int(dx_offset), _ptr(dres), ws, nbytes,
-                _stream(dy.device)))
-    return (dx, dres) if want_residual else dx
+    return _backward_data("strided", dy, w, stride, y, act, alpha, dy_offset, y_offset, dx, dx_offset, want_residual)
 
 
 def conv2d_strided_backward_weights_device(x, dy, ksize, stride=1, y=None, act="linear", alpha=0.2, dy_offset=0, y_offset=0, cout=None,
@@ -271,25 +294,7 @@ def conv2d_strided_backward_weights_device(x, dy, ksize, stride=1, y=None, act="
     W / stride,C], y, act, alpha and the offsets as in conv2d_strided_backward_data_device; cout: the layer's output channels
     (default: all of dy's).  Returns (dw [ksize,ksize,Cin,Cout], db [Cout] or None without want_bias): new tensors.
     Asynchronous on the current stream."""
-    _check_conv_act(act, alpha)
-    if stride not in (1, 2):
-        raise ValueError("stride must be 1 or 2, got %r" % (stride,))
-    if x.dim() == 4 and (x.shape[1] % stride or x.shape[2] % stride):
-        raise ValueError("the backward of a stride-2 layer needs an even frame, got %d x %d" % tuple(x.shape[1:3]))
-    B, H, W, Cin = x.shape if x.dim() == 4 else (0, 0, 0, 0)
-    _check_wide_weights(x, dy, (B, H // stride, W // stride))
-    Cout = int(cout) if cout is not None else dy.shape[3]
-    Cdy, y, Cy = _check_conv_backward(dy, y, act, dy_offset, y_offset, Cout)
-    ksize = int(ksize)
-    nbytes = conv2d_wide_backward_workspace_bytes(B, H, W, Cin, ksize, Cout, stride)
-    dw = torch.empty((ksize, ksize, Cin, Cout), dtype=torch.float32, device=x.device)
-    db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_bias else None
-    with torch.cuda.device(x.device):
-        with _convb_ws.hold(x.device, nbytes) as ws:
-            _lib.check(_lib.load().dtfill_conv2d_strided_backward_weights(
-                x.data_ptr(), dy.data_ptr(), Cdy, int(dy_offset), _ptr(y), Cy, int(y_offset), B, H, W, Cin, ksize, Cout, stride,
-                _lib.CONV_ACTS[act], float(alpha), dw.data_ptr(), _ptr(db), ws, nbytes, _stream(x.device)))
-    return dw, db
+    return _backward_weights("strided", x, dy, ksize, stride, y, act, alpha, dy_offset, y_offset, cout, want_bias)
 
 
 def conv2d_transpose_backward_data_device(dy, w_packed, y=None, act="linear", alpha=0.2, dy_offset=0, y_offset=0, dx=None, dx_offset=0):
@@ -297,22 +302,7 @@ def conv2d_transpose_backward_data_device(dy, w_packed, y=None, act="linear", al
     dtfill_conv2d_transpose_backward_data.  dy: [B,2H,2W,C], read at dy_offset; w_packed: the [3,3,Cin,Cout] the forward takes;
     y: the forward's output, needed unless act is "linear".  dx: [B,H,W,C'], written at dx_offset .. dx_offset + Cin - 1; a
     new [B,H,W,Cin] tensor by default.  Returns dx.  Asynchronous on the current stream."""
-    _check_conv_act(act, alpha)
-    _check_tensor(w_packed, "w_packed", layout="[3,3,Cin,Cout]")
-    Cin, Cout = w_packed.shape[2], w_packed.shape[3]
-    Cdy, y, Cy = _check_conv_backward(dy, y, act, dy_offset, y_offset, Cout)
-    if dy.dim() != 4 or tuple(w_packed.shape[:2]) != (3, 3) or w_packed.device != dy.device or dy.shape[1] % 2 or dy.shape[2] % 2:
-        raise ValueError("dy must be [B,2H,2W,C] and w_packed [3,3,Cin,Cout] on %s, got %s and %s"
-                         % (dy.device, tuple(dy.shape), tuple(w_packed.shape)))
-    B, H, W = dy.shape[0], dy.shape[1] // 2, dy.shape[2] // 2
-    dx = _check_conv_out(dy, dx, dx_offset, (B, H, W), Cin)
-    nbytes = conv2d_wide_backward_workspace_bytes(B, H, W, Cin, 3, Cout, 2, True)
-    with torch.cuda.device(dy.device):
-        with _convb_ws.hold(dy.device, nbytes) as ws:
-            _lib.check(_lib.load().dtfill_conv2d_transpose_backward_data(
-                dy.data_ptr(), Cdy, int(dy_offset), _ptr(y), Cy, int(y_offset), w_packed.data_ptr(), B, H, W, Cin, Cout,
-                _lib.CONV_ACTS[act], float(alpha), dx.data_ptr(), dx.shape[3], int(dx_offset), ws, nbytes, _stream(dy.device)))
-    return dx
+    return _backward_data("transposed", dy, w_packed, 2, y, act, alpha, dy_offset, y_offset, dx, dx_offset)
 
 
 def conv2d_transpose_backward_weights_device(x, dy, y=None, act="linear", alpha=0.2, dy_offset=0, y_offset=0, cout=None, want_bias=True):
@@ -320,20 +310,7 @@ def conv2d_transpose_backward_weights_device(x, dy, y=None, act="linear", alpha=
     include/dtfill.h, dtfill_conv2d_transpose_backward_weights.  x: the forward's input [B,H,W,Cin]; dy [B,2H,2W,C].  Returns
     (dw in the packed layout [3,3,Cin,Cout], db [Cout] or None without want_bias): new tensors; the gradient of the Keras kernel
     [3,3,Cout,Cin] is dw.permute(0, 1, 3, 2).  Asynchronous on the current stream."""
-    _check_conv_act(act, alpha)
-    B, H, W, Cin = x.shape if x.dim() == 4 else (0, 0, 0, 0)
-    _check_wide_weights(x, dy, (B, 2 * H, 2 * W))
-    Cout = int(cout) if cout is not None else dy.shape[3]
-    Cdy, y, Cy = _check_conv_backward(dy, y, act, dy_offset, y_offset, Cout)
-    nbytes = conv2d_wide_backward_workspace_bytes(B, H, W, Cin, 3, Cout, 2, True)
-    dw = torch.empty((3, 3, Cin, Cout), dtype=torch.float32, device=x.device)
-    db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_bias else None
-    with torch.cuda.device(x.device):
-        with _convb_ws.hold(x.device, nbytes) as ws:
-            _lib.check(_lib.load().dtfill_conv2d_transpose_backward_weights(
-                x.data_ptr(), dy.data_ptr(), Cdy, int(dy_offset), _ptr(y), Cy, int(y_offset), B, H, W, Cin, Cout,
-                _lib.CONV_ACTS[act], float(alpha), dw.data_ptr(), _ptr(db), ws, nbytes, _stream(x.device)))
-    return dw, db
+    return _backward_weights("transposed", x, dy, 3, 2, y, act, alpha, dy_offset, y_offset, cout, want_bias)
 
 
 def pack_transpose_kernel(kernel):

@@ -369,3 +369,62 @@ def test_device_layer(pkg, L):
         dev.conv2d_strided_backward_weights_device(t(np.zeros((1, 5, 6, 16), F)), t(np.zeros((1, 3, 3, 16), F)), 3, 2)
     with pytest.raises(pkg.DtfillError):
         dev.conv2d_wide_backward_workspace_bytes(2, 9, 33, 8, 3, 16)
+
+
+SHARED = (2, 33, 67)  # 2 x 2 segments, a ragged last strip, a row end that is no multiple of the four-pixel k-step
+
+
+def _shared_domain_layer(ksize, cin, seed):
+    """A leaky layer of Cout == 16 on SHARED as device tensors: x, w, and dy and y at channel AT of wider tensors."""
+    import torch
+
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    x, w, dy, y = strided_case(ksize, 1, cin, 16, seed, SHARED)
+    return t(x), t(w), t(_wide(dy)), t(_wide(y))
+
+
+@pytest.mark.parametrize("ksize,cin", ((3, 16), (7, 64), (1, 32)))
+def test_device_layer_dw_of_both_entry_points_on_the_shared_domain(pkg, L, ksize, cin):
+    """include/dtfill.h on dtfill_conv2d_strided_backward_weights: at stride 1 and Cout == 16 dw and db are
+    dtfill_conv2d_backward_weights' values (the sign of a zero aside), here through the two device functions."""
+    dev = pkg.device
+    tx, _, tdy, ty = _shared_domain_layer(ksize, cin, 11)
+    dw, db = dev.conv2d_backward_weights_device(tx, tdy, ksize, ty, "leaky", 0.2, dy_offset=AT, y_offset=AT, cout=16)
+    got_dw, got_db = dev.conv2d_strided_backward_weights_device(tx, tdy, ksize, 1, ty, "leaky", 0.2, dy_offset=AT, y_offset=AT, cout=16)
+    R.assert_same(got_dw.cpu().numpy(), dw.cpu().numpy(), "dw")
+    R.assert_same(got_db.cpu().numpy(), db.cpu().numpy(), "db")
+
+
+@pytest.mark.parametrize("ksize,cin", ((3, 32), (5, 64)))
+def test_device_layer_dx_of_both_entry_points_on_the_shared_domain(pkg, L, ksize, cin):
+    """Cin >= 32, Cout == 16, stride 1: both data calls run the same chain, and dx is the same bit for bit."""
+    dev = pkg.device
+    _, tw, tdy, ty = _shared_domain_layer(ksize, cin, 12)
+    dx = dev.conv2d_backward_data_device(tdy, tw, ty, "leaky", 0.2, dy_offset=AT, y_offset=AT)
+    got = dev.conv2d_strided_backward_data_device(tdy, tw, 1, ty, "leaky", 0.2, dy_offset=AT, y_offset=AT)
+    assert got.shape == dx.shape == SHARED + (cin,)
+    assert np.array_equal(got.cpu().numpy().view(np.uint32), dx.cpu().numpy().view(np.uint32))
+
+
+def test_autograd_conv2d_reads_a_sliced_gradient_in_place(pkg, L):
+    """Two stems joined by torch.cat under a 3x3 layer: each stem's gradient arrives as 16 channels of the layer's 32-wide dx.
+    The stems' kernel and bias gradients are those of contiguous copies of the two halves, bit for bit."""
+    import torch
+
+    dev, conv2d = pkg.device, pkg.autograd.conv2d
+    B, H, W = 1, 5, 9
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    planes = [t(fwd.case(3, 1, 16, (B, H, W), 20 + i)[0][..., 0]) for i in range(2)]
+    stems = [[t(a).requires_grad_() for a in fwd.case(3, 1, 16, (B, H, W), 30 + i)[1:]] for i in range(2)]
+    w, bias = (t(a).requires_grad_() for a in fwd.case(3, 32, 16, (B, H, W), 40)[1:])
+    ys = [conv2d(p, k, b, "leaky", 0.2) for p, (k, b) in zip(planes, stems)]
+    out = conv2d(torch.cat(ys, dim=3), w, bias, "leaky", 0.2)
+    upstream = t(fwd.case(1, 16, 16, (B, H, W), 50)[0])
+    out.backward(upstream)
+    with torch.no_grad():
+        dx = dev.conv2d_backward_data_device(upstream, w.detach(), out.detach(), "leaky", 0.2)
+        for i, (p, (k, b), y) in enumerate(zip(planes, stems, ys)):
+            half = dx[..., 16 * i:16 * i + 16].contiguous()
+            dw, db = dev.conv2d_backward_weights_device(p, half, 3, y.detach(), "leaky", 0.2)
+            assert np.array_equal(k.grad.cpu().numpy().view(np.uint32), dw.cpu().numpy().view(np.uint32)), "stem %d: kernel" % i
+            assert np.array_equal(b.grad.cpu().numpy().view(np.uint32), db.cpu().numpy().view(np.uint32)), "stem %d: bias" % i
