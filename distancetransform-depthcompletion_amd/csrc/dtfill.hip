@@ -72,6 +72,7 @@
 #include <stdlib.h>
 #include <initializer_list>
 #include <type_traits>
+#include <utility>
 #include "../../include/dtfill.h"
 
 typedef uint16_t u16;
@@ -209,8 +210,8 @@ struct Marks {
     }
 };
 
-// k_mask<OM, VEC>, VEC when the rows can be read 16 bytes at a time.  With DTFILL_FLAG_OUTLIER_REMOVAL the predicates see
-// outlier_removal(x): k_mask<1>, then k_mask<2> redoes the frames that hold a negative value.
+// k_mask_plain; with DTFILL_FLAG_OUTLIER_REMOVAL the predicates see outlier_removal(x): k_mask<1, VEC>, VEC when the rows can be
+// read 16 bytes at a time, then k_mask<2, VEC> redoes the frames that hold a negative value.
 void launch_mask(const Pass &p, unsigned flags, hipStream_t st) {
     const bool vec = (p.W & 3) == 0 && (reinterpret_cast<uintptr_t>(p.x) & 15) == 0;
     const dim3 g(p.B, (p.H + 3) / 4);  // (frames along x)
@@ -222,8 +223,9 @@ void launch_mask(const Pass &p, unsigned flags, hipStream_t st) {
         filter<<<g, 256, 0, st>>>(p);
         redo<<<g, 256, 0, st>>>(p);
     } else {
-        auto *const plain = vec ? k_mask<0, true> : k_mask<0, false>;
-        plain<<<g, 256, 0, st>>>(p);
+        // a wave takes the rows that fit one batch of words: one row of a KITTI frame, two of NYU's
+        const int rows = max(1, MW_NW / p.Wd);
+        k_mask_plain<<<dim3(p.B, (p.H + 4 * rows - 1) / (4 * rows)), 256, 0, st>>>(p);
     }
 }
 

@@ -3,16 +3,19 @@
 #pragma once
 
 // ------------------------------------------------------------------------------------------------
-// k_mask: one wave per image row.  Source predicate exactly as tools.py:8, mask = (1.0 - x) > thr (1 = fill, 0 = source);
-// value predicate as tools.py:22, x > thr.  Per 64-pixel word: the two bit words and the row-local exclusive popcount; per
-// row: totals (+ "masks differ" in bit 31), and the row's and the frame's per-pass flags cleared.  A row is read in chunks of 256 pixels = four words, a batch of chunks in flight:
-//   VEC (W % 4 == 0, 16-byte aligned frames): a lane reads 4 consecutive pixels in one load; its four predicate bits form a
-//        nibble, and the 16 lanes of a DPP row combine theirs into one word.
-//   !VEC: a lane reads pixel 64 q + lane of each of the chunk's four words q; word q is a ballot.
-// Either way the 16 lanes of group lane >> 4 hold word lane >> 4 of the chunk.
+// k_mask: source predicate exactly as tools.py:8, mask = (1.0 - x) > thr (1 = fill, 0 = source); value predicate as
+// tools.py:22, x > thr.  Per 64-pixel word: the two bit words and the row-local exclusive popcount; per row: totals (+ "masks
+// differ" in bit 31), and the row's and the frame's per-pass flags cleared.
+//   k_mask_plain (below mask_body): the pass without the outlier filter; a word is the lane mask of a compare.
+//   k_mask<OM, VEC>, OM = 1, 2: outlier_removal() in front of the predicates, one wave per image row.  A row is read in chunks
+//   of 256 pixels = four words, a batch of chunks in flight:
+//     VEC (W % 4 == 0, 16-byte aligned frames): a lane reads 4 consecutive pixels in one load; its four predicate bits form a
+//          nibble, and the 16 lanes of a DPP row combine theirs into one word.
+//     !VEC: a lane reads pixel 64 q + lane of each of the chunk's four words q; word q is a ballot.
+//   Either way the 16 lanes of group lane >> 4 hold word lane >> 4 of the chunk.
 // ------------------------------------------------------------------------------------------------
 constexpr int M4_NC = 8;  // 256-pixel chunks per batch (2048 pixels) with 16-byte loads
-constexpr int M1_NC = 2;  // ... with dword loads (more in flight measured slower without the filter)
+constexpr int M1_NC = 2;  // ... with dword loads
 
 template <int CTRL>
 __device__ __forceinline__ u32 dpp_or(u32 v) {  // v | v of the lane CTRL pairs it with (inside a row of 16)
@@ -52,7 +55,7 @@ __device__ __forceinline__ u32 drop_bits(const u32 *s_drop, int u, int lane) {
     return d;
 }
 
-// OM != 0: outlier_removal() (data_read.py:103-128) in front of the predicates, see dtfill_outlier.hpp: the candidates of the
+// outlier_removal() (data_read.py:103-128) in front of the predicates, see dtfill_outlier.hpp: the candidates of the
 // batch's pixels in registers (v > 1.0; every pixel when OM == 2) are listed in LDS, one lane each gathers a candidate's 25 taps,
 // and the pixels it removes read as 0.0f below.  OM == 1 raises negflag[b] on a negative value, the OM == 2 launch redoes
 // exactly those frames.
@@ -62,8 +65,9 @@ __device__ __forceinline__ void mask_body(const float *__restrict__ x, int H, in
                                           u16 *__restrict__ wpre_v, u32 *__restrict__ rowcnt_s, u32 *__restrict__ rowcnt_v,
                                           int *__restrict__ negflag, u32 *__restrict__ rowfar, int *__restrict__ fflag2,
                                           int *__restrict__ frame_status, int *__restrict__ finfo, int *__restrict__ route, bool clear) {
-    __shared__ u16 s_list[OM ? 4 : 1][OM ? M4_NC * 256 : 1];
-    __shared__ u32 s_drop[OM ? 4 : 1][OM ? M4_NC * 8 : 1];
+    static_assert(OM == 1 || OM == 2, "the pass without the filter is k_mask_plain");
+    __shared__ u16 s_list[4][M4_NC * 256];
+    __shared__ u32 s_drop[4][M4_NC * 8];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // (frames along grid x: with a batch of a multiple of eight frames a frame's rows are one XCD's, where the window kernel's blocks of
     // that frame will look for its bit words)
@@ -91,43 +95,39 @@ __device__ __forceinline__ void mask_body(const float *__restrict__ x, int H, in
                 v[u] = make_float4(f[0], f[1], f[2], f[3]);
             }
         }
-        if (OM) {
-            if (lane < M4_NC * 8) s_drop[wave][lane] = 0u;
-            int n = 0;  // wave-uniform
+        if (lane < M4_NC * 8) s_drop[wave][lane] = 0u;
+        int n = 0;  // wave-uniform
 #pragma unroll
-            for (int u = 0; u < NC; ++u) {
-                if (c0 + u >= nchunk) break;
-                const float f[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+        for (int u = 0; u < NC; ++u) {
+            if (c0 + u >= nchunk) break;
+            const float f[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const bool in = ((c0 + u) << 8) + chunk_px<VEC>(VEC ? 0 : q, lane) < W;
-                    neg |= in && f[q] < 0.0f;
-                    const bool cand = in && (OM == 2 || f[q] > 1.0f);
-                    const u64 bal = __ballot(cand);
-                    if (cand) s_list[wave][n + (int)__builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0u))] = (u16)((u << 8) + chunk_px<VEC>(q, lane));
-                    n += __popcll(bal);
-                }
+            for (int q = 0; q < 4; ++q) {
+                const bool in = ((c0 + u) << 8) + chunk_px<VEC>(VEC ? 0 : q, lane) < W;
+                neg |= in && f[q] < 0.0f;
+                const bool cand = in && (OM == 2 || f[q] > 1.0f);
+                const u64 bal = __ballot(cand);
+                if (cand) s_list[wave][n + (int)__builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0u))] = (u16)((u << 8) + chunk_px<VEC>(q, lane));
+                n += __popcll(bal);
             }
-            __builtin_amdgcn_wave_barrier();
-            const float *xf = x + (size_t)b * H * W;
-            for (int t = lane; t < n; t += 64) {
-                const int jr = s_list[wave][t], j = (c0 << 8) + jr;
-                const bool drop = is_outlier([&](int ti, int tj) {
-                    return xf[(size_t)reflect101(i + ti - 3, H) * W + reflect101(j + tj - 3, W)];  // neighbouring rows: cache hits
-                });
-                if (drop) atomicOr(&s_drop[wave][jr >> 5], 1u << (jr & 31));
-            }
-            __builtin_amdgcn_wave_barrier();
         }
+        __builtin_amdgcn_wave_barrier();
+        const float *xf = x + (size_t)b * H * W;
+        for (int t = lane; t < n; t += 64) {
+            const int jr = s_list[wave][t], j = (c0 << 8) + jr;
+            const bool drop = is_outlier([&](int ti, int tj) {
+                return xf[(size_t)reflect101(i + ti - 3, H) * W + reflect101(j + tj - 3, W)];  // neighbouring rows: cache hits
+            });
+            if (drop) atomicOr(&s_drop[wave][jr >> 5], 1u << (jr & 31));
+        }
+        __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int u = 0; u < NC; ++u) {
             if (c0 + u >= nchunk) break;  // wave-uniform
             float f[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-            if (OM) {
-                const u32 d = drop_bits<VEC>(s_drop[wave], u, lane);
+            const u32 d = drop_bits<VEC>(s_drop[wave], u, lane);
 #pragma unroll
-                for (int q = 0; q < 4; ++q) f[q] = ((d >> q) & 1u) ? 0.0f : f[q];
-            }
+            for (int q = 0; q < 4; ++q) f[q] = ((d >> q) & 1u) ? 0.0f : f[q];
             u32 ns = 0, nv = 0;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -177,6 +177,98 @@ template <int OM, bool VEC>
 __global__ __launch_bounds__(256) void k_mask(const Pass p) {
     mask_body<OM, VEC>(p.x, p.H, p.W, p.Wd, p.src_thr, p.val_thr, p.srcbits, p.valbits, p.wpre_s, p.wpre_v, p.rowcnt_s, p.rowcnt_v,
                        p.negflag, p.rowfar, p.fflag2, p.status, p.finfo, p.route, p.ride != 0);
+}
+
+// v with lane K's value replaced by the wave-uniform s
+template <int K>
+__device__ __forceinline__ u32 lane_set(u32 v, u32 s) {
+    asm("v_writelane_b32 %0, %1, %2" : "+v"(v) : "s"(s), "n"(K));
+    return v;
+}
+// f(integral_constant<int, K>) for every K: the lane of lane_set is an immediate
+template <class F, int... K>
+__device__ __forceinline__ void for_words(std::integer_sequence<int, K...>, F f) {
+    (f(std::integral_constant<int, K>{}), ...);
+}
+// The plain pass (no outlier filter): a lane reads pixel 64 k + lane of word k, so the compare's 64-bit result IS the bit word:
+// the word's count is a scalar popcount, the row-local prefix a scalar sum, "the masks differ" a scalar xor.  Lane k of the
+// wave collects word k of a batch of MW_NW words (the batch's loads are all in flight before the first compare) and stores it
+// with its two prefixes: four stores per batch.  Any W, any alignment: the partial last word of a row is loaded and stored
+// apart.  A frame's waves (4 gridDim.y of them) share its rows evenly, wave g takes the rows [g H / n, (g + 1) H / n):
+// launch_mask gives a wave the rows that fill one batch.  (8 waves a SIMD are asked for: left alone the compiler keeps 101 SGPRs, 7 waves.)
+constexpr int MW_NW = 20;  // 64-pixel words per batch (a KITTI row; 1280 pixels in flight)
+__global__ __launch_bounds__(256, 8) void k_mask_plain(const Pass p) {
+    const float *__restrict__ x = p.x;
+    const int H = p.H, W = p.W, Wd = p.Wd;  // (Wd = nfull, + 1 with a partial last word)
+    const float src_thr = p.src_thr, val_thr = p.val_thr;
+    const bool clear = p.ride != 0;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // (frames along grid x: see mask_body)
+    const int b = blockIdx.x;
+    const u32 nwave = gridDim.y * 4u, g = blockIdx.y * 4u + (u32)wave;  // (nwave <= H + 3 <= 2^13: the products fit)
+    const int i1 = (int)((g + 1u) * (u32)H / nwave);
+    const int nfull = W >> 6;
+    const u64 tail = (1ull << (W & 63)) - 1ull;
+    for (int i = (int)(g * (u32)H / nwave); i < i1; ++i) {
+        const float *row = x + ((size_t)b * H + i) * W;
+        const size_t wrow = ((size_t)b * H + i) * Wd;
+        u32 run_s = 0, run_v = 0;  // wave-uniform
+        u64 mis = 0;
+        float vt = 0.0f;  // the partial last word of the row (word nfull), on its way with the first batch
+        if (lane < (W & 63)) vt = row[(nfull << 6) + lane];
+        for (int k0 = 0; k0 < nfull; k0 += MW_NW) {  // the full words
+            float v[MW_NW];
+#pragma unroll
+            for (int k = 0; k < MW_NW; ++k)
+                if (k0 + k < nfull) v[k] = row[((k0 + k) << 6) + lane];  // wave-uniform
+            u32 s_lo = 0, s_hi = 0, v_lo = 0, v_hi = 0, pre_s = 0, pre_v = 0;  // lane k: word k0 + k
+            for_words(std::make_integer_sequence<int, MW_NW>{}, [&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                if (k0 + k >= nfull) return;  // wave-uniform
+                const u64 ws = __ballot(!((1.0f - v[k]) > src_thr)), wv = __ballot(v[k] > val_thr);
+                s_lo = lane_set<k>(s_lo, (u32)ws);
+                s_hi = lane_set<k>(s_hi, (u32)(ws >> 32));
+                v_lo = lane_set<k>(v_lo, (u32)wv);
+                v_hi = lane_set<k>(v_hi, (u32)(wv >> 32));
+                pre_s = lane_set<k>(pre_s, run_s);
+                pre_v = lane_set<k>(pre_v, run_v);
+                run_s += (u32)__popcll(ws);
+                run_v += (u32)__popcll(wv);
+                mis |= ws ^ wv;
+            });
+            const int k = k0 + lane;
+            if (lane < MW_NW && k < nfull) {
+                p.srcbits[wrow + k] = (u64)s_hi << 32 | s_lo;
+                p.valbits[wrow + k] = (u64)v_hi << 32 | v_lo;
+                p.wpre_s[wrow + k] = (u16)pre_s;
+                p.wpre_v[wrow + k] = (u16)pre_v;
+            }
+        }
+        if (W & 63) {  // the pixels at or beyond W are no source and no value
+            const u64 ws = __ballot(!((1.0f - vt) > src_thr)) & tail, wv = __ballot(vt > val_thr) & tail;
+            if (lane == 0) {
+                p.srcbits[wrow + nfull] = ws;
+                p.valbits[wrow + nfull] = wv;
+                p.wpre_s[wrow + nfull] = (u16)run_s;
+                p.wpre_v[wrow + nfull] = (u16)run_v;
+            }
+            run_s += (u32)__popcll(ws);
+            run_v += (u32)__popcll(wv);
+            mis |= ws ^ wv;
+        }
+        if (lane == 0) {
+            p.rowcnt_s[(size_t)b * H + i] = run_s;
+            p.rowcnt_v[(size_t)b * H + i] = run_v | (mis ? 0x80000000u : 0u);
+            // clear: as mask_body
+            if (clear) p.rowfar[(size_t)b * H + i] = 0u;
+            if (clear && i == 0) {
+                p.fflag2[b] = 0;
+                p.status[b] = DTFILL_FRAME_OK;
+                p.finfo[b * FI_STRIDE + FI_SKY] = 0;
+                p.route[b] = ROUTE_UNKNOWN;
+            }
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
