@@ -36,11 +36,11 @@ def __getattr__(name):
         import importlib
 
         return importlib.import_module(__name__ + ".nyu").nyu_read_device
-    if name in ("conv2d_strided", "conv2d_transpose", "pack_transpose_kernel"):  # numpy forms of the wide convolutions
+    if name in ("conv2d_strided", "conv2d_transpose", "conv2d_image", "pack_transpose_kernel"):  # numpy forms of the wide and image convolutions
         import importlib
 
         return getattr(importlib.import_module(__name__ + ".net"), name)
-    if name == "net":  # <package>.net.SparsityCNN and .ResNet18 (inference), .SparsityCNNTrainable (a torch.nn.Module); imports torch
+    if name == "net":  # <package>.net.SparsityCNN, .ResNet18 and .ResNet18Image (inference), .SparsityCNNTrainable (a torch.nn.Module); imports torch
         import importlib
 
         return importlib.import_module(__name__ + ".net")
@@ -56,7 +56,7 @@ __all__ = [
     "depth_read", "depth_read_batch", "rgb_read", "rgb_read_batch", "rgb_read_device", "nearest_source",
     "map_points_on_image", "project_points", "project_points_device", "get_all_points", "unproject_frames",
     "unproject_device", "unproject_backward_device", "nyu_read_batch", "nyu_read_device", "nyu_taps",
-    "conv2d", "conv2d_strided", "conv2d_transpose", "pack_transpose_kernel", "net", "demo", "fill", "DtFill",
+    "conv2d", "conv2d_strided", "conv2d_transpose", "conv2d_image", "pack_transpose_kernel", "net", "demo", "fill", "DtFill",
     "shard_range", "gather_frames", "fill_sharded", "release_host_slab", "build", "load", "METRICS", "DtfillError",
     "Result", "Result_NYU", "depth_floor", "depth_to_png16", "kitti_rows", "nyu_eval_crop",
 ]

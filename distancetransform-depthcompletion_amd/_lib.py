@@ -108,6 +108,9 @@ _ABI = {
     "dtfill_conv2d_strided_backward_weights": (ci, [vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp, vp, vp, sz, vp]),
     "dtfill_conv2d_transpose_backward_data": (ci, [vp, ci, ci, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, cf, vp, ci, ci, vp, sz, vp]),
     "dtfill_conv2d_transpose_backward_weights": (ci, [vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp, vp, vp, sz, vp]),
+    "dtfill_conv2d_image_backward_workspace_bytes": (sz, [ci, ci, ci, ci, ci, ci]),
+    "dtfill_conv2d_image_backward_weights": (ci, [vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp, vp, vp, sz, vp]),
+    "dtfill_conv2d_image": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, cf, vp, ci, ci, vp]),
     "dtfill_conv2d_strided": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, vp, ci, cf, vp, ci, ci, vp]),
     "dtfill_conv2d_transpose": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, cf, vp, ci, ci, vp]),
     "dtfill_conv2d": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, cf, vp, ci, ci, vp]),

@@ -251,7 +251,7 @@ def _channel_slice(g):
 
 
 class _Conv(torch.autograd.Function):
-    """y of a convolution of `kind` (net._KINDS: narrow, strided, transposed) by its device function; the backward asks the
+    """y of a convolution of `kind` (net._KINDS: narrow, strided, transposed, image) by its device function; the backward asks the
     library only for the gradients that are needed, through net.py's two cores."""
 
     @staticmethod
@@ -260,6 +260,8 @@ class _Conv(torch.autograd.Function):
             y = device.conv2d_device(x, w, bias, act, alpha)
         elif kind == "strided":
             y = device.conv2d_strided_device(x, w, bias, stride, residual, act, alpha)
+        elif kind == "image":
+            y = device.conv2d_image_device(x, w, bias, act, alpha)
         else:  # w: the packed kernel [3,3,Cin,Cout]
             y = device.conv2d_transpose_device(x, w, bias, act, alpha)
         ctx.set_materialize_grads(False)  # an unused y arrives as None: nothing is launched for it
@@ -306,6 +308,21 @@ def conv2d(x, w, bias=None, act="linear", alpha=0.2):
     of conv1a's input gradient) is read in place, at dy_offset.  The shapes are dtfill_conv2d's domain (DtfillError otherwise).
     No host synchronisation in either direction; the workspace is the stream's cached one."""
     return _conv("narrow", x, w, bias, None, 1, act, alpha)
+
+
+def conv2d_image(x, w, bias=None, act="linear", alpha=0.2):
+    """The layer that reads the image as a differentiable operator: img_conv of net.py's ResNet18_NO_BN_l2_image under
+    train.py:232-254's tape.  x: contiguous float32 CUDA tensor [B,H,W,Cin] with Cin 2, 3 or 4, a constant; w: [ksize,ksize,Cin,
+    Cout], a Keras Conv2D.kernel as stored, Cout a multiple of 16; bias: [Cout] or None.  Returns y [B,H,W,Cout] by
+    device.conv2d_image_device (include/dtfill.h, dtfill_conv2d_image).  Differentiable in w and bias, once, by
+    dtfill_conv2d_image_backward_weights in its fixed two-level order; a gradient of y that is a channel slice of a wider
+    contiguous tensor (torch.cat's backward) is read in place.  There is no gradient for x: the image is data, train.py:253
+    differentiates with respect to the variables only, and the library has no such kernel; an x that requires a gradient
+    raises ValueError rather than receiving none silently.  No host synchronisation in either direction."""
+    if x.requires_grad:
+        raise ValueError("conv2d_image has no gradient for x: the image is data (train.py:253 differentiates with respect to the "
+                         "variables only); pass x.detach()")
+    return _conv("image", x, w, bias, None, 1, act, alpha)
 
 
 def conv2d_strided(x, w, bias=None, stride=1, residual=None, act="linear", alpha=0.2):

@@ -1207,6 +1207,20 @@ static int conv_check(const float *x, int B, int H, int W, int Cin, const float 
 // the channel counts of the wide kernels: whole groups in, whole N-tiles out
 static bool conv_wide_channels(int Cin, int Cout) { return Cin >= CV_G && Cin % CV_G == 0 && Cout >= 16 && Cout % 16 == 0; }
 
+// the channel counts of the image layer: fewer than a k-step in, whole N-tiles out
+static bool conv_image_channels(int Cin, int Cout) { return Cin >= 2 && Cin <= 4 && Cout >= 16 && Cout % 16 == 0; }
+
+int dtfill_conv2d_image(const float *x, int B, int H, int W, int Cin, const float *w, const float *bias, int ksize, int Cout, int act,
+                        float alpha, float *out, int out_channels, int out_offset, void *stream) {
+    const int rc = conv_check(x, B, H, W, Cin, w, Cout, act, alpha, out, out_channels, out_offset, H, W);
+    if (rc != DTFILL_OK) return rc;
+    if ((ksize != 1 && ksize != 3 && ksize != 5 && ksize != 7) || !conv_image_channels(Cin, Cout)) return DTFILL_ERR_SHAPE;
+    const int r = (ksize - 1) / 2;
+    const ConvArgs a{x, w, bias, nullptr, out, B, H, W, Cin, Cout, H, W, r, r, out_channels, out_offset, act, alpha};
+    conv_image_launch(static_cast<hipStream_t>(stream), a, ksize);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
 int dtfill_conv2d_strided(const float *x, int B, int H, int W, int Cin, const float *w, const float *bias, int ksize, int Cout,
                           int stride, const float *residual, int act, float alpha, float *out, int out_channels, int out_offset,
                           void *stream) {
@@ -1252,8 +1266,8 @@ static bool convb_slice(int B, int H, int W, int channels, int width, int offset
     return offset >= 0 && width >= 1 && (long long)offset + channels <= width && (long long)B * H * W * width < (1ll << 31);
 }
 
-// The domain of the six backward calls and everything they and the two size functions derive from a layer; false outside
-// the domain.  The narrow rule is dtfill_conv2d's with B H W Cin < 2^31.  The wide rule: whole groups in, whole N-tiles out,
+// The domain of the seven backward calls and everything they and the three size functions derive from a layer; false outside
+// the domain.  The narrow rule is dtfill_conv2d's with B H W Cin < 2^31; the image rule is dtfill_conv2d_image's.  The wide rule: whole groups in, whole N-tiles out,
 // the frame of dy [Ho,Wo] of a strided layer (stride 2: of an even frame) or [2H,2W] of the transposed one, and x, dy and a
 // segment's partials each below 2^31 floats.
 static bool convb_plan(const ConvBwLayer &l, ConvBwPlan *p) {
@@ -1261,7 +1275,10 @@ static bool convb_plan(const ConvBwLayer &l, ConvBwPlan *p) {
     const bool k1357 = ksize == 1 || ksize == 3 || ksize == 5 || ksize == 7;
     if (B < 1 || H < 1 || W < 1) return false;
     long long ho = H, wo = W;
-    if (l.narrow) {
+    if (l.image) {
+        if (!k1357 || l.stride != 1 || l.transposed || !conv_image_channels(Cin, Cout)) return false;
+        if ((long long)B * H * W * max(Cin, Cout) >= (1ll << 31) || ((long long)ksize * ksize * Cin + 1) * Cout >= (1ll << 31)) return false;
+    } else if (l.narrow) {
         if (!k1357 || l.stride != 1 || l.transposed) return false;
         if (Cin != 1 && (Cin < CV_G || Cin > 4 * CV_G || Cin % CV_G)) return false;
         if (Cout != 1 && Cout != 16) return false;
@@ -1289,7 +1306,7 @@ static bool convb_plan(const ConvBwLayer &l, ConvBwPlan *p) {
     p->wt = align256(pixels * Cout * sizeof(float));
     p->tmp = p->wt + align256(taps * Cin * Cout * sizeof(float));
     const bool spread = !l.transposed && l.stride == 2 && ksize == 1;  // the chain's values before k_convb_spread
-    const size_t data = p->tmp + (spread ? align256(pixels * Cin * sizeof(float)) : 0);
+    const size_t data = l.image ? 0 : p->tmp + (spread ? align256(pixels * Cin * sizeof(float)) : 0);  // (the image layer has no dx)
     const size_t weights = align256((size_t)B * p->segs_y * p->segs_x * (taps * Cin + 1) * Cout * sizeof(float));
     p->bytes = data > weights ? data : weights;
     return true;
@@ -1308,7 +1325,7 @@ size_t dtfill_conv2d_wide_backward_workspace_bytes(int B, int H, int W, int Cin,
     return convb_workspace_bytes(ConvBwLayer{B, H, W, Cin, ksize, Cout, stride, transposed != 0, false});
 }
 
-// what the six backward calls check alike, in the header's order; the layer's plan and the kernels' view of dy and y over the
+// what the seven backward calls check alike, in the header's order; the layer's plan and the kernels' view of dy and y over the
 // plan's small frame
 static int convb_check(const ConvBwLayer &l, const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels,
                        int y_offset, int act, float alpha, const void *workspace, size_t ws_bytes, ConvBwPlan *p, ConvBwArgs *a) {
@@ -1351,6 +1368,17 @@ static int convb_weights(const ConvBwLayer &l, const float *x, const float *dy, 
     a.HL = p.HL, a.WL = p.WL;
     convb_weights_launch(static_cast<hipStream_t>(stream), l, a, dw, db, workspace);
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+size_t dtfill_conv2d_image_backward_workspace_bytes(int B, int H, int W, int Cin, int ksize, int Cout) {
+    return convb_workspace_bytes(ConvBwLayer{B, H, W, Cin, ksize, Cout, 1, false, false, true});
+}
+
+int dtfill_conv2d_image_backward_weights(const float *x, const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels,
+                                         int y_offset, int B, int H, int W, int Cin, int ksize, int Cout, int act, float alpha,
+                                         float *dw, float *db, void *workspace, size_t ws_bytes, void *stream) {
+    return convb_weights(ConvBwLayer{B, H, W, Cin, ksize, Cout, 1, false, false, true}, x, dy, dy_channels, dy_offset, y, y_channels,
+                         y_offset, act, alpha, dw, db, workspace, ws_bytes, stream);
 }
 
 int dtfill_conv2d_backward_data(const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels, int y_offset,

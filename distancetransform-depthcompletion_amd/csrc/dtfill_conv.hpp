@@ -1,7 +1,8 @@
 // dtfill_conv.hpp -- 'same' float32 convolutions in a fixed summation order on the matrix cores: the layers of SparsityCNN
 // (solution_DeepNet/net.py:11-242) and the wide layers of ResNet18_NO_BN_l2 (net.py:245-745), stride 1 and 2 with TensorFlow's
-// 'same' rule, many output-channel tiles, a fused residual add, and the 3x3 stride-2 transposed convolution.  include/dtfill.h,
-// dtfill_conv2d(), dtfill_conv2d_strided() and dtfill_conv2d_transpose(), has the contracts.  Part of libdtfill.so; included
+// 'same' rule, many output-channel tiles, a fused residual add, and the 3x3 stride-2 transposed convolution; and the layer of
+// ResNet18_NO_BN_l2_image that reads the image, 2 to 4 channels into many (k_conv_image, with its own note).  include/dtfill.h,
+// dtfill_conv2d(), dtfill_conv2d_strided(), dtfill_conv2d_transpose() and dtfill_conv2d_image(), has the contracts.  Part of libdtfill.so; included
 // by dtfill.hip inside its anonymous namespace (one translation unit).
 #pragma once
 
@@ -390,6 +391,97 @@ __global__ __launch_bounds__(256) void k_conv_mfma(ConvArgs a, int tiles_x, int 
     }
 }
 
+// dtfill_conv2d_image: CIN of 2, 3 or 4 (the RGB stem img_conv, net.py:3407) into many output channels.  One group, so the
+// chain is the taps in raster order and within a tap the channels: KS KS CIN links laid flat, link l = tap CIN + c, and k-step
+// s holds the links 4 s .. 4 s + 3, whichever taps they belong to.  The count is no multiple of 4 in general (27 for the stem):
+// the links past the chain's end in the last step have +0 on BOTH sides, the x operand never read, so that only the sign of a
+// zero can change and no zero meets a non-finite partner.  The tile is ConvPlain<KS, 1>'s, four M-tiles a wave, and a work
+// item is k_conv_wide's (pixel tile, pass of CV_NB N-tiles): one LDS operand read feeds CV_NB MFMAs.  The LDS image is plain,
+// [row][column][CIN] as x itself is, so the links of a tile row's window are consecutive floats: link l of the pixel at
+// float P CIN lies at P CIN + l + (l / (KS CIN)) (LW - KS) CIN, and w[l][o] is w's own layout.  A lane reads one float a step
+// (ds_read_b32, banks of 32 lanes: pixels CIN floats apart, two-way conflicts at CIN 3 and 4; the kernel is bound by its stores).
+// The weights of a step are asked for a step ahead of their use.
+template <int KS, int CIN>
+__global__ __launch_bounds__(256, 2) void k_conv_image(ConvArgs a, int tiles_x, int tiles_y, int npass, long long n_items) {
+    typedef ConvPlain<KS, 1> G;
+    constexpr int R = (KS - 1) / 2, LH = G::LH, LW = G::LWH, LINKS = KS * KS * CIN, STEPS = (LINKS + 3) / 4, ROW = KS * CIN;
+    constexpr int UN = KS <= 3 ? STEPS : 1;  // the short chains are unrolled whole
+    static_assert(CIN >= 2 && CIN <= 4 && G::TH == CV_TH && G::MT == 4 && G::LWS == LW, "ConvPlain<KS, 1>'s tile, fewer channels than a k-step");
+    __shared__ __attribute__((aligned(16))) float s_x[LH * LW * CIN];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int m = lane & 15, kq = lane >> 4;
+    const int H = a.H, W = a.W, Cout = a.Cout;
+    int P[4];  // the float offset of M-tile q's pixel under tap (0, 0)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) P[q] = ((2 * wave + (q >> 1)) * LW + CV_M * (q & 1) + m) * CIN;
+    // the lane's link of step s, 4 s + kq: whether it is one of the chain's, and where its operands lie
+    auto link = [&](int s, bool &real, int &xoff, int &woff) {
+        const int l = 4 * s + kq;
+        real = l < LINKS;
+        xoff = real ? l + (l / ROW) * (LW - KS) * CIN : 0;
+        woff = real ? l * Cout : 0;
+    };
+    for (long long item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const ConvItem it = conv_item<1>(item, tiles_x, tiles_y, npass);
+        const int h0 = it.ty * CV_TH, v0 = it.tx * CV_TW, n0 = it.pass * 16 * CV_NB;
+        const int nt = min(CV_NB, (Cout - n0) / 16);
+        const float *xb = a.x + (size_t)it.b * H * W * CIN;
+        const float *wl = a.w + n0 + m;
+        // ---- the haloed tile, +0 outside the frame: a row of it is LW CIN consecutive floats of x ----
+        for (int e = t; e < LH * LW * CIN; e += 256) {
+            const int r = e / (LW * CIN), rest = e - r * (LW * CIN);
+            const int h = h0 + r - R, v = v0 + rest / CIN - R;
+            s_x[e] = h >= 0 && h < H && v >= 0 && v < W ? xb[((size_t)h * W + (v0 - R)) * CIN + rest] : 0.0f;
+        }
+        cv_f4 acc[4][CV_NB];
+        conv_zero(acc);
+        bool real;
+        int xoff, woff;
+        float wr[CV_NB];
+        link(0, real, xoff, woff);
+#pragma unroll
+        for (int n = 0; n < CV_NB; ++n) wr[n] = real && n < nt ? wl[woff + 16 * n] : 0.0f;
+        __syncthreads();
+#pragma unroll UN
+        for (int s = 0; s < STEPS; ++s) {
+            float xv[4], wn[CV_NB];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) xv[q] = real ? s_x[P[q] + xoff] : 0.0f;
+            if (s + 1 < STEPS) {
+                link(s + 1, real, xoff, woff);
+#pragma unroll
+                for (int n = 0; n < CV_NB; ++n) wn[n] = real && n < nt ? wl[woff + 16 * n] : 0.0f;
+            }
+#pragma unroll
+            for (int n = 0; n < CV_NB; ++n)
+                if (n < nt) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) acc[q][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[q], wr[n], acc[q][n], 0, 0, 0);
+                }
+            if (s + 1 < STEPS) {
+#pragma unroll
+                for (int n = 0; n < CV_NB; ++n) wr[n] = wn[n];
+            }
+        }
+        __syncthreads();  // the tile is rewritten by the next item
+        // ---- the epilogue (see the note above): M-tile q is the half q & 1 of the wave's row q >> 1 ----
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int h = h0 + 2 * wave + (q >> 1);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int v = v0 + CV_M * (q & 1) + 4 * kq + e;
+                if (h < H && v < W) {
+                    const size_t pixel = ((size_t)it.b * H + h) * W + v;
+#pragma unroll
+                    for (int n = 0; n < CV_NB; ++n)
+                        if (n < nt) conv_store<false>(acc[q][n][e], a, pixel, n0 + 16 * n + m);
+                }
+            }
+        }
+    }
+}
+
 // Cout == 1: pixel blockIdx.x * 256 + threadIdx.x of the n = B H W, the chain as the contract writes it.  VEC: Cin is a multiple of
 // 4 and x is 16-byte aligned, the channels of a tap come by 16-byte loads.
 template <bool VEC>
@@ -488,5 +580,21 @@ inline void conv_launch(hipStream_t st, const ConvArgs &a, int ksize) {
         case 3: conv_mfma_launch<3>(st, a); break;
         case 5: conv_mfma_launch<5>(st, a); break;
         default: conv_mfma_launch<7>(st, a); break;
+    }
+}
+
+// dtfill_conv2d_image: Cin is 2, 3 or 4, Cout a multiple of 16
+template <int KS>
+void conv_image_launch_k(hipStream_t st, const ConvArgs &a) {
+    const conv_kernel k = a.Cin == 2 ? k_conv_image<KS, 2> : a.Cin == 3 ? k_conv_image<KS, 3> : k_conv_image<KS, 4>;
+    conv_launch_items(st, a, a.Ho, a.Wo, CV_TH, 1, k, k);  // (scalar loads of x: one kernel for any alignment)
+}
+
+inline void conv_image_launch(hipStream_t st, const ConvArgs &a, int ksize) {
+    switch (ksize) {
+        case 1: conv_image_launch_k<1>(st, a); break;
+        case 3: conv_image_launch_k<3>(st, a); break;
+        case 5: conv_image_launch_k<5>(st, a); break;
+        default: conv_image_launch_k<7>(st, a); break;
     }
 }

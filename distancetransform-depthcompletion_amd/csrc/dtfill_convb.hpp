@@ -2,8 +2,9 @@
 // SparsityCNN (solution_DeepNet/net.py:11-242), what train.py:232-254's tape needs of a convolution.  include/dtfill.h,
 // dtfill_conv2d_backward_data() and dtfill_conv2d_backward_weights(), has the contracts.  Part of libdtfill.so; included by
 // dtfill.hip inside its anonymous namespace, after dtfill_conv.hpp, whose kernels the input gradient runs on.  The kernels of
-// the wide layers of ResNet18_NO_BN_l2 (dtfill_conv2d_strided, dtfill_conv2d_transpose) are the second part of this file; the
-// host side, the last, is one path for all six entry points: dtfill.hip's convb_plan checks a ConvBwLayer's domain and derives
+// the wide layers of ResNet18_NO_BN_l2 (dtfill_conv2d_strided, dtfill_conv2d_transpose) are the second part of this file, the
+// weight gradient of the image layer (dtfill_conv2d_image) the third; the
+// host side, the last, is one path for all seven entry points: dtfill.hip's convb_plan checks a ConvBwLayer's domain and derives
 // its frames, segment counts and workspace layout (ConvBwPlan), and convb_data_launch and convb_weights_launch each hold one
 // dispatch, in which the narrow layers' kernels are branches beside the wide ones'.
 #pragma once
@@ -489,10 +490,121 @@ void convb_dw_wide_launch(hipStream_t st, const ConvBwWide &a, float *part, long
         }
 }
 
-// ---- the host side: one layer record, one plan (dtfill.hip's convb_plan), one dispatch per gradient for all six entry points ----
+// ------------------------------------------------------------------------------------------------
+// The image layer: dw and db of dtfill_conv2d_image (CIN of 2, 3 or 4 into a multiple of 16 channels).  There is no dx: the
+// image is data.  k_convb_dw_image is k_convb_dw's Cin == 1 form grown two ways.  The 16 rows of a tile are (tap, channel)
+// pairs in dw's own order, row = tap CIN + c; there are KS KS CIN of them in CBI_NT(..) tiles, and the first free row, which
+// always exists (KS KS is odd and CIN <= 4: the count is no multiple of 16), is the row of ones that makes db.  And there is
+// an N loop: a work item is (segment, pass of CBI_NB tiles of 16 output channels), the pass fastest; the staged strip of x
+// serves the pass's tiles, wave k holding tile k of the pass with one accumulator per row tile (13 at 7x7x4, 2 for the RGB
+// stem: independent chains).  The strips are CBI_RS rows, g as [tile][pixel][16] and x plain, [row][column][CIN], read one
+// float a lane at a constant offset a row tile.  Edge k-steps as in k_convb_dw.
+// ------------------------------------------------------------------------------------------------
+constexpr int CBI_NB = 4;  // N-tiles of a pass: one a wave
+constexpr int CBI_RS = 2;  // rows of a strip
+static_assert(CB_R % CBI_RS == 0, "a segment is whole strips");
+
+template <int KS, int CIN>
+__global__ __launch_bounds__(256, 2) void k_convb_dw_image(ConvBwArgs a, float *__restrict__ part, int npass, long long n_items) {
+    constexpr int R = (KS - 1) / 2, ROWS = KS * KS * CIN, NT = (ROWS + 16) / 16, NB = CBI_NB, RS = CBI_RS;
+    constexpr int LH = RS + KS - 1, LW = CB_C + KS - 1;
+    static_assert(CIN >= 2 && CIN <= 4 && ROWS % 16 != 0, "the last tile has a free row for db");
+    __shared__ __attribute__((aligned(16))) float s_x[LH * LW * CIN];
+    __shared__ __attribute__((aligned(16))) float s_g[NB * RS * CB_C * 16];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int m = lane & 15, kq = lane >> 4;  // A: row m, pixel kq; B: pixel kq, output channel m; D: channel m, rows 4 kq ..+3
+    const int H = a.H, W = a.W, Cout = a.Cout;
+    const size_t pstride = (size_t)(ROWS + 1) * Cout;
+    // the lane's float offset into s_x of row tile n's operand, at the strip's first pixel (rows ROWS and beyond read nothing)
+    int aoff[NT];
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+        const int row = min(16 * n + m, ROWS - 1), tap = row / CIN;
+        aoff[n] = ((tap / KS) * LW + tap % KS + kq) * CIN + row - tap * CIN;
+    }
+    for (long long item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const int pass = (int)(item % npass);
+        const long long seg = item / npass;
+        const int sx = (int)(seg % a.segs_x), sy = (int)(seg / a.segs_x % a.segs_y), b = (int)(seg / a.segs_x / a.segs_y);
+        const int h0 = sy * CB_R, v0 = sx * CB_C, n0 = pass * NB, nt = min(NB, Cout / 16 - n0);
+        const size_t fb = (size_t)b * H * W;
+        const float *xb = a.x + fb * CIN;
+        ConvBwArgs g = a;  // dy and y from the item's frame and the pass's first channel on
+        g.dy += fb * g.dy_channels + n0 * 16;
+        if (g.act == DTFILL_CONV_LEAKY) g.y += fb * g.y_channels + n0 * 16;
+        const int cols = min(CB_C, W - v0), steps = (cols + 3) / 4, whole = cols / 4;  // k-steps of a row; those wholly inside
+        cv_f4 acc[NT];
+#pragma unroll
+        for (int n = 0; n < NT; ++n) acc[n] = cv_f4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+        for (int h1 = h0; h1 < min(h0 + CB_R, H); h1 += RS) {
+            // ---- the haloed strip of x, +0 outside the frame (a row of it is LW CIN consecutive floats of x) ----
+            for (int e = t; e < LH * LW * CIN; e += 256) {
+                const int r = e / (LW * CIN), rest = e - r * (LW * CIN);
+                const int h = h1 + r - R, v = v0 + rest / CIN - R;
+                s_x[e] = h >= 0 && h < H && v >= 0 && v < W ? xb[((size_t)h * W + (v0 - R)) * CIN + rest] : 0.0f;
+            }
+            // ---- the strip of g of the pass's nt tiles, [tile][pixel][16], +0 outside the frame ----
+            for (int e = t; e < nt * RS * CB_C * 4; e += 256) {
+                const int p = e >> 2, s = e & 3;  // p: (tile, row, column)
+                const int n = p / (RS * CB_C), row = p / CB_C % RS, col = p % CB_C;
+                const int h = h1 + row, v = v0 + col;
+                cv_f4 f{0.0f, 0.0f, 0.0f, 0.0f};
+                if (h < H && v < W) f = convb_g4(g, (size_t)h * W + v, n * 16 + 4 * s, a.gvec);
+                *reinterpret_cast<cv_f4 *>(s_g + p * 16 + 4 * s) = f;
+            }
+            __syncthreads();
+            // ---- the strip's links of every chain, in raster order (EDGE: as in k_convb_dw) ----
+            const int rows = min(RS, H - h1);
+            auto k_step = [&](auto edge, int row, int s) {
+                const bool real = !decltype(edge)::value || v0 + 4 * s + kq < W;
+                const float gv = s_g[((wave * RS + row) * CB_C + 4 * s + kq) * 16 + m];
+                const int at = (row * LW + 4 * s) * CIN;
+#pragma unroll
+                for (int n = 0; n < NT; ++n) {
+                    const int r = 16 * n + m;  // (only the last tile has rows beyond the chain's)
+                    const float xv = n + 1 < NT || r < ROWS ? s_x[at + aoff[n]] : r == ROWS ? 1.0f : 0.0f;
+                    acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(real ? xv : 0.0f, gv, acc[n], 0, 0, 0);
+                }
+            };
+            if (wave < nt) {
+#pragma unroll 1
+                for (int row = 0; row < rows; ++row) {
+#pragma unroll 1
+                    for (int s = 0; s < whole; ++s) k_step(std::false_type{}, row, s);
+                    if (whole < steps) k_step(std::true_type{}, row, whole);
+                }
+            }
+            __syncthreads();  // the strips are rewritten by the next one, or the next item
+        }
+        // ---- the segment's partials: [row][Cout] as dw is, then db ----
+        if (wave < nt) {
+            float *ps = part + (size_t)seg * pstride + (n0 + wave) * 16 + m;
+#pragma unroll
+            for (int n = 0; n < NT; ++n)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int r = 16 * n + 4 * kq + e;
+                    if (r <= ROWS) ps[(size_t)r * Cout] = acc[n][e];
+                }
+        }
+    }
+}
+
+template <int KS>
+void convb_dw_image_launch(hipStream_t st, const ConvBwArgs &a, float *part, long long nseg) {
+    const int npass = (a.Cout / 16 + CBI_NB - 1) / CBI_NB;  // (< 2^25: a multiple of 16 below 2^31)
+    const long long n_items = nseg * npass;
+    const int grid = (int)(n_items < CV_MAX_BLOCKS ? n_items : CV_MAX_BLOCKS);
+    (a.Cin == 2 ? k_convb_dw_image<KS, 2> : a.Cin == 3 ? k_convb_dw_image<KS, 3> : k_convb_dw_image<KS, 4>)<<<grid, 256, 0, st>>>(a, part, npass,
+                                                                                                                              n_items);
+}
+
+// ---- the host side: one layer record, one plan (dtfill.hip's convb_plan), one dispatch per gradient for all seven entry points ----
 struct ConvBwLayer {  // a layer as its backward sees it: the forward's input [B,H,W,Cin] and what made its output
     int B, H, W, Cin, ksize, Cout, stride;
     bool transposed, narrow;  // narrow: dtfill_conv2d's domain (Cin 1/16/32/48/64, Cout 1/16, stride 1) and kernels; else the wide ones
+    bool image = false;       // dtfill_conv2d_image's domain (Cin 2/3/4, Cout a multiple of 16, stride 1): weights only, its own kernel
 };
 
 struct ConvBwPlan {         // what convb_plan derives from a layer in its domain
@@ -545,7 +657,14 @@ inline void convb_weights_launch(hipStream_t st, const ConvBwLayer &l, const Con
     float *part = static_cast<float *>(workspace);
     const int nseg = l.B * a.b.segs_y * a.b.segs_x;                      // (< 2^31: the small frames' pixels are)
     const int ndw = l.ksize * l.ksize * l.Cin * l.Cout, pstride = ndw + l.Cout;  // (< 2^31: the entry points' domain)
-    if (l.Cout == 1) {
+    if (l.image) {
+        switch (l.ksize) {
+            case 1: convb_dw_image_launch<1>(st, a.b, part, nseg); break;
+            case 3: convb_dw_image_launch<3>(st, a.b, part, nseg); break;
+            case 5: convb_dw_image_launch<5>(st, a.b, part, nseg); break;
+            default: convb_dw_image_launch<7>(st, a.b, part, nseg); break;
+        }
+    } else if (l.Cout == 1) {
         k_convb_dw_lane<<<dim3((unsigned)nseg, (unsigned)((pstride + 255) / 256)), 256, 0, st>>>(a.b, l.ksize, part);
     } else if (l.narrow) {
         switch (l.ksize) {

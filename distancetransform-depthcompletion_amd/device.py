@@ -842,7 +842,8 @@ def __getattr__(name):
     if name in ("conv2d_device", "conv2d_strided_device", "conv2d_transpose_device", "conv2d_backward_data_device",
                 "conv2d_backward_weights_device", "conv2d_backward_workspace_bytes", "conv2d_strided_backward_data_device",
                 "conv2d_strided_backward_weights_device", "conv2d_transpose_backward_data_device",
-                "conv2d_transpose_backward_weights_device", "conv2d_wide_backward_workspace_bytes"):  # likewise in net.py
+                "conv2d_transpose_backward_weights_device", "conv2d_wide_backward_workspace_bytes", "conv2d_image_device",
+                "conv2d_image_backward_weights_device", "conv2d_image_backward_workspace_bytes"):  # likewise in net.py
         from . import net
 
         return getattr(net, name)

@@ -12,8 +12,12 @@ a call of _backward_data or _backward_weights, which hold the checks, the frames
 once, under a kind (narrow, strided, transposed) whose entry in _KINDS supplies the frame arithmetic, the symbol and the
 arguments only that kind takes.
 
-The other ten models of the reference's net.py are not here; what they need beyond these two (widths in multiples of 16, stride
-2, Conv2DTranspose, the residual add) is.  conv2d_device, conv2d_strided_device and conv2d_transpose_device, the device
+ResNet18Image and ResNet18ImageTrainable are ResNet18_NO_BN_l2_image (net.py:3383-3893), the image-guided network demo.py
+defaults to: ResNet18 with img_conv, the layer that reads the [B,H,W,3] image (dtfill_conv2d_image, conv2d_image_device, and
+conv2d_image_backward_weights_device, a fourth kind with no data gradient), in front of the stems.
+
+The other nine models of the reference's net.py are not here.  ResNet18_NO_BN_l2_light_image lacks only its own trunk wiring:
+its layers are all here.  The _large models still need max_pool and the stride-4 and stride-8 layers.  conv2d_device, conv2d_strided_device and conv2d_transpose_device, the device
 functions of one convolution, are reached as device.<name> as well; they live here, beside device.py's helpers, with their
 argument checks in tests/test_conv2d.py, tests/test_gpu_conv2d.py, tests/test_conv2d_strided.py and
 tests/test_gpu_conv2d_strided.py.
@@ -125,7 +129,8 @@ def _check_conv_backward(dy, y, act, dy_offset, y_offset, Cout):
     return Cdy, y, _check_conv_slice(y, "y", dy, y_offset, Cout)
 
 
-# What tells the three kinds of layer apart in the backward.  data, weights: the ABI's symbols; abi_shape(ksize, Cout, stride):
+# What tells the four kinds of layer apart in the backward.  data, weights: the ABI's symbols (data None: the image layer has
+# no data gradient); abi_shape(ksize, Cout, stride):
 # what they take between Cin and act; has_residual: the data call takes dresidual; ws_bytes(L, B, H, W, Cin, ksize, Cout,
 # stride): the library's size function; ksize: the [3,3,..] rule, or None for any square kernel; x_frame(Ho, Wo, stride): the
 # forward's input frame under a dy of [Ho,Wo], and dy_frame(H, W, stride) the reverse, each None where the kind has no such
@@ -146,6 +151,10 @@ _KINDS = {
                         lambda L, B, H, W, Cin, ksize, Cout, s: L.dtfill_conv2d_wide_backward_workspace_bytes(B, H, W, Cin, 3, Cout, 2, 1),
                         "w_packed", "[3,3,Cin,Cout]", 3, "[B,2H,2W,C]", False,
                         lambda Ho, Wo, s: None if Ho % 2 or Wo % 2 else (Ho // 2, Wo // 2), lambda H, W, s: (2 * H, 2 * W)),
+    # the layer that reads the image: no data call, the image is data
+    "image": _Kind(None, "dtfill_conv2d_image_backward_weights", lambda ksize, Cout, s: (ksize, Cout), False,
+                   lambda L, B, H, W, Cin, ksize, Cout, s: L.dtfill_conv2d_image_backward_workspace_bytes(B, H, W, Cin, ksize, Cout),
+                   "w", "[ksize,ksize,Cin,Cout]", None, "[B,H,W,C]", False, lambda Ho, Wo, s: (Ho, Wo), lambda H, W, s: (H, W)),
 }
 
 
@@ -313,6 +322,37 @@ def conv2d_transpose_backward_weights_device(x, dy, y=None, act="linear", alpha=
     return _backward_weights("transposed", x, dy, 3, 2, y, act, alpha, dy_offset, y_offset, cout, want_bias)
 
 
+def conv2d_image_device(x, w, bias=None, act="linear", alpha=0.2, out=None, out_offset=0):
+    """A stride-1 'same' float32 convolution of an image of 2, 3 or 4 channels into a multiple of 16 channels, in the fixed
+    summation order of include/dtfill.h, dtfill_conv2d_image (img_conv of net.py's ResNet18_NO_BN_l2_image).  x: contiguous
+    float32 CUDA tensor [B,H,W,Cin], what rgb_read_device emits; w: [ksize,ksize,Cin,Cout], a Keras Conv2D.kernel as stored;
+    bias: [Cout] or None; act, alpha, out and out_offset as in conv2d_device.  Returns out.  Asynchronous on the current stream;
+    the shapes the library takes are the header's (DtfillError otherwise)."""
+    B, H, W, Cin, Cout = _check_conv_args(x, w, bias, act, "[ksize,ksize,Cin,Cout]")
+    out = _check_conv_out(x, out, out_offset, (B, H, W), Cout)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dtfill_conv2d_image(x.data_ptr(), B, H, W, Cin, w.data_ptr(), _ptr(bias), w.shape[0], Cout,
+                                                   _lib.CONV_ACTS[act], float(alpha), out.data_ptr(), out.shape[3],
+                                                   int(out_offset), _stream(x.device)))
+    return out
+
+
+def conv2d_image_backward_workspace_bytes(B, H, W, Cin, ksize, Cout):
+    """The bytes of workspace conv2d_image_backward_weights_device needs (dtfill_conv2d_image_backward_workspace_bytes): host
+    arithmetic, no device.  DtfillError for a shape outside dtfill_conv2d_image's domain."""
+    return _device._sized(_lib.load().dtfill_conv2d_image_backward_workspace_bytes(int(B), int(H), int(W), int(Cin), int(ksize),
+                                                                                  int(Cout)))
+
+
+def conv2d_image_backward_weights_device(x, dy, ksize, y=None, act="linear", alpha=0.2, dy_offset=0, y_offset=0, cout=None,
+                                         want_bias=True):
+    """The gradients of conv2d_image_device with respect to w and bias, in the fixed two-level order of include/dtfill.h,
+    dtfill_conv2d_image_backward_weights.  x: the forward's input [B,H,W,Cin]; dy, y, act, alpha, the offsets and cout as in
+    conv2d_backward_weights_device.  Returns (dw [ksize,ksize,Cin,Cout], db [Cout] or None without want_bias): new tensors.
+    There is no data gradient: the image is data.  Asynchronous on the current stream."""
+    return _backward_weights("image", x, dy, ksize, 1, y, act, alpha, dy_offset, y_offset, cout, want_bias)
+
+
 def pack_transpose_kernel(kernel):
     """A Keras Conv2DTranspose.kernel [3,3,Cout,Cin] -> the ABI's [3,3,Cin,Cout], contiguous float32: the last two axes
     exchanged, once, when the weights are loaded."""
@@ -346,6 +386,13 @@ def conv2d_transpose(x, kernel, bias=None, act="linear", alpha=0.2):
     (packed here), bias [Cout].  Returns float32 [B,2H,2W,Cout]."""
     a, k, b = _uploaded(x, kernel, bias)
     return conv2d_transpose_device(a, k.permute(0, 1, 3, 2).contiguous(), b, act, alpha).cpu().numpy()
+
+
+def conv2d_image(x, kernel, bias=None, act="linear", alpha=0.2):
+    """conv2d_image_device as a numpy function: x [B,H,W,Cin] with Cin 2, 3 or 4, kernel [ksize,ksize,Cin,Cout] and bias [Cout]
+    as Keras stores them.  Returns float32 [B,H,W,Cout]."""
+    a, k, b = _uploaded(x, kernel, bias)
+    return conv2d_image_device(a, k, b, act, alpha).cpu().numpy()
 
 
 def stem_layers(scale_num):
@@ -421,6 +468,19 @@ def layer_shapes_resnet18(scale_num=4, if_correct=True):
     return shapes
 
 
+IMAGE_WIDTH = 64  # channels img_conv writes in front of the stems: conv1a of the image network reads [image | stems]
+
+
+def layer_shapes_resnet18_image(scale_num=4, if_correct=True):
+    """{layer name: (ksize, Cin, Cout)} of the layers ResNet18_NO_BN_l2_image's forward uses (net.py:3383-3893): those of
+    layer_shapes_resnet18 and img_conv, the layer that reads the image, whose 64 channels stand in front of the stems, so the
+    three layers that read that tensor are 64 channels wider."""
+    shapes = layer_shapes_resnet18(scale_num, if_correct)
+    wide = IMAGE_WIDTH + STEM_WIDTH * scale_num
+    shapes.update(img_conv=(3, 3, IMAGE_WIDTH), conv1a=(3, wide, 64), conv1a_extra=(1, wide, 64), upsample_1_post=(3, 64 + wide, 64))
+    return shapes
+
+
 def _keras_shape(name, k, cin, cout):
     return (k, k, cout, cin) if name in RESNET_TRANSPOSED else (k, k, cin, cout)
 
@@ -430,16 +490,21 @@ def glorot_weights_resnet18(seed, scale_num=4, if_correct=True, bias=0.0):
     return _glorot(layer_shapes_resnet18, seed, scale_num, if_correct, bias)
 
 
+def glorot_weights_resnet18_image(seed, scale_num=4, if_correct=True, bias=0.0):
+    """glorot_weights() for ResNet18Image: float32 numpy arrays of Keras' shapes, [3,3,Cout,Cin] for the transposed layers."""
+    return _glorot(layer_shapes_resnet18_image, seed, scale_num, if_correct, bias)
+
+
 class _Buffers:
     """What one (device, B, H, W) needs: the weights' device copies are the instance's, these are the activations."""
 
-    def __init__(self, device, B, H, W, scale_num):
+    def __init__(self, device, B, H, W, scale_num, image_width=0):
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
         self.new = new
         self.mask, self.scaled, self.correct = new(B, H, W), new(B, H, W), new(B, H, W)
         self.a16, self.b16, self.one = new(B, H, W, 16), new(B, H, W, 16), new(B, H, W, 1)
         self.fills = [new(B, H, W) for _ in range(scale_num - 1)]
-        self.stems = new(B, H, W, STEM_WIDTH * scale_num)
+        self.stems = new(B, H, W, image_width + STEM_WIDTH * scale_num)  # [image | stems] in the image network
         self.output, self.correct_out = new(B, H, W), new(B, H, W)
 
 
@@ -486,8 +551,8 @@ class _LidarNet:
                              torch.tensor(self.scale_range, dtype=torch.float32, device=dev))
         return self._on[dev]
 
-    def _head(self, on, threshold, scale, x, t):
-        """x [B,H,W] -> t.correct, and the stems' [B,H,W,16 scale_num] in t.stems."""
+    def _head(self, on, threshold, scale, x, t, stem_offset=0):
+        """x [B,H,W] -> t.correct, and the stems' [B,H,W,16 scale_num] in t.stems from channel stem_offset on."""
         B, H, W = x.shape
         torch.gt(x, threshold, out=t.mask)  # valued_mask, as float32
         torch.div(x, scale, out=t.scaled)  # (a tensor divisor: an IEEE division, not a product with 1 / scale_range)
@@ -501,7 +566,7 @@ class _LidarNet:
             torch.mul(t.scaled, t.mask, out=t.correct)
         lidars = _device.generate_multi_channel_device(t.correct, t.mask, self.table_size, self.scale_num, outs=t.fills)
         for k, name in enumerate(stem_layers(self.scale_num)):  # tf.concat: each stem writes its 16 channels
-            self._conv(on, lidars[k], name, "leaky", t.stems, STEM_WIDTH * k)
+            self._conv(on, lidars[k], name, "leaky", t.stems, stem_offset + STEM_WIDTH * k)
 
 
 class SparsityCNN(_LidarNet):
@@ -633,14 +698,14 @@ class _ResNetBuffers(_Buffers):
     """_Buffers and, per level k (1 / 2^(k-1) of the frame each way, RESNET_WIDTHS[k-1] channels), three tensors that take turns
     and the wide tensor a tf.concat([up, skip]) of that level is."""
 
-    def __init__(self, device, B, H, W, scale_num):
-        super().__init__(device, B, H, W, scale_num)
+    def __init__(self, device, B, H, W, scale_num, image_width=0):
+        super().__init__(device, B, H, W, scale_num, image_width)
         self.level, self.wide = [], []
         for k, width in enumerate(RESNET_WIDTHS):
             frame = (B, H >> k, W >> k)
             self.level.append([self.new(*frame, width) for _ in range(3)])
             if k < 3:  # [up | skip]: level 1's is upsample_1's 64 channels and the stems, the others twice the level's width
-                self.wide.append(self.new(*frame, 64 + STEM_WIDTH * scale_num if k == 0 else 2 * width))
+                self.wide.append(self.new(*frame, 64 + image_width + STEM_WIDTH * scale_num if k == 0 else 2 * width))
         self.wide1 = self.new(B, H, W, 128)  # upsample_2's 64 channels and tensor_1_total
 
 
@@ -673,22 +738,35 @@ class ResNet18(_LidarNet):
         kernel, bias = on[name]
         return conv2d_transpose_device(x, kernel, bias, "leaky", LEAKY_ALPHA, out)
 
+    IMAGE_WIDTH = 0  # channels of an image layer in front of the stems (ResNet18Image)
+
     def __call__(self, input_lidar):
         """input_lidar: contiguous float32 CUDA tensor [B,H,W] in metres, H and W multiples of 8.  Returns (output *
         scale_range, lidar_correct * scale_range), net.py:745, each [B,H,W]."""
+        return self._run(input_lidar, None)
+
+    def _run(self, input_lidar, rgb):
+        """The forward of both networks; rgb: the image network's second input, already detached, or None."""
         x = input_lidar.detach()
         if x.dim() == 3 and (x.shape[1] % 8 or x.shape[2] % 8):
             raise ValueError("H and W must be multiples of 8, got %d x %d" % tuple(x.shape[1:]))
         _check_tensor(x, "input_lidar")
         B, H, W = x.shape
         dev = x.device
+        if rgb is not None:
+            _check_tensor(rgb, "input_rgb", layout="[B,H,W,3]")
+            if tuple(rgb.shape) != (B, H, W, 3) or rgb.device != dev:
+                raise ValueError("input_rgb must be [%d,%d,%d,3] on %s, got %s" % (B, H, W, dev, tuple(rgb.shape)))
         with torch.cuda.device(dev):
             on, threshold, scale = self._state(dev)
             key = (dev, B, H, W)
             if key not in self._buffers:
-                self._buffers[key] = _ResNetBuffers(dev, B, H, W, self.scale_num)
+                self._buffers[key] = _ResNetBuffers(dev, B, H, W, self.scale_num, self.IMAGE_WIDTH)
             t = self._buffers[key]
-            self._head(on, threshold, scale, x, t)
+            self._head(on, threshold, scale, x, t, self.IMAGE_WIDTH)
+            if rgb is not None:  # net.py:3645-3649: tf.concat([img_conv_1, lidar_conv_total]), the image's channels first
+                kernel, bias = on["img_conv"]
+                conv2d_image_device(rgb, kernel, bias, "leaky", LEAKY_ALPHA, t.stems, 0)
             below = t.stems
             for k in range(4):  # net.py:551-674; `below` ends as tensor_<k+1>_total (level 4: tensor_4)
                 p, q, r = t.level[k]
@@ -713,6 +791,28 @@ class ResNet18(_LidarNet):
             torch.mul(t.one.view(B, H, W), scale, out=t.output)
             torch.mul(t.correct, scale, out=t.correct_out)
         return t.output, t.correct_out
+
+
+class ResNet18Image(ResNet18):
+    """net.py's ResNet18_NO_BN_l2_image (net.py:3383-3893, demo.py:27's default) for inference: ResNet18 with the image beside
+    the LiDAR.  The reference's class is ResNet18_NO_BN_l2 line for line but for img_conv = Conv2D(64, (3,3)) on input_rgb
+    (dtfill_conv2d_image), whose leaky output is concatenated IN FRONT of the stems: conv1a, conv1a_extra and upsample_1_post
+    read 64 channels more.  Here img_conv writes the channels 0 .. 63 of the stems tensor and stem k the channels 64 + 16 k on.
+    weights: as ResNet18's with img_conv (layer_shapes_resnet18_image).
+
+    Called as net(input_lidar, input_rgb); input_rgb: contiguous float32 CUDA tensor [B,H,W,3], what rgb_read_device emits
+    (img_batch[:, 96:] / 255.0, demo.py:296, train.py:213).  Everything else as ResNet18: detached, no host synchronisation, no
+    activation buffer allocated after the first call at a shape, the returned tensors are the instance's own."""
+
+    NAME = "ResNet18_NO_BN_l2_image"
+    KNOWN = tuple(layer_shapes_resnet18_image(4, True)) + ("lidar_conv_extra_3",)
+    layer_shapes = staticmethod(layer_shapes_resnet18_image)
+    IMAGE_WIDTH = IMAGE_WIDTH
+
+    def __call__(self, input_lidar, input_rgb):
+        """input_lidar: [B,H,W] in metres, H and W multiples of 8; input_rgb: [B,H,W,3].  Returns (output * scale_range,
+        lidar_correct * scale_range), net.py:3893, each [B,H,W]."""
+        return self._run(input_lidar, input_rgb.detach())
 
 
 class ResNet18Trainable(_TrainableNet):
@@ -751,6 +851,13 @@ class ResNet18Trainable(_TrainableNet):
     def forward(self, input_lidar):
         """input_lidar: contiguous float32 CUDA tensor [B,H,W] in metres, H and W multiples of 8, a constant.  Returns two
         [B,H,W] tensors."""
+        return self._run(input_lidar, None)
+
+    def _image(self, rgb):
+        """The image layer's output, which stands in front of the stems (ResNet18ImageTrainable)."""
+        raise NotImplementedError
+
+    def _run(self, input_lidar, rgb):
         x = input_lidar.detach()
         if x.dim() == 3 and (x.shape[1] % 8 or x.shape[2] % 8):
             raise ValueError("H and W must be multiples of 8, got %d x %d" % tuple(x.shape[1:]))
@@ -758,6 +865,8 @@ class ResNet18Trainable(_TrainableNet):
         B, H, W = x.shape
         with torch.cuda.device(x.device):
             correct, stems = self._head(x)
+            if rgb is not None:  # net.py:3645-3649
+                stems = torch.cat([self._image(rgb), stems], dim=3)
             below, totals = stems, []
             for level in (1, 2, 3, 4):  # net.py:551-674
                 name, stride = "conv%d" % level, 1 if level == 1 else 2
@@ -775,3 +884,32 @@ class ResNet18Trainable(_TrainableNet):
             t = self._wide(up, "upsample_1_post")
             output = self._conv(t, "conv_output", "linear").view(B, H, W)
             return output * self._scale, correct * self._scale
+
+
+class ResNet18ImageTrainable(ResNet18Trainable):
+    """net.py's ResNet18_NO_BN_l2_image under a tape: ResNet18Image as a torch.nn.Module, ResNet18Trainable with img_conv
+    (autograd.conv2d_image) in front of the stems.  weights: as ResNet18Image takes them; the parameters are <layer>.kernel and
+    <layer>.bias, img_conv's among them.  forward(input_lidar, input_rgb) returns the bits ResNet18Image returns for the same
+    weights.  input_rgb is a constant: the image is data, img_conv has no data gradient, and an input_rgb that requires a
+    gradient raises ValueError.
+
+    The tensor with three consumers at level 1 is now the [image | stems] concat, 64 + 16 scale_num wide: its gradient is
+    (d conv1a + d conv1a_extra) + d concat, two-term sums as before; img_conv reads the channels 0 .. 63 of it in place and stem
+    k the channels 64 + 16 k on (torch.cat's backward hands out slices, autograd's convolutions read them at an offset)."""
+
+    INFERENCE = ResNet18Image
+
+    def _image(self, rgb):
+        from . import autograd
+
+        return autograd.conv2d_image(rgb, self.img_conv.kernel, self.img_conv.bias, "leaky", LEAKY_ALPHA)
+
+    def forward(self, input_lidar, input_rgb):
+        """input_lidar: [B,H,W] in metres, H and W multiples of 8; input_rgb: contiguous float32 CUDA tensor [B,H,W,3]; both
+        constants.  Returns two [B,H,W] tensors."""
+        if input_rgb.requires_grad:
+            raise ValueError("input_rgb is a constant: the image is data and img_conv has no data gradient; pass input_rgb.detach()")
+        _check_tensor(input_rgb, "input_rgb", layout="[B,H,W,3]")
+        if input_lidar.dim() == 3 and (tuple(input_rgb.shape) != tuple(input_lidar.shape) + (3,) or input_rgb.device != input_lidar.device):
+            raise ValueError("input_rgb must be %s on %s, got %s" % (tuple(input_lidar.shape) + (3,), input_lidar.device, tuple(input_rgb.shape)))
+        return self._run(input_lidar, input_rgb)

@@ -934,6 +934,63 @@ int dtfill_conv2d_transpose_backward_weights(const float *x,
                                              void *workspace, size_t ws_bytes, void *stream);
 
 /*
+ * dtfill_conv2d_image and dtfill_conv2d_image_backward_weights: the layer that reads the image, img_conv = Conv2D(64, (3,3)) of
+ * ResNet18_NO_BN_l2_image (solution_DeepNet/net.py:3407, 3645) and of its _light_image and _large_image kin, on the [B,H,W,3]
+ * tensor dtfill_rgb_read() emits, in the same sense as dtfill_conv2d below: every output bit is fixed here.
+ *
+ * dtfill_conv2d_image.  Stride 1, 'same', NHWC.  x: float32 [B,H,W,Cin], Cin 2, 3 or 4; w: float32 [ksize,ksize,Cin,Cout], a
+ * Keras Conv2D.kernel as stored (cross-correlation); ksize 1, 3, 5 or 7; Cout a multiple of 16, at least 16; bias: [Cout],
+ * nullable; act, alpha, out, out_channels and out_offset as in dtfill_conv2d.
+ * THE CONTRACT is dtfill_conv2d's statement with its single group (Cin < 16).  Per output (b, h, v, o), r = (ksize - 1) / 2:
+ *   acc = +0
+ *   for i in 0 .. ksize - 1:  for j in 0 .. ksize - 1:         the taps in raster order
+ *     for c in 0 .. Cin - 1:
+ *       a = x[b, h + i - r, v + j - r, c] inside the frame, +0.0f outside it        (padding taps are links of the chain)
+ *       acc = fmaf(a, w[i, j, c, o], acc)
+ *   y = acc + bias[o]                                          one rounded add; skipped when bias is NULL
+ *   y = act == DTFILL_CONV_LEAKY ? (y > 0 ? y : y * alpha) : y
+ * The chain has ksize^2 Cin links, 27 for the RGB stem, which do not fill whole matrix-core steps of four: a link that pads
+ * the last step has +0 as BOTH operands.  So only the sign of a zero can change, +0 and -0 count as equal, and no zero ever
+ * meets a non-finite partner: an infinite input or weight makes NaN only where the statement above does.  Non-finite values
+ * follow fmaf.  The bits are a function of the inputs and the shape alone, never of the tiling, the grid or the position in
+ * the batch.  A float32 evaluation in any other order lies within gamma_(K+2) (sum |x| |w| + |bias|), K = ksize^2 Cin.
+ * Pointers need float alignment only.  Asynchronous on `stream`; no workspace, no allocation, no atomics, no host
+ * synchronisation.  out may not alias x.
+ * Returns, all checked before any HIP call and in this order: DTFILL_ERR_NULL for a NULL x, w or out; DTFILL_ERR_SHAPE unless
+ * ksize is 1, 3, 5 or 7, Cin is 2, 3 or 4, Cout is a multiple of 16 and at least 16, 0 <= out_offset and out_offset + Cout <=
+ * out_channels, B, H, W >= 1, B H W max(Cin, out_channels) < 2^31, act is one of the two values and alpha is finite; then
+ * DTFILL_ERR_LAUNCH if a launch failed.
+ *
+ * dtfill_conv2d_image_backward_weights.  dw: float32 [ksize,ksize,Cin,Cout]; db: float32 [Cout], nullable; both fully
+ * overwritten.  THE CONTRACT is dtfill_conv2d_backward_weights' two-level statement with Cout any multiple of 16:
+ * g = y > 0 ? dy : dy * alpha; level 1 an fmaf chain per segment of DTFILL_CONV_BW_ROWS x DTFILL_CONV_BW_COLS pixels in raster
+ * order, p = fmaf(x[b, h + i - r, v + j - r, c] or +0.0f, g[b, h, v, o], p); level 2 the segments' partials added in (b, t, s)
+ * order from +0, one rounded add each; db with a = 1.0f.  dy, y, their widths and offsets, act and alpha as there.
+ * THERE IS NO DATA GRADIENT: the image is data.  train.py:253 differentiates with respect to the model's variables only, and
+ * nothing upstream of img_conv has one.
+ * workspace: dtfill_conv2d_image_backward_workspace_bytes(B, H, W, Cin, ksize, Cout) bytes, 256-byte aligned: the segments'
+ * partials, 4 S (ksize^2 Cin + 1) Cout bytes with S = B ceil(H / R) ceil(W / C), rounded up to 256.  Pure host arithmetic; 0
+ * for a shape outside the domain.  Asynchronous on `stream`: no allocation, no float atomics, no host synchronisation.
+ * Returns as dtfill_conv2d_backward_weights, all checked before any HIP call and in this order: DTFILL_ERR_NULL for a NULL x,
+ * dy, dw, workspace, or a NULL y under DTFILL_CONV_LEAKY; DTFILL_ERR_SHAPE unless the shape is in dtfill_conv2d_image's domain,
+ * every offset lies in its tensor, B H W max(Cin, Cout, dy_channels, y_channels) < 2^31, (ksize^2 Cin + 1) Cout < 2^31, act is one
+ * of the two values and alpha is finite and >= 0; DTFILL_ERR_WORKSPACE for a workspace too small or not aligned; then
+ * DTFILL_ERR_LAUNCH.
+ */
+size_t dtfill_conv2d_image_backward_workspace_bytes(int B, int H, int W, int Cin, int ksize, int Cout);
+int dtfill_conv2d_image_backward_weights(const float *x,
+                                         const float *dy, int dy_channels, int dy_offset,
+                                         const float *y /* nullable if linear */, int y_channels, int y_offset,
+                                         int B, int H, int W, int Cin, int ksize, int Cout,
+                                         int act, float alpha,
+                                         float *dw, float *db /* nullable */,
+                                         void *workspace, size_t ws_bytes, void *stream);
+int dtfill_conv2d_image(const float *x, int B, int H, int W, int Cin,
+                        const float *w, const float *bias /* nullable */, int ksize, int Cout,
+                        int act, float alpha,
+                        float *out, int out_channels, int out_offset, void *stream);
+
+/*
  * dtfill_conv2d_strided and dtfill_conv2d_transpose: the wide layers of ResNet18_NO_BN_l2 (solution_DeepNet/net.py:245-745),
  * in the same sense as dtfill_conv2d below, whose statement they extend: every output bit is fixed here.  Convolutions with
  * Cin == 1 or Cout == 1 (the correction branch, the stems, conv_output) stay with dtfill_conv2d.
