@@ -16,7 +16,7 @@ from .tools import depth_read, depth_read_batch, nearest_source, rgb_read, rgb_r
 from .tools import map_points_on_image, project_points
 from .tools import get_all_points, unproject_frames
 from .tools import nyu_read_batch, nyu_taps
-from .tools import conv2d
+from .tools import conv2d, max_pool
 from . import demo  # demo.py's own generate_multi_channel / _with_image / create_weight_matrix, reached as <package>.demo.*
 from .postfill import Result, Result_NYU, depth_floor, depth_to_png16, kitti_rows, nyu_eval_crop
 
@@ -56,7 +56,7 @@ __all__ = [
     "depth_read", "depth_read_batch", "rgb_read", "rgb_read_batch", "rgb_read_device", "nearest_source",
     "map_points_on_image", "project_points", "project_points_device", "get_all_points", "unproject_frames",
     "unproject_device", "unproject_backward_device", "nyu_read_batch", "nyu_read_device", "nyu_taps",
-    "conv2d", "conv2d_strided", "conv2d_transpose", "conv2d_image", "pack_transpose_kernel", "net", "demo", "fill", "DtFill",
+    "conv2d", "max_pool", "conv2d_strided", "conv2d_transpose", "conv2d_image", "pack_transpose_kernel", "net", "demo", "fill", "DtFill",
     "shard_range", "gather_frames", "fill_sharded", "release_host_slab", "build", "load", "METRICS", "DtfillError",
     "Result", "Result_NYU", "depth_floor", "depth_to_png16", "kitti_rows", "nyu_eval_crop",
 ]

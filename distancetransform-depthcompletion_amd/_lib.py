@@ -111,10 +111,13 @@ _ABI = {
     "dtfill_conv2d_image_backward_workspace_bytes": (sz, [ci, ci, ci, ci, ci, ci]),
     "dtfill_conv2d_image_backward_weights": (ci, [vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp, vp, vp, sz, vp]),
     "dtfill_conv2d_image": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, cf, vp, ci, ci, vp]),
+    "dtfill_max_pool_pyramid": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, ci, ci, vp, ci, ci, vp, ci, ci, vp]),
+    "dtfill_max_pool_pyramid_backward": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, ci, ci, vp, ci, ci, vp, ci, ci, vp, vp]),
     "dtfill_conv2d_strided": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, vp, ci, cf, vp, ci, ci, vp]),
     "dtfill_conv2d_transpose": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, cf, vp, ci, ci, vp]),
     "dtfill_conv2d": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, cf, vp, ci, ci, vp]),
 }
+POOL_LEVELS = (2, 4, 8)  # the window sizes of dtfill_max_pool_pyramid, in the order of its out and dy arguments
 SYMBOLS = tuple(_ABI)
 del vp, ci, cf, sz, cu, ll, cs  # (the table's shorthands, not names of this module)
 STATS = ("all", "window", "anydist", "sky", "points", "colt")  # DTFILL_STATS_*

@@ -291,6 +291,41 @@ class _Conv(torch.autograd.Function):
         return None, dx, (dw if want_w else None), db, dr, None, None, None
 
 
+class _MaxPoolPyramid(torch.autograd.Function):
+    """The pooled tensors of `levels` from x by one forward call; the backward is one call too, with whichever gradients arrived."""
+
+    @staticmethod
+    def forward(ctx, x, levels):
+        outs = device.max_pool_pyramid_device(x, levels)
+        ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None: a NULL dy
+        ctx.levels = levels
+        ctx.save_for_backward(x)  # the winners are found again from x: no argmax tensor is kept
+        return outs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        if not ctx.needs_input_grad[0] or all(g is None for g in grads):
+            return None, None
+        (x,) = ctx.saved_tensors
+        slices = [(None, 0) if g is None else _channel_slice(g) for g in grads]
+        dx = device.max_pool_pyramid_backward_device(x, [t for t, _ in slices], ctx.levels, 0, x.shape[3], [at for _, at in slices])
+        return dx, None
+
+
+def max_pool_pyramid(x, levels=(2, 4, 8)):
+    """tf.nn.max_pool of one tensor by every k of `levels` (2, 4, 8; ksize = strides = k, 'SAME') as one differentiable operator:
+    the three pools net.py's ResNet18_NO_BN_l2_light_image takes of conv1_pre's output (net.py:4285, 4320, 4353).  x: contiguous
+    float32 CUDA tensor [B,H,W,C], C a multiple of 4, H and W multiples of the largest level.  Returns a tuple of tensors
+    [B,H/k,W/k,C] along `levels` by device.max_pool_pyramid_device (include/dtfill.h, dtfill_max_pool_pyramid): x is read once.
+    Differentiable in x, once: the backward is ONE call of dtfill_max_pool_pyramid_backward with whichever gradients arrived
+    (an unused output is a NULL dy), which finds the winners again from x and writes dx = (t_2 + t_4) + t_8 in that fixed
+    grouping, so x receives one gradient from the three pools and every bit of it is a function of the inputs alone.  A gradient
+    that is a channel slice of a wider contiguous tensor (torch.cat's backward) is read in place.  No host synchronisation in
+    either direction."""
+    return _MaxPoolPyramid.apply(x, tuple(int(k) for k in levels))
+
+
 def _conv(kind, x, w, bias, residual, stride, act, alpha):
     if not alpha >= 0:
         raise ValueError("alpha must be >= 0 (the derivative is taken by the sign of the output), got %r" % (alpha,))

@@ -65,6 +65,7 @@
 // dtfill_conv2d (SparsityCNN's layers), dtfill_conv2d_strided and dtfill_conv2d_transpose (ResNet18's wide layers), all three
 // dtfill_conv.hpp's, and their gradients dtfill_conv2d_backward_data and dtfill_conv2d_backward_weights (dtfill_conv2d's) and
 // dtfill_conv2d_strided_backward_data / _weights and dtfill_conv2d_transpose_backward_data / _weights, all dtfill_convb.hpp's.
+// dtfill_max_pool_pyramid and its backward (dtfill_pool.hpp) are compare-and-select work again, and memory-bound.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -105,6 +106,7 @@ namespace {
 #include "dtfill_near.hpp"
 #include "dtfill_conv.hpp"
 #include "dtfill_convb.hpp"
+#include "dtfill_pool.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -1422,6 +1424,67 @@ int dtfill_conv2d_transpose_backward_weights(const float *x, const float *dy, in
                                              float *dw, float *db, void *workspace, size_t ws_bytes, void *stream) {
     return convb_weights(ConvBwLayer{B, H, W, Cin, 3, Cout, 2, true, false}, x, dy, dy_channels, dy_offset, y, y_channels, y_offset,
                          act, alpha, dw, db, workspace, ws_bytes, stream);
+}
+
+// What the two pool entry points check alike; `lv`: the outs (forward) or the dys (backward) of levels 2, 4, 8, whose widths
+// and offsets count only where the pointer is not NULL.  *K: the largest requested level, 1 if there is none.
+static int pool_check(int B, int H, int W, int C, int x_channels, int x_offset, const void *const lv[3], const int lc[3],
+                      const int lo[3], int *K) {
+    *K = lv[2] ? 8 : lv[1] ? 4 : lv[0] ? 2 : 1;
+    if (B < 1 || H < 1 || W < 1 || H % *K || W % *K) return DTFILL_ERR_SHAPE;
+    if ((long long)B * H >= (1ll << 31) || (long long)B * H * W >= (1ll << 31)) return DTFILL_ERR_SHAPE;
+    if (C < 4 || C % 4 || x_channels % 4 || x_offset % 4) return DTFILL_ERR_SHAPE;
+    if (!convb_slice(B, H, W, C, x_channels, x_offset)) return DTFILL_ERR_SHAPE;
+    for (int l = 0; l < 3; ++l) {
+        const int k = 2 << l;
+        if (lv[l] && (lc[l] % 4 || lo[l] % 4 || !convb_slice(B, H / k, W / k, C, lc[l], lo[l]))) return DTFILL_ERR_SHAPE;
+    }
+    return DTFILL_OK;
+}
+
+static bool pool_vec(std::initializer_list<const void *> ptrs) {
+    for (const void *p : ptrs)
+        if ((uintptr_t)p & 15) return false;
+    return true;
+}
+
+int dtfill_max_pool_pyramid(const float *x, int B, int H, int W, int C, int x_channels, int x_offset, float *out2, int out2_channels,
+                            int out2_offset, float *out4, int out4_channels, int out4_offset, float *out8, int out8_channels,
+                            int out8_offset, void *stream) {
+    if (!x || (!out2 && !out4 && !out8)) return DTFILL_ERR_NULL;
+    const void *const lv[3] = {out2, out4, out8};
+    const int lc[3] = {out2_channels, out4_channels, out8_channels}, lo[3] = {out2_offset, out4_offset, out8_offset};
+    int K;
+    const int rc = pool_check(B, H, W, C, x_channels, x_offset, lv, lc, lo, &K);
+    if (rc != DTFILL_OK) return rc;
+    PoolArgs a{x, {nullptr, nullptr, nullptr}, {out2, out4, out8}, nullptr, B, H, W, C, x_channels, x_offset,
+               {lc[0], lc[1], lc[2]}, {lo[0], lo[1], lo[2]}, (long long)B * (H / K) * (W / K) * (C / 4)};
+    const bool vec = pool_vec({x, out2, out4, out8});
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (K == 8) pool_launch<8>(st, a, vec);
+    else if (K == 4) pool_launch<4>(st, a, vec);
+    else pool_launch<2>(st, a, vec);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+int dtfill_max_pool_pyramid_backward(const float *x, int B, int H, int W, int C, int x_channels, int x_offset, const float *dy2,
+                                     int dy2_channels, int dy2_offset, const float *dy4, int dy4_channels, int dy4_offset,
+                                     const float *dy8, int dy8_channels, int dy8_offset, float *dx, void *stream) {
+    if (!x || !dx) return DTFILL_ERR_NULL;
+    const void *const lv[3] = {dy2, dy4, dy8};
+    const int lc[3] = {dy2_channels, dy4_channels, dy8_channels}, lo[3] = {dy2_offset, dy4_offset, dy8_offset};
+    int K;
+    const int rc = pool_check(B, H, W, C, x_channels, x_offset, lv, lc, lo, &K);
+    if (rc != DTFILL_OK) return rc;
+    PoolArgs a{x, {dy2, dy4, dy8}, {nullptr, nullptr, nullptr}, dx, B, H, W, C, x_channels, x_offset,
+               {lc[0], lc[1], lc[2]}, {lo[0], lo[1], lo[2]}, (long long)B * (H / K) * (W / K) * (C / 4)};
+    const bool vec = pool_vec({x, dy2, dy4, dy8, dx});
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (K == 8) pool_backward_launch<8>(st, a, vec);
+    else if (K == 4) pool_backward_launch<4>(st, a, vec);
+    else if (K == 2) pool_backward_launch<2>(st, a, vec);
+    else pool_backward_launch<1>(st, a, vec);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 
 }  // extern "C"

@@ -847,6 +847,10 @@ def __getattr__(name):
         from . import net
 
         return getattr(net, name)
+    if name in ("max_pool_pyramid_device", "max_pool_pyramid_backward_device"):  # likewise in pool.py
+        from . import pool
+
+        return getattr(pool, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 

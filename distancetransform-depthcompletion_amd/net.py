@@ -16,8 +16,13 @@ ResNet18Image and ResNet18ImageTrainable are ResNet18_NO_BN_l2_image (net.py:338
 defaults to: ResNet18 with img_conv, the layer that reads the [B,H,W,3] image (dtfill_conv2d_image, conv2d_image_device, and
 conv2d_image_backward_weights_device, a fourth kind with no data gradient), in front of the stems.
 
-The other nine models of the reference's net.py are not here.  ResNet18_NO_BN_l2_light_image lacks only its own trunk wiring:
-its layers are all here.  The _large models still need max_pool and the stride-4 and stride-8 layers.  conv2d_device, conv2d_strided_device and conv2d_transpose_device, the device
+ResNet18LightImage and ResNet18LightImageTrainable are ResNet18_NO_BN_l2_light_image (net.py:3895-4426), the image-guided network
+at 64 channels on every level.  Its call() pools conv1_pre's output by 2, 4 and 8 (tf.nn.max_pool, net.py:4285, 4320, 4353):
+that is ONE dtfill_max_pool_pyramid call here (device.max_pool_pyramid_device, autograd.max_pool_pyramid).
+
+The other eight models of the reference's net.py are not here.  ResNet18_NO_BN_l2_large_image lacks only its own trunk wiring: it
+has no pooling and no stride-4 or stride-8 layer (those are commented-out lines of the reference), so its layers are all here.
+conv2d_device, conv2d_strided_device and conv2d_transpose_device, the device
 functions of one convolution, are reached as device.<name> as well; they live here, beside device.py's helpers, with their
 argument checks in tests/test_conv2d.py, tests/test_gpu_conv2d.py, tests/test_conv2d_strided.py and
 tests/test_gpu_conv2d_strided.py.
@@ -481,6 +486,30 @@ def layer_shapes_resnet18_image(scale_num=4, if_correct=True):
     return shapes
 
 
+LIGHT_WIDTH = 64  # channels of every level of the light network, and of conv1_pre's output, the tensor it pools
+LIGHT_POOLS = (2, 4, 8)  # tf.nn.max_pool of conv1_pre's output behind levels 2, 3 and 4 (net.py:4285, 4320, 4353)
+
+
+def layer_shapes_resnet18_light_image(scale_num=4, if_correct=True):
+    """{layer name: (ksize, Cin, Cout)} of the layers ResNet18_NO_BN_l2_light_image's forward uses (net.py:3895-4426): 64 channels
+    on every level.  conv1_pre folds the stems into 64 channels; conv1a and conv1a_extra read [image | conv1_pre]; the layers
+    that read a level's tensor concatenated with a pooled conv1_pre output (conv3a, conv4a, their _extra, upsample_4) read 128
+    channels, and the two _post layers whose skip tensor is such a concat read 192."""
+    shapes = _head_shapes(scale_num, if_correct)
+    w = LIGHT_WIDTH
+    shapes.update(img_conv=(3, 3, IMAGE_WIDTH), conv1_pre=(3, STEM_WIDTH * scale_num, w))
+    for level, below in enumerate((IMAGE_WIDTH + w, w, 2 * w, 2 * w), 1):
+        shapes["conv%da" % level] = (3, below, w)
+        shapes["conv%db" % level] = (3, w, w)
+        shapes["conv%da_extra" % level] = (1, below, w)
+        shapes["conv%dc" % level] = (3, w, w)
+        shapes["conv%dd" % level] = (3, w, w)
+    shapes.update(upsample_4=(3, 2 * w, w), upsample_4_post=(3, 3 * w, w), upsample_3=(3, w, w), upsample_3_post=(3, 3 * w, w),
+                  upsample_2=(3, w, w), upsample_2_post=(3, 2 * w, w), upsample_1=(3, w, w), upsample_1_post=(3, 2 * w, w),
+                  conv_output=(1, w, 1))
+    return shapes
+
+
 def _keras_shape(name, k, cin, cout):
     return (k, k, cout, cin) if name in RESNET_TRANSPOSED else (k, k, cin, cout)
 
@@ -493,6 +522,11 @@ def glorot_weights_resnet18(seed, scale_num=4, if_correct=True, bias=0.0):
 def glorot_weights_resnet18_image(seed, scale_num=4, if_correct=True, bias=0.0):
     """glorot_weights() for ResNet18Image: float32 numpy arrays of Keras' shapes, [3,3,Cout,Cin] for the transposed layers."""
     return _glorot(layer_shapes_resnet18_image, seed, scale_num, if_correct, bias)
+
+
+def glorot_weights_resnet18_light_image(seed, scale_num=4, if_correct=True, bias=0.0):
+    """glorot_weights() for ResNet18LightImage: float32 numpy arrays of Keras' shapes, [3,3,Cout,Cin] for the transposed layers."""
+    return _glorot(layer_shapes_resnet18_light_image, seed, scale_num, if_correct, bias)
 
 
 class _Buffers:
@@ -815,6 +849,88 @@ class ResNet18Image(ResNet18):
         return self._run(input_lidar, input_rgb.detach())
 
 
+class _LightBuffers(_Buffers):
+    """_Buffers and the light network's activations: three 64-channel tensors per level that take turns, and the tensors a
+    tf.concat of the reference is.  total1: [image | conv1_pre]; pooled[k]: [the level's tensor | max_pool by k of conv1_pre]
+    at 1 / k of the frame, k = 2, 4, 8; cat[n]: [upsample_n | its skip tensor], n = 4, 3, 2, 1."""
+
+    def __init__(self, device, B, H, W, scale_num):
+        super().__init__(device, B, H, W, scale_num)
+        w = LIGHT_WIDTH
+        self.level = [[self.new(B, H >> k, W >> k, w) for _ in range(3)] for k in range(4)]
+        self.total1 = self.new(B, H, W, IMAGE_WIDTH + w)
+        self.pooled = {k: self.new(B, H // k, W // k, 2 * w) for k in LIGHT_POOLS}
+        self.cat = {4: self.new(B, H // 4, W // 4, 3 * w), 3: self.new(B, H // 2, W // 2, 3 * w), 2: self.new(B, H, W, 2 * w),
+                    1: self.new(B, H, W, 2 * w)}
+
+
+class ResNet18LightImage(ResNet18Image):
+    """net.py's ResNet18_NO_BN_l2_light_image (net.py:3895-4426) for inference: the image-guided network at 64 channels on every
+    level, the variant for full KITTI frames.  weights: {layer name: (kernel, bias)} under the reference's attribute names
+    (layer_shapes_resnet18_light_image), as Keras stores them.  Beside the narrower layers it differs from ResNet18Image in
+    this: conv1_pre, a linear 3x3 layer, folds the stems into lidar_conv_total, 64 channels; conv1a and conv1a_extra read
+    [image | lidar_conv_total]; lidar_conv_total is max-pooled by 2, 4 and 8 and concatenated BEHIND tensor_2_total,
+    tensor_3_total and tensor_4, and those 128-wide tensors feed the next level and the skip concats; level 4 has no second
+    residual; the last concat is [upsample_1 | lidar_conv_total].
+
+    Here conv1_pre writes the channels 64 .. 127 of the [image | total] tensor, and ONE dtfill_max_pool_pyramid call reads them
+    there and writes the upper halves of the three levels' wide tensors, whose lower halves conv2d, conv3d and conv4d write: the
+    three pools cost one pass over the full-resolution tensor.  Called as net(input_lidar, input_rgb); H and W multiples of 8;
+    detached, no host synchronisation, no activation buffer allocated after the first call at a shape, the returned tensors are
+    the instance's own: as ResNet18Image."""
+
+    NAME = "ResNet18_NO_BN_l2_light_image"
+    KNOWN = tuple(layer_shapes_resnet18_light_image(4, True)) + ("lidar_conv_extra_3",)
+    layer_shapes = staticmethod(layer_shapes_resnet18_light_image)
+
+    def _run(self, input_lidar, rgb):
+        x = input_lidar.detach()
+        if x.dim() == 3 and (x.shape[1] % 8 or x.shape[2] % 8):
+            raise ValueError("H and W must be multiples of 8, got %d x %d" % tuple(x.shape[1:]))
+        _check_tensor(x, "input_lidar")
+        B, H, W = x.shape
+        dev = x.device
+        _check_tensor(rgb, "input_rgb", layout="[B,H,W,3]")
+        if tuple(rgb.shape) != (B, H, W, 3) or rgb.device != dev:
+            raise ValueError("input_rgb must be [%d,%d,%d,3] on %s, got %s" % (B, H, W, dev, tuple(rgb.shape)))
+        w = LIGHT_WIDTH
+        with torch.cuda.device(dev):
+            on, threshold, scale = self._state(dev)
+            key = (dev, B, H, W)
+            if key not in self._buffers:
+                self._buffers[key] = _LightBuffers(dev, B, H, W, self.scale_num)
+            t = self._buffers[key]
+            self._head(on, threshold, scale, x, t)
+            kernel, bias = on["img_conv"]  # net.py:4166-4222: lidar_conv_total_1 = tf.concat([img_conv_1, lidar_conv_total])
+            conv2d_image_device(rgb, kernel, bias, "leaky", LEAKY_ALPHA, t.total1, 0)
+            kernel, bias = on["conv1_pre"]  # no leaky_relu follows it
+            conv2d_strided_device(t.stems, kernel, bias, 1, None, "linear", LEAKY_ALPHA, t.total1, IMAGE_WIDTH)
+            _device.max_pool_pyramid_device(t.total1, LIGHT_POOLS, IMAGE_WIDTH, w, [t.pooled[k] for k in LIGHT_POOLS], [w] * 3)
+            below = t.total1
+            for k in range(4):  # net.py:4224-4355; `below` ends as tensor_<k+1>_total (level 4: tensor_4), 128 wide from level 2 on
+                p, q, r = t.level[k]
+                name, stride = "conv%d" % (k + 1), 1 if k == 0 else 2
+                out = q if k == 0 else t.pooled[1 << k]  # conv<k+1>d writes in front of the pooled channels
+                self._wide(on, below, name + "a", p, stride)
+                self._wide(on, below, name + "a_extra", q, stride, act="linear")
+                self._wide(on, p, name + "b", r, residual=q)
+                self._wide(on, r, name + "c", p)
+                self._wide(on, p, name + "d", out, residual=r if k < 3 else None)
+                below = out
+            skips = {4: t.pooled[4], 3: t.pooled[2], 2: t.level[0][1], 1: t.total1[..., IMAGE_WIDTH:]}
+            for n in (4, 3, 2):  # net.py:4360-4404: upsample_<n>, the concat with its skip tensor, upsample_<n>_post
+                self._up(on, below, "upsample_%d" % n, t.cat[n])
+                t.cat[n][..., w:].copy_(skips[n])
+                below = self._wide(on, t.cat[n], "upsample_%d_post" % n, t.level[n - 2][0])
+            self._wide(on, below, "upsample_1", t.cat[1])  # net.py:4408-4422
+            t.cat[1][..., w:].copy_(skips[1])
+            self._wide(on, t.cat[1], "upsample_1_post", t.level[0][2])
+            self._conv(on, t.level[0][2], "conv_output", "linear", t.one)
+            torch.mul(t.one.view(B, H, W), scale, out=t.output)
+            torch.mul(t.correct, scale, out=t.correct_out)
+        return t.output, t.correct_out
+
+
 class ResNet18Trainable(_TrainableNet):
     """net.py's ResNet18_NO_BN_l2 under a tape: the network of ResNet18 above as a torch.nn.Module, the network train.py:113
     trains, for train.py:232-254's step.  weights: as ResNet18 takes them; they become the parameters <layer>.kernel and
@@ -913,3 +1029,51 @@ class ResNet18ImageTrainable(ResNet18Trainable):
         if input_lidar.dim() == 3 and (tuple(input_rgb.shape) != tuple(input_lidar.shape) + (3,) or input_rgb.device != input_lidar.device):
             raise ValueError("input_rgb must be %s on %s, got %s" % (tuple(input_lidar.shape) + (3,), input_lidar.device, tuple(input_rgb.shape)))
         return self._run(input_lidar, input_rgb)
+
+
+class ResNet18LightImageTrainable(ResNet18ImageTrainable):
+    """net.py's ResNet18_NO_BN_l2_light_image under a tape: ResNet18LightImage as a torch.nn.Module over the same operators as
+    ResNet18ImageTrainable and autograd.max_pool_pyramid.  weights: as ResNet18LightImage takes them; the parameters are
+    <layer>.kernel and <layer>.bias in Keras' layouts.  forward(input_lidar, input_rgb) returns the bits ResNet18LightImage
+    returns for the same weights; input_rgb is a constant.
+
+    Every float32 gradient sum of the tape has two terms.  lidar_conv_total, conv1_pre's output, has three consumers, the image
+    concat, the pools and the last concat: the first two read one identity view, and the three pools are ONE operator whose
+    backward sums its levels in a fixed grouping, so the tensor's gradient is (d concat_image + d pools) + d concat_1.  The
+    128-wide tensors of levels 2 and 3 have three consumers each, conv(k+1)a, conv(k+1)a_extra and the skip concat: the two
+    convolutions read one view, as in ResNet18Trainable, as they do of tensor_1_total."""
+
+    INFERENCE = ResNet18LightImage
+
+    def _run(self, input_lidar, rgb):
+        from . import autograd
+
+        x = input_lidar.detach()
+        if x.dim() == 3 and (x.shape[1] % 8 or x.shape[2] % 8):
+            raise ValueError("H and W must be multiples of 8, got %d x %d" % tuple(x.shape[1:]))
+        _check_tensor(x, "input_lidar")
+        B, H, W = x.shape
+        with torch.cuda.device(x.device):
+            correct, stems = self._head(x)
+            total = self._wide(stems, "conv1_pre", act="linear")  # lidar_conv_total, net.py:4220
+            both = total.view_as(total)  # ONE consumer of it for the image concat and the pools; the last concat is the other
+            pooled = dict(zip((2, 3, 4), autograd.max_pool_pyramid(both, LIGHT_POOLS)))  # level -> the pool behind its tensor
+            below, totals = torch.cat([self._image(rgb), both], dim=3), []
+            for level in (1, 2, 3, 4):  # net.py:4224-4355
+                name, stride = "conv%d" % level, 1 if level == 1 else 2
+                both = below.view_as(below)  # ONE consumer of `below` for the two convolutions; the skip concat is the other
+                t = self._wide(both, name + "a", stride)
+                add = self._wide(both, name + "a_extra", stride, act="linear")
+                mid = self._wide(t, name + "b", residual=add)
+                t = self._wide(mid, name + "c")
+                below = self._wide(t, name + "d", residual=mid if level < 4 else None)
+                if level > 1:
+                    below = torch.cat([below, pooled[level]], dim=3)
+                totals.append(below)
+            for level in (4, 3, 2):  # net.py:4360-4404
+                up = torch.cat([self._up(below, "upsample_%d" % level), totals[level - 2]], dim=3)
+                below = self._wide(up, "upsample_%d_post" % level)
+            up = torch.cat([self._wide(below, "upsample_1"), total], dim=3)  # net.py:4408-4422: lidar_conv_total, not the stems
+            t = self._wide(up, "upsample_1_post")
+            output = self._conv(t, "conv_output", "linear").view(B, H, W)
+            return output * self._scale, correct * self._scale

@@ -165,6 +165,17 @@ def conv2d(x, kernel, bias=None, act="linear", alpha=0.2):
     return _device.conv2d_device(_upload(a, dev), _upload(k, dev), b, act, alpha).cpu().numpy()
 
 
+def max_pool(x, ksize):
+    """tf.nn.max_pool(x, ksize, ksize, 'SAME') as a numpy function (include/dtfill.h, dtfill_max_pool_pyramid with one level):
+    x [B,H,W,C] with C a multiple of 4, ksize 2, 4 or 8, H and W multiples of it.  The winner of a window is its first NaN if
+    it holds one, else its raster-first maximum.  Returns float32 [B,H/ksize,W/ksize,C]."""
+    a = _as_f32_frames(x)
+    if a.ndim != 4:
+        raise ValueError("max_pool expects x [B,H,W,C]")
+    dev = _device.default_op().device
+    return _device.max_pool_pyramid_device(_upload(a, dev), (int(ksize),))[0].cpu().numpy()
+
+
 def subsample_lidar(sparse_depth, intrinsic, extrinsic, keep_ratio=0.25, n_bins=64):
     """subsample_Lidar_train.py / subsample_Lidar_val.py: get_all_points -> calculate_angle -> sample(keep_ratio) ->
     map_points_on_image, in one call (the caller's `* 256 -> uint16` PNG write stays as it is).  sparse_depth [H,W],

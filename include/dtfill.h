@@ -991,6 +991,57 @@ int dtfill_conv2d_image(const float *x, int B, int H, int W, int Cin,
                         float *out, int out_channels, int out_offset, void *stream);
 
 /*
+ * dtfill_max_pool_pyramid and dtfill_max_pool_pyramid_backward: tf.nn.max_pool of ONE tensor by 2, 4 and 8 (ksize = strides,
+ * padding 'SAME') in one pass, which is what ResNet18_NO_BN_l2_light_image does with the output of conv1_pre
+ * (solution_DeepNet/net.py:4285, 4320, 4353), and its gradient.  The forward reads x once and writes up to three tensors; the
+ * backward writes dx once, in a fixed order.  With two of the three levels NULL a call is a plain max_pool of size 2, 4 or 8.
+ *
+ * x: float32 [B,H,W,x_channels], NHWC, of which the channels x_offset .. x_offset + C - 1 are pooled.  out_k (k = 2, 4, 8):
+ * float32 [B,H/k,W/k,out_k_channels], of which only the channels out_k_offset .. out_k_offset + C - 1 are written and the
+ * others left as they were (tf.concat); a NULL out_k skips that level, and its width and offset are then not looked at.
+ * H and W must be multiples of the largest requested k.  Under that rule TensorFlow's 'SAME' pads nothing and equals 'VALID';
+ * the network cannot run at any other size anyway, since its transposed layers double (ResNet18's multiples-of-8 rule).
+ *
+ * THE CONTRACT, forward.  For level k, output (b, h, v, c), the window is the pixels (k h + i, k v + j), 0 <= i, j < k,
+ * scanned in raster order, i outermost:
+ *   best = the first element
+ *   for every later element e:  if best is not NaN and (e > best or e is NaN): best = e
+ * So the first NaN of the window wins if there is one; otherwise the first element that no other exceeds.  +0 and -0 compare
+ * equal, so the earlier of the two wins.  The output is the winner's own bits.  Every level's winner is the raster-first one
+ * of ITS window: a level-8 winner is not the first in any order of 2x2 or 4x4 blocks.  (Maxima at pixels (1,0) and (0,2) of
+ * one 4x4 window lie in its 2x2 blocks 0 and 1; the winner is (0,2).)
+ *
+ * THE CONTRACT, backward.  Winners are recomputed from x; no argmax tensor is stored.  dy_k: float32 [B,H/k,W/k,dy_k_channels]
+ * read at dy_k_offset .. + C - 1, nullable; dx: float32 [B,H,W,C], dense.  Per input element p, in float32:
+ *   t_k   = dy_k at p's level-k window, if p is that window's winner and dy_k is not NULL;  +0 otherwise
+ *   dx[p] = (t_2 + t_4) + t_8                                  two rounded adds, in this grouping
+ * Every element of dx is written, zeros included.  The windows of one level are disjoint: no atomics, no workspace, and
+ * the bits are a function of the inputs alone.  H and W must be multiples of the largest k whose dy is not NULL; with every
+ * dy NULL any frame is taken and dx is all +0.
+ * That first-in-scan-order is TensorFlow's own choice of winner is restated here from its CPU kernel's loop, not tested:
+ * TensorFlow is not part of this project's tests.  What the tests pin is this statement, and torch where torch is unambiguous
+ * (values without NaN; gradients without ties).
+ *
+ * Pointers need float alignment only; when x, dx and every out or dy are 16-byte aligned, all accesses are 16-byte ones.
+ * No out may alias x; dx may not alias x or any dy.  Asynchronous on `stream`; no workspace, no allocation, no atomics, no
+ * host synchronisation.
+ * Returns, all checked before any HIP call and in this order: DTFILL_ERR_NULL for a NULL x, a NULL dx, or (forward) every out
+ * NULL; DTFILL_ERR_SHAPE unless B, H, W >= 1, H and W are multiples of the largest requested k, C >= 4, C, x_channels,
+ * x_offset and the width and offset of every requested level are multiples of 4, 0 <= offset and offset + C <= width for x and
+ * for every requested level, B H W x_channels < 2^31 and B (H/k) (W/k) width_k < 2^31; then DTFILL_ERR_LAUNCH if a launch
+ * failed.
+ */
+int dtfill_max_pool_pyramid(const float *x, int B, int H, int W, int C, int x_channels, int x_offset,
+                            float *out2 /* nullable */, int out2_channels, int out2_offset,
+                            float *out4 /* nullable */, int out4_channels, int out4_offset,
+                            float *out8 /* nullable */, int out8_channels, int out8_offset, void *stream);
+int dtfill_max_pool_pyramid_backward(const float *x, int B, int H, int W, int C, int x_channels, int x_offset,
+                                     const float *dy2 /* nullable */, int dy2_channels, int dy2_offset,
+                                     const float *dy4 /* nullable */, int dy4_channels, int dy4_offset,
+                                     const float *dy8 /* nullable */, int dy8_channels, int dy8_offset,
+                                     float *dx /* dense [B,H,W,C] */, void *stream);
+
+/*
  * dtfill_conv2d_strided and dtfill_conv2d_transpose: the wide layers of ResNet18_NO_BN_l2 (solution_DeepNet/net.py:245-745),
  * in the same sense as dtfill_conv2d below, whose statement they extend: every output bit is fixed here.  Convolutions with
  * Cin == 1 or Cout == 1 (the correction branch, the stems, conv_output) stay with dtfill_conv2d.
