@@ -39,8 +39,8 @@ def __getattr__(name):
     if name in ("conv2d_strided", "conv2d_transpose", "conv2d_image", "pack_transpose_kernel"):  # numpy forms of the wide and image convolutions
         import importlib
 
-        return getattr(importlib.import_module(__name__ + ".net"), name)
-    if name == "net":  # <package>.net.SparsityCNN, .ResNet18 and .ResNet18Image (inference), .SparsityCNNTrainable (a torch.nn.Module); imports torch
+        return getattr(importlib.import_module(__name__ + ".conv"), name)
+    if name == "net":  # <package>.net: the networks, inference classes and their torch.nn.Module forms; imports torch
         import importlib
 
         return importlib.import_module(__name__ + ".net")

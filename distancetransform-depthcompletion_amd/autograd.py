@@ -25,7 +25,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import device
-from . import net as _net
+from .conv import _backward_data, _backward_weights, _forward
 
 
 class _WindowSteps(torch.autograd.Function):
@@ -251,19 +251,12 @@ def _channel_slice(g):
 
 
 class _Conv(torch.autograd.Function):
-    """y of a convolution of `kind` (net._KINDS: narrow, strided, transposed, image) by its device function; the backward asks the
-    library only for the gradients that are needed, through net.py's two cores."""
+    """y of a convolution of `kind` (conv._KINDS: narrow, strided, transposed, image; w of a transposed one is the packed kernel
+    [3,3,Cin,Cout]); the backward asks the library only for the gradients that are needed.  Both through conv.py's cores."""
 
     @staticmethod
     def forward(ctx, kind, x, w, bias, residual, stride, act, alpha):
-        if kind == "narrow":
-            y = device.conv2d_device(x, w, bias, act, alpha)
-        elif kind == "strided":
-            y = device.conv2d_strided_device(x, w, bias, stride, residual, act, alpha)
-        elif kind == "image":
-            y = device.conv2d_image_device(x, w, bias, act, alpha)
-        else:  # w: the packed kernel [3,3,Cin,Cout]
-            y = device.conv2d_transpose_device(x, w, bias, act, alpha)
+        y = _forward(kind, x, w, bias, stride, residual, act, alpha, None, 0)
         ctx.set_materialize_grads(False)  # an unused y arrives as None: nothing is launched for it
         ctx.kind, ctx.stride, ctx.act, ctx.alpha = kind, stride, act, alpha
         ctx.save_for_backward(x, w, None if act == "linear" else y)  # (a linear layer's derivative does not read y)
@@ -279,7 +272,7 @@ class _Conv(torch.autograd.Function):
         dy, at = _channel_slice(g_y)
         dx = dr = dw = db = None
         if want_x:
-            dx = _net._backward_data(ctx.kind, dy, w, ctx.stride, y, ctx.act, ctx.alpha, at, 0, None, 0, want_r)
+            dx = _backward_data(ctx.kind, dy, w, ctx.stride, y, ctx.act, ctx.alpha, at, 0, None, 0, want_r)
             if want_r:
                 dx, dr = dx
             dx = dx.view(x.shape)  # ([B,H,W,1] of a plane x)
@@ -287,7 +280,7 @@ class _Conv(torch.autograd.Function):
             g = dy[..., at:at + w.shape[3]]
             dr = (g if y is None else torch.where(y > 0, g, g * ctx.alpha)).contiguous()
         if want_w or want_b:
-            dw, db = _net._backward_weights(ctx.kind, x, dy, w.shape[0], ctx.stride, y, ctx.act, ctx.alpha, at, 0, w.shape[3], want_b)
+            dw, db = _backward_weights(ctx.kind, x, dy, w.shape[0], ctx.stride, y, ctx.act, ctx.alpha, at, 0, w.shape[3], want_b)
         return None, dx, (dw if want_w else None), db, dr, None, None, None
 
 

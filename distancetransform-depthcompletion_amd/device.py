@@ -843,10 +843,10 @@ def __getattr__(name):
                 "conv2d_backward_weights_device", "conv2d_backward_workspace_bytes", "conv2d_strided_backward_data_device",
                 "conv2d_strided_backward_weights_device", "conv2d_transpose_backward_data_device",
                 "conv2d_transpose_backward_weights_device", "conv2d_wide_backward_workspace_bytes", "conv2d_image_device",
-                "conv2d_image_backward_weights_device", "conv2d_image_backward_workspace_bytes"):  # likewise in net.py
-        from . import net
+                "conv2d_image_backward_weights_device", "conv2d_image_backward_workspace_bytes"):  # likewise in conv.py
+        from . import conv
 
-        return getattr(net, name)
+        return getattr(conv, name)
     if name in ("max_pool_pyramid_device", "max_pool_pyramid_backward_device"):  # likewise in pool.py
         from . import pool
 
