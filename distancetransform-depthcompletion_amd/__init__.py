@@ -48,6 +48,10 @@ def __getattr__(name):
         import importlib
 
         return importlib.import_module(__name__ + ".autograd")
+    if name == "optim":  # <package>.optim.KerasAdam, adam_step_device and the numpy adam_step: train.py's optimizer (imports torch)
+        import importlib
+
+        return importlib.import_module(__name__ + ".optim")
     raise AttributeError(name)
 
 
@@ -56,7 +60,7 @@ __all__ = [
     "depth_read", "depth_read_batch", "rgb_read", "rgb_read_batch", "rgb_read_device", "nearest_source",
     "map_points_on_image", "project_points", "project_points_device", "get_all_points", "unproject_frames",
     "unproject_device", "unproject_backward_device", "nyu_read_batch", "nyu_read_device", "nyu_taps",
-    "conv2d", "max_pool", "conv2d_strided", "conv2d_transpose", "conv2d_image", "pack_transpose_kernel", "net", "demo", "fill", "DtFill",
+    "conv2d", "max_pool", "conv2d_strided", "conv2d_transpose", "conv2d_image", "pack_transpose_kernel", "net", "optim", "demo", "fill", "DtFill",
     "shard_range", "gather_frames", "fill_sharded", "release_host_slab", "build", "load", "METRICS", "DtfillError",
     "Result", "Result_NYU", "depth_floor", "depth_to_png16", "kitti_rows", "nyu_eval_crop",
 ]

@@ -113,11 +113,17 @@ _ABI = {
     "dtfill_conv2d_image": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, cf, vp, ci, ci, vp]),
     "dtfill_max_pool_pyramid": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, ci, ci, vp, ci, ci, vp, ci, ci, vp]),
     "dtfill_max_pool_pyramid_backward": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, ci, ci, vp, ci, ci, vp, ci, ci, vp, vp]),
+    "dtfill_adam_state_floats": (sz, [vp, ci]),
+    "dtfill_adam_record_bytes": (sz, []),
+    "dtfill_adam_init": (ci, [vp, vp]),
+    "dtfill_adam_step": (ci, [vp, vp, vp, ci, vp, vp, vp, cf, cf, cf, cf, vp]),
     "dtfill_conv2d_strided": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, vp, ci, cf, vp, ci, ci, vp]),
     "dtfill_conv2d_transpose": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, cf, vp, ci, ci, vp]),
     "dtfill_conv2d": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, cf, vp, ci, ci, vp]),
 }
 POOL_LEVELS = (2, 4, 8)  # the window sizes of dtfill_max_pool_pyramid, in the order of its out and dy arguments
+ADAM_GROUP = 128  # DTFILL_ADAM_GROUP: the variables one launch of dtfill_adam_step takes
+ADAM_CHUNK = 4096  # DTFILL_ADAM_CHUNK: the elements a block of it owns
 SYMBOLS = tuple(_ABI)
 del vp, ci, cf, sz, cu, ll, cs  # (the table's shorthands, not names of this module)
 STATS = ("all", "window", "anydist", "sky", "points", "colt")  # DTFILL_STATS_*

@@ -66,6 +66,7 @@
 // dtfill_conv.hpp's, and their gradients dtfill_conv2d_backward_data and dtfill_conv2d_backward_weights (dtfill_conv2d's) and
 // dtfill_conv2d_strided_backward_data / _weights and dtfill_conv2d_transpose_backward_data / _weights, all dtfill_convb.hpp's.
 // dtfill_max_pool_pyramid and its backward (dtfill_pool.hpp) are compare-and-select work again, and memory-bound.
+// dtfill_adam_step (dtfill_adam.hpp) is the training step's last line: Keras' Adam over every variable, one streaming pass.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -107,6 +108,7 @@ namespace {
 #include "dtfill_conv.hpp"
 #include "dtfill_convb.hpp"
 #include "dtfill_pool.hpp"
+#include "dtfill_adam.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -1484,6 +1486,69 @@ int dtfill_max_pool_pyramid_backward(const float *x, int B, int H, int W, int C,
     else if (K == 4) pool_backward_launch<4>(st, a, vec);
     else if (K == 2) pool_backward_launch<2>(st, a, vec);
     else pool_backward_launch<1>(st, a, vec);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+// counts[0 .. n): every count in [1, 2^31); *total: the floats of m (and of v), each segment rounded up to 4 floats
+static bool adam_layout(const long long *counts, int n, unsigned long long *total) {
+    *total = 0;
+    for (int i = 0; i < n; ++i) {
+        if (counts[i] < 1 || counts[i] >= (1ll << 31)) return false;
+        *total += ((unsigned long long)counts[i] + 3) & ~3ull;
+    }
+    return *total / 4 <= 0xffffffffull;  // a segment's offset travels as a 32-bit count of quads
+}
+
+size_t dtfill_adam_state_floats(const long long *counts, int n) {
+    unsigned long long total;
+    return counts && n >= 1 && adam_layout(counts, n, &total) ? (size_t)total : 0;
+}
+
+size_t dtfill_adam_record_bytes(void) { return sizeof(AdamRecord); }
+
+int dtfill_adam_init(void *record, void *stream) {
+    if (!record) return DTFILL_ERR_NULL;
+    k_adam_init<><<<1, 64, 0, static_cast<hipStream_t>(stream)>>>(static_cast<AdamRecord *>(record));
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+int dtfill_adam_step(float *const *params, const float *const *grads, const long long *counts, int n, float *m, float *v,
+                     void *record, float lr, float beta1, float beta2, float eps, void *stream) {
+    if (!params || !grads || !counts || !m || !v || !record) return DTFILL_ERR_NULL;
+    if (n < 1) return DTFILL_ERR_SHAPE;
+    int stepped = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!params[i]) return DTFILL_ERR_NULL;
+        stepped += grads[i] != nullptr;
+    }
+    if (!stepped) return DTFILL_ERR_NULL;
+    unsigned long long total;
+    if (!adam_layout(counts, n, &total)) return DTFILL_ERR_SHAPE;
+    if (!(lr >= 0.0f) || !isfinite(lr) || !(eps >= 0.0f) || !isfinite(eps)) return DTFILL_ERR_SHAPE;
+    if (!(beta1 >= 0.0f && beta1 < 1.0f) || !(beta2 >= 0.0f && beta2 < 1.0f)) return DTFILL_ERR_SHAPE;
+    for (int i = 0; i < n; ++i) {
+        const uintptr_t p = (uintptr_t)params[i], g = (uintptr_t)grads[i], bytes = (uintptr_t)counts[i] * 4;
+        if (g && p < g + bytes && g < p + bytes) return DTFILL_ERR_SHAPE;
+    }
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    AdamArgs a;
+    a.m = m, a.v = v, a.rec = static_cast<const AdamRecord *>(record);
+    a.lr = lr, a.b1 = beta1, a.b2 = beta2, a.eps = eps, a.n = 0, a.pad_ = 0;
+    unsigned long long at = 0;
+    u32 chunks = 0;
+    for (int i = 0; i < n; ++i) {
+        if (grads[i]) {
+            const int k = a.n++;
+            a.p[k] = params[i], a.g[k] = grads[i], a.seg4[k] = (u32)(at / 4), a.count[k] = (u32)counts[i];
+            a.end[k] = chunks += (u32)((counts[i] + ADAM_CHUNK - 1) / ADAM_CHUNK);  // <= 128 * 2^19 a launch
+        }
+        at += ((unsigned long long)counts[i] + 3) & ~3ull;
+        if (a.n == ADAM_GROUP || (a.n && i == n - 1)) {
+            k_adam<><<<chunks, ADAM_THREADS, 0, st>>>(a);
+            a.n = 0, chunks = 0;
+        }
+    }
+    k_adam_advance<><<<1, 64, 0, st>>>(static_cast<AdamRecord *>(record), beta1, beta2);
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 

@@ -1042,6 +1042,61 @@ int dtfill_max_pool_pyramid_backward(const float *x, int B, int H, int W, int C,
                                      float *dx /* dense [B,H,W,C] */, void *stream);
 
 /*
+ * dtfill_adam_step: the optimizer step of the reference's training loop, train.py:169 and :253-254 --
+ * tf.keras.optimizers.Adam(lr, beta_1 = 0.9), the "epsilon-hat" rule with eps = 1e-7 -- for every variable of a network in one
+ * fused pass, with every bit fixed here.  tests/adam_ref.py is this statement in numpy.
+ *
+ * params, grads, counts: HOST arrays of n entries; params[i] and grads[i] are DEVICE pointers to counts[i] float32 each.  A NULL
+ * grads[i] says that variable i has no gradient in this step: its values and its moments are left as they are, and its
+ * params[i] is not dereferenced (it must still not be NULL).  The arrays are read during the call and may be freed after it.
+ * m, v: two flat float32 device buffers of dtfill_adam_state_floats(counts, n) floats each, owned by the caller, zero at the
+ * start.  Variable i's moments lie at offset o_i in both: o_0 = 0, o_(i+1) = o_i + counts[i] rounded up to a multiple of 4, over
+ * ALL n entries, the skipped ones too, so a variable's segment does not depend on who has a gradient.  The padding floats are
+ * never read and never written.
+ * record: dtfill_adam_record_bytes() device bytes, 8-byte aligned: { int64 t; float64 b1p; float64 b2p }, the step count and
+ * the running powers beta1^t, beta2^t.  dtfill_adam_init() sets it to { 0, 1.0, 1.0 } on `stream`; zero bytes are NOT a valid
+ * record.  lr, beta1, beta2, eps: float32, as launch arguments: a schedule changes lr from one call to the next.
+ *
+ * THE CONTRACT.  Scalars, float64, one rounding per operation:
+ *   b1p' = b1p * (double)beta1;   b2p' = b2p * (double)beta2;   t' = t + 1           one product each, no pow
+ *   alpha = (float)( ((double)lr * sqrt(1 - b2p')) / (1 - b1p') )                    correctly rounded sqrt and divide, then
+ *                                                                                    ONE rounding to float32
+ *   c1 = 1.0f - beta1;   c2 = 1.0f - beta2                                           float32 subtractions
+ * Every element of every variable that has a gradient, float32, one rounding per operation, nothing contracted into an FMA:
+ *   m' = m + c1 * (g - m)
+ *   v' = v + c2 * (g * g - v)
+ *   p' = p - (alpha * m') / (sqrtf(v') + eps)                                        correctly rounded sqrt and divide
+ * Denormals are kept (g = 1e-20f gives v' = 0x00000047 after one step), NaN and Inf go where IEEE sends them (any NaN counts
+ * as any other), and no element is skipped or clamped.  The record holds t', b1p', b2p' after the call.
+ * Keras forms alpha in float32 with a pow; this one is the correctly rounded value of the same expression in the running
+ * products (a float32 restatement of Keras' differs from it by up to 54 ulp of alpha in the first 20 000 steps: the
+ * cancellation in 1 - 0.999^t).  The element rule is restated from TensorFlow's ApplyAdam functor from memory; TensorFlow
+ * is not part of this project's tests.
+ *
+ * How it runs: up to DTFILL_ADAM_GROUP variables per launch, their pointers, counts and offsets by value in the launch's
+ * arguments -- no device table, no copy, nothing that outlives the call -- and more variables in more launches of the same
+ * kernel; a block owns DTFILL_ADAM_CHUNK consecutive elements of one variable.  The update launches only read the record; a
+ * one-wave launch behind the last of them, on the same stream, advances it.  Where params[i], grads[i], m and v are all 16-byte
+ * aligned, variable i moves in 16-byte accesses; any float-aligned pointer is legal.  Asynchronous on `stream`; no workspace,
+ * no allocation, no atomics, no host synchronisation.  Two calls on one record must be ordered by their streams.
+ *
+ * Returns, all checked before any HIP call and in this order: DTFILL_ERR_NULL for a NULL params, grads, counts, m, v or
+ * record; DTFILL_ERR_SHAPE for n < 1; DTFILL_ERR_NULL for a NULL params[i], or when every grads[i] is NULL; DTFILL_ERR_SHAPE for
+ * a count < 1 or >= 2^31, more than 2^34 - 4 state floats, an lr or eps that is negative or not finite, a beta outside [0, 1),
+ * or a params[i] whose counts[i] floats overlap its grads[i]'s; then DTFILL_ERR_LAUNCH if a launch failed.
+ * dtfill_adam_state_floats: the floats EACH of m and v holds; 0 for a list dtfill_adam_step would refuse.
+ * dtfill_adam_init: DTFILL_ERR_NULL for a NULL record, DTFILL_ERR_LAUNCH if the launch failed.
+ */
+#define DTFILL_ADAM_GROUP 128  /* variables per launch: 128 x 28 bytes of table + 48 of scalars = 3632 < HIP's 4096 of arguments */
+#define DTFILL_ADAM_CHUNK 4096 /* elements per block: 256 lanes x four 16-byte accesses per array */
+size_t dtfill_adam_state_floats(const long long *counts, int n);
+size_t dtfill_adam_record_bytes(void);
+int dtfill_adam_init(void *record, void *stream);
+int dtfill_adam_step(float *const *params, const float *const *grads /* entries nullable */, const long long *counts, int n,
+                     float *m, float *v, void *record,
+                     float lr, float beta1, float beta2, float eps, void *stream);
+
+/*
  * dtfill_conv2d_strided and dtfill_conv2d_transpose: the wide layers of ResNet18_NO_BN_l2 (solution_DeepNet/net.py:245-745),
  * in the same sense as dtfill_conv2d below, whose statement they extend: every output bit is fixed here.  Convolutions with
  * Cin == 1 or Cout == 1 (the correction branch, the stems, conv_output) stay with dtfill_conv2d.
