@@ -36,7 +36,9 @@ def __getattr__(name):
         import importlib
 
         return importlib.import_module(__name__ + ".nyu").nyu_read_device
-    if name in ("conv2d_strided", "conv2d_transpose", "conv2d_image", "pack_transpose_kernel"):  # numpy forms of the wide and image convolutions
+    if name in ("conv2d_strided", "conv2d_transpose", "conv2d_image", "pack_transpose_kernel",  # numpy forms of the wide and image convolutions
+                "conv2d_strided_bf16", "conv2d_transpose_bf16", "pack_bf16_device", "conv2d_strided_bf16_device",
+                "conv2d_transpose_bf16_device"):  # and the bf16 forms of the wide ones
         import importlib
 
         return getattr(importlib.import_module(__name__ + ".conv"), name)
@@ -60,7 +62,8 @@ __all__ = [
     "depth_read", "depth_read_batch", "rgb_read", "rgb_read_batch", "rgb_read_device", "nearest_source",
     "map_points_on_image", "project_points", "project_points_device", "get_all_points", "unproject_frames",
     "unproject_device", "unproject_backward_device", "nyu_read_batch", "nyu_read_device", "nyu_taps",
-    "conv2d", "max_pool", "conv2d_strided", "conv2d_transpose", "conv2d_image", "pack_transpose_kernel", "net", "optim", "demo", "fill", "DtFill",
+    "conv2d", "max_pool", "conv2d_strided", "conv2d_transpose", "conv2d_image", "pack_transpose_kernel", "conv2d_strided_bf16",
+    "conv2d_transpose_bf16", "pack_bf16_device", "conv2d_strided_bf16_device", "conv2d_transpose_bf16_device", "net", "optim", "demo", "fill", "DtFill",
     "shard_range", "gather_frames", "fill_sharded", "release_host_slab", "build", "load", "METRICS", "DtfillError",
     "Result", "Result_NYU", "depth_floor", "depth_to_png16", "kitti_rows", "nyu_eval_crop",
 ]

@@ -117,6 +117,10 @@ _ABI = {
     "dtfill_adam_record_bytes": (sz, []),
     "dtfill_adam_init": (ci, [vp, vp]),
     "dtfill_adam_step": (ci, [vp, vp, vp, ci, vp, vp, vp, cf, cf, cf, cf, vp]),
+    "dtfill_conv2d_bf16_packed_elems": (sz, [ci, ci, ci]),
+    "dtfill_conv2d_pack_bf16": (ci, [vp, ci, ci, ci, vp, vp]),
+    "dtfill_conv2d_strided_bf16": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, vp, ci, cf, vp, ci, ci, vp]),
+    "dtfill_conv2d_transpose_bf16": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, cf, vp, ci, ci, vp]),
     "dtfill_conv2d_strided": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, vp, ci, cf, vp, ci, ci, vp]),
     "dtfill_conv2d_transpose": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, cf, vp, ci, ci, vp]),
     "dtfill_conv2d": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, cf, vp, ci, ci, vp]),

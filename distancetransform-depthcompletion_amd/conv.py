@@ -14,6 +14,12 @@ docstring: conv2d_device, conv2d_strided_device, conv2d_transpose_device and con
 calls the cores directly with the kind it carries.  conv2d_strided, conv2d_transpose and conv2d_image are the numpy forms
 (tools.conv2d is the narrow one's).
 
+The strided and the transposed kind have a second forward, on the bf16 matrix cores with float32 accumulation
+(dtfill_conv2d_strided_bf16, dtfill_conv2d_transpose_bf16: the header states what is promised about its bits): pack_bf16_device
+makes the packed weights once, conv2d_strided_bf16_device and conv2d_transpose_bf16_device take them in place of w through one
+core, _forward_bf16, under the same _KINDS record; conv2d_strided_bf16 and conv2d_transpose_bf16 are the numpy forms.  Inference
+only: there is no bf16 backward.
+
 The *_device functions and the size functions are reached as device.<name> as well, and everything here as net.<name>; they live
 here, beside device.py's helpers, as the pools do in pool.py.  Their argument checks are held by tests/test_conv2d*.py, the
 kernels by tests/test_gpu_conv2d*.py.
@@ -135,16 +141,11 @@ _KINDS = {
 }
 
 
-def _forward(kind, x, w, bias, stride, residual, act, alpha, out, out_offset):
-    """The forward of a layer of `kind`: the four public functions' shared sequence, once."""
+def _check_frames(kind, x, Cout, stride, residual, out, out_offset):
+    """The residual and out of a forward of `kind` against the output frame of x [B,H,W,..] at `stride`; returns out, a new
+    [B,Ho,Wo,Cout] tensor when None."""
     k = _KINDS[kind]
-    if stride not in (1, 2):
-        raise ValueError("stride must be 1 or 2, got %r" % (stride,))
-    B, H, W, Cin, Cout = _check_conv_args(x, w, bias, act, k.w_layout, plane_ok=k.plane_ok)
-    ksize = w.shape[0]
-    if ksize != (k.ksize or ksize):
-        raise ValueError("%s must be %s, got %s" % (k.w_name, k.w_layout, tuple(w.shape)))
-    frame = (B,) + k.out_frame(H, W, stride)
+    frame = (x.shape[0],) + k.out_frame(x.shape[1], x.shape[2], stride)
     if residual is not None:
         if not k.has_residual:
             raise ValueError("a %s layer takes no residual" % kind)
@@ -154,6 +155,19 @@ def _forward(kind, x, w, bias, stride, residual, act, alpha, out, out_offset):
     out = _check_conv_out(x, out, out_offset, frame, Cout)
     if residual is not None and out.data_ptr() == residual.data_ptr():
         raise ValueError("out may not alias residual")
+    return out
+
+
+def _forward(kind, x, w, bias, stride, residual, act, alpha, out, out_offset):
+    """The forward of a layer of `kind`: the four public functions' shared sequence, once."""
+    k = _KINDS[kind]
+    if stride not in (1, 2):
+        raise ValueError("stride must be 1 or 2, got %r" % (stride,))
+    B, H, W, Cin, Cout = _check_conv_args(x, w, bias, act, k.w_layout, plane_ok=k.plane_ok)
+    ksize = w.shape[0]
+    if ksize != (k.ksize or ksize):
+        raise ValueError("%s must be %s, got %s" % (k.w_name, k.w_layout, tuple(w.shape)))
+    out = _check_frames(kind, x, Cout, stride, residual, out, out_offset)
     with torch.cuda.device(x.device):
         _lib.check(getattr(_lib.load(), k.forward)(
             x.data_ptr(), B, H, W, Cin, w.data_ptr(), _ptr(bias), *k.abi_shape(ksize, Cout, stride),
@@ -342,6 +356,86 @@ def conv2d_image_backward_weights_device(x, dy, ksize, y=None, act="linear", alp
     conv2d_backward_weights_device.  Returns (dw [ksize,ksize,Cin,Cout], db [Cout] or None without want_bias): new tensors.
     There is no data gradient: the image is data.  Asynchronous on the current stream."""
     return _backward_weights("image", x, dy, ksize, 1, y, act, alpha, dy_offset, y_offset, cout, want_bias)
+
+
+def pack_bf16_device(w, transposed=False):
+    """The packed bf16 weights the bf16 convolutions take, made on the device by dtfill_conv2d_pack_bf16.  w: contiguous float32
+    CUDA tensor in the form the float32 function takes: [ksize,ksize,Cin,Cout] with ksize 1 or 3, and with transposed the
+    already exchanged [3,3,Cin,Cout] (pack_transpose_kernel).  Returns a new bfloat16 tensor [ksize,ksize,G,Cout / 16,64,8],
+    G = ceil(Cin / 32): the matrix cores' B fragments, rounded to nearest even, half groups zero-filled.  The layout is the
+    header's and opaque: hand the tensor to conv2d_strided_bf16_device or conv2d_transpose_bf16_device and nothing else.
+    Asynchronous on the current stream."""
+    _require_gpu()
+    _check_tensor(w, "w", layout="[3,3,Cin,Cout]" if transposed else "[ksize,ksize,Cin,Cout]")
+    ksize, Cin, Cout = w.shape[0], w.shape[2], w.shape[3]
+    if w.shape[1] != ksize or (transposed and ksize != 3):
+        raise ValueError("w must be %s, got %s" % ("[3,3,Cin,Cout]" if transposed else "[ksize,ksize,Cin,Cout]", tuple(w.shape)))
+    L = _lib.load()
+    elems = _device._sized(L.dtfill_conv2d_bf16_packed_elems(ksize, Cin, Cout))
+    packed = torch.empty((ksize, ksize, elems // (ksize * ksize * (Cout // 16) * 512), Cout // 16, 64, 8), dtype=torch.bfloat16,
+                         device=w.device)
+    with torch.cuda.device(w.device):
+        _lib.check(L.dtfill_conv2d_pack_bf16(w.data_ptr(), ksize, Cin, Cout, packed.data_ptr(), _stream(w.device)))
+    return packed
+
+
+def _forward_bf16(kind, x, packed, bias, stride, residual, act, alpha, out, out_offset):
+    """The forward of a wide layer of `kind` on the bf16 matrix cores: _forward's sequence over the packed weights, whose
+    shape [ksize,ksize,G,Cout / 16,64,8] says the layer's ksize and Cout; Cin is x's."""
+    k = _KINDS[kind]
+    if stride not in (1, 2):
+        raise ValueError("stride must be 1 or 2, got %r" % (stride,))
+    _check_act(act)
+    _check_tensor(x, "x", layout="[B,H,W,Cin]")
+    B, H, W, Cin = x.shape
+    if not isinstance(packed, torch.Tensor) or packed.dtype != torch.bfloat16 or packed.dim() != 6 or not packed.is_contiguous():
+        raise ValueError("w_packed must be what pack_bf16_device returns, a contiguous bfloat16 tensor of six axes")
+    ksize, Cout = packed.shape[0], 16 * packed.shape[3]
+    if (tuple(packed.shape[1:3]) + tuple(packed.shape[4:]) != (ksize, -(-Cin // 32), 64, 8) or ksize != (k.ksize or ksize)
+            or packed.device != x.device):
+        raise ValueError("w_packed must be pack_bf16_device's of a %s kernel with Cin = %d on %s, got %s"
+                         % (k.w_layout, Cin, x.device, tuple(packed.shape)))
+    if bias is not None:
+        _check_tensor(bias, "bias", layout="[Cout]")
+        if bias.shape[0] != Cout or bias.device != x.device:
+            raise ValueError("bias must be [%d] on %s, got %s" % (Cout, x.device, tuple(bias.shape)))
+    out = _check_frames(kind, x, Cout, stride, residual, out, out_offset)
+    with torch.cuda.device(x.device):
+        _lib.check(getattr(_lib.load(), k.forward + "_bf16")(
+            x.data_ptr(), B, H, W, Cin, packed.data_ptr(), _ptr(bias), *k.abi_shape(ksize, Cout, stride),
+            *((_ptr(residual),) if k.has_residual else ()), _lib.CONV_ACTS[act], float(alpha), out.data_ptr(), out.shape[3],
+            int(out_offset), _stream(x.device)))
+    return out
+
+
+def conv2d_strided_bf16_device(x, w_packed, bias=None, stride=1, residual=None, act="linear", alpha=0.2, out=None, out_offset=0):
+    """conv2d_strided_device on the bf16 matrix cores with float32 accumulation (include/dtfill.h, dtfill_conv2d_strided_bf16):
+    x, bias, residual and out are the float32 tensors of conv2d_strided_device, w_packed is pack_bf16_device(w) of its w, ksize
+    1 or 3.  The operands are rounded to bf16 (to nearest even), the sum and the finish are float32; the result lies within the
+    header's bound of the exact sum and its bits are a function of the inputs and the shape alone.  Returns out.  Asynchronous
+    on the current stream."""
+    return _forward_bf16("strided", x, w_packed, bias, stride, residual, act, alpha, out, out_offset)
+
+
+def conv2d_transpose_bf16_device(x, w_packed, bias=None, act="linear", alpha=0.2, out=None, out_offset=0):
+    """conv2d_transpose_device on the bf16 matrix cores with float32 accumulation (dtfill_conv2d_transpose_bf16): w_packed is
+    pack_bf16_device(w, transposed=True) of the [3,3,Cin,Cout] kernel conv2d_transpose_device takes.  Everything else as
+    conv2d_strided_bf16_device.  Returns out, [B,2H,2W,C].  Asynchronous on the current stream."""
+    return _forward_bf16("transposed", x, w_packed, bias, 2, None, act, alpha, out, out_offset)
+
+
+def conv2d_strided_bf16(x, kernel, bias=None, stride=1, residual=None, act="linear", alpha=0.2):
+    """conv2d_strided_bf16_device as a numpy function: the arguments of conv2d_strided, the kernel packed here.  Returns
+    float32 [B,Ho,Wo,Cout]."""
+    a, k, b, r = _uploaded(x, kernel, bias, residual)
+    return conv2d_strided_bf16_device(a, pack_bf16_device(k), b, stride, r, act, alpha).cpu().numpy()
+
+
+def conv2d_transpose_bf16(x, kernel, bias=None, act="linear", alpha=0.2):
+    """conv2d_transpose_bf16_device as a numpy function: the arguments of conv2d_transpose, kernel [3,3,Cout,Cin] as Keras
+    stores a Conv2DTranspose's (exchanged and packed here).  Returns float32 [B,2H,2W,Cout]."""
+    a, k, b = _uploaded(x, kernel, bias)
+    return conv2d_transpose_bf16_device(a, pack_bf16_device(k.permute(0, 1, 3, 2).contiguous(), transposed=True), b, act, alpha).cpu().numpy()
 
 
 def pack_transpose_kernel(kernel):

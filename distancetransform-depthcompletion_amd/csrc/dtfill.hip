@@ -67,6 +67,8 @@
 // dtfill_conv2d_strided_backward_data / _weights and dtfill_conv2d_transpose_backward_data / _weights, all dtfill_convb.hpp's.
 // dtfill_max_pool_pyramid and its backward (dtfill_pool.hpp) are compare-and-select work again, and memory-bound.
 // dtfill_adam_step (dtfill_adam.hpp) is the training step's last line: Keras' Adam over every variable, one streaming pass.
+// dtfill_conv2d_strided_bf16 and dtfill_conv2d_transpose_bf16 (dtfill_convh.hpp) are the wide layers on the bf16 matrix cores,
+// the opt-in inference precision, over weights packed once by dtfill_conv2d_pack_bf16.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -109,6 +111,7 @@ namespace {
 #include "dtfill_convb.hpp"
 #include "dtfill_pool.hpp"
 #include "dtfill_adam.hpp"
+#include "dtfill_convh.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -1549,6 +1552,53 @@ int dtfill_adam_step(float *const *params, const float *const *grads, const long
         }
     }
     k_adam_advance<><<<1, 64, 0, st>>>(static_cast<AdamRecord *>(record), beta1, beta2);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+// The bf16 forms of the wide layers (dtfill_convh.hpp).  They stand last so that their kernels are asked for last.
+static bool convh_channels(int ksize, int Cin, int Cout) {
+    return (ksize == 1 || ksize == 3) && conv_wide_channels(Cin, Cout);
+}
+
+size_t dtfill_conv2d_bf16_packed_elems(int ksize, int Cin, int Cout) {
+    if (!convh_channels(ksize, Cin, Cout) || (long long)Cin * Cout >= (1ll << 31)) return 0;
+    const long long quads = convh_packed_quads(ksize, Cin, Cout);
+    return quads * CH_Q < (1ll << 31) ? (size_t)quads * CH_Q : 0;
+}
+
+int dtfill_conv2d_pack_bf16(const float *w, int ksize, int Cin, int Cout, void *out, void *stream) {
+    if (!w || !out) return DTFILL_ERR_NULL;
+    if (!dtfill_conv2d_bf16_packed_elems(ksize, Cin, Cout) || ((uintptr_t)out & 15)) return DTFILL_ERR_SHAPE;
+    const long long quads = convh_packed_quads(ksize, Cin, Cout);
+    k_convh_pack<><<<(unsigned)((quads + 255) / 256), 256, 0, static_cast<hipStream_t>(stream)>>>(w, Cin, Cout, static_cast<ch_b8 *>(out), quads);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+int dtfill_conv2d_strided_bf16(const float *x, int B, int H, int W, int Cin, const void *w, const float *bias, int ksize, int Cout,
+                               int stride, const float *residual, int act, float alpha, float *out, int out_channels,
+                               int out_offset, void *stream) {
+    if (!x || !w || !out) return DTFILL_ERR_NULL;
+    if (stride != 1 && stride != 2) return DTFILL_ERR_SHAPE;
+    if (H < 1 || W < 1 || !dtfill_conv2d_bf16_packed_elems(ksize, Cin, Cout) || ((uintptr_t)w & 15)) return DTFILL_ERR_SHAPE;
+    int Ho, Wo, pt, pl;
+    conv2_same(H, ksize, stride, &Ho, &pt);
+    conv2_same(W, ksize, stride, &Wo, &pl);
+    const float *wp = static_cast<const float *>(w);  // (ConvArgs carries the packed array as it carries a float32 one)
+    const int rc = conv_check(x, B, H, W, Cin, wp, Cout, act, alpha, out, out_channels, out_offset, Ho, Wo);
+    if (rc != DTFILL_OK) return rc;
+    const ConvArgs a{x, wp, bias, residual, out, B, H, W, Cin, Cout, Ho, Wo, pt, pl, out_channels, out_offset, act, alpha};
+    convh_strided_launch<>(static_cast<hipStream_t>(stream), a, ksize, stride);
+    return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+int dtfill_conv2d_transpose_bf16(const float *x, int B, int H, int W, int Cin, const void *w, const float *bias, int Cout, int act,
+                                 float alpha, float *out, int out_channels, int out_offset, void *stream) {
+    const float *wp = static_cast<const float *>(w);
+    const int rc = conv_check(x, B, H, W, Cin, wp, Cout, act, alpha, out, out_channels, out_offset, 2ll * H, 2ll * W);
+    if (rc != DTFILL_OK) return rc;
+    if (!dtfill_conv2d_bf16_packed_elems(3, Cin, Cout) || ((uintptr_t)w & 15)) return DTFILL_ERR_SHAPE;
+    const ConvArgs a{x, wp, bias, nullptr, out, B, H, W, Cin, Cout, 2 * H, 2 * W, 0, 0, out_channels, out_offset, act, alpha};
+    convh_transpose_launch<>(static_cast<hipStream_t>(stream), a);
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 

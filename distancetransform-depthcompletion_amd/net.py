@@ -32,8 +32,9 @@ from .conv import (_Kind, _KINDS, _backward_data, _backward_weights, _check_act,
                    conv2d_backward_data_device, conv2d_backward_weights_device, conv2d_backward_workspace_bytes, conv2d_device,
                    conv2d_image, conv2d_image_backward_weights_device, conv2d_image_backward_workspace_bytes, conv2d_image_device,
                    conv2d_strided, conv2d_strided_backward_data_device, conv2d_strided_backward_weights_device,
-                   conv2d_strided_device, conv2d_transpose, conv2d_transpose_backward_data_device,
-                   conv2d_transpose_backward_weights_device, conv2d_transpose_device, conv2d_wide_backward_workspace_bytes,
+                   conv2d_strided_bf16, conv2d_strided_bf16_device, conv2d_strided_device, conv2d_transpose,
+                   conv2d_transpose_backward_data_device, conv2d_transpose_backward_weights_device, conv2d_transpose_bf16,
+                   conv2d_transpose_bf16_device, conv2d_transpose_device, conv2d_wide_backward_workspace_bytes, pack_bf16_device,
                    pack_transpose_kernel)
 from .device import _check_tensor
 
@@ -42,6 +43,7 @@ STEM_WIDTH = 16  # channels every stem writes of the [B,H,W,16 * scale_num] tens
 RESNET_WIDTHS = (64, 128, 256, 512)  # channels of levels 1 .. 4; level k lives at 1 / 2^(k-1) of the frame each way
 RESNET_STRIDE2 = ("conv2a", "conv2a_extra", "conv3a", "conv3a_extra", "conv4a", "conv4a_extra")
 RESNET_TRANSPOSED = ("upsample_4", "upsample_3", "upsample_2")  # Conv2DTranspose: Keras stores [3,3,Cout,Cin]
+PRECISIONS = ("float32", "bf16")  # of the inference ResNets' wide and transposed layers; everything else is float32 in both
 IMAGE_WIDTH = 64  # channels img_conv writes in front of the stems: conv1a of the image network reads [image | stems]
 LIGHT_WIDTH = 64  # channels of every level of the light network, and of conv1_pre's output, the tensor it pools
 LIGHT_POOLS = (2, 4, 8)  # tf.nn.max_pool of conv1_pre's output behind levels 2, 3 and 4 (net.py:4285, 4320, 4353)
@@ -350,9 +352,33 @@ class _ResNet(_LidarNet):
     convolution upsample_1) writing the channels from 0 of a cat tensor, and one strided torch copy of the skip tensor into the
     channels above: one memory pass beside a layer of hundreds of MFLOP per kilopixel.  A concat in FRONT of a layer's input
     costs nothing: img_conv writes the channels 0 .. IMAGE_WIDTH - 1 of the base tensor and the stems (or PRE) the channels
-    behind; conv<k>d of a pooled level writes the channels from 0 of pooled[f], whose upper channels the pyramid call wrote."""
+    behind; conv<k>d of a pooled level writes the channels from 0 of pooled[f], whose upper channels the pyramid call wrote.
+
+    precision: "float32", the default, is the fixed-order float32 chain in every layer.  "bf16" runs the layers that go through
+    _wide and _up (every layer of the trunk but img_conv and conv_output) on the bf16 matrix cores with float32 accumulation
+    (dtfill_conv2d_strided_bf16, dtfill_conv2d_transpose_bf16) over weights packed once per device; the activations stay
+    float32 in memory, so the buffers, the concat offsets and the skip copies are the same, and the head, the fill, the stems,
+    the correction branch, img_conv, the pooling and conv_output stay float32.  Inference only: the Trainable classes have no
+    such argument."""
 
     IMAGE_WIDTH, WIDTHS, PRE, POOLS, LIDAR_SKIP = 0, RESNET_WIDTHS, None, (), False
+
+    def __init__(self, weights, table_size=7, if_correct=True, scale_range=90.0, scale_num=4, precision="float32"):
+        if precision not in PRECISIONS:
+            raise ValueError("precision must be one of %s, got %r" % (PRECISIONS, precision))
+        super().__init__(weights, table_size, if_correct, scale_range, scale_num)
+        self.precision = precision
+        head = set(_head_shapes(scale_num, self.if_correct)) | {"img_conv", "conv_output"}
+        self.wide_layers = tuple(n for n in self.shapes if n not in head)  # the layers _wide and _up run
+        self._packed = {}  # device -> {name: the packed bf16 kernel}, under "bf16"
+
+    def _state(self, dev):
+        """_LidarNet._state; under "bf16" the wide layers' kernels are packed on dev behind their upload, once."""
+        state = super()._state(dev)
+        if self.precision == "bf16" and dev not in self._packed:
+            with torch.cuda.device(dev):
+                self._packed[dev] = {n: pack_bf16_device(state[0][n][0], n in RESNET_TRANSPOSED) for n in self.wide_layers}
+        return state
 
     @classmethod
     def layer_shapes(cls, scale_num=4, if_correct=True):
@@ -388,10 +414,14 @@ class _ResNet(_LidarNet):
 
     def _wide(self, on, x, name, out, stride=1, residual=None, act="leaky", out_offset=0):
         kernel, bias = on[name]
+        if self.precision == "bf16":
+            return conv2d_strided_bf16_device(x, self._packed[x.device][name], bias, stride, residual, act, LEAKY_ALPHA, out, out_offset)
         return conv2d_strided_device(x, kernel, bias, stride, residual, act, LEAKY_ALPHA, out, out_offset)
 
     def _up(self, on, x, name, out):
         kernel, bias = on[name]
+        if self.precision == "bf16":
+            return conv2d_transpose_bf16_device(x, self._packed[x.device][name], bias, "leaky", LEAKY_ALPHA, out)
         return conv2d_transpose_device(x, kernel, bias, "leaky", LEAKY_ALPHA, out)
 
     def _run(self, input_lidar, rgb):
@@ -454,7 +484,9 @@ class ResNet18(_ResNet):
 
     The head is SparsityCNN's, the trunk _ResNet's.  H and W must be multiples of 8: with any other size the reference's own
     concat fails.  Detached, no host synchronisation, no activation buffer allocated after the first call at a shape, the
-    returned tensors are the instance's own, one stream at a time: as SparsityCNN."""
+    returned tensors are the instance's own, one stream at a time: as SparsityCNN.  precision = "bf16" (default "float32") runs
+    the trunk's wide and transposed layers on the bf16 matrix cores (_ResNet has what that changes and what it does not); the
+    image networks below take it too."""
 
     NAME = "ResNet18_NO_BN_l2"
 

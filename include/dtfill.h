@@ -1097,6 +1097,63 @@ int dtfill_adam_step(float *const *params, const float *const *grads /* entries 
                      float lr, float beta1, float beta2, float eps, void *stream);
 
 /*
+ * dtfill_conv2d_strided_bf16 and dtfill_conv2d_transpose_bf16: the two calls below on the bf16 matrix cores with float32
+ * accumulation, the opt-in inference precision of the three ResNets (precision = "bf16").  The float32 calls stay the default
+ * and the only ones training uses.  The argument lists and tensors are the twins': x, bias, residual and out stay float32 in
+ * memory, out_channels and out_offset behave as there, and the output size and the padding are the same 'same' rule.  w is NOT
+ * the float32 kernel but the packed bf16 array dtfill_conv2d_pack_bf16() makes of it, 16-byte aligned.
+ * Accepted shapes: ksize 1 or 3; stride 1 or 2 (the transposed form is always 3x3, stride 2); Cin a multiple of 16 and at
+ * least 16; Cout a multiple of 16 and at least 16.  The kernel works in groups of 32 input channels; a trailing half group
+ * (Cin = 16 or 48 mod 32: conv1a at scale_num 1 or 3) has +0 on both sides, x and w.
+ *
+ * THE CONTRACT.  bf16(.) is round-to-nearest-even on the float32 value to 8 significand bits; NaN stays NaN and a value that
+ * rounds past the largest finite bf16 goes to +-inf.  Per output:
+ *   acc = the float32-accumulated sum of bf16(x) * bf16(w) over the same taps and channels as the float32 contract, padding
+ *         taps +0
+ *   y = acc + bias[o];  y = y + residual[..];  y = leaky(y)     the float32 finish of the twins, unchanged, in this order
+ * Every product of two bf16 values is exact in float32 (8 + 8 significand bits).  The order and the rounding of the additions
+ * INSIDE one bf16 MFMA (v_mfma_f32_16x16x32_bf16: 32 products and the accumulator) are the hardware's and are not documented,
+ * so the output bits are NOT stated by a chain, as the float32 contract's are.  What is promised:
+ *   (a) The sequence of MFMAs per output is fixed: groups of 32 input channels outermost, then the taps in raster order (the
+ *       transposed form: the taps of the output's parity in raster order), one k-step per (group, tap).  The bits are a
+ *       function of the inputs and the shape alone: not of the tile, the grid, the position in the batch or the run.
+ *   (b) |y - exact| <= 2 n 2^-23 (S + |bias| + |residual|), S = sum |bf16(x)| |bf16(w)| over the output's terms,
+ *       n = ksize^2 32 ceil(Cin / 32), where exact is the sum and the finish in real arithmetic.  The bound holds for a
+ *       sequential or a tree order, for rounding to nearest or truncation of every internal addition, and for alignment of an
+ *       instruction's 33 addends to the largest of them.  Where all partial sums are exactly representable (small integers)
+ *       the result is exact.
+ * Subnormal bf16 operands may be flushed by the hardware; the contract leaves them open.  +0 and -0 count as equal.
+ * residual may alias x; neither may alias out.
+ *
+ * dtfill_conv2d_pack_bf16: a small device kernel that rounds w to bf16 and lays it out as the matrix cores' B fragments.
+ * w: float32 in the form the float32 entry point takes, [ksize,ksize,Cin,Cout]; for the transposed layer the already
+ * exchanged [3,3,Cin,Cout].  out: dtfill_conv2d_bf16_packed_elems(ksize, Cin, Cout) bf16 elements (2 bytes each), 16-byte
+ * aligned.  The layout, for the record; callers must go through this function and treat the array as opaque:
+ *   out[(((T G + g) N + n) 64 + 16 kq + m) 8 + j] = bf16(w[T][32 g + 8 kq + j][16 n + m]),  +0 where 32 g + 8 kq + j >= Cin
+ *   T = tap (ky ksize + kx), G = ceil(Cin / 32) groups, N = Cout / 16 N-tiles, kq < 4, m < 16, j < 8:
+ * a lane's 8 k-values of one output channel are 16 contiguous bytes, the 16 channels of an N-tile 256 contiguous bytes, the
+ * fragment of one (tap, group, N-tile) 1024 contiguous bytes; half groups are zero-filled.
+ * dtfill_conv2d_bf16_packed_elems = ksize^2 G N 512; 0 for a shape the calls refuse.
+ *
+ * All three: asynchronous on `stream`; no workspace, no allocation, no atomics, no host synchronisation.  x needs float
+ * alignment only and is read by 16-byte loads where its address allows.
+ * Returns, all checked before any HIP call.  The two convolutions: as their twins', with ksize 1 or 3 only, and
+ * DTFILL_ERR_SHAPE for a w that is not 16-byte aligned.  dtfill_conv2d_pack_bf16: DTFILL_ERR_NULL for a NULL w or out;
+ * DTFILL_ERR_SHAPE unless ksize is 1 or 3, Cin and Cout are multiples of 16 and at least 16, the packed array has fewer than
+ * 2^31 elements and out is 16-byte aligned; then DTFILL_ERR_LAUNCH if the launch failed.
+ */
+size_t dtfill_conv2d_bf16_packed_elems(int ksize, int Cin, int Cout);
+int dtfill_conv2d_pack_bf16(const float *w, int ksize, int Cin, int Cout, void *out, void *stream);
+int dtfill_conv2d_strided_bf16(const float *x, int B, int H, int W, int Cin,
+                               const void *w /* packed bf16 */, const float *bias /* nullable */, int ksize, int Cout, int stride,
+                               const float *residual /* nullable */, int act, float alpha,
+                               float *out, int out_channels, int out_offset, void *stream);
+int dtfill_conv2d_transpose_bf16(const float *x, int B, int H, int W, int Cin,
+                                 const void *w /* packed bf16 */, const float *bias /* nullable */, int Cout,
+                                 int act, float alpha,
+                                 float *out, int out_channels, int out_offset, void *stream);
+
+/*
  * dtfill_conv2d_strided and dtfill_conv2d_transpose: the wide layers of ResNet18_NO_BN_l2 (solution_DeepNet/net.py:245-745),
  * in the same sense as dtfill_conv2d below, whose statement they extend: every output bit is fixed here.  Convolutions with
  * Cin == 1 or Cout == 1 (the correction branch, the stems, conv_output) stay with dtfill_conv2d.
