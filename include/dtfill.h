@@ -1111,18 +1111,29 @@ int dtfill_adam_step(float *const *params, const float *const *grads /* entries 
  *   acc = the float32-accumulated sum of bf16(x) * bf16(w) over the same taps and channels as the float32 contract, padding
  *         taps +0
  *   y = acc + bias[o];  y = y + residual[..];  y = leaky(y)     the float32 finish of the twins, unchanged, in this order
- * Every product of two bf16 values is exact in float32 (8 + 8 significand bits).  The order and the rounding of the additions
+ * A product of two bf16 values has 16 significant bits and is exact in float32 where it is at least 2^-126 in magnitude (or
+ * +-0); below that float32 keeps only the bits from 2^-149 up, so a smaller product is rounded once, by less than 2^-149
+ * (two normal operands near 2^-70 already give one).  The order and the rounding of the additions
  * INSIDE one bf16 MFMA (v_mfma_f32_16x16x32_bf16: 32 products and the accumulator) are the hardware's and are not documented,
  * so the output bits are NOT stated by a chain, as the float32 contract's are.  What is promised:
  *   (a) The sequence of MFMAs per output is fixed: groups of 32 input channels outermost, then the taps in raster order (the
  *       transposed form: the taps of the output's parity in raster order), one k-step per (group, tap).  The bits are a
  *       function of the inputs and the shape alone: not of the tile, the grid, the position in the batch or the run.
- *   (b) |y - exact| <= 2 n 2^-23 (S + |bias| + |residual|), S = sum |bf16(x)| |bf16(w)| over the output's terms,
+ *   (b) |y - exact| <= 2 n 2^-23 (S + |bias| + |residual|) + n 2^-149, S = sum |bf16(x)| |bf16(w)| over the output's terms,
  *       n = ksize^2 32 ceil(Cin / 32), where exact is the sum and the finish in real arithmetic.  The bound holds for a
  *       sequential or a tree order, for rounding to nearest or truncation of every internal addition, and for alignment of an
- *       instruction's 33 addends to the largest of them.  Where all partial sums are exactly representable (small integers)
- *       the result is exact.
- * Subnormal bf16 operands may be flushed by the hardware; the contract leaves them open.  +0 and -0 count as equal.
+ *       instruction's 33 addends to the largest of them.  The absolute term is the products': at most n of them, each rounded
+ *       or truncated once by less than 2^-149 where it lies below 2^-126.  It stands for gradual underflow, which is what the
+ *       matrix cores do (measured on an MI355X with normal operands near 2^-70 and 2^-60: no small product or partial sum is
+ *       flushed, and the worst error is 0.036 of this bound; with S below 2^-126, where every addition is exact, it is
+ *       6.7 x 2^-149 at n = 288: the products are rounded, not truncated).  An addition
+ *       whose result is below 2^-126 is exact, and one above is within the first term.  Where all partial sums are exactly
+ *       representable (small integers) the result is exact.  With S below FLT_MAX no partial sum in any order overflows and
+ *       y is finite unless the finish overflows; where every product of an output has one sign and the exact sum lies beyond
+ *       FLT_MAX by more than the bound, y is the infinity of that sign.  Sums of mixed signs with S beyond FLT_MAX are open:
+ *       an inner order may meet inf - inf.
+ * Subnormal bf16 operands may be flushed by the hardware; the contract leaves them open (an MI355X keeps them, in x and in w;
+ * the tests take either, but one of the two throughout a call).  +0 and -0 count as equal.
  * residual may alias x; neither may alias out.
  *
  * dtfill_conv2d_pack_bf16: a small device kernel that rounds w to bf16 and lays it out as the matrix cores' B fragments.

@@ -83,10 +83,13 @@ def conv2d_transpose_bf16_ref(x, w, bias=None, act=R2.LINEAR, alpha=0.2):
 
 
 def bound(ksize, cin, S, bias=None, residual=None):
-    """The contract's bound (b) per output: 2 n 2^-23 (S + |bias| + |residual|)."""
+    """The contract's bound (b) per output: 2 n 2^-23 (S + |bias| + |residual|) + n 2^-149."""
     total = S + (0 if bias is None else np.abs(np.asarray(bias, np.float64)))
     total = total + (0 if residual is None else np.abs(np.asarray(residual, np.float64)))
-    return 2.0 * bound_terms(ksize, cin) * 2.0 ** -23 * total
+    return 2.0 * bound_terms(ksize, cin) * 2.0 ** -23 * total + bound_terms(ksize, cin) * TINY
+
+
+TINY = 2.0 ** -149  # the absolute term's unit: a product below 2^-126 is rounded once, to a multiple of 2^-149
 
 
 def packed_elems(ksize, cin, cout):

@@ -16,6 +16,8 @@ C. CLASSES: float32's range on the matrix cores.  Values are a seeded normal tim
 import numpy as np
 
 import conv2_ref as R2
+import conv2b_ref as RW
+import conv_bf16_ref as HB
 import conv_ref as R
 import convb_ref as RB
 import test_gpu_conv2d as fwd  # case(): numpy only at import
@@ -161,6 +163,8 @@ def tile(c, seed=0):
     """The T frames of a tiled case and the reference on them.  Returns a dict of float32 arrays: the inputs (x, w, bias,
     residual / x, w, dy, y: dy and y as their whole tensors, `width` wide with poison beside the slice) and `want`, the
     expected output of one period ([T, ...]; dw: the level-1 partials of the tile's segments in (b, t, s) order)."""
+    if c.get("bf16"):
+        return bf16_tile(c, seed)
     ksize, cin, cout, H, W = c["ksize"], c["cin"], c["cout"], c["H"], c["W"]
     shape = (T, H, W)
     if c["entry"] in ("dx", "dw"):
@@ -330,6 +334,259 @@ def forward_ref(entry, x, w, b, stride=1, act=R.LEAKY):
     if entry == "strided":
         return R2.strided_ref(x, w, b, stride, None, act, ALPHA)
     return R.conv_ref(x, w, b, act, ALPHA)
+
+
+# ================================================================================================ the newer backward kernels
+# Part A for k_convb_dw_wide, k_convb_dw_image and the data gradients of the wide layers (tests/test_gpu_conv2d_backward_limits.py).
+# k_convb_dw_wide takes its segment from the grid's z axis, and convb_dw_wide_launch repeats the launch from seg0 = 65535 on:
+# frames whose SEGMENT frame is 1 x 129 have three segments (the last of one column), and B = 21879 of them 65637 = 65535 + 102,
+# so that segment 65535 is column 0 of frame 21845: the second launch begins on a frame boundary and ends inside a frame.
+# k_convb_dw_image has an item loop past CV_MAX_BLOCKS as k_convb_dw has: one segment a frame, 2^20 + 101 frames, or two
+# passes a segment and 2^19 + 50 frames.  H, W: the layer's input frame.  dy and y are the channels at .. of tensors `width` wide.
+GRID_Z = 65535  # the segments of one launch of k_convb_dw_wide
+_BW = 21879  # 3 * 21879 = 65637
+
+
+def _w(entry, ksize, stride, cin, cout, act, H, W, B=_BW, transposed=False, width=None, at=0, dres=False, mis=0):
+    return dict(entry=entry, ksize=ksize, stride=stride, cin=cin, cout=cout, act=act, H=H, W=W, B=B, transposed=transposed,
+                width=cout if width is None else width, at=at, dres=dres, mis=mis)
+
+
+WLOOP = {
+    "dw wide 1x1x16->32": _w("dw_wide", 1, 1, 16, 32, R.LEAKY, 1, 129, width=48, at=16),
+    "dw wide 3x3x16->32": _w("dw_wide", 3, 1, 16, 32, R.LEAKY, 1, 129, width=48, at=16),
+    "dw wide 3x3x16->32, x, dy and y 4 bytes off": _w("dw_wide", 3, 1, 16, 32, R.LEAKY, 1, 129, width=48, at=16, mis=4),
+    "dw wide 5x5x16->32": _w("dw_wide", 5, 1, 16, 32, R.LINEAR, 1, 129, width=48, at=16),
+    "dw wide 7x7x16->32": _w("dw_wide", 7, 1, 16, 32, R.LINEAR, 1, 129, width=48, at=16),
+    "dw wide 1x1x16->32 stride 2": _w("dw_wide", 1, 2, 16, 32, R.LEAKY, 2, 258, width=48, at=16),
+    "dw wide 3x3x16->32 stride 2": _w("dw_wide", 3, 2, 16, 32, R.LINEAR, 2, 258, width=48, at=16),
+    "dw wide transposed 16->32": _w("dw_wide", 3, 2, 16, 32, R.LINEAR, 1, 129, transposed=True),
+    "dx wide 1x1x16->32 stride 2": _w("dx_wide", 1, 2, 16, 32, R.LEAKY, 2, 258, width=48, at=16),
+    "dx wide transposed 16->32": _w("dx_wide", 3, 2, 16, 32, R.LINEAR, 1, 129, transposed=True),
+    "dw image 3x3x3->16": _w("dw_image", 3, 1, 3, 16, R.LEAKY, 1, 5, B=MAX_BLOCKS + 101),
+    "dw image 7x7x4->16": _w("dw_image", 7, 1, 4, 16, R.LINEAR, 1, 1, B=MAX_BLOCKS + 101),
+    "dw image 3x3x3->128": _w("dw_image", 3, 1, 3, 128, R.LINEAR, 1, 1, B=MAX_BLOCKS // 2 + 50),
+}
+
+
+# Part B for the same entry points and for dtfill_conv2d_image: every tensor argument past byte offset 4 GiB in some case, a
+# case past 2 GiB and one at the largest batch the shape rule admits per group, on FRAME (the stride-2 layers: its double, the
+# image weight gradient: SEGMENT).  x of the image layers has at most 4 channels and cannot pass 4 GiB within the rule
+# (B H W max(Cin, Cout) < 2^31 with Cout >= 16).  The workspace of the data gradient holds g for the whole batch: where dy of a
+# 64-channel layer passes 4 GiB, so does the workspace.  All dy and y of the dw wide cases of A and B but the "4 bytes off"
+# one are 16-byte aligned with widths that are multiples of 4: the VEC = true bodies; that one case runs VEC = false.
+_P4, _P2 = 2 ** 30, 2 ** 29
+WLARGE = {
+    "dx strided 1x1x64->64, dy, dx, dresidual and the workspace past 4 GiB": _w("dx_wide", 1, 1, 64, 64, R.LINEAR, *FRAME, B=batch_past(_P4, _PX * 64),
+                                                                             dres=True),
+    "dx strided 1x1x64->64 stride 2, dx past 4 GiB": _w("dx_wide", 1, 2, 64, 64, R.LEAKY, 18, 66, B=batch_past(_P4, 4 * _PX * 64)),
+    "dx strided 3x3x16->16, dy 128 wide at the limit": _w("dx_wide", 3, 1, 16, 16, R.LINEAR, *FRAME, B=(2 ** 31 - 1) // (_PX * 128), width=128, at=48),
+    "dx transposed 64->16, dy, y, dx and the workspace past 4 GiB": _w("dx_wide", 3, 2, 64, 16, R.LEAKY, *FRAME, B=batch_past(_P4, 4 * _PX * 16),
+                                                                    transposed=True),
+    "dw strided 1x1x64->16, x, dy and y past 4 GiB": _w("dw_wide", 1, 1, 64, 16, R.LEAKY, *FRAME, B=batch_past(_P4, _PX * 64), width=64, at=32),
+    "dw strided 3x3x16->16 stride 2, x past 2 GiB": _w("dw_wide", 3, 2, 16, 16, R.LEAKY, 18, 66, B=batch_past(_P2, 4 * _PX * 16)),
+    "dw strided 1x1x64->16, x at the limit": _w("dw_wide", 1, 1, 64, 16, R.LINEAR, *FRAME, B=(2 ** 31 - 1) // (_PX * 64)),
+    "dw transposed 64->16, x, dy and y past 4 GiB": _w("dw_wide", 3, 2, 64, 16, R.LEAKY, *FRAME, B=batch_past(_P4, _PX * 64), transposed=True),
+    "dw image 3x3x4->16, dy and y past 4 GiB": _w("dw_image", 3, 1, 4, 16, R.LEAKY, *SEGMENT, B=batch_past(_P4, _SPX * 64), width=64, at=32),
+    "dw image 3x3x3->16, dy past 2 GiB": _w("dw_image", 3, 1, 3, 16, R.LINEAR, *SEGMENT, B=batch_past(_P2, _SPX * 32), width=32, at=16),
+    "dw image 3x3x4->16, dy 128 wide at the limit": _w("dw_image", 3, 1, 4, 16, R.LINEAR, *SEGMENT, B=(2 ** 31 - 1) // (_SPX * 128), width=128, at=48),
+}
+# dtfill_conv2d_image itself: records of LARGE's kind (entry "conv2d": conv_ref is its statement too), read by tile(),
+# device_bytes() and periods()
+ILARGE = {
+    "image 3x3x3->64, out past 2 GiB": _large(_P2, _PX * 64, entry="conv2d", ksize=3, cin=3, cout=64, H=FRAME[0], W=FRAME[1]),
+    "image 3x3x4->64, out past 4 GiB": _large(_P4, _PX * 64, entry="conv2d", ksize=3, cin=4, cout=64, H=FRAME[0], W=FRAME[1]),
+    "image 3x3x4->16 at 16 of 128, out at the limit": _large("limit", _PX * 128, entry="conv2d", ksize=3, cin=4, cout=16, out_channels=128,
+                                                             out_offset=16, H=FRAME[0], W=FRAME[1]),
+}
+# (entry, what is at 2^31, arguments); H, W: the layer's input frame.  "ws0": the size function answers 0 there too.
+WREFUSED = (
+    ("image", "B H W Cout", dict(B=2 ** 15, H=32, W=32, cin=4, cout=64, ksize=3)),
+    ("image", "B H W out_channels", dict(B=2 ** 14, H=32, W=32, cin=4, cout=16, ksize=3, out_channels=128)),
+    ("dw_image", "B H W Cout", dict(B=2 ** 15, H=32, W=32, cin=4, cout=64, ksize=3, ws0=True)),
+    ("dw_image", "B H W dy_channels", dict(B=2 ** 14, H=32, W=32, cin=4, cout=16, ksize=3, dy_channels=128)),
+    ("dw_image", "B H W y_channels", dict(B=2 ** 14, H=32, W=32, cin=4, cout=16, ksize=3, y_channels=128)),
+    ("dx_wide", "B H W Cin", dict(B=2 ** 15, H=32, W=32, cin=64, cout=16, ksize=3, stride=1, ws0=True)),
+    ("dw_wide", "B H W Cin", dict(B=2 ** 15, H=32, W=32, cin=64, cout=16, ksize=3, stride=1, ws0=True)),
+    ("dx_wide", "B Ho Wo Cout", dict(B=2 ** 15, H=32, W=32, cin=16, cout=64, ksize=3, stride=1, ws0=True)),
+    ("dw_wide", "B 2H 2W Cout", dict(B=2 ** 15, H=16, W=16, cin=16, cout=64, ksize=3, stride=2, transposed=True, ws0=True)),
+    ("dx_wide", "B Ho Wo dy_channels", dict(B=2 ** 14, H=32, W=32, cin=16, cout=16, ksize=3, stride=1, dy_channels=128)),
+    ("dw_wide", "B Ho Wo y_channels", dict(B=2 ** 14, H=32, W=32, cin=16, cout=16, ksize=1, stride=1, y_channels=128)),
+    ("dx_wide", "B 2H 2W dy_channels", dict(B=2 ** 14, H=16, W=16, cin=16, cout=16, ksize=3, stride=2, transposed=True, dy_channels=128)),
+    ("dw_wide", "B 2H 2W y_channels", dict(B=2 ** 14, H=16, W=16, cin=16, cout=16, ksize=3, stride=2, transposed=True, y_channels=128)),
+    ("dx_wide", "B H W dx_channels", dict(B=2 ** 14, H=32, W=32, cin=16, cout=16, ksize=3, stride=1, dx_channels=128)),  # needs a real workspace
+    ("dx_wide", "B H W dx_channels (transposed)", dict(B=2 ** 14, H=32, W=32, cin=16, cout=16, ksize=3, stride=2, transposed=True,
+                                                      dx_channels=128)),
+)
+
+
+def wrefused_count(entry, a):
+    """The element count the rule that refuses the call looks at."""
+    n = a["B"] * a["H"] * a["W"]
+    if entry == "image":
+        return n * max(a["cin"], a["cout"], a.get("out_channels", 0))
+    (Ho, Wo), _ = wframes(dict(a, transposed=a.get("transposed", False), stride=a.get("stride", 1)))
+    no = a["B"] * Ho * Wo
+    return max(n * max(a["cin"], a.get("dx_channels", 0)), no * max(a["cout"], a.get("dy_channels", 0), a.get("y_channels", 0)))
+
+
+def wframes(c):
+    """((Ho, Wo) of dy, the frame the segments lie over) of a case of WLOOP."""
+    H, W = c["H"], c["W"]
+    if c["transposed"]:
+        return (2 * H, 2 * W), (H, W)
+    return (H // c["stride"], W // c["stride"]), (H // c["stride"], W // c["stride"])
+
+
+def wsegments(c):
+    Hs, Ws = wframes(c)[1]
+    return c["B"] * _cdiv(Hs, SEG_ROWS) * _cdiv(Ws, SEG_COLS)
+
+
+def witems(c):
+    """The work items of k_convb_dw_image's launch: segments times passes of four N-tiles."""
+    assert c["entry"] == "dw_image"
+    return wsegments(c) * _cdiv(c["cout"] // 16, 4)
+
+
+def wworkspace_bytes(c):
+    """dtfill_conv2d_wide_backward_workspace_bytes and dtfill_conv2d_image_backward_workspace_bytes restated: the larger of g,
+    the repacked kernel and the 1x1 stride-2 chain's values (dx; none for the image layer) and the segments' partials (dw)."""
+    (Ho, Wo), _ = wframes(c)
+    taps, cin, cout, pixels = c["ksize"] ** 2, c["cin"], c["cout"], c["B"] * Ho * Wo
+    spread = not c["transposed"] and c["stride"] == 2 and c["ksize"] == 1
+    data = 0 if c["entry"] == "dw_image" else _align(4 * pixels * cout) + _align(4 * taps * cin * cout) + (_align(4 * pixels * cin) if spread else 0)
+    return max(data, _align(4 * wsegments(c) * (taps * cin + 1) * cout))
+
+
+def wdevice_bytes(c, chunk=COMPARE_CHUNK):
+    (Ho, Wo), _ = wframes(c)
+    n = 4 * c["B"] * c["H"] * c["W"] * c["cin"]  # x, or dx
+    dres = 4 * c["B"] * Ho * Wo * c["cout"] if c["dres"] else 0
+    return n + 4 * c["B"] * Ho * Wo * c["width"] * (2 if c["act"] == R.LEAKY else 1) + dres + wworkspace_bytes(c) + 4 * chunk
+
+
+def wtile(c, seed=0):
+    """The T frames of a case of WLOOP and the reference on them: x, w, dy and y (whole tensors, poison beside the slice) and
+    `want`: dx of the tile, or the level-1 partials [T * segments of a frame, ksize^2 Cin + 1, Cout] in (b, t, s) order."""
+    ksize, stride, cin, cout, act = c["ksize"], c["stride"], c["cin"], c["cout"], c["act"]
+    (Ho, Wo), _ = wframes(c)
+    x, w, _ = fwd.case(ksize, cin, cout, (T, c["H"], c["W"]), seed)
+    dy, _, _ = fwd.case(1, cout, cout, (T, Ho, Wo), seed + 1000)
+    y, _, _ = fwd.case(1, cout, cout, (T, Ho, Wo), seed + 2000)
+    y[np.random.default_rng(seed).random(y.shape) < 0.05] = -0.0
+    g = RB.g_ref(dy, y, act, ALPHA)
+    if c["entry"] == "dx_wide":
+        want = RW.transpose_dx_ref(dy, y, w, act, ALPHA) if c["transposed"] else RW.strided_dx_ref(dy, y, w, stride, act, ALPHA)
+    elif c["entry"] == "dw_image":
+        want = RB.partials(x, g, ksize)
+    elif c["transposed"]:
+        part, pb = RW.transpose_partials(x, g)
+        want = np.concatenate([part.reshape(len(part), 9 * cin, cout), pb[:, None, :]], axis=1)
+    else:
+        want = RW.strided_partials(x, g, ksize, stride)
+    return dict(x=x, w=w, dy=widened(dy, c["width"], c["at"]), y=widened(y, c["width"], c["at"]), want=want, dres=g if c["dres"] else None)
+
+
+# ================================================================================================ the bf16 calls (k_convh_wide)
+# The same three parts for dtfill_conv2d_strided_bf16 and dtfill_conv2d_transpose_bf16 (tests/test_gpu_conv2d_bf16_limits.py).
+# bf16 output bits are not stated by a chain, so the tiles of A and B are small integers (x in -8 .. 8, w in -4 .. 4, the
+# residual in -9 .. 9, the bias an odd multiple of 0.5, alpha 0.5): every partial sum is exact in any order, the contract then
+# promises the exact result, the expectation is an int64 sum, and no output is a zero.  Cases carry bf16=True and are otherwise
+# the float32 tables' records: items(), tiles(), out_frame(), device_bytes() and periods() read them as they are (TH, NPAR and
+# the passes of k_convh_wide are k_conv_wide's; w is the packed array, a few KB).
+HALPHA = 0.5
+
+
+def _h(**kw):
+    return dict(kw, bf16=True, ksize=kw.get("ksize", 3))
+
+
+HLOOP = {
+    "bf16 1x1x16->16": _h(entry="strided", body="k_convh_wide<ConvPlain<1,1>>", ksize=1, cin=16, cout=16, stride=1, B=_B3, H=17, W=1),
+    "bf16 3x3x16->128 residual": _h(entry="strided", body="k_convh_wide<ConvPlain<3,1>>", cin=16, cout=128, stride=1, residual=True, B=_B2,
+                                    H=1, W=3),
+    "bf16 3x3x48->16": _h(entry="strided", body="k_convh_wide<ConvPlain<3,1>>", cin=48, cout=16, stride=1, B=_B3, H=17, W=1),
+    "bf16 1x1x16->16 stride 2": _h(entry="strided", body="k_convh_wide<ConvPlain<1,2>>", ksize=1, cin=16, cout=16, stride=2, B=_B3, H=17, W=1),
+    "bf16 3x3x16->16 stride 2": _h(entry="strided", body="k_convh_wide<ConvPlain<3,2>>", cin=16, cout=16, stride=2, B=_B3, H=17, W=1,
+                                   misaligned=True),
+    "bf16 transpose 16->16": _h(entry="transpose", body="k_convh_wide<ConvTransposed>", cin=16, cout=16, B=_B12, H=1, W=65, misaligned=True),
+}
+
+
+def _hlarge(past, by, **kw):
+    return _h(**_large(past, by, H=FRAME[0], W=FRAME[1], **kw))
+
+
+HLARGE = {
+    "bf16 strided 3x3x64->16, x past 2 GiB": _hlarge(2 ** 29, _PX * 64, entry="strided", cin=64, cout=16, stride=1),
+    "bf16 strided 3x3x64->16 stride 2, x past 4 GiB": _hlarge(2 ** 30, _PX * 64, entry="strided", cin=64, cout=16, stride=2),
+    "bf16 strided 1x1x16->64 at 16 of 80, out and residual past 4 GiB": _hlarge(2 ** 30, _PX * 64, entry="strided", ksize=1, cin=16, cout=64,
+                                                                               stride=1, residual=True, out_channels=80, out_offset=16),
+    "bf16 strided 1x1x64->16 stride 2, x at the limit": _hlarge("limit", _PX * 64, entry="strided", ksize=1, cin=64, cout=16, stride=2),
+    "bf16 transpose 64->16, x and out past 2 GiB": _hlarge(2 ** 29, _PX * 64, entry="transpose", cin=64, cout=16),
+    "bf16 transpose 16->16, out past 4 GiB": _hlarge(2 ** 30, 4 * _PX * 16, entry="transpose", cin=16, cout=16),
+    "bf16 transpose 64->16, x and out at the limit": _hlarge("limit", _PX * 64, entry="transpose", cin=64, cout=16),
+}
+
+# (entry, what is at 2^31, arguments) for the bf16 calls, as REFUSED
+HREFUSED = (
+    ("strided", "B H W Cin", dict(B=2 ** 15, H=32, W=32, cin=64, cout=16, ksize=3, stride=1)),
+    ("strided", "B Ho Wo Cout", dict(B=2 ** 14, H=32, W=32, cin=16, cout=128, ksize=1, stride=1)),
+    ("strided", "B Ho Wo out_channels", dict(B=2 ** 14, H=64, W=64, cin=16, cout=16, ksize=3, stride=2, out_channels=128)),
+    ("transpose", "B H W Cin", dict(B=2 ** 15, H=32, W=32, cin=64, cout=16, ksize=3)),
+    ("transpose", "B Ho Wo Cout", dict(B=2 ** 14, H=16, W=32, cin=16, cout=64, ksize=3)),
+    ("transpose", "B Ho Wo out_channels", dict(B=2 ** 14, H=16, W=32, cin=16, cout=16, ksize=3, out_channels=64)),
+)
+
+
+def bf16_tile(c, seed=0):
+    """tile() for a bf16 case: integer frames and the int64 sum, finished in float64 (exact: quarters of small integers)."""
+    ksize, cin, cout, H, W = c["ksize"], c["cin"], c["cout"], c["H"], c["W"]
+    rng = np.random.default_rng(seed)
+    x = rng.integers(-8, 9, (T, H, W, cin)).astype(F)
+    w = rng.integers(-4, 5, (ksize, ksize, cin, cout)).astype(F)
+    b = (rng.integers(-9, 9, cout) + 0.5).astype(F)
+    res = rng.integers(-9, 10, (T,) + out_frame(c) + (cout,)).astype(F) if c.get("residual") else None
+    total = HB.transpose_sum(x, w, np.int64) if c["entry"] == "transpose" else HB.strided_sum(x, w, c["stride"], np.int64)
+    y = total.astype(np.float64) + b + (0 if res is None else res)
+    want = np.where(y > 0, y, y * HALPHA).astype(F)
+    return dict(x=x, w=w, bias=b, residual=res, want=widened(want, c.get("out_channels", cout), c.get("out_offset", 0)))
+
+
+# ---- C for the bf16 calls.  Values are scaled() values rounded to bf16 on the host, so that the reference's operands are the
+# kernel's.  (exponent range of x, of w, of the bias; None: no bias)
+HLAYERS = ((3, 1, False, 32, 48), (3, 2, False, 32, 48), (1, 1, False, 48, 32), (3, 2, True, 32, 48))  # ksize, stride, transposed, Cin, Cout
+HLAYER_IDS = ["3x3x32->48", "3x3x32->48 stride 2", "1x1x48->32", "transposed 32->48"]
+FLT_MAX = float(np.finfo(F).max)
+HCLASSES = {
+    "near the top": ((58, 61), (58, 61), (100, 110)),  # w is then scaled by a power of two: top_case()
+    "over the top": ((62, 63), (63, 64), None),
+    "small products": ((-75, -66), (-66, -58), (-135, -128)),
+    "tiny products": ((-82, -74), (-66, -58), None),  # S below 2^-126: every partial sum is subnormal, every addition exact
+    "subnormal x": ((-134, -128), (20, 30), (-108, -100)),
+    "subnormal w": ((20, 30), (-134, -128), (-108, -100)),
+}
+
+
+def hclass_case(name, ksize, cin, cout, shape, seed, stride=1, transposed=False, sign=1):
+    """x, w, bias (or None) of bf16 value class `name`; x and w hold bf16 values, except in "near the top".
+    near the top: x and w are left unrounded on purpose.  The statement rounds them itself, so the reference's operands are still
+    the kernel's, and the kernel's own rounding (ch_round) stays under test: with operands rounded on the host a ch_round that
+    truncates would change nothing here, and this class is the control that the range classes do not mask it.  w is scaled by the power of two that puts the largest S of the outputs into [FLT_MAX / 4, FLT_MAX / 2).
+    over the top: x > 0 and sign * w > 0 throughout, so that every product has one sign and the partial sums are monotone."""
+    (x0, x1), (w0, w1), bexp = HCLASSES[name]
+    rng = np.random.default_rng(seed)
+    x, w = scaled(rng, shape + (cin,), x0, x1), scaled(rng, (ksize, ksize, cin, cout), w0, w1)
+    b = None if bexp is None else scaled(rng, (cout,), *bexp)
+    if name == "near the top":  # unrounded: here the rounding is the kernel's own, which the statement repeats
+        xr, wr = np.abs(HB.bf16_round(x)), np.abs(HB.bf16_round(w))
+        S = HB.transpose_sum(xr, wr) if transposed else HB.strided_sum(xr, wr, stride)
+        return x, np.ldexp(w, int(np.floor(np.log2(FLT_MAX / 2 / S.max())))).astype(F), b
+    x, w = HB.bf16_round(x), HB.bf16_round(w)
+    if name == "over the top":
+        x, w = np.abs(x), (sign * np.abs(w)).astype(F)
+    return x, w, b
 
 
 def flushed(a):

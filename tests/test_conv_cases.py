@@ -198,3 +198,305 @@ def test_backward_classes_show_what_they_are_for(name, ksize, cin, cout):
         else:
             for what, got in (("dx", dx), ("dw", dw)):
                 assert _share(np.isinf(got)) >= 0.1 and _share(np.isfinite(got)) >= 0.1, (seed, shape, what, _share(np.isinf(got)))
+
+
+# ================================================================================================ the bf16 calls
+import conv_bf16_ref as HB  # noqa: E402
+
+
+def test_bf16_loop_cases_lie_just_past_the_grid_limit():
+    """As for LOOP: a hundred items past 2^20 on tiny frames; all five geometries at Cin = Cout = 16; a half group with two
+    groups an item; two passes with a residual; a stride-2 and the transposed case again off the 16-byte path; and a frame
+    whose items do not divide the grid in every geometry but the two-pass one."""
+    for name, c in CC.HLOOP.items():
+        n = CC.items(c)
+        assert CC.MAX_BLOCKS + 24 <= n < CC.MAX_BLOCKS + 2 ** 10, (name, n)
+        assert c["H"] * c["W"] <= CC.TILE_H * CC.TILE_W and c["bf16"]
+        assert CC.device_bytes(c) <= 3e9, (name, CC.device_bytes(c))
+    bodies = {c["body"] for c in CC.HLOOP.values()}
+    assert bodies == {"k_convh_wide<ConvPlain<%s>>" % g for g in ("1,1", "3,1", "1,2", "3,2")} | {"k_convh_wide<ConvTransposed>"}
+    for body in bodies:
+        cases = [c for c in CC.HLOOP.values() if c["body"] == body]
+        assert any(c["cin"] == 16 and c["cout"] == 16 for c in cases) or body == "k_convh_wide<ConvPlain<3,1>>", body
+        assert any(CC.MAX_BLOCKS % CC.items_per_frame(c) for c in cases), body  # item k + 2^20 is another tile, parity or pass
+    assert {CC.items_per_frame(c) for c in CC.HLOOP.values()} >= {3, 12}
+    half = CC.HLOOP["bf16 3x3x48->16"]
+    assert half["cin"] % HB.GROUP == 16 and -(-half["cin"] // HB.GROUP) == 2
+    wide = CC.HLOOP["bf16 3x3x16->128 residual"]
+    assert wide["cout"] // CC.PASS_CHANNELS == 2 and wide["residual"]
+    off = [c for c in CC.HLOOP.values() if c.get("misaligned")]
+    assert any(c.get("stride") == 2 for c in off) and any(c["entry"] == "transpose" for c in off)
+
+
+def test_bf16_large_cases_pass_their_thresholds():
+    for name, c in CC.HLARGE.items():
+        B, by = c["B"], c["by"]
+        if c["past"] == "limit":
+            assert 2 ** 31 - by <= B * by < 2 ** 31 and 4 * B * by > 8e9, name
+        else:
+            assert (B - CC.T) * by >= c["past"] > (B - CC.T - 1) * by, name
+        Ho, Wo = CC.out_frame(c)
+        x_elems, out_elems = c["H"] * c["W"] * c["cin"], Ho * Wo * c.get("out_channels", c["cout"])
+        assert by in (x_elems, out_elems, Ho * Wo * c["cout"]), name  # `by` is a frame of a tensor of the call
+        assert B * x_elems < 2 ** 31 and B * out_elems < 2 ** 31, name  # the shape rule
+        assert CC.device_bytes(c, LC.CHUNK_BYTES) < 20e9, (name, CC.device_bytes(c, LC.CHUNK_BYTES))
+    for entry in ("strided", "transpose"):
+        mine = {c["past"] for c in CC.HLARGE.values() if c["entry"] == entry}
+        assert mine == {2 ** 29, 2 ** 30, "limit"}, entry
+    past4 = lambda frame: [n for n, c in CC.HLARGE.items() if (c["B"] - CC.T) * frame(c) >= 2 ** 30]  # noqa: E731
+    x4 = past4(lambda c: c["H"] * c["W"] * c["cin"])
+    assert any("strided" in n for n in x4) and any("transpose" in n for n in x4)
+    out4 = past4(lambda c: CC.out_frame(c)[0] * CC.out_frame(c)[1] * c["cout"])
+    assert any("transpose" in n for n in out4)
+    sl = CC.HLARGE["bf16 strided 1x1x16->64 at 16 of 80, out and residual past 4 GiB"]
+    assert sl in [CC.HLARGE[n] for n in out4] and sl["residual"] and sl["out_offset"] == 16 and sl["out_channels"] == 80
+
+
+def test_bf16_refused_calls_stand_exactly_at_the_limit():
+    for entry, what, a in CC.HREFUSED:
+        assert CC.refused_count(entry, a) == 2 ** 31, (entry, what)
+        assert a["B"] * a["H"] * a["W"] < 2 ** 31 and a["cin"] % 16 == 0 and a["cout"] % 16 == 0 and a["ksize"] in (1, 3)
+    assert {(e, w.split()[-1]) for e, w, _ in CC.HREFUSED} == {(e, t) for e in ("strided", "transpose") for t in ("Cin", "Cout", "out_channels")}
+
+
+@pytest.fixture(scope="module", params=[("HLOOP", n) for n in CC.HLOOP] + [("HLARGE", n) for n in CC.HLARGE], ids=lambda p: "%s: %s" % p)
+def htiled(request):
+    table, name = request.param
+    c = getattr(CC, table)[name]
+    return c, CC.tile(c)
+
+
+def test_bf16_tiles_are_exact_alias_free_and_have_no_zero_output(htiled):
+    c, d = htiled
+    for what, period in CC.periods(c, d):
+        assert period % CC.T == 0
+        LC.assert_alias_free(CC.T, period // CC.T)
+    at, cout = c.get("out_offset", 0), c["cout"]
+    want = d["want"][..., at:at + cout]
+    assert (want != 0).all() and np.isfinite(want).all() and (want * 4 == np.rint(want * 4)).all()
+    rest = np.delete(d["want"], np.s_[at:at + cout], axis=-1)
+    assert (rest.view(np.uint32) == CC.POISON).all()
+    for k in ("x", "w", "residual"):
+        if d.get(k) is not None:
+            assert (HB.bf16_round(d[k]) == d[k]).all() and (d[k] == np.rint(d[k])).all(), k  # integers that bf16 holds
+    assert (d["bias"] * 2 % 2 == 1).all()  # odd multiples of 0.5: no sum is a zero
+    # every partial sum in any order is an integer below 2^24 in magnitude: the contract's "exact" clause applies
+    assert 8 * 4 * HB.bound_terms(c["ksize"], c["cin"]) + 9 + 9 < 2 ** 24
+    for k in ("x", "residual"):
+        if d.get(k) is not None:
+            assert len({d[k][t].tobytes() for t in range(CC.T)}) == CC.T, k
+    # and the tile's expectation is the statement's (the float64 sum, the float32 finish)
+    ref = HB.conv2d_transpose_bf16_ref(d["x"], d["w"], d["bias"], R.LEAKY, CC.HALPHA)[0] if c["entry"] == "transpose" else \
+        HB.conv2d_strided_bf16_ref(d["x"], d["w"], d["bias"], c["stride"], d["residual"], R.LEAKY, CC.HALPHA)[0]
+    assert (ref.view(np.uint32) == want.view(np.uint32)).all()
+
+
+# ---- part C of the bf16 calls: what each class is for
+def _hsums(x, w, stride, transposed):
+    xr, wr = HB.bf16_round(x), HB.bf16_round(w)
+    if transposed:
+        return HB.transpose_sum(xr, wr), HB.transpose_sum(np.abs(xr), np.abs(wr))
+    return HB.strided_sum(xr, wr, stride), HB.strided_sum(np.abs(xr), np.abs(wr), stride)
+
+
+@pytest.mark.parametrize("ksize,stride,transposed,cin,cout", CC.HLAYERS, ids=CC.HLAYER_IDS)
+@pytest.mark.parametrize("name", list(CC.HCLASSES))
+def test_bf16_classes_show_what_they_are_for(name, ksize, stride, transposed, cin, cout):
+    n, fmax = HB.bound_terms(ksize, cin), CC.FLT_MAX
+    for seed, shape in RUNS:
+        x, w, b = CC.hclass_case(name, ksize, cin, cout, shape, seed, stride, transposed)
+        total, S = _hsums(x, w, stride, transposed)
+        if name == "near the top":  # S in its window; the rounding is left to the kernel, so some operands are no bf16 values
+            assert fmax / 8 <= S.max() < fmax / 2, (seed, shape, S.max() / fmax)
+            assert _share(HB.bf16_round(x) != x) > 0.9 and np.isfinite(HB.bf16_round(x)).all() and np.isfinite(HB.bf16_round(w)).all()
+            assert np.abs(b).max() < fmax / 2 ** 10  # the finish cannot overflow either
+            continue
+        assert (HB.bf16_round(x) == x).all() and (HB.bf16_round(w) == w).all()  # the reference's operands are the kernel's
+        if name == "over the top":  # one sign, and the exact sum beyond FLT_MAX by more than the bound, either sign of w
+            assert (x > 0).all() and (w > 0).all() and (total == S).all()
+            assert (S - HB.bound(ksize, cin, S) > 2.0 ** 128).all(), (seed, shape, S.min() / fmax)
+            xn, wn, _ = CC.hclass_case(name, ksize, cin, cout, shape, seed, stride, transposed, -1)
+            assert (xn == x).all() and (wn == -w).all()
+        elif name in ("small products", "tiny products"):  # normal operands; a tenth of the products inexact in float32
+            assert CC.is_normal(x).all() and CC.is_normal(w).all()
+            p = x.reshape(-1, 1, cin, 1).astype(np.float64) * w.reshape(1, ksize * ksize, cin, cout).astype(np.float64)
+            assert _share(p.astype(F).astype(np.float64) != p) >= 0.1, (seed, shape)
+            if name == "small products":  # sums from 2^-149 to 2^-120, on either side of 2^-126
+                assert _share((np.abs(total) >= 2.0 ** -149) & (np.abs(total) < 2.0 ** -120)) >= 0.9
+                assert _share(np.abs(total) < 2.0 ** -126) >= 0.1 and _share(np.abs(total) >= 2.0 ** -126) >= 0.1
+            else:  # no partial sum in any order reaches 2^-126, and the sums are no zeros
+                assert S.max() < 2.0 ** -126 and b is None and _share(np.abs(total) >= 2.0 ** -149) >= 0.9
+        else:  # subnormal operands that survive the rounding, and two references further apart than their bounds together
+            sub = x if name == "subnormal x" else w
+            assert _share(CC.is_subnormal(sub)) >= 0.5
+            ftotal, fS = _hsums(CC.flushed(x), CC.flushed(w), stride, transposed)
+            apart = np.abs(total - ftotal) > HB.bound(ksize, cin, S, b) + HB.bound(ksize, cin, fS, b)
+            assert _share(apart) >= 0.1, (seed, shape, _share(apart))
+
+
+# ================================================================================================ the newer backward kernels
+def test_wide_loop_cases_reach_the_second_launch_and_the_second_item():
+    wide = {n: c for n, c in CC.WLOOP.items() if c["entry"] == "dw_wide"}
+    for name, c in wide.items():
+        _, (Hs, Ws) = CC.wframes(c)
+        assert (Hs, Ws) == (1, 129) and CC.wsegments(c) == 3 * c["B"] == 65637 == CC.GRID_Z + 102, name
+        assert CC.GRID_Z % 3 == 0 and CC.GRID_Z // 3 == 21845  # segment 65535 is column 0 of frame 21845 ...
+        assert (CC.wsegments(c) - CC.GRID_Z) == 102 and Ws % CC.SEG_COLS == 1  # ... and the last segment of a frame has one column
+        assert c["cin"] in (16, 32) and c["cout"] == 32
+    # one call for each instantiation dtfill.hip asks convb_dw_wide_launch for
+    assert {(c["ksize"], c["stride"], c["transposed"]) for c in wide.values()} == {(1, 1, False), (3, 1, False), (5, 1, False), (7, 1, False),
+                                                                                    (1, 2, False), (3, 2, False), (3, 2, True)}
+    dx = {n: c for n, c in CC.WLOOP.items() if c["entry"] == "dx_wide"}
+    assert {(c["ksize"], c["stride"], c["transposed"]) for c in dx.values()} == {(1, 2, False), (3, 2, True)}  # k_convb_spread; the transposed one
+    image = {n: c for n, c in CC.WLOOP.items() if c["entry"] == "dw_image"}
+    for name, c in image.items():
+        assert CC.MAX_BLOCKS + 24 <= CC.witems(c) < CC.MAX_BLOCKS + 2 ** 10 and c["H"] * c["W"] <= 5, name
+        assert CC.wsegments(c) == c["B"]  # one segment a frame
+    assert {(c["ksize"], c["cin"], c["cout"]) for c in image.values()} == {(3, 3, 16), (7, 4, 16), (3, 3, 128)}
+    two = image["dw image 3x3x3->128"]
+    assert CC.witems(two) == 2 * two["B"] and CC.MAX_BLOCKS % 2 == 0  # item k + 2^20 is the same pass of another segment ...
+    assert (7 * 7 * 4 + 16) // 16 == 13  # thirteen row tiles
+
+
+def test_wide_loop_cases_stay_under_3_gb_or_at_their_floor():
+    """Every case stays under 3 GB but six whose workspace the rule itself puts above it, at the smallest channels the issue's
+    shapes allow: a row of ksize^2 Cin + 1 partials of Cout floats a segment (5x5 and 7x7 at Cin 16, Cout 32 over 65637 segments;
+    the image layers over 2^20 segments at Cout 16 and 2^19 at Cout 128), and for the transposed layer g beside dy, both
+    B 2H 2W Cout floats.  Each stays within 1 GB of its floor."""
+    floors = {"dw wide 5x5x16->32": 4 * 65637 * (25 * 16 + 1) * 32, "dw wide 7x7x16->32": 4 * 65637 * (49 * 16 + 1) * 32,
+              "dw wide transposed 16->32": 2 * 4 * 21879 * 2 * 258 * 32, "dx wide transposed 16->32": 2 * 4 * 21879 * 2 * 258 * 32,
+              "dw image 7x7x4->16": 4 * (2 ** 20 + 101) * (49 * 4 + 1) * 16, "dw image 3x3x3->128": 4 * (2 ** 19 + 50) * 28 * 128}
+    for name, c in CC.WLOOP.items():
+        if name in floors:
+            assert floors[name] > 2.8e9 and floors[name] <= CC.wdevice_bytes(c) < floors[name] + 1e9, (name, CC.wdevice_bytes(c))
+        else:
+            assert CC.wdevice_bytes(c) <= 3e9, (name, CC.wdevice_bytes(c))
+        assert CC.wworkspace_bytes(c) % 256 == 0
+
+
+@pytest.fixture(scope="module", params=list(CC.WLOOP))
+def wtiled(request):
+    c = CC.WLOOP[request.param]
+    return c, CC.wtile(c)
+
+
+def test_wide_loop_tiles_are_alias_free_and_their_sums_are_sums_of_something(wtiled):
+    c, d = wtiled
+    for key in ("x", "dy", "y"):
+        assert d[key].shape[0] == CC.T and len({d[key][t].tobytes() for t in range(CC.T)}) == CC.T, key
+        LC.assert_alias_free(CC.T, d[key].size // CC.T)
+    want = d["want"]
+    assert np.isfinite(want).all()
+    if c["entry"] == "dx_wide":
+        LC.assert_alias_free(CC.T, want.size // CC.T)
+        on = want[:, ::2, ::2] if not c["transposed"] else want  # the 1x1 stride-2 layer: +0 off the even grid, by the contract
+        assert (on != 0).all() and ((want == 0).mean() == (0.0 if c["transposed"] else 0.75))
+        assert not (want.view(np.uint32) == 0x80000000).any()
+    else:  # compared on the host, where a zero's sign is left open; H = 1: the middle row of taps is the one inside the frame
+        per_frame = len(want) // CC.T
+        assert per_frame == (1 if c["entry"] == "dw_image" else 3)
+        dw, db = CC.split_dw(CC.level2(want, 4 * len(want)), c["ksize"], c["cin"])
+        mid = dw[c["ksize"] // 2] if c["W"] > 1 else dw[c["ksize"] // 2, c["ksize"] // 2]
+        # (a 1 x 1 frame: T products a sum, of values a third of which are zeros)
+        assert (mid != 0).mean() > (0.9 if c["W"] > 1 else 0.5) and (db != 0).mean() > 0.9, (mid != 0).mean()
+        assert len({p.tobytes() for p in want}) == len(want)  # every segment of the tile has partials of its own
+
+
+def wsizes(c):
+    """The elements of every tensor argument of a case of WLARGE, and its workspace bytes."""
+    (Ho, Wo), _ = CC.wframes(c)
+    n, no = c["B"] * c["H"] * c["W"], c["B"] * Ho * Wo
+    e = {"dy": no * c["width"]}
+    if c["act"] == R.LEAKY:
+        e["y"] = no * c["width"]
+    e["dx" if c["entry"] == "dx_wide" else "x"] = n * c["cin"]
+    if c["dres"]:
+        e["dresidual"] = no * c["cout"]
+    return e
+
+
+def test_backward_large_cases_pass_their_thresholds():
+    past4 = {"wide": set(), "image": set()}
+    for name, c in CC.WLARGE.items():
+        group = "image" if c["entry"] == "dw_image" else "wide"
+        e = wsizes(c)
+        assert all(v < 2 ** 31 for v in e.values()), name  # the shape rule
+        assert CC.wdevice_bytes(c, LC.CHUNK_BYTES) < 20e9, (name, CC.wdevice_bytes(c, LC.CHUNK_BYTES))
+        frame = {k: v // c["B"] for k, v in e.items()}
+        over = lambda least: {k for k in e if (c["B"] - CC.T) * frame[k] >= least}  # noqa: E731: the last T frames start beyond
+        if "past 4 GiB" in name:
+            named = {k for k in e if k in name.split(" past 4 GiB")[0].replace(",", " ").split()}
+            assert named and named <= over(2 ** 30), (name, named, over(2 ** 30))
+            past4[group] |= over(2 ** 30)
+            assert "workspace" not in name or CC.wworkspace_bytes(c) > 2 ** 32, name  # g of a 64-channel dy for the whole batch
+        elif "past 2 GiB" in name:
+            assert over(2 ** 29) and not over(2 ** 30), name
+        else:
+            assert "at the limit" in name and any(2 ** 31 - frame[k] <= v < 2 ** 31 for k, v in e.items()), name
+        assert c["at"] + c["cout"] <= c["width"]
+    assert past4["wide"] == {"dy", "y", "dx", "dresidual", "x"} and past4["image"] == {"dy", "y"}
+    for group in ("dx_wide", "dw_wide", "dw_image"):
+        names = " ".join(n for n, c in CC.WLARGE.items() if c["entry"] == group)
+        assert "past 4 GiB" in names and "at the limit" in names, group
+    assert sum("past 2 GiB" in n for n in CC.WLARGE) == 2  # one for the wide calls, one for the image layer
+    assert {(c["stride"], c["transposed"]) for c in CC.WLARGE.values() if c["entry"] == "dx_wide"} == {(1, False), (2, False), (2, True)}
+    for name, c in CC.ILARGE.items():
+        B, by = c["B"], c["by"]
+        Ho, Wo = CC.out_frame(c)
+        assert by == Ho * Wo * c.get("out_channels", c["cout"]) and c["cin"] in (3, 4), name
+        assert B * by < 2 ** 31 and CC.device_bytes(c, LC.CHUNK_BYTES) < 20e9
+        if c["past"] == "limit":
+            assert 2 ** 31 - by <= B * by
+        else:
+            assert (B - CC.T) * by >= c["past"] > (B - CC.T - 1) * by, name
+    assert {c["past"] for c in CC.ILARGE.values()} == {2 ** 29, 2 ** 30, "limit"}
+
+
+def test_backward_refused_calls_stand_exactly_at_the_limit():
+    for entry, what, a in CC.WREFUSED:
+        assert CC.wrefused_count(entry, a) == 2 ** 31, (entry, what)
+        n = a["B"] * a["H"] * a["W"]
+        if entry == "image":
+            counts = [n * a["cin"], n * a["cout"], n * a.get("out_channels", 0)]
+        else:
+            (Ho, Wo), _ = CC.wframes(dict(a, transposed=a.get("transposed", False), stride=a.get("stride", 1)))
+            no = a["B"] * Ho * Wo
+            counts = [n * a["cin"], n * a.get("dx_channels", 0), no * a["cout"], no * a.get("dy_channels", 0), no * a.get("y_channels", 0)]
+        assert sorted(counts)[-1] == 2 ** 31 and sorted(counts)[-2] < 2 ** 31, (entry, what, counts)  # one count alone is at the limit
+    has = {(e, w.split()[-1] if "(" not in w else "dx_channels") for e, w, _ in CC.WREFUSED}
+    assert has >= {("image", "Cout"), ("image", "out_channels"), ("dw_image", "Cout"), ("dw_image", "dy_channels"), ("dw_image", "y_channels"),
+                   ("dx_wide", "Cin"), ("dw_wide", "Cin"), ("dx_wide", "Cout"), ("dw_wide", "Cout"), ("dx_wide", "dy_channels"),
+                   ("dw_wide", "y_channels"), ("dx_wide", "dx_channels")}
+    assert {a.get("transposed", False) for e, _, a in CC.WREFUSED if e in ("dx_wide", "dw_wide")} == {False, True}
+
+
+@pytest.fixture(scope="module", params=[("WLARGE", n) for n in CC.WLARGE] + [("ILARGE", n) for n in CC.ILARGE], ids=lambda p: "%s: %s" % p)
+def blarge(request):
+    table, name = request.param
+    c = getattr(CC, table)[name]
+    return table, c, (CC.wtile(c) if table == "WLARGE" else CC.tile(c))
+
+
+def test_backward_large_tiles_are_alias_free_and_have_no_open_zero(blarge):
+    table, c, d = blarge
+    if table == "ILARGE":
+        for _, period in CC.periods(c, d):
+            LC.assert_alias_free(CC.T, period // CC.T)
+        at = c.get("out_offset", 0)
+        assert (d["want"][..., at:at + c["cout"]] != 0).all()
+        return
+    for key in ("x", "dy", "y"):
+        assert len({d[key][t].tobytes() for t in range(CC.T)}) == CC.T, key
+        LC.assert_alias_free(CC.T, d[key].size // CC.T)
+    want = d["want"]
+    assert np.isfinite(want).all()
+    if c["entry"] == "dx_wide":
+        LC.assert_alias_free(CC.T, want.size // CC.T)
+        spread = not c["transposed"] and c["stride"] == 2 and c["ksize"] == 1
+        assert ((want[:, ::2, ::2] if spread else want) != 0).all()  # off the even grid the 1x1 stride-2 layer writes +0, by the contract
+        if c["dres"]:  # dresidual is g = dy here (LINEAR): a copy, zeros of dy included, bit for bit
+            LC.assert_alias_free(CC.T, d["dres"].size // CC.T)
+            assert c["act"] == R.LINEAR and (d["dres"].view(np.uint32) == d["dy"][..., c["at"]:c["at"] + c["cout"]].view(np.uint32)).all()
+    else:
+        dw, db = CC.split_dw(CC.level2(want, 4 * len(want)), c["ksize"], c["cin"])
+        assert (dw != 0).mean() > 0.9 and (db != 0).all()
