@@ -38,7 +38,11 @@ def __getattr__(name):
         return importlib.import_module(__name__ + ".nyu").nyu_read_device
     if name in ("conv2d_strided", "conv2d_transpose", "conv2d_image", "pack_transpose_kernel",  # numpy forms of the wide and image convolutions
                 "conv2d_strided_bf16", "conv2d_transpose_bf16", "pack_bf16_device", "conv2d_strided_bf16_device",
-                "conv2d_transpose_bf16_device"):  # and the bf16 forms of the wide ones
+                "conv2d_transpose_bf16_device",  # and the bf16 forms of the wide ones, forward and backward
+                "conv2d_strided_backward_data_bf16_device", "conv2d_strided_backward_weights_bf16_device", "conv2d_transpose_backward_data_bf16_device",
+                "conv2d_transpose_backward_weights_bf16_device", "conv2d_wide_backward_bf16_workspace_bytes",
+                "conv2d_strided_backward_data_bf16", "conv2d_strided_backward_weights_bf16", "conv2d_transpose_backward_data_bf16",
+                "conv2d_transpose_backward_weights_bf16"):
         import importlib
 
         return getattr(importlib.import_module(__name__ + ".conv"), name)

@@ -121,6 +121,11 @@ _ABI = {
     "dtfill_conv2d_pack_bf16": (ci, [vp, ci, ci, ci, vp, vp]),
     "dtfill_conv2d_strided_bf16": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, vp, ci, cf, vp, ci, ci, vp]),
     "dtfill_conv2d_transpose_bf16": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, cf, vp, ci, ci, vp]),
+    "dtfill_conv2d_wide_backward_bf16_workspace_bytes": (sz, [ci, ci, ci, ci, ci, ci, ci, ci]),
+    "dtfill_conv2d_strided_backward_data_bf16": (ci, [vp, ci, ci, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp, ci, ci, vp, vp, sz, vp]),
+    "dtfill_conv2d_strided_backward_weights_bf16": (ci, [vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp, vp, vp, sz, vp]),
+    "dtfill_conv2d_transpose_backward_data_bf16": (ci, [vp, ci, ci, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, cf, vp, ci, ci, vp, sz, vp]),
+    "dtfill_conv2d_transpose_backward_weights_bf16": (ci, [vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp, vp, vp, sz, vp]),
     "dtfill_conv2d_strided": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, vp, ci, cf, vp, ci, ci, vp]),
     "dtfill_conv2d_transpose": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, cf, vp, ci, ci, vp]),
     "dtfill_conv2d": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, cf, vp, ci, ci, vp]),

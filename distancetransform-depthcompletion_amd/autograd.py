@@ -25,7 +25,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import device
-from .conv import _backward_data, _backward_weights, _forward
+from .conv import PRECISIONS, _backward_data, _backward_weights, _forward, _forward_bf16, pack_bf16_device
 
 
 class _WindowSteps(torch.autograd.Function):
@@ -255,10 +255,13 @@ class _Conv(torch.autograd.Function):
     [3,3,Cin,Cout]); the backward asks the library only for the gradients that are needed.  Both through conv.py's cores."""
 
     @staticmethod
-    def forward(ctx, kind, x, w, bias, residual, stride, act, alpha):
-        y = _forward(kind, x, w, bias, stride, residual, act, alpha, None, 0)
+    def forward(ctx, kind, x, w, bias, residual, stride, act, alpha, precision="float32"):
+        if precision == "bf16":  # w is packed for this call; the float32 x, w and y are what the backward reads
+            y = _forward_bf16(kind, x, pack_bf16_device(w, kind == "transposed"), bias, stride, residual, act, alpha, None, 0)
+        else:
+            y = _forward(kind, x, w, bias, stride, residual, act, alpha, None, 0)
         ctx.set_materialize_grads(False)  # an unused y arrives as None: nothing is launched for it
-        ctx.kind, ctx.stride, ctx.act, ctx.alpha = kind, stride, act, alpha
+        ctx.kind, ctx.stride, ctx.act, ctx.alpha, ctx.precision = kind, stride, act, alpha, precision
         ctx.save_for_backward(x, w, None if act == "linear" else y)  # (a linear layer's derivative does not read y)
         return y
 
@@ -267,12 +270,12 @@ class _Conv(torch.autograd.Function):
     def backward(ctx, g_y):
         want_x, want_w, want_b, want_r = ctx.needs_input_grad[1:5]
         if g_y is None or not (want_x or want_w or want_b or want_r):
-            return (None,) * 8
+            return (None,) * 9
         x, w, y = ctx.saved_tensors
         dy, at = _channel_slice(g_y)
         dx = dr = dw = db = None
         if want_x:
-            dx = _backward_data(ctx.kind, dy, w, ctx.stride, y, ctx.act, ctx.alpha, at, 0, None, 0, want_r)
+            dx = _backward_data(ctx.kind, dy, w, ctx.stride, y, ctx.act, ctx.alpha, at, 0, None, 0, want_r, ctx.precision)
             if want_r:
                 dx, dr = dx
             dx = dx.view(x.shape)  # ([B,H,W,1] of a plane x)
@@ -280,8 +283,9 @@ class _Conv(torch.autograd.Function):
             g = dy[..., at:at + w.shape[3]]
             dr = (g if y is None else torch.where(y > 0, g, g * ctx.alpha)).contiguous()
         if want_w or want_b:
-            dw, db = _backward_weights(ctx.kind, x, dy, w.shape[0], ctx.stride, y, ctx.act, ctx.alpha, at, 0, w.shape[3], want_b)
-        return None, dx, (dw if want_w else None), db, dr, None, None, None
+            dw, db = _backward_weights(ctx.kind, x, dy, w.shape[0], ctx.stride, y, ctx.act, ctx.alpha, at, 0, w.shape[3], want_b,
+                                       ctx.precision)
+        return None, dx, (dw if want_w else None), db, dr, None, None, None, None
 
 
 class _MaxPoolPyramid(torch.autograd.Function):
@@ -319,10 +323,12 @@ def max_pool_pyramid(x, levels=(2, 4, 8)):
     return _MaxPoolPyramid.apply(x, tuple(int(k) for k in levels))
 
 
-def _conv(kind, x, w, bias, residual, stride, act, alpha):
+def _conv(kind, x, w, bias, residual, stride, act, alpha, precision="float32"):
     if not alpha >= 0:
         raise ValueError("alpha must be >= 0 (the derivative is taken by the sign of the output), got %r" % (alpha,))
-    return _Conv.apply(kind, x, w, bias, residual, stride, act, float(alpha))
+    if precision not in PRECISIONS:
+        raise ValueError("precision must be one of %s, got %r" % (PRECISIONS, precision))
+    return _Conv.apply(kind, x, w, bias, residual, stride, act, float(alpha), precision)
 
 
 def conv2d(x, w, bias=None, act="linear", alpha=0.2):
@@ -353,7 +359,7 @@ def conv2d_image(x, w, bias=None, act="linear", alpha=0.2):
     return _conv("image", x, w, bias, None, 1, act, alpha)
 
 
-def conv2d_strided(x, w, bias=None, stride=1, residual=None, act="linear", alpha=0.2):
+def conv2d_strided(x, w, bias=None, stride=1, residual=None, act="linear", alpha=0.2, precision="float32"):
     """A wide 'same' float32 convolution of stride 1 or 2 with its residual add and its activation as a differentiable operator:
     a layer of net.py's ResNet18_NO_BN_l2 under train.py:232-254's tape.  x: contiguous float32 CUDA tensor [B,H,W,Cin]; w:
     [ksize,ksize,Cin,Cout], a Keras Conv2D.kernel as stored; bias: [Cout] or None; residual: [B,Ho,Wo,Cout] or None, added in
@@ -362,15 +368,22 @@ def conv2d_strided(x, w, bias=None, stride=1, residual=None, act="linear", alpha
     residual (g itself), dtfill_conv2d_strided_backward_weights those of w and bias, each only where it is needed, in their
     fixed summation orders.  A gradient of y that is a channel slice of a wider contiguous tensor (torch.cat's backward) is
     read in place.  The reference's kernel_regularizer takes no part: train.py:253 differentiates total_loss alone.  At
-    stride 2 H and W must be even.  No host synchronisation in either direction."""
-    return _conv("strided", x, w, bias, residual, int(stride), act, alpha)
+    stride 2 H and W must be even.  No host synchronisation in either direction.
+    precision = "bf16" (ksize 1 or 3): the node packs w (dtfill_conv2d_pack_bf16), runs dtfill_conv2d_strided_bf16 and keeps
+    the float32 x, w and y; its backward calls dtfill_conv2d_strided_backward_data_bf16 and _weights_bf16.  One tape node, the
+    same tensors saved, the sliced gradient read in place and no host synchronisation, as under "float32"; the gradients are
+    float32 tensors within the header's bounds and their bits are a function of the inputs and the shape alone.  Anything
+    else than "float32" or "bf16" raises ValueError."""
+    return _conv("strided", x, w, bias, residual, int(stride), act, alpha, precision)
 
 
-def conv2d_transpose(x, kernel, bias=None, act="linear", alpha=0.2):
+def conv2d_transpose(x, kernel, bias=None, act="linear", alpha=0.2, precision="float32"):
     """tf.keras.layers.Conv2DTranspose(Cout, 3, strides=2, padding='same') with its activation as a differentiable operator.
     x: contiguous float32 CUDA tensor [B,H,W,Cin]; kernel: [3,3,Cout,Cin], the layer's kernel as Keras stores it; bias: [Cout]
     or None.  Returns y [B,2H,2W,Cout] by device.conv2d_transpose_device (include/dtfill.h, dtfill_conv2d_transpose).  The
     pack to the ABI's [3,3,Cin,Cout] is a permute inside the graph, so the kernel's gradient arrives in Keras' layout through
     autograd's own permute.  Differentiable in x, kernel and bias, once, by dtfill_conv2d_transpose_backward_data and _weights
-    in their fixed summation orders.  No weight-decay term, as in conv2d_strided.  No host synchronisation."""
-    return _conv("transposed", x, kernel.permute(0, 1, 3, 2).contiguous(), bias, None, 2, act, alpha)
+    in their fixed summation orders.  No weight-decay term, as in conv2d_strided.  No host synchronisation.
+    precision = "bf16": dtfill_conv2d_transpose_bf16 forward and dtfill_conv2d_transpose_backward_data_bf16 and _weights_bf16
+    backward, as conv2d_strided states."""
+    return _conv("transposed", x, kernel.permute(0, 1, 3, 2).contiguous(), bias, None, 2, act, alpha, precision)

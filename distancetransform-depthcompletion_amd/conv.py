@@ -17,8 +17,11 @@ calls the cores directly with the kind it carries.  conv2d_strided, conv2d_trans
 The strided and the transposed kind have a second forward, on the bf16 matrix cores with float32 accumulation
 (dtfill_conv2d_strided_bf16, dtfill_conv2d_transpose_bf16: the header states what is promised about its bits): pack_bf16_device
 makes the packed weights once, conv2d_strided_bf16_device and conv2d_transpose_bf16_device take them in place of w through one
-core, _forward_bf16, under the same _KINDS record; conv2d_strided_bf16 and conv2d_transpose_bf16 are the numpy forms.  Inference
-only: there is no bf16 backward.
+core, _forward_bf16, under the same _KINDS record; conv2d_strided_bf16 and conv2d_transpose_bf16 are the numpy forms.  Their
+backward on the same matrix cores (dtfill_conv2d_strided_backward_data_bf16 and its three siblings) goes through
+_backward_data and _backward_weights under precision = "bf16", which the _KINDS record maps to the symbols and the size
+function: conv2d_strided_backward_data_bf16_device and the other three *_bf16_device functions, and their numpy forms without
+the suffix _device.  They take the plain float32 w, not the packed one: the weights change every step and the call packs them.
 
 The *_device functions and the size functions are reached as device.<name> as well, and everything here as net.<name>; they live
 here, beside device.py's helpers, as the pools do in pool.py.  Their argument checks are held by tests/test_conv2d*.py, the
@@ -112,9 +115,11 @@ def _check_conv_backward(dy, y, act, dy_offset, y_offset, Cout):
 # ksize: the [3,3,..] rule, or None for any square kernel; plane_ok: x may be a [B,H,W] plane; out_frame(H, W, stride): the
 # forward's output frame for ANY input frame (TensorFlow's 'same' rule, ceil(H / stride)); x_frame(Ho, Wo, stride): the
 # forward's input frame under a dy of [Ho,Wo], and dy_frame(H, W, stride) the reverse, each None where the kind has no such
-# layer (the backward's evenness rule).
+# layer (the backward's evenness rule).  ws_bytes_bf16: the size function of the backward under precision = "bf16", whose symbols
+# are data and weights with "_bf16" appended; None where the kind has no such backward.
 _Kind = collections.namedtuple("_Kind", "forward data weights abi_shape has_residual ws_bytes w_name w_layout ksize dy_layout "
-                                        "plane_ok out_frame x_frame dy_frame")
+                                        "plane_ok out_frame x_frame dy_frame ws_bytes_bf16", defaults=(None,))
+PRECISIONS = ("float32", "bf16")
 _KINDS = {
     "narrow": _Kind("dtfill_conv2d", "dtfill_conv2d_backward_data", "dtfill_conv2d_backward_weights",
                     lambda ksize, Cout, s: (ksize, Cout), False,
@@ -126,13 +131,15 @@ _KINDS = {
                      lambda L, B, H, W, Cin, ksize, Cout, s: L.dtfill_conv2d_wide_backward_workspace_bytes(B, H, W, Cin, ksize, Cout, s, 0),
                      "w", "[ksize,ksize,Cin,Cout]", None, "[B,Ho,Wo,C]", False,
                      lambda H, W, s: (-(-H // s), -(-W // s)), lambda Ho, Wo, s: (s * Ho, s * Wo),
-                     lambda H, W, s: None if H % s or W % s else (H // s, W // s)),
+                     lambda H, W, s: None if H % s or W % s else (H // s, W // s),
+                     lambda L, B, H, W, Cin, ksize, Cout, s: L.dtfill_conv2d_wide_backward_bf16_workspace_bytes(B, H, W, Cin, ksize, Cout, s, 0)),
     "transposed": _Kind("dtfill_conv2d_transpose", "dtfill_conv2d_transpose_backward_data", "dtfill_conv2d_transpose_backward_weights",
                         lambda ksize, Cout, s: (Cout,), False,
                         lambda L, B, H, W, Cin, ksize, Cout, s: L.dtfill_conv2d_wide_backward_workspace_bytes(B, H, W, Cin, 3, Cout, 2, 1),
                         "w_packed", "[3,3,Cin,Cout]", 3, "[B,2H,2W,C]", False,
                         lambda H, W, s: (2 * H, 2 * W), lambda Ho, Wo, s: None if Ho % 2 or Wo % 2 else (Ho // 2, Wo // 2),
-                        lambda H, W, s: (2 * H, 2 * W)),
+                        lambda H, W, s: (2 * H, 2 * W),
+                        lambda L, B, H, W, Cin, ksize, Cout, s: L.dtfill_conv2d_wide_backward_bf16_workspace_bytes(B, H, W, Cin, 3, Cout, 2, 1)),
     # the layer that reads the image: no data call, the image is data
     "image": _Kind("dtfill_conv2d_image", None, "dtfill_conv2d_image_backward_weights", lambda ksize, Cout, s: (ksize, Cout), False,
                    lambda L, B, H, W, Cin, ksize, Cout, s: L.dtfill_conv2d_image_backward_workspace_bytes(B, H, W, Cin, ksize, Cout),
@@ -176,16 +183,22 @@ def _forward(kind, x, w, bias, stride, residual, act, alpha, out, out_offset):
     return out
 
 
-def _check_backward_kind(kind, act, alpha, stride):
+def _check_backward_kind(kind, act, alpha, stride, precision="float32"):
+    """Returns (the kind's record, the suffix of its backward symbols under `precision`, its size function)."""
+    if precision not in PRECISIONS:
+        raise ValueError("precision must be one of %s, got %r" % (PRECISIONS, precision))
+    k = _KINDS[kind]
+    if precision == "bf16" and k.ws_bytes_bf16 is None:
+        raise ValueError("a %s layer has no bf16 backward" % kind)
     _check_act(act, alpha)
     if stride not in (1, 2):
         raise ValueError("stride must be 1 or 2, got %r" % (stride,))
-    return _KINDS[kind]
+    return (k, "_bf16", k.ws_bytes_bf16) if precision == "bf16" else (k, "", k.ws_bytes)
 
 
-def _backward_data(kind, dy, w, stride, y, act, alpha, dy_offset, y_offset, dx, dx_offset, want_residual=False):
+def _backward_data(kind, dy, w, stride, y, act, alpha, dy_offset, y_offset, dx, dx_offset, want_residual=False, precision="float32"):
     """The data gradient of a layer of `kind`: the public functions' shared sequence, once."""
-    k = _check_backward_kind(kind, act, alpha, stride)
+    k, suffix, ws_bytes = _check_backward_kind(kind, act, alpha, stride, precision)
     _check_tensor(w, k.w_name, layout=k.w_layout)
     ksize, Cin, Cout = w.shape[0], w.shape[2], w.shape[3]
     Cdy, y, Cy = _check_conv_backward(dy, y, act, dy_offset, y_offset, Cout)
@@ -199,19 +212,19 @@ def _backward_data(kind, dy, w, stride, y, act, alpha, dy_offset, y_offset, dx, 
         raise ValueError("dx may not alias y")
     dres = torch.empty(tuple(dy.shape[:3]) + (Cout,), dtype=torch.float32, device=dy.device) if want_residual else None
     L = _lib.load()
-    nbytes = _device._sized(k.ws_bytes(L, B, H, W, Cin, ksize, Cout, stride))
+    nbytes = _device._sized(ws_bytes(L, B, H, W, Cin, ksize, Cout, stride))
     with torch.cuda.device(dy.device):
         with _convb_ws.hold(dy.device, nbytes) as ws:
-            _lib.check(getattr(L, k.data)(
+            _lib.check(getattr(L, k.data + suffix)(
                 dy.data_ptr(), Cdy, int(dy_offset), _ptr(y), Cy, int(y_offset), w.data_ptr(), B, H, W, Cin,
                 *k.abi_shape(ksize, Cout, stride), _lib.CONV_ACTS[act], float(alpha), dx.data_ptr(), dx.shape[3], int(dx_offset),
                 *((_ptr(dres),) if k.has_residual else ()), ws, nbytes, _stream(dy.device)))
     return (dx, dres) if want_residual else dx
 
 
-def _backward_weights(kind, x, dy, ksize, stride, y, act, alpha, dy_offset, y_offset, cout, want_bias):
+def _backward_weights(kind, x, dy, ksize, stride, y, act, alpha, dy_offset, y_offset, cout, want_bias, precision="float32"):
     """The weight and bias gradients of a layer of `kind`: the shared sequence, once."""
-    k = _check_backward_kind(kind, act, alpha, stride)
+    k, suffix, ws_bytes = _check_backward_kind(kind, act, alpha, stride, precision)
     plane = k.plane_ok and x.dim() == 3
     _check_tensor(x, "x", layout="[B,H,W]" if plane else "[B,H,W,Cin]")
     B, H, W, Cin = (*x.shape, 1) if plane else x.shape
@@ -224,12 +237,12 @@ def _backward_weights(kind, x, dy, ksize, stride, y, act, alpha, dy_offset, y_of
     Cdy, y, Cy = _check_conv_backward(dy, y, act, dy_offset, y_offset, Cout)
     ksize = int(ksize)
     L = _lib.load()
-    nbytes = _device._sized(k.ws_bytes(L, B, H, W, Cin, ksize, Cout, stride))
+    nbytes = _device._sized(ws_bytes(L, B, H, W, Cin, ksize, Cout, stride))
     dw = torch.empty((ksize, ksize, Cin, Cout), dtype=torch.float32, device=x.device)
     db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_bias else None
     with torch.cuda.device(x.device):
         with _convb_ws.hold(x.device, nbytes) as ws:
-            _lib.check(getattr(L, k.weights)(
+            _lib.check(getattr(L, k.weights + suffix)(
                 x.data_ptr(), dy.data_ptr(), Cdy, int(dy_offset), _ptr(y), Cy, int(y_offset), B, H, W, Cin,
                 *k.abi_shape(ksize, Cout, stride), _lib.CONV_ACTS[act], float(alpha), dw.data_ptr(), _ptr(db), ws, nbytes,
                 _stream(x.device)))
@@ -436,6 +449,80 @@ def conv2d_transpose_bf16(x, kernel, bias=None, act="linear", alpha=0.2):
     stores a Conv2DTranspose's (exchanged and packed here).  Returns float32 [B,2H,2W,Cout]."""
     a, k, b = _uploaded(x, kernel, bias)
     return conv2d_transpose_bf16_device(a, pack_bf16_device(k.permute(0, 1, 3, 2).contiguous(), transposed=True), b, act, alpha).cpu().numpy()
+
+
+def conv2d_wide_backward_bf16_workspace_bytes(B, H, W, Cin, ksize, Cout, stride=1, transposed=False):
+    """The bytes of workspace either bf16 backward call of a wide layer needs (dtfill_conv2d_wide_backward_bf16_workspace_bytes):
+    host arithmetic, no device.  DtfillError for a shape outside the domain (ksize 1 or 3)."""
+    return _device._sized(_lib.load().dtfill_conv2d_wide_backward_bf16_workspace_bytes(int(B), int(H), int(W), int(Cin), int(ksize),
+                                                                                      int(Cout), int(stride), int(bool(transposed))))
+
+
+def conv2d_strided_backward_data_bf16_device(dy, w, stride=1, y=None, act="linear", alpha=0.2, dy_offset=0, y_offset=0, dx=None,
+                                             dx_offset=0, want_residual=False):
+    """conv2d_strided_backward_data_device on the bf16 matrix cores with float32 accumulation (include/dtfill.h,
+    dtfill_conv2d_strided_backward_data_bf16): the same float32 tensors, w the plain float32 [ksize,ksize,Cin,Cout] with ksize
+    1 or 3 (packed inside the call).  g = dy act'(y) is made in float32 and dresidual is g exactly; dx is the bf16 forward over
+    g under the flipped or exchanged kernel, bit for bit, within the header's bound.  Asynchronous on the current stream."""
+    return _backward_data("strided", dy, w, stride, y, act, alpha, dy_offset, y_offset, dx, dx_offset, want_residual, "bf16")
+
+
+def conv2d_strided_backward_weights_bf16_device(x, dy, ksize, stride=1, y=None, act="linear", alpha=0.2, dy_offset=0, y_offset=0,
+                                                cout=None, want_bias=True):
+    """conv2d_strided_backward_weights_device on the bf16 matrix cores with float32 accumulation
+    (dtfill_conv2d_strided_backward_weights_bf16): x and g rounded to bf16 in registers, one MFMA per 32 pixels, tap and tile
+    into float32 partials per segment, the segments added in float32 in a fixed order.  The bits are a function of the inputs
+    and the shape alone and lie within the header's bound of the exact sum.  Returns (dw, db or None): new float32 tensors."""
+    return _backward_weights("strided", x, dy, ksize, stride, y, act, alpha, dy_offset, y_offset, cout, want_bias, "bf16")
+
+
+def conv2d_transpose_backward_data_bf16_device(dy, w_packed, y=None, act="linear", alpha=0.2, dy_offset=0, y_offset=0, dx=None,
+                                               dx_offset=0):
+    """conv2d_transpose_backward_data_device on the bf16 matrix cores (dtfill_conv2d_transpose_backward_data_bf16): w_packed is
+    the float32 [3,3,Cin,Cout] that function takes.  Everything else as conv2d_strided_backward_data_bf16_device."""
+    return _backward_data("transposed", dy, w_packed, 2, y, act, alpha, dy_offset, y_offset, dx, dx_offset, False, "bf16")
+
+
+def conv2d_transpose_backward_weights_bf16_device(x, dy, y=None, act="linear", alpha=0.2, dy_offset=0, y_offset=0, cout=None,
+                                                  want_bias=True):
+    """conv2d_transpose_backward_weights_device on the bf16 matrix cores (dtfill_conv2d_transpose_backward_weights_bf16).
+    Returns (dw in the packed layout [3,3,Cin,Cout], db or None).  As conv2d_strided_backward_weights_bf16_device."""
+    return _backward_weights("transposed", x, dy, 3, 2, y, act, alpha, dy_offset, y_offset, cout, want_bias, "bf16")
+
+
+def _numpy_or_none(t):
+    return None if t is None else t.cpu().numpy()
+
+
+def conv2d_strided_backward_data_bf16(dy, kernel, stride=1, y=None, act="linear", alpha=0.2, want_residual=False):
+    """conv2d_strided_backward_data_bf16_device as a numpy function: dy [B,Ho,Wo,Cout], kernel [ksize,ksize,Cin,Cout], y like dy
+    or None.  Returns float32 dx [B,stride Ho,stride Wo,Cin], or (dx, dresidual) with want_residual."""
+    d, k, yy = _uploaded(dy, kernel, y)
+    out = conv2d_strided_backward_data_bf16_device(d, k, stride, yy, act, alpha, want_residual=want_residual)
+    return tuple(t.cpu().numpy() for t in out) if want_residual else out.cpu().numpy()
+
+
+def conv2d_strided_backward_weights_bf16(x, dy, ksize, stride=1, y=None, act="linear", alpha=0.2, want_bias=True):
+    """conv2d_strided_backward_weights_bf16_device as a numpy function.  Returns float32 (dw [ksize,ksize,Cin,Cout], db [Cout] or
+    None)."""
+    a, d, yy = _uploaded(x, dy, y)
+    return tuple(_numpy_or_none(t) for t in conv2d_strided_backward_weights_bf16_device(a, d, ksize, stride, yy, act, alpha,
+                                                                                       want_bias=want_bias))
+
+
+def conv2d_transpose_backward_data_bf16(dy, kernel, y=None, act="linear", alpha=0.2):
+    """conv2d_transpose_backward_data_bf16_device as a numpy function: dy [B,2H,2W,Cout], kernel [3,3,Cout,Cin] as Keras stores a
+    Conv2DTranspose's (exchanged here).  Returns float32 dx [B,H,W,Cin]."""
+    d, k, yy = _uploaded(dy, kernel, y)
+    return conv2d_transpose_backward_data_bf16_device(d, k.permute(0, 1, 3, 2).contiguous(), yy, act, alpha).cpu().numpy()
+
+
+def conv2d_transpose_backward_weights_bf16(x, dy, y=None, act="linear", alpha=0.2, want_bias=True):
+    """conv2d_transpose_backward_weights_bf16_device as a numpy function.  Returns float32 (dw [3,3,Cout,Cin] in Keras' layout, db
+    [Cout] or None)."""
+    a, d, yy = _uploaded(x, dy, y)
+    dw, db = conv2d_transpose_backward_weights_bf16_device(a, d, yy, act, alpha, want_bias=want_bias)
+    return dw.permute(0, 1, 3, 2).contiguous().cpu().numpy(), _numpy_or_none(db)
 
 
 def pack_transpose_kernel(kernel):

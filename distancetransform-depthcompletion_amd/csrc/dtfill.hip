@@ -112,6 +112,7 @@ namespace {
 #include "dtfill_pool.hpp"
 #include "dtfill_adam.hpp"
 #include "dtfill_convh.hpp"
+#include "dtfill_convhb.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -1301,6 +1302,7 @@ static bool convb_plan(const ConvBwLayer &l, ConvBwPlan *p) {
         } else if (l.stride != 1 || !k1357) {
             return false;
         }
+        if (l.bf16 && ksize != 1 && ksize != 3) return false;  // dtfill_conv2d_strided_bf16's domain
         if ((long long)B * H * W * Cin >= (1ll << 31) || B * ho * wo * Cout >= (1ll << 31)) return false;
         if (((long long)ksize * ksize * Cin + 1) * Cout >= (1ll << 31)) return false;
     }
@@ -1311,7 +1313,8 @@ static bool convb_plan(const ConvBwLayer &l, ConvBwPlan *p) {
     p->segs_y = (p->Hs + CB_R - 1) / CB_R, p->segs_x = (p->Ws + CB_C - 1) / CB_C;
     const size_t taps = (size_t)ksize * ksize, pixels = (size_t)B * p->Ho * p->Wo;
     p->wt = align256(pixels * Cout * sizeof(float));
-    p->tmp = p->wt + align256(taps * Cin * Cout * sizeof(float));
+    // the kernel the data gradient runs under: float32 wT or wX, or their packed bf16 array (Cout in, Cin out)
+    p->tmp = p->wt + align256(l.bf16 ? (size_t)convh_packed_quads(ksize, Cout, Cin) * sizeof(ch_b8) : taps * Cin * Cout * sizeof(float));
     const bool spread = !l.transposed && l.stride == 2 && ksize == 1;  // the chain's values before k_convb_spread
     const size_t data = l.image ? 0 : p->tmp + (spread ? align256(pixels * Cin * sizeof(float)) : 0);  // (the image layer has no dx)
     const size_t weights = align256((size_t)B * p->segs_y * p->segs_x * (taps * Cin + 1) * Cout * sizeof(float));
@@ -1351,20 +1354,20 @@ static int convb_check(const ConvBwLayer &l, const float *dy, int dy_channels, i
 
 static int convb_data(const ConvBwLayer &l, const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels,
                       int y_offset, const float *w, int act, float alpha, float *dx, int dx_channels, int dx_offset, float *dresidual,
-                      void *workspace, size_t ws_bytes, void *stream) {
+                      void *workspace, size_t ws_bytes, void *stream, decltype(convb_data_launch) *launch = convb_data_launch) {
     if (!w || !dx) return DTFILL_ERR_NULL;
     ConvBwPlan p;
     ConvBwArgs a;
     const int rc = convb_check(l, dy, dy_channels, dy_offset, y, y_channels, y_offset, act, alpha, workspace, ws_bytes, &p, &a);
     if (rc != DTFILL_OK) return rc;
     if (!convb_slice(l.B, l.H, l.W, l.Cin, dx_channels, dx_offset)) return DTFILL_ERR_SHAPE;
-    convb_data_launch(static_cast<hipStream_t>(stream), l, p, a, w, dx, dx_channels, dx_offset, dresidual, workspace);
+    launch(static_cast<hipStream_t>(stream), l, p, a, w, dx, dx_channels, dx_offset, dresidual, workspace);
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 
 static int convb_weights(const ConvBwLayer &l, const float *x, const float *dy, int dy_channels, int dy_offset, const float *y,
                          int y_channels, int y_offset, int act, float alpha, float *dw, float *db, void *workspace, size_t ws_bytes,
-                         void *stream) {
+                         void *stream, decltype(convb_weights_launch) *launch = convb_weights_launch) {
     if (!x || !dw) return DTFILL_ERR_NULL;
     ConvBwPlan p;
     ConvBwWide a;
@@ -1373,7 +1376,7 @@ static int convb_weights(const ConvBwLayer &l, const float *x, const float *dy, 
     a.b.x = x;
     a.b.xvec = ((uintptr_t)x & 15) == 0;  // (Cin is a multiple of 16 wherever 16-byte loads of x are used)
     a.HL = p.HL, a.WL = p.WL;
-    convb_weights_launch(static_cast<hipStream_t>(stream), l, a, dw, db, workspace);
+    launch(static_cast<hipStream_t>(stream), l, a, dw, db, workspace);
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
 }
 
@@ -1600,6 +1603,42 @@ int dtfill_conv2d_transpose_bf16(const float *x, int B, int H, int W, int Cin, c
     const ConvArgs a{x, wp, bias, nullptr, out, B, H, W, Cin, Cout, 2 * H, 2 * W, 0, 0, out_channels, out_offset, act, alpha};
     convh_transpose_launch<>(static_cast<hipStream_t>(stream), a);
     return hipGetLastError() == hipSuccess ? DTFILL_OK : DTFILL_ERR_LAUNCH;
+}
+
+// The bf16 forms of the wide layers' backward (dtfill_convhb.hpp): the float32 calls' checks and plan under ConvBwLayer::bf16, the
+// launches handed in here so that their kernels are asked for behind every older one.
+size_t dtfill_conv2d_wide_backward_bf16_workspace_bytes(int B, int H, int W, int Cin, int ksize, int Cout, int stride, int transposed) {
+    return convb_workspace_bytes(ConvBwLayer{B, H, W, Cin, ksize, Cout, stride, transposed != 0, false, false, true});
+}
+
+int dtfill_conv2d_strided_backward_data_bf16(const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels,
+                                             int y_offset, const float *w, int B, int H, int W, int Cin, int ksize, int Cout, int stride,
+                                             int act, float alpha, float *dx, int dx_channels, int dx_offset, float *dresidual,
+                                             void *workspace, size_t ws_bytes, void *stream) {
+    return convb_data(ConvBwLayer{B, H, W, Cin, ksize, Cout, stride, false, false, false, true}, dy, dy_channels, dy_offset, y, y_channels,
+                      y_offset, w, act, alpha, dx, dx_channels, dx_offset, dresidual, workspace, ws_bytes, stream, convhb_data_launch<>);
+}
+
+int dtfill_conv2d_strided_backward_weights_bf16(const float *x, const float *dy, int dy_channels, int dy_offset, const float *y,
+                                                int y_channels, int y_offset, int B, int H, int W, int Cin, int ksize, int Cout,
+                                                int stride, int act, float alpha, float *dw, float *db, void *workspace, size_t ws_bytes,
+                                                void *stream) {
+    return convb_weights(ConvBwLayer{B, H, W, Cin, ksize, Cout, stride, false, false, false, true}, x, dy, dy_channels, dy_offset, y,
+                         y_channels, y_offset, act, alpha, dw, db, workspace, ws_bytes, stream, convhb_weights_launch<>);
+}
+
+int dtfill_conv2d_transpose_backward_data_bf16(const float *dy, int dy_channels, int dy_offset, const float *y, int y_channels,
+                                               int y_offset, const float *w, int B, int H, int W, int Cin, int Cout, int act, float alpha,
+                                               float *dx, int dx_channels, int dx_offset, void *workspace, size_t ws_bytes, void *stream) {
+    return convb_data(ConvBwLayer{B, H, W, Cin, 3, Cout, 2, true, false, false, true}, dy, dy_channels, dy_offset, y, y_channels, y_offset,
+                      w, act, alpha, dx, dx_channels, dx_offset, nullptr, workspace, ws_bytes, stream, convhb_data_launch<>);
+}
+
+int dtfill_conv2d_transpose_backward_weights_bf16(const float *x, const float *dy, int dy_channels, int dy_offset, const float *y,
+                                                  int y_channels, int y_offset, int B, int H, int W, int Cin, int Cout, int act,
+                                                  float alpha, float *dw, float *db, void *workspace, size_t ws_bytes, void *stream) {
+    return convb_weights(ConvBwLayer{B, H, W, Cin, 3, Cout, 2, true, false, false, true}, x, dy, dy_channels, dy_offset, y, y_channels,
+                         y_offset, act, alpha, dw, db, workspace, ws_bytes, stream, convhb_weights_launch<>);
 }
 
 }  // extern "C"

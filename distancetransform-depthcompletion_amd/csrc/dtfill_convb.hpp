@@ -605,6 +605,7 @@ struct ConvBwLayer {  // a layer as its backward sees it: the forward's input [B
     int B, H, W, Cin, ksize, Cout, stride;
     bool transposed, narrow;  // narrow: dtfill_conv2d's domain (Cin 1/16/32/48/64, Cout 1/16, stride 1) and kernels; else the wide ones
     bool image = false;       // dtfill_conv2d_image's domain (Cin 2/3/4, Cout a multiple of 16, stride 1): weights only, its own kernel
+    bool bf16 = false;        // a wide layer on the bf16 matrix cores (dtfill_convhb.hpp): ksize 1 or 3, the packed kernel in the workspace
 };
 
 struct ConvBwPlan {         // what convb_plan derives from a layer in its domain

@@ -845,7 +845,8 @@ def __getattr__(name):
                 "conv2d_transpose_backward_weights_device", "conv2d_wide_backward_workspace_bytes", "conv2d_image_device",
                 "conv2d_image_backward_weights_device", "conv2d_image_backward_workspace_bytes", "pack_bf16_device",
                 "conv2d_strided_bf16_device", "conv2d_transpose_bf16_device", "conv2d_strided_bf16",
-                "conv2d_transpose_bf16"):  # likewise in conv.py
+                "conv2d_transpose_bf16", "conv2d_strided_backward_data_bf16_device", "conv2d_strided_backward_weights_bf16_device", "conv2d_transpose_backward_data_bf16_device",
+                "conv2d_transpose_backward_weights_bf16_device", "conv2d_wide_backward_bf16_workspace_bytes"):  # likewise in conv.py
         from . import conv
 
         return getattr(conv, name)

@@ -35,7 +35,11 @@ from .conv import (_Kind, _KINDS, _backward_data, _backward_weights, _check_act,
                    conv2d_strided_bf16, conv2d_strided_bf16_device, conv2d_strided_device, conv2d_transpose,
                    conv2d_transpose_backward_data_device, conv2d_transpose_backward_weights_device, conv2d_transpose_bf16,
                    conv2d_transpose_bf16_device, conv2d_transpose_device, conv2d_wide_backward_workspace_bytes, pack_bf16_device,
-                   pack_transpose_kernel)
+                   pack_transpose_kernel, conv2d_strided_backward_data_bf16, conv2d_strided_backward_data_bf16_device,
+                   conv2d_strided_backward_weights_bf16, conv2d_strided_backward_weights_bf16_device,
+                   conv2d_transpose_backward_data_bf16, conv2d_transpose_backward_data_bf16_device,
+                   conv2d_transpose_backward_weights_bf16, conv2d_transpose_backward_weights_bf16_device,
+                   conv2d_wide_backward_bf16_workspace_bytes)
 from .device import _check_tensor
 
 LEAKY_ALPHA = 0.2  # tf.nn.leaky_relu's default
@@ -43,7 +47,7 @@ STEM_WIDTH = 16  # channels every stem writes of the [B,H,W,16 * scale_num] tens
 RESNET_WIDTHS = (64, 128, 256, 512)  # channels of levels 1 .. 4; level k lives at 1 / 2^(k-1) of the frame each way
 RESNET_STRIDE2 = ("conv2a", "conv2a_extra", "conv3a", "conv3a_extra", "conv4a", "conv4a_extra")
 RESNET_TRANSPOSED = ("upsample_4", "upsample_3", "upsample_2")  # Conv2DTranspose: Keras stores [3,3,Cout,Cin]
-PRECISIONS = ("float32", "bf16")  # of the inference ResNets' wide and transposed layers; everything else is float32 in both
+PRECISIONS = ("float32", "bf16")  # of the ResNets' wide and transposed layers (conv.PRECISIONS); everything else is float32 in both
 IMAGE_WIDTH = 64  # channels img_conv writes in front of the stems: conv1a of the image network reads [image | stems]
 LIGHT_WIDTH = 64  # channels of every level of the light network, and of conv1_pre's output, the tensor it pools
 LIGHT_POOLS = (2, 4, 8)  # tf.nn.max_pool of conv1_pre's output behind levels 2, 3 and 4 (net.py:4285, 4320, 4353)
@@ -358,8 +362,9 @@ class _ResNet(_LidarNet):
     _wide and _up (every layer of the trunk but img_conv and conv_output) on the bf16 matrix cores with float32 accumulation
     (dtfill_conv2d_strided_bf16, dtfill_conv2d_transpose_bf16) over weights packed once per device; the activations stay
     float32 in memory, so the buffers, the concat offsets and the skip copies are the same, and the head, the fill, the stems,
-    the correction branch, img_conv, the pooling and conv_output stay float32.  Inference only: the Trainable classes have no
-    such argument."""
+    the correction branch, img_conv, the pooling and conv_output stay float32.  The Trainable classes have no such argument:
+    they have a settable attribute, model.precision = "bf16" (ResNet18Trainable), and pack the kernels inside every call,
+    because they change every step."""
 
     IMAGE_WIDTH, WIDTHS, PRE, POOLS, LIDAR_SKIP = 0, RESNET_WIDTHS, None, (), False
 
@@ -596,21 +601,42 @@ class ResNet18Trainable(_TrainableNet):
       tensor's gradient is (d concat_image + d pools) + d concat_1.
     - img_conv reads the channels 0 .. IMAGE_WIDTH - 1 of the base tensor's gradient in place and stem k the channels behind
       (torch.cat's backward hands out slices, autograd's convolutions read them at an offset).
-    No host synchronisation in either direction; activations are new tensors of each call."""
+    No host synchronisation in either direction; activations are new tensors of each call.
+
+    precision is an attribute of the instance, not an argument of the constructor (whose signature is every trainable
+    network's): model.precision = "bf16", at any time between two steps; anything but "float32" or "bf16" raises ValueError
+    there.  "float32", the default, is the fixed-order float32 chain in every layer and every gradient.  "bf16" is mixed
+    precision for the layers that go through _wide and _up, forward (the bits of the inference class under precision="bf16")
+    and backward (dtfill_conv2d_strided_backward_data_bf16 and its siblings): operands rounded to bf16 in registers, float32
+    accumulation.  The head, the stems, img_conv, the pools, conv_output, the loss and KerasAdam stay float32; activations
+    and gradients are float32 in memory; the parameters and the optimizer state are float32 master copies, packed anew inside
+    every call.  No loss scaling is needed: bf16 has float32's exponent range and g stays float32 in memory, so a small
+    gradient does not underflow on its way down as it would in float16."""
 
     INFERENCE = ResNet18
+    _precision = "float32"
+
+    @property
+    def precision(self):
+        return self._precision
+
+    @precision.setter
+    def precision(self, precision):
+        if precision not in PRECISIONS:
+            raise ValueError("precision must be one of %s, got %r" % (PRECISIONS, precision))
+        self._precision = precision
 
     def _wide(self, x, name, stride=1, residual=None, act="leaky"):
         from . import autograd
 
         layer = getattr(self, name)
-        return autograd.conv2d_strided(x, layer.kernel, layer.bias, stride, residual, act, LEAKY_ALPHA)
+        return autograd.conv2d_strided(x, layer.kernel, layer.bias, stride, residual, act, LEAKY_ALPHA, self.precision)
 
     def _up(self, x, name):
         from . import autograd
 
         layer = getattr(self, name)
-        return autograd.conv2d_transpose(x, layer.kernel, layer.bias, "leaky", LEAKY_ALPHA)
+        return autograd.conv2d_transpose(x, layer.kernel, layer.bias, "leaky", LEAKY_ALPHA, self.precision)
 
     def forward(self, input_lidar):
         """input_lidar: contiguous float32 CUDA tensor [B,H,W] in metres, H and W multiples of 8, a constant.  Returns two

@@ -1099,7 +1099,7 @@ int dtfill_adam_step(float *const *params, const float *const *grads /* entries 
 /*
  * dtfill_conv2d_strided_bf16 and dtfill_conv2d_transpose_bf16: the two calls below on the bf16 matrix cores with float32
  * accumulation, the opt-in inference precision of the three ResNets (precision = "bf16").  The float32 calls stay the default
- * and the only ones training uses.  The argument lists and tensors are the twins': x, bias, residual and out stay float32 in
+ * (training under bf16: the backward calls further down).  The argument lists and tensors are the twins': x, bias, residual and out stay float32 in
  * memory, out_channels and out_offset behave as there, and the output size and the padding are the same 'same' rule.  w is NOT
  * the float32 kernel but the packed bf16 array dtfill_conv2d_pack_bf16() makes of it, 16-byte aligned.
  * Accepted shapes: ksize 1 or 3; stride 1 or 2 (the transposed form is always 3x3, stride 2); Cin a multiple of 16 and at
@@ -1163,6 +1163,91 @@ int dtfill_conv2d_transpose_bf16(const float *x, int B, int H, int W, int Cin,
                                  const void *w /* packed bf16 */, const float *bias /* nullable */, int Cout,
                                  int act, float alpha,
                                  float *out, int out_channels, int out_offset, void *stream);
+
+/*
+ * The backward of the wide layers on the bf16 matrix cores with float32 accumulation: what precision = "bf16" trains with.
+ * The four calls below are dtfill_conv2d_strided_backward_data / _weights and dtfill_conv2d_transpose_backward_data / _weights
+ * with the same argument lists, and dtfill_conv2d_wide_backward_bf16_workspace_bytes is their size function (0 for a shape
+ * they refuse).  x, dy, y, w, dx, dresidual, dw and db are float32 in memory; dy and y are read at a channel offset of a wider
+ * tensor and dx is written at one, as there.  w is the PLAIN float32 kernel the float32 calls take ([ksize,ksize,Cin,Cout], the
+ * exchanged [3,3,Cin,Cout] of the transposed layer): the weights change every step, so the data call packs what it needs
+ * into the workspace itself.  Domain: ksize 1 or 3, stride 1 or 2, Cin and Cout multiples of 16 and at least 16, H and W even
+ * at stride 2; pixel and element limits, the workspace rule (256-byte aligned, at least the size function's bytes) and the
+ * order of the return codes are the twins'.  The float32 calls stay the default.
+ *
+ * g = dy * act'(y) is the float32 calls' g, computed in float32 (a compare on y and one rounded product), and dresidual = g is
+ * exact, from the same pass.  x^ = bf16(x), g^ = bf16(g), w^ = bf16(w): dtfill_conv2d_strided_bf16's rounding (to nearest even,
+ * NaN kept, past the largest finite bf16 to +-inf), made in registers while staging; nothing bf16 is kept in memory but the
+ * packed kernel in the workspace.
+ *
+ * dx, by identity with the bf16 forward calls over the dense g [B,Ho,Wo,Cout], linear, no bias:
+ *   stride 1          == dtfill_conv2d_strided_bf16(g, pack(wT), stride 1),  wT[i][j][o][c] = w[ksize-1-i][ksize-1-j][c][o]
+ *   3x3, stride 2     == dtfill_conv2d_transpose_bf16(g, pack(wX)),          wX[i][j][o][c] = w[i][j][c][o]
+ *   transposed layer  == dtfill_conv2d_strided_bf16(g, pack(wX), 3x3, stride 2)
+ *   1x1, stride 2     the 1x1 stride-1 bf16 call over g under pack(wX) at the even pixels of dx, +0 literally at the others
+ * bit for bit, so dx has that contract: a fixed sequence of MFMAs per output and its bound (b) with n = ksize^2 32
+ * ceil(Cout / 32) and S = sum |g^| |w^| over the output's terms.
+ *
+ * dw and db.  Not a chain either, for the reason given there.  What is promised:
+ *   (a) A fixed sequence.  Segments of DTFILL_CONV_BW_ROWS x DTFILL_CONV_BW_COLS pixels lie over the small frame exactly as
+ *       in dtfill_conv2d_strided_backward_weights (the output frame of a strided layer, the input frame of the transposed
+ *       one).  Inside a segment the rows go in order; inside a row, k-steps of 32 consecutive pixels go in order, and a
+ *       position of a k-step past the frame is +0 on BOTH operands (a segment's row is two whole k-steps: none crosses a
+ *       segment).  Per (k-step, tap, 16 x 16 tile of (input channel, output channel)) there is ONE v_mfma_f32_16x16x32_bf16
+ *       into a float32 accumulator that lives from +0 across the whole segment; operand pixel u of the step sits at the
+ *       MFMA's k index 8 (u / 4 % 4) + 4 (u / 16) + u % 4 on both operands.  db[o] is the same sequence with the other
+ *       operand 1.0 (exact in bf16), the sum of g^; the transposed layer keeps its four chains, ((q00 + q01) + q10) + q11 in
+ *       float32.  The segments' partials [segment][tap][Cin][Cout] (+ db) are then added in float32 in (frame, segment row,
+ *       segment column) order, from +0, one rounding each.  So the bits are a function of the inputs and the shape alone:
+ *       not of the grid, the pass, the position in the batch beyond the order just stated, the run or the stream.
+ *   (b) |dw[e] - exact| <= 2 n 2^-23 S + n 2^-149,  exact = the sum of x^ g^ over the element's terms in real arithmetic,
+ *       S = sum |x^| |g^| over them, n = P + N: P the padded pixel count, sum over the frames' segments of (rows of the
+ *       segment) x 32 ceil(columns of the segment / 32), N = B segs_y segs_x the number of segments.  Derivation, as for
+ *       dtfill_conv2d_strided_bf16.  The value is made by P additions of a product inside MFMAs (the +0 positions
+ *       included) and N additions of a partial.  Each is off by at most one unit in the last place of the running sum,
+ *       whether the hardware rounds to nearest or truncates, sequentially or as a tree, and every running sum is at most
+ *       S (1 + o(1)) in magnitude: (P + N) 2^-23 S to first order.  An MFMA may also align its 33 addends to the
+ *       largest of them and drop what falls below its last place, at most 2^-23 of that largest (<= S) per addend:
+ *       another P 2^-23 S.  Together at most (2 P + N) 2^-23 S <= 2 n 2^-23 S.  The absolute term is the products': at
+ *       most P of them, each rounded or truncated once by less than 2^-149 where it lies below 2^-126; an addition whose
+ *       result is below 2^-126 is exact.  db: the same with x^ = 1 (for the transposed layer P counts the four chains'
+ *       positions, 4 P, and N the three additions more per segment).  Where every partial sum is exactly representable
+ *       (small integers) dw and db are exact.
+ * Non-finite values: padding and the positions past the frame are a staged +0, so +0 * NaN = NaN as in the float32 calls,
+ * and the set of NaN entries of dw and db equals theirs on the same inputs (with finite products: a bf16 overflow of a
+ * finite x or g to inf is dtfill_conv2d_strided_bf16's rule).  +0 and -0 count as equal.
+ *
+ * The workspace holds g, the packed kernel and the 1x1 stride-2 values for the data call, the partials for the weights call;
+ * either call may use the whole of it, so two calls that share one must be ordered on a stream.  Asynchronous on `stream`;
+ * no allocation, no atomics, no host synchronisation.  Returns: as the twins', in their order.
+ */
+size_t dtfill_conv2d_wide_backward_bf16_workspace_bytes(int B, int H, int W, int Cin, int ksize, int Cout, int stride, int transposed);
+int dtfill_conv2d_strided_backward_data_bf16(const float *dy, int dy_channels, int dy_offset,
+                                             const float *y /* nullable if linear */, int y_channels, int y_offset,
+                                             const float *w, int B, int H, int W, int Cin, int ksize, int Cout, int stride,
+                                             int act, float alpha,
+                                             float *dx, int dx_channels, int dx_offset, float *dresidual /* nullable */,
+                                             void *workspace, size_t ws_bytes, void *stream);
+int dtfill_conv2d_strided_backward_weights_bf16(const float *x,
+                                                const float *dy, int dy_channels, int dy_offset,
+                                                const float *y /* nullable if linear */, int y_channels, int y_offset,
+                                                int B, int H, int W, int Cin, int ksize, int Cout, int stride,
+                                                int act, float alpha,
+                                                float *dw, float *db /* nullable */,
+                                                void *workspace, size_t ws_bytes, void *stream);
+int dtfill_conv2d_transpose_backward_data_bf16(const float *dy, int dy_channels, int dy_offset,
+                                               const float *y /* nullable if linear */, int y_channels, int y_offset,
+                                               const float *w /* packed [3,3,Cin,Cout] */, int B, int H, int W, int Cin, int Cout,
+                                               int act, float alpha,
+                                               float *dx, int dx_channels, int dx_offset,
+                                               void *workspace, size_t ws_bytes, void *stream);
+int dtfill_conv2d_transpose_backward_weights_bf16(const float *x,
+                                                  const float *dy, int dy_channels, int dy_offset,
+                                                  const float *y /* nullable if linear */, int y_channels, int y_offset,
+                                                  int B, int H, int W, int Cin, int Cout,
+                                                  int act, float alpha,
+                                                  float *dw /* packed layout */, float *db /* nullable */,
+                                                  void *workspace, size_t ws_bytes, void *stream);
 
 /*
  * dtfill_conv2d_strided and dtfill_conv2d_transpose: the wide layers of ResNet18_NO_BN_l2 (solution_DeepNet/net.py:245-745),
