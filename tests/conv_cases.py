@@ -19,6 +19,7 @@ import conv2_ref as R2
 import conv2b_ref as RW
 import conv_bf16_ref as HB
 import conv_ref as R
+import convb_bf16_ref as HBB
 import convb_ref as RB
 import test_gpu_conv2d as fwd  # case(): numpy only at import
 import test_gpu_conv2d_backward as bwd  # case()
@@ -455,7 +456,9 @@ def wworkspace_bytes(c):
     (Ho, Wo), _ = wframes(c)
     taps, cin, cout, pixels = c["ksize"] ** 2, c["cin"], c["cout"], c["B"] * Ho * Wo
     spread = not c["transposed"] and c["stride"] == 2 and c["ksize"] == 1
-    data = 0 if c["entry"] == "dw_image" else _align(4 * pixels * cout) + _align(4 * taps * cin * cout) + (_align(4 * pixels * cin) if spread else 0)
+    # the kernel the data gradient runs under: float32, or (bf16) the packed array of the forward over g, Cout in and Cin out
+    kernel = 2 * HB.packed_elems(c["ksize"], cout, cin) if c.get("bf16") else 4 * taps * cin * cout
+    data = 0 if c["entry"] == "dw_image" else _align(4 * pixels * cout) + _align(kernel) + (_align(4 * pixels * cin) if spread else 0)
     return max(data, _align(4 * wsegments(c) * (taps * cin + 1) * cout))
 
 
@@ -469,6 +472,8 @@ def wdevice_bytes(c, chunk=COMPARE_CHUNK):
 def wtile(c, seed=0):
     """The T frames of a case of WLOOP and the reference on them: x, w, dy and y (whole tensors, poison beside the slice) and
     `want`: dx of the tile, or the level-1 partials [T * segments of a frame, ksize^2 Cin + 1, Cout] in (b, t, s) order."""
+    if c.get("bf16"):
+        return bf16_wtile(c, seed)
     ksize, stride, cin, cout, act = c["ksize"], c["stride"], c["cin"], c["cout"], c["act"]
     (Ho, Wo), _ = wframes(c)
     x, w, _ = fwd.case(ksize, cin, cout, (T, c["H"], c["W"]), seed)
@@ -603,3 +608,66 @@ def is_subnormal(a):
 def is_normal(a):
     a = np.asarray(a, F)
     return np.isfinite(a) & (np.abs(a) >= np.finfo(F).tiny)
+
+
+# ================================================================================================ the bf16 backward calls
+# Parts A and B for dtfill_conv2d_strided_backward_data_bf16 / _weights_bf16 and the transposed pair (k_convhb_dw_wide,
+# k_convhb_pack and k_convh_wide behind the workspace plan; tests/test_gpu_conv2d_bf16_backward_limits.py).  The records are
+# WLOOP's and WLARGE's own, with bf16=True: wframes(), wsegments(), wworkspace_bytes() and wdevice_bytes() read them as they are.
+# k_convhb_dw_wide has its own seg0 / gl0 launch loop and its own 32-bit frame offsets; the group axis's repeat (gl0) needs
+# more than a million channels, a weight tensor past the shape rule's own limit, and stays unreachable as for the twin.
+# Tiles are small integers (bf16_wtile): every level-1 partial is exact in any order, `want` is the int64 partials, and level2()
+# is the contract's stated float32 chain over them.
+HBALPHA = 0.25  # exact on the integers
+HBLOOP = {"bf16 " + n: dict(c, bf16=True) for n, c in WLOOP.items() if c["entry"] != "dw_image" and c["ksize"] <= 3}
+HBLARGE = {"bf16 " + n: dict(c, bf16=True) for n, c in WLARGE.items()
+           if c["entry"] != "dw_image" and n != "dx strided 3x3x16->16, dy 128 wide at the limit"}
+HBREFUSED = tuple(r for r in WREFUSED if r[0] in ("dx_wide", "dw_wide"))
+
+
+def bf16_partials(x, g4, ksize, stride, transposed):
+    """Level 1 of the bf16 weight sum over integer operands (g4 = 4 g), in int64: [segments, ksize^2 Cin + 1, Cout] in (b, t, s)
+    order, each row the sum over the segment's pixels alone, the last row db's."""
+    xi, g4 = np.rint(x).astype(np.int64), np.asarray(g4, np.int64)
+    cout = g4.shape[3]
+    Hs, Ws = (x.shape[1], x.shape[2]) if transposed else (g4.shape[1], g4.shape[2])
+    rows = []
+    for b, h0, h1, v0, v1 in RB.segments(len(x), Hs, Ws):
+        small = xi if transposed else g4
+        cut = np.zeros_like(small[b:b + 1])
+        cut[0, h0:h1, v0:v1] = small[b, h0:h1, v0:v1]
+        if transposed:
+            dw, _ = HBB.dw_sum(cut, g4[b:b + 1], 3, 2, True, np.int64)
+            db = g4[b, 2 * h0:2 * h1, 2 * v0:2 * v1].reshape(-1, cout).sum(axis=0)  # the segment's four parities
+        else:
+            dw, db = HBB.dw_sum(xi[b:b + 1], cut, ksize, stride, False, np.int64)
+        rows.append(np.concatenate([dw.reshape(-1, cout), db[None]], axis=0))
+    return np.stack(rows)
+
+
+def bf16_wtile(c, seed=0):
+    """wtile() for a bf16 case: x in -8 .. 8, w in -4 .. 4, dy in -3 .. 3, alpha 0.25, y of either sign with a few -0.  The dx
+    cases take w in 1 .. 4 and dy in 1 .. 3: every sum is positive, so no expected dx or dresidual is a zero (the device
+    comparison is by bits, and the contracts leave a zero's sign open).  Every operand is exact in bf16 and every partial sum a
+    multiple of 2^-2 below 2^22: exact in any order, asserted."""
+    ksize, stride, cin, cout, act, tr = c["ksize"], c["stride"], c["cin"], c["cout"], c["act"], c["transposed"]
+    (Ho, Wo), _ = wframes(c)
+    rng = np.random.default_rng(seed)
+    dx_case = c["entry"] == "dx_wide"
+    x = rng.integers(-8, 9, (T, c["H"], c["W"], cin)).astype(F)
+    w = rng.integers(1 if dx_case else -4, 5, (ksize, ksize, cin, cout)).astype(F)
+    dy = rng.integers(1 if dx_case else -3, 4, (T, Ho, Wo, cout)).astype(F)
+    y = rng.standard_normal((T, Ho, Wo, cout)).astype(F)
+    y[rng.random(y.shape) < 0.05] = -0.0
+    g = RB.g_ref(dy, y, act, HBALPHA)
+    g4 = np.rint(g.astype(np.float64) * 4).astype(np.int64)
+    assert np.array_equal(g4 / 4.0, g.astype(np.float64))
+    for a in (x, w, g):
+        assert np.array_equal(HB.bf16_round(a), a), "an operand is not exact in bf16"
+    if dx_case:
+        total = HBB.dx_sum(g4, np.rint(w).astype(np.int64), stride, tr, np.int64)
+    else:
+        total = bf16_partials(x, g4, ksize, stride, tr)
+    assert np.abs(total).max() < 2 ** 24
+    return dict(x=x, w=w, dy=widened(dy, c["width"], c["at"]), y=widened(y, c["width"], c["at"]), want=(total / 4.0).astype(F),
+                dres=g if c["dres"] else None)

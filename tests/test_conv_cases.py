@@ -500,3 +500,98 @@ def test_backward_large_tiles_are_alias_free_and_have_no_open_zero(blarge):
     else:
         dw, db = CC.split_dw(CC.level2(want, 4 * len(want)), c["ksize"], c["cin"])
         assert (dw != 0).mean() > 0.9 and (db != 0).all()
+
+
+# ================================================================================================ the bf16 backward calls
+def test_bf16_backward_loop_cases_reach_the_second_launch():
+    wide = {n: c for n, c in CC.HBLOOP.items() if c["entry"] == "dw_wide"}
+    for name, c in wide.items():
+        _, (Hs, Ws) = CC.wframes(c)
+        assert c["bf16"] and (Hs, Ws) == (1, 129) and CC.wsegments(c) == 3 * c["B"] == 65637 == CC.GRID_Z + 102, name
+        assert CC.GRID_Z % 3 == 0  # segment 65535 is column 0 of frame 21845: the second launch begins on a frame boundary ...
+        assert (CC.wsegments(c) - CC.GRID_Z) % 3 != 0 or Ws % CC.SEG_COLS == 1  # ... and its last frame ends with a segment of one column
+        assert c["cin"] // 16 < CC.GRID_Z  # one launch along the group axis: gl0 stays 0 within the shape rule
+    # one call for each instantiation convhb_weights_launch asks for, the 3x3 stride-1 one on both bodies
+    assert sorted((c["ksize"], c["stride"], c["transposed"], c["mis"]) for c in wide.values()) == [
+        (1, 1, False, 0), (1, 2, False, 0), (3, 1, False, 0), (3, 1, False, 4), (3, 2, False, 0), (3, 2, True, 0)]
+    dx = {n: c for n, c in CC.HBLOOP.items() if c["entry"] == "dx_wide"}
+    assert {(c["ksize"], c["stride"], c["transposed"]) for c in dx.values()} == {(1, 2, False), (3, 2, True)} and len(CC.HBLOOP) == 8
+    for name, c in CC.HBLOOP.items():
+        floor = 2 * 4 * 21879 * 2 * 258 * 32 if c["transposed"] else 0  # g beside dy, both B 2H 2W Cout floats
+        assert max(floor, 0) <= CC.wdevice_bytes(c) < max(3e9, floor + 1e9), (name, CC.wdevice_bytes(c))
+        assert CC.wworkspace_bytes(c) % 256 == 0 and CC.wworkspace_bytes(c) <= CC.wworkspace_bytes(dict(c, bf16=False))
+
+
+@pytest.fixture(scope="module", params=[("HBLOOP", n) for n in CC.HBLOOP] + [("HBLARGE", n) for n in CC.HBLARGE], ids=lambda p: "%s: %s" % p)
+def hbtiled(request):
+    table, name = request.param
+    c = getattr(CC, table)[name]
+    return c, CC.wtile(c)  # asserts bf16 operands and partial sums below 2^24 quarter-units
+
+
+def test_bf16_backward_tiles_are_exact_alias_free_and_have_no_open_zero(hbtiled):
+    c, d = hbtiled
+    for key in ("x", "dy", "y"):
+        assert d[key].shape[0] == CC.T and len({d[key][t].tobytes() for t in range(CC.T)}) == CC.T, key
+        LC.assert_alias_free(CC.T, d[key].size // CC.T)
+    want = d["want"]
+    assert np.isfinite(want).all() and np.array_equal(np.rint(want * 4), want * 4)
+    if c["entry"] == "dx_wide":
+        LC.assert_alias_free(CC.T, want.size // CC.T)
+        spread = not c["transposed"] and c["stride"] == 2 and c["ksize"] == 1
+        assert ((want[:, ::2, ::2] if spread else want) > 0).all() and not (want.view(np.uint32) == 0x80000000).any()
+        assert not spread or (want == 0).mean() == 0.75  # +0 off the even grid, by the contract
+        at = c["at"]
+        dy, y = d["dy"][..., at:at + c["cout"]], d["y"][..., at:at + c["cout"]]
+        x = CC.HBB.dx_sum(RB.g_ref(dy, y, c["act"], CC.HBALPHA), d["w"], c["stride"], c["transposed"])  # the float64 statement agrees
+        assert np.array_equal(x, want.astype(np.float64))
+        if c["dres"]:
+            LC.assert_alias_free(CC.T, d["dres"].size // CC.T)
+            assert (d["dres"] != 0).all()
+    else:
+        (_, _), (Hs, Ws) = CC.wframes(c)
+        per_frame = -(-Hs // CC.SEG_ROWS) * -(-Ws // CC.SEG_COLS)
+        assert len(want) == CC.T * per_frame and len({p.tobytes() for p in want}) == len(want)  # every segment has partials of its own
+        # the partials of a frame add up to the statement over the whole frame
+        at = c["at"]
+        g = RB.g_ref(d["dy"][..., at:at + c["cout"]], d["y"][..., at:at + c["cout"]], c["act"], CC.HBALPHA)
+        dw, db = CC.HBB.dw_sum(d["x"], g, c["ksize"], c["stride"], c["transposed"])
+        total = want.astype(np.float64).sum(axis=0)
+        assert np.array_equal(total[:-1].reshape(dw.shape), dw) and np.array_equal(total[-1], db)
+        l2dw, l2db = CC.split_dw(CC.level2(want, 4 * len(want)), c["ksize"], c["cin"])
+        assert (l2dw != 0).mean() > (0.25 if Hs == 1 and c["ksize"] == 3 else 0.9) and (l2db != 0).mean() > 0.9
+
+
+def test_bf16_backward_large_cases_pass_their_thresholds():
+    past4 = set()
+    for name, c in CC.HBLARGE.items():
+        e = wsizes(c)
+        assert c["bf16"] and all(v < 2 ** 31 for v in e.values()), name  # the shape rule
+        assert CC.wdevice_bytes(c, LC.CHUNK_BYTES) < 20e9, (name, CC.wdevice_bytes(c, LC.CHUNK_BYTES))
+        frame = {k: v // c["B"] for k, v in e.items()}
+        over = lambda least: {k for k in e if (c["B"] - CC.T) * frame[k] >= least}  # noqa: E731: the last T frames start beyond
+        if "past 4 GiB" in name:
+            named = {k for k in e if k in name.split(" past 4 GiB")[0].replace(",", " ").split()}
+            assert named and named <= over(2 ** 30), (name, named, over(2 ** 30))
+            past4 |= over(2 ** 30)
+            if "workspace" in name:  # p.wt, the packed kernel, lies behind a g of more than 4 GiB
+                (Ho, Wo), _ = CC.wframes(c)
+                assert 4 * c["B"] * Ho * Wo * c["cout"] > 2 ** 32 and CC.wworkspace_bytes(c) > 2 ** 32, name
+        elif "past 2 GiB" in name:
+            assert over(2 ** 29) and not over(2 ** 30), name
+        else:
+            assert "at the limit" in name and any(2 ** 31 - frame[k] <= v < 2 ** 31 for k, v in e.items()), name
+    assert past4 == {"dy", "y", "dx", "dresidual", "x"}
+    shapes = sorted((c["entry"], c["ksize"], c["stride"], c["transposed"], c["cin"], c["cout"]) for c in CC.HBLARGE.values())
+    assert shapes == [("dw_wide", 1, 1, False, 64, 16), ("dw_wide", 1, 1, False, 64, 16), ("dw_wide", 3, 2, False, 16, 16),
+                      ("dw_wide", 3, 2, True, 64, 16), ("dx_wide", 1, 1, False, 64, 64), ("dx_wide", 1, 2, False, 64, 64),
+                      ("dx_wide", 3, 2, True, 64, 16)]
+    spread = [c for c in CC.HBLARGE.values() if c["entry"] == "dx_wide" and c["stride"] == 2 and not c["transposed"]]
+    assert len(spread) == 1 and spread[0]["ksize"] == 1  # where p.tmp is in use
+
+
+def test_bf16_backward_refused_calls_are_the_twins_wide_rows():
+    assert len(CC.HBREFUSED) == 10 and all(a["ksize"] in (1, 3) for _, _, a in CC.HBREFUSED)  # the bf16 domain
+    for entry, what, a in CC.HBREFUSED:
+        assert CC.wrefused_count(entry, a) == 2 ** 31, (entry, what)
+    assert {(e, a.get("transposed", False)) for e, _, a in CC.HBREFUSED} == {("dx_wide", False), ("dx_wide", True), ("dw_wide", False), ("dw_wide", True)}

@@ -61,14 +61,23 @@ def workspace_bytes(L, c):
     B, H, W, cin, cout, ksize = (c[k] for k in ("B", "H", "W", "cin", "cout", "ksize"))
     if c["entry"] == "dw_image":
         return L.dtfill_conv2d_image_backward_workspace_bytes(B, H, W, cin, ksize, cout)
+    if c.get("bf16"):
+        return L.dtfill_conv2d_wide_backward_bf16_workspace_bytes(B, H, W, cin, ksize, cout, c.get("stride", 1), int(c.get("transposed", False)))
     return L.dtfill_conv2d_wide_backward_workspace_bytes(B, H, W, cin, ksize, cout, c.get("stride", 1), int(c.get("transposed", False)))
 
 
 def call(L, c, x, grad, w, dx, dres, dw, db, ws, nws):
-    """The entry point of record c on raw pointers; grad: (dy, width, at, y, width, at)."""
+    """The entry point of record c on raw pointers; grad: (dy, width, at, y, width, at).  bf16=True in the record: the bf16 twin
+    of the wide call, under conv_cases.HBALPHA."""
     B, H, W, cin, cout, ksize, act = (c[k] for k in ("B", "H", "W", "cin", "cout", "ksize", "act"))
     stride, tr = c.get("stride", 1), c.get("transposed", False)
     dxc = c.get("dx_channels", cin)
+    if c.get("bf16"):
+        name = "dtfill_conv2d_%s_backward_%s_bf16" % ("transpose" if tr else "strided", "data" if c["entry"] == "dx_wide" else "weights")
+        layer = (B, H, W, cin, cout) if tr else (B, H, W, cin, ksize, cout, stride)
+        if c["entry"] == "dx_wide":
+            return getattr(L, name)(*grad, w, *layer, act, CC.HBALPHA, dx, dxc, 0, *(() if tr else (dres,)), ws, nws, None)
+        return getattr(L, name)(x, *grad, *layer, act, CC.HBALPHA, dw, db, ws, nws, None)
     if c["entry"] == "dx_wide":
         if tr:
             return L.dtfill_conv2d_transpose_backward_data(*grad, w, B, H, W, cin, cout, act, CC.ALPHA, dx, dxc, 0, ws, nws, None)

@@ -52,13 +52,17 @@ def _workspace(L, shape, cin, ksize, cout, stride, transposed, bf16):
 
 
 def _placed(a, dense):
-    """dy or y as the call reads it: (array, width, offset): at channel AT of a wider poisoned tensor, or dense."""
+    """dy or y as the call reads it: (array, width, offset): at channel AT of a wider poisoned tensor, or dense.  y = None (a
+    linear layer's NULL) stays None."""
+    if a is None:
+        return None, 0, 0
     return (a, a.shape[3], 0) if dense else (wb._wide(a), wb._width(a.shape[3]), AT)
 
 
 def run_data(L, dy, y, w, stride, transposed=False, alpha=ALPHA, dx_channels=None, dx_offset=0, mis=0, residual=False, stream=None,
-             dense=False, bf16=True):
-    """The data gradient on guarded buffers; returns the whole dx tensor [B,H,W,dx_channels] (and dresidual with `residual`)."""
+             dense=False, bf16=True, act=ACT):
+    """The data gradient on guarded buffers; returns the whole dx tensor [B,H,W,dx_channels] (and dresidual with `residual`).
+    y = None passes NULL (act = R.LINEAR)."""
     import torch
 
     B, Hg, Wg, cout = dy.shape
@@ -66,21 +70,22 @@ def run_data(L, dy, y, w, stride, transposed=False, alpha=ALPHA, dx_channels=Non
     H, W = (Hg // 2, Wg // 2) if transposed else (stride * Hg, stride * Wg)
     dx_channels = cin if dx_channels is None else dx_channels
     (wdy, width, at), (wy, _, _) = _placed(dy, dense), _placed(y, dense)
-    gdy, gy, gw = fwd._up(wdy, mis), fwd._up(wy, mis), fwd._up(w, mis)
+    gdy, gy, gw = fwd._up(wdy, mis), (None if y is None else fwd._up(wy, mis)), fwd._up(w, mis)
     gdx = fwd._poisoned((B, H, W, dx_channels), mis)
     gres = fwd._poisoned(dy.shape, mis) if residual else None
     ws, nbytes = _workspace(L, (B, H, W), cin, ksize, cout, 2 if transposed else stride, int(transposed), bf16)
     torch.cuda.synchronize()
-    head = (gdy.ptr, width, at, gy.ptr, width, at, gw.ptr, B, H, W, cin)
+    head = (gdy.ptr, width, at, gy.ptr if gy else None, width, at, gw.ptr, B, H, W, cin)
     if transposed:
-        rc = _symbol(L, True, "data", bf16)(*head, cout, ACT, alpha, gdx.ptr, dx_channels, dx_offset, ws.ptr, nbytes, stream)
+        rc = _symbol(L, True, "data", bf16)(*head, cout, act, alpha, gdx.ptr, dx_channels, dx_offset, ws.ptr, nbytes, stream)
     else:
-        rc = _symbol(L, False, "data", bf16)(*head, ksize, cout, stride, ACT, alpha, gdx.ptr, dx_channels, dx_offset,
+        rc = _symbol(L, False, "data", bf16)(*head, ksize, cout, stride, act, alpha, gdx.ptr, dx_channels, dx_offset,
                                              gres.ptr if gres else None, ws.ptr, nbytes, stream)
     assert rc == 0, rc
     torch.cuda.synchronize()
     bwd._unchanged(gdy, wdy, "dy")
-    bwd._unchanged(gy, wy, "y")
+    if gy:
+        bwd._unchanged(gy, wy, "y")
     bwd._unchanged(gw, w, "w")
     gdx.check("dx")
     ws.check("workspace")
@@ -91,20 +96,21 @@ def run_data(L, dy, y, w, stride, transposed=False, alpha=ALPHA, dx_channels=Non
     return dx, gres.view(torch.float32, dy.shape).cpu().numpy()
 
 
-def run_weights(L, x, dy, y, ksize, stride, transposed=False, alpha=ALPHA, want_db=True, mis=0, stream=None, dense=False, bf16=True):
-    """The weight gradient on guarded buffers; returns (dw, db or None)."""
+def run_weights(L, x, dy, y, ksize, stride, transposed=False, alpha=ALPHA, want_db=True, mis=0, stream=None, dense=False, bf16=True,
+                act=ACT):
+    """The weight gradient on guarded buffers; returns (dw, db or None).  y = None passes NULL (act = R.LINEAR)."""
     import torch
 
     B, H, W, cin = x.shape
     cout = dy.shape[3]
     (wdy, width, at), (wy, _, _) = _placed(dy, dense), _placed(y, dense)
-    gx, gdy, gy = fwd._up(x, mis), fwd._up(wdy, mis), fwd._up(wy, mis)
+    gx, gdy, gy = fwd._up(x, mis), fwd._up(wdy, mis), (None if y is None else fwd._up(wy, mis))
     gdw = fwd._poisoned((ksize, ksize, cin, cout), mis)
     gdb = fwd._poisoned((cout,), mis) if want_db else None
     ws, nbytes = _workspace(L, (B, H, W), cin, ksize, cout, 2 if transposed else stride, int(transposed), bf16)
     torch.cuda.synchronize()
-    head = (gx.ptr, gdy.ptr, width, at, gy.ptr, width, at, B, H, W, cin)
-    tail = (ACT, alpha, gdw.ptr, gdb.ptr if gdb else None, ws.ptr, nbytes, stream)
+    head = (gx.ptr, gdy.ptr, width, at, gy.ptr if gy else None, width, at, B, H, W, cin)
+    tail = (act, alpha, gdw.ptr, gdb.ptr if gdb else None, ws.ptr, nbytes, stream)
     if transposed:
         rc = _symbol(L, True, "weights", bf16)(*head, cout, *tail)
     else:
@@ -113,7 +119,8 @@ def run_weights(L, x, dy, y, ksize, stride, transposed=False, alpha=ALPHA, want_
     torch.cuda.synchronize()
     bwd._unchanged(gx, x, "x")
     bwd._unchanged(gdy, wdy, "dy")
-    bwd._unchanged(gy, wy, "y")
+    if gy:
+        bwd._unchanged(gy, wy, "y")
     gdw.check("dw")
     ws.check("workspace")
     if gdb:
